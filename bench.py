@@ -7,8 +7,11 @@ a synthetic Jordan algebra of order N = 4096 with 34 basis matrices.  Inputs (C_
 resident in HBM before the timed region; the setup stage (src/partitions.jl:117-142) is outside
 the hot path.
 
-Three instances of configs[3] are measured; `value` is the first, the other two are reported in
-`workloads` of the same JSON line (each with reductions/s, iteration count, per-phase ms):
+A plain run sets up, warms up, times --steps reductions of one instance (--workload, default the
+first below), writes their outputs under --dump-outputs DIR if given, and prints the result line.
+--full adds everything else: the per-phase split of the timed steps, a correctness check after
+them, the other two instances in `workloads` (each with reductions/s, iteration count, per-phase
+ms), the variants, the per-kernel roofline figures and the CPU-oracle baseline:
   closed_scheme     the 34-class scheme circulant(Z_32) (x) {I, J-I}_128 handed over as the SDP
                     data itself (C takes a distinct value per class): the loop confirms the
                     closure in ONE iteration, all blocks have size 1;
@@ -146,6 +149,47 @@ class Workload:
         self.dev = dev
 
 
+DUMP_LABEL_SAMPLE = 1 << 20       # label entries written (4 MiB as float32); the whole n x n matrix is 64 MiB at N = 4096
+DUMP_IMAGE_BYTES = 48 * 1000 ** 2  # block images beyond this are sampled: with the labels, the dump stays under 64 MB
+
+
+def dump_outputs(path, w, ctx, restarts):
+    """--dump-outputs: what the last timed step handed its caller (restart 0 of a batched step), as .npy files.
+    labels_sample  float32  the canonical labels (column-major n x n) at fixed seeded positions
+    class_sizes    float64  entries per label 0..dim over the WHOLE label matrix
+    block_sizes    float64  blkSizes, in the order of the block images
+    block_images   float64  basis_image: dim x sum_sq, class-major, each block column-major (a fixed seeded sample if large)
+    summary        float64  [dim, number of blocks, sum_sq, loop iterations]"""
+    os.makedirs(path, exist_ok=True)
+    tP, blk = (w.bP[0], w.bblk[0]) if restarts > 1 else (w.tP, w.blk)
+    last = w.last
+    labels = tP.cpu().numpy().astype(np.int64)
+    sizes = last["sizes"]
+    if sizes is None and not last["images"]:
+        sizes = []  # restart 0 of the batch failed (a randomized failure): no sizes, no images
+    if sizes is None:
+        buf = np.zeros(max(1, last["nblocks"]), dtype=np.int32)
+        if restarts > 1:
+            st = ctx._lib.sdpsr_batch_block_sizes(ctx._h, 0, buf.ctypes.data_as(C.c_void_p))
+        else:
+            st = ctx._lib.sdpsr_block_sizes(ctx._h, buf.ctypes.data_as(C.c_void_p))
+        sizes = [int(v) for v in buf if v > 0] if st == 0 else []
+    images = np.zeros(0)
+    if last["images"] and blk is not None and blk.numel() >= last["dim"] * last["sum_sq"]:
+        images = blk[: last["dim"] * last["sum_sq"]].cpu().numpy()
+        if images.nbytes > DUMP_IMAGE_BYTES:
+            keep = np.random.default_rng(2).choice(images.size, DUMP_IMAGE_BYTES // 8, replace=False)
+            images = images[np.sort(keep)]
+    pick = np.sort(np.random.default_rng(1).choice(labels.size, min(labels.size, DUMP_LABEL_SAMPLE), replace=False))
+    out = {"labels_sample": labels[pick].astype(np.float32),
+           "class_sizes": np.bincount(labels, minlength=last["dim"] + 1).astype(np.float64),
+           "block_sizes": np.array(sizes, dtype=np.float64),
+           "block_images": images.astype(np.float64),
+           "summary": np.array([last["dim"], len(sizes), last["sum_sq"], last["iters"]], dtype=np.float64)}
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def launch_ranks(n_ranks, argv):
     """Parent of `bench.py --gpus N`: N child processes with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set,
     stdout and stderr inherited (rank 0 prints the JSON line).  This process never initialises a GPU."""
@@ -206,6 +250,10 @@ def main():
                          "thread, one stream each); 1 = the headline definition (one reduction at a time)")
     ap.add_argument("--cpu-samples", type=int, default=1, help="samples of the CPU-oracle reduction at the headline order (the median is reported; one takes ~50 s)")
     ap.add_argument("--square-kernel", type=int, default=0, help="sdpsr_opts.square_kernel (0 default, 1 = 128 x 128 tiles, 64 = persistent forced)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the phase split, the other instances, the variants, the roofline and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (rank 0) to DIR/<name>.npy, float32 / float64, at most 64 MB")
     args = ap.parse_args()
     global BENCH_N
     BENCH_N = args.n
@@ -299,6 +347,7 @@ def main():
             if check and st[i] == 0:
                 assert dd[i] == w.d and bool((w.bP[i] == w.golden).all()), "partition differs from the generator's closure"
                 assert ssq[i] == sum(x * x for x in w.blocks), (ssq[i], w.blocks)
+        w.last = {"dim": int(dd[0]), "nblocks": int(nb[0]), "sum_sq": int(ssq[0]), "iters": int(it[0]), "images": st[0] == 0, "sizes": None}  # restart 0, for --dump-outputs
         return [int(x) for x in st], sum(int(x) for x in it)
 
     def one_step(w, acc, cx, check=False, collective=True, timers=True):
@@ -390,7 +439,9 @@ def main():
                 acc.bd_adopted += 1
             if check:
                 assert sorted(agreed_sizes) == w.blocks, (sorted(agreed_sizes), w.blocks)
+            w.last = {"dim": dd.value, "nblocks": len(agreed_sizes), "sum_sq": ssq.value, "iters": it.value, "images": st_bd == 0, "sizes": list(agreed_sizes)}
             return len(agreed_sizes)
+        w.last = {"dim": dd.value, "nblocks": nb.value, "sum_sq": ssq.value, "iters": it.value, "images": True, "sizes": None}
         if check:
             sizes = np.zeros(nb.value, dtype=np.int32)
             cx.check(lib.sdpsr_block_sizes(cx._h, sizes.ctypes.data_as(C.c_void_p)))
@@ -498,18 +549,25 @@ def main():
         fr = torch.tensor([float(failed_restarts + (acc.bd_adopted if RPG == 1 else 0))], dtype=torch.float64, device=dev)
         dist.all_reduce(fr, op=dist.ReduceOp.SUM)
         failed_restarts = int(fr.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, w0, ctx, RPG)
     acc_timed = acc
-    if not args.timers_in_timed_region and RPG == 1:
+    # one-restart steps record phase events in the timed region only with --timers-in-timed-region; otherwise the
+    # split needs the instrumented pass below, which --full runs
+    phases_measured = args.timers_in_timed_region or RPG > 1
+    if args.full and not args.timers_in_timed_region and RPG == 1:
         # the per-phase HIP events (about thirty records per reduction) stay out of the timed region: the phase
         # split comes from an instrumented pass of the same number of steps right after it
         acc_timed = Acc()
         for _ in range(args.steps):
             retrying(lambda: one_step(w0, acc_timed, ctx))
         acc_timed.iters = acc.iters
-    if RPG > 1:
-        batched_step(w0, Acc(), ctx, check=True)
-    else:
-        retrying(lambda: one_step(w0, Acc(), ctx, check=True))  # results still correct after the timed region
+        phases_measured = True
+    if args.full:
+        if RPG > 1:
+            batched_step(w0, Acc(), ctx, check=True)
+        else:
+            retrying(lambda: one_step(w0, Acc(), ctx, check=True))  # results still correct after the timed region
 
     def measure(w, cx, steps):
         """rank 0 only, no collectives: reductions/s of another instance / driver"""
@@ -542,13 +600,14 @@ def main():
     workloads = {args.workload: {"value": round(total_red / dt, 3), "unit": "reductions/s", "ms_per_step": round(dt / args.steps * 1e3, 3),
                                  "steps": args.steps, "N": w0.n, "dim": w0.d, "blocks": f"{len(w0.blocks)} x size {w0.blocks[0]}" if len(set(w0.blocks)) == 1 else w0.blocks,
                                  "iterations_per_reduction": acc_timed.iters / max(1, args.steps), "randomized_retries": retries,
-                                 "phase_ms_per_step": phases(acc_timed, args.steps), "instance": w0.note, "timed_region": True}}
+                                 "phase_ms_per_step": phases(acc_timed, args.steps) if phases_measured else None, "instance": w0.note, "timed_region": True}}
     meets_warmup = acc_warm.meets
     variants = {}
     kernels = {}
     roof = None
     cpu = None
-    if rank == 0 and not args.skip_roofline and args.eig_driver == 0 and n in (4096, 8192) and RPG == 1:
+    extras = args.full and not args.skip_roofline  # everything beyond the headline figure
+    if rank == 0 and extras and args.eig_driver == 0 and n in (4096, 8192) and RPG == 1:
         for name in ("closed_scheme", "theta_c32xk128", "theta_er7xk72"):
             if name != args.workload:
                 wk = build(name)
@@ -650,7 +709,7 @@ def main():
     # every call, src/partitions.jl:109-116; the Julia shim passes SDPSR_MEM_HOST): C_L, X0_L, U uploaded, labels and
     # block images downloaded inside the call.  One call; a 4-restart batch from host arrays (ONE upload for the four);
     # and the problem handle (upload once, outside the calls) with host outputs.
-    if rank == 0 and not args.skip_roofline and RPG == 1:
+    if rank == 0 and extras and RPG == 1:
         try:
             CLh, X0h, Uh = w0.host
             nn = w0.n
@@ -734,7 +793,7 @@ def main():
         ctx.check(L.load_prof_library().sdpsr_profile_kernel(ctx._h, kind, nn, aux, reps, C.byref(v)))
         return v.value
 
-    if rank == 0 and not args.skip_roofline:
+    if rank == 0 and extras:
         d, r = w0.d, w0.r
         flops = 2.0 * n ** 3
         # the int8 square is launched exactly as the product path launches it: all its channels in
@@ -919,8 +978,8 @@ def main():
                                    f"square_mode={args.mode}, {args.channels or 2} channels" + ("" if args.channels else " + 1 confirm round"), "N": w0.n, "dim": w0.d, "restarts_per_step": world * RPG, "restarts_per_gpu": RPG,
                        "restarts_not_delivered": failed_restarts,
                        "iterations_per_reduction": acc_timed.iters / max(1, args.steps)},
-            "phase_ms_per_step": phases(acc_timed, args.steps),
-            "phase_ms_source": "HIP events inside the timed steps" if args.timers_in_timed_region else
+            "phase_ms_per_step": phases(acc_timed, args.steps) if phases_measured else None,
+            "phase_ms_source": "HIP events inside the timed steps" if args.timers_in_timed_region else "not measured: run with --full" if not phases_measured else
                                "an instrumented pass of the same steps right after the timed region (the timed steps carry no phase events)",
             "partition_meets": {"warmup": meets_warmup, "timed": acc.meets,
                                 "note": "agreement steps in which the ranks' partitions differed and the hash-meet ran (rank 0's count)"},

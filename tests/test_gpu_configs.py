@@ -490,6 +490,44 @@ def test_bench_restarts_per_gpu_batches_in_one_call():
 
 
 @pytest.mark.gpu
+def test_bench_dump_outputs_are_the_instance_and_repeat(problems, tmp_path):
+    """A plain `bench.py --dump-outputs DIR` times exactly --steps steps, measures nothing beyond the headline, and writes
+    what its last timed step delivered: the generator's closure (labels at the seeded positions, class sizes), blocks of
+    size 1, dim x sum_sq block images.  A second run with the same arguments writes the same partition outputs."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n = 1024
+    Ls, d = problems.synthetic_jordan_partition(n, seed=1)
+    runs = []
+    for k in range(2):
+        out_dir = tmp_path / f"run{k}"
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "2", "--n", str(n),
+                              "--dump-outputs", str(out_dir)], capture_output=True, text=True, timeout=900)
+        assert out.returncode == 0, out.stderr[-3000:]
+        js = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])
+        assert js["steps"] == 3 and js["ms_per_step"] > 0 and js["value"] > 0
+        assert js["variants"] == {} and js["kernels"] == {} and js["roofline"] is None and js["cpu_baseline"] is None
+        assert list(js["workloads"]) == ["closed_scheme"] and js["phase_ms_per_step"] is None
+        files = {f: np.load(out_dir / f) for f in sorted(os.listdir(out_dir))}
+        assert set(files) == {"labels_sample.npy", "class_sizes.npy", "block_sizes.npy", "block_images.npy", "summary.npy"}
+        assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+        assert sum(os.path.getsize(out_dir / f) for f in files) <= 64 * 1000 ** 2
+        pick = np.sort(np.random.default_rng(1).choice(n * n, min(n * n, 1 << 20), replace=False))
+        assert np.array_equal(files["labels_sample.npy"], Ls.ravel(order="F")[pick].astype(np.float32))
+        assert np.array_equal(files["class_sizes.npy"], np.bincount(Ls.ravel(), minlength=d + 1).astype(np.float64))
+        assert np.array_equal(files["block_sizes.npy"], np.ones(d))
+        dim, nblocks, sum_sq, iters = files["summary.npy"]
+        assert (dim, nblocks, sum_sq, iters) == (d, d, d, 1)
+        assert files["block_images.npy"].shape == (d * d,) and np.isfinite(files["block_images.npy"]).all()
+        runs.append(files)
+    for f in ("labels_sample.npy", "class_sizes.npy", "block_sizes.npy", "summary.npy"):
+        assert np.array_equal(runs[0][f], runs[1][f]), f
+
+
+@pytest.mark.gpu
 def test_rccl_backend_runs_the_agreement_collectives_single_rank():
     """gpurun exposes one GPU, so RCCL cannot be run with two ranks here (it refuses two ranks on one device; the two-rank
     flow is tested over gloo above).  What CAN be shown on this box is that the `nccl` (= RCCL) branch of the agreement

@@ -13,7 +13,7 @@ stats() {  # tag, bench args...
   cp $(find /tmp/st_$tag -name "*kernel_stats.csv" | head -1) $O/bench_${tag}_kernel_stats.csv
 }
 if [ "$WHAT" = all ] || [ "$WHAT" = bench ]; then
-  python3 bench.py > $O/bench_n4096.json 2> $O/bench_n4096.err
+  python3 bench.py --full > $O/bench_n4096.json 2> $O/bench_n4096.err
 fi
 if [ "$WHAT" = all ] || [ "$WHAT" = stats ]; then
   stats n4096 --steps 30 --warmup 5
@@ -33,7 +33,7 @@ if [ "$WHAT" = all ] || [ "$WHAT" = refine ]; then
   cp gpurun_out/pmc_refine_FETCH_SIZE.csv $O/ 2>/dev/null; cp gpurun_out/pmc_refine_WRITE_SIZE.csv $O/ 2>/dev/null
 fi
 if [ "$WHAT" = all ] || [ "$WHAT" = n8192 ]; then
-  python3 bench.py --n 8192 --steps 10 --warmup 2 > $O/bench_n8192.json 2> $O/bench_n8192.err
+  python3 bench.py --full --n 8192 --steps 10 --warmup 2 > $O/bench_n8192.json 2> $O/bench_n8192.err
   stats n8192 --n 8192 --steps 10 --warmup 2
 fi
 if [ "$WHAT" = all ] || [ "$WHAT" = configs ]; then
