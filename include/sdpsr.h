@@ -140,8 +140,8 @@ enum {
        (DESIGN.md 4.1), kept for comparison */
     SDPSR_FLAG_SYTRD_ONE_LAUNCH = 1u << 14,
     /* A/B: every host wait of the loop is a wait for the stream and every verdict is read where it arises (rounds 1-4) --
-       no return on the label pass's report, no verdicts deferred to the reduction's later waits (round 5).  Same
-       partition, iterations and dimension trajectory either way. */
+       no return on the label pass's report, no speculated confirm round, no verdicts deferred to the reduction's later
+       waits (round 5).  Same partition, iterations, dimension trajectory and random draws either way. */
     SDPSR_FLAG_WAIT_FOR_EVERY_VERDICT = 1u << 15
 };
 
@@ -218,7 +218,10 @@ int sdpsr_wait_stream(sdpsr_ctx* ctx, void* hip_stream);
           initial partition is formed from the lower triangle.
    A wrong hint is the caller's error (the result is then the partition of the mirrored lower triangle). */
 int sdpsr_hint_symmetric_basis(sdpsr_ctx* ctx, int yes);
-/* Reseed (tests; independent restarts use distinct seeds per rank). */
+/* Reseed (tests; independent restarts use distinct seeds per rank).  A call's random draws depend only on the seed
+   position (the seed and the draws made since sdpsr_set_seed), the inputs and the opts -- never on earlier calls on
+   the ctx: a guess the library takes from its history (the speculated confirm round) changes the work done, not the
+   draws, and a reduction repeated after a wrong guess starts again from the seed position of its entry. */
 int sdpsr_set_seed(sdpsr_ctx* ctx, uint64_t seed);
 /* Dimension trajectory of the last sdpsr_admissible_subspace call on ctx -- what the reference logs under
    verbose (src/partitions.jl:150,156,187-188): dims[0] = dim(S) after S = refine!(Part(CL), Part(X0L)),

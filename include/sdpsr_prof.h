@@ -40,6 +40,10 @@ int sdpsr_profile_clock(sdpsr_ctx* ctx, int kind, int64_t n, int64_t aux, int re
 /* Host waits for a stream of ctx since its creation (every wait of the library goes through one function): the host round
    trips of a reduction = the difference around it. */
 int sdpsr_profile_host_waits(sdpsr_ctx* ctx, uint64_t* out);
+/* Counters of ctx (restart 0) or of batch restart `restart` (as sdpsr_batch_block_sizes): out[0] = random draws so far
+   (the ctx's stream position, reset by sdpsr_set_seed), out[1] = squares the loop has launched, out[2] = of those, squares
+   launched speculatively, out[3] = the symmetric-basis hint bits the last admissible_subspace run used. */
+int sdpsr_profile_loop_counts(sdpsr_ctx* ctx, int32_t restart, uint64_t* out);
 /* Stage 2 of a two-stage tridiagonalisation (band -> tridiagonal by Householder bulge chasing, one workgroup per sweep,
    hand-offs through progress words), built to be measured: A_host n x n dense symmetric with bandwidth b (16, 32 or 64),
    d_host (n), e_host (n - 1) the tridiagonal result, out[0] = kernel milliseconds, out[1] = 1 if the chase gave up. */

@@ -178,6 +178,8 @@ def load_prof_library():
     lib.sdpsr_profile_band_reduce.argtypes = [vp, i64, C.c_int, vp, C.POINTER(C.c_double)]
     lib.sdpsr_profile_host_waits.restype = C.c_int
     lib.sdpsr_profile_host_waits.argtypes = [vp, C.POINTER(C.c_uint64)]
+    lib.sdpsr_profile_loop_counts.restype = C.c_int
+    lib.sdpsr_profile_loop_counts.argtypes = [vp, C.c_int32, C.POINTER(C.c_uint64)]
     lib.sdpsr_profile_sytrd_graphs.restype = C.c_int
     lib.sdpsr_profile_sytrd_graphs.argtypes = [vp, C.POINTER(C.c_double)]
     _prof = lib

@@ -46,6 +46,8 @@ class NotConverged(SdpsrError):
     pass
 
 
+BAD_STATE = 10  # SDPSR_BAD_STATE
+
 _EXC = {1: InvalidDecompositionField, 2: NumericalInconsistency, 3: DimensionMismatch,
         4: LabelOverflow, 9: NotConverged}
 
@@ -507,8 +509,9 @@ class Problem:
             rc = lib.sdpsr_problem_reduce_batch(ctx._h, self._h, R, C.cast(sd, C.c_void_p), atol, epsilon, C.cast(pP, C.c_void_p), dd, it, nb, ssq, ss,
                                                 C.cast(pb, C.c_void_p) if pb is not None else None, caps, st, L.MEM_HOST)
             # the call's own status counts unless some restart reports one: a failure before the restarts start (bad
-            # arguments, memory) must not read as R clean restarts of dimension 0
-            if rc != 0 and all(x in (0, -1) for x in st):
+            # arguments, memory) must not read as R clean restarts of dimension 0.  The library presets every status to
+            # BAD_STATE before anything can fail; -1 is this binding's own sentinel.
+            if rc != 0 and (all(x in (-1, BAD_STATE) for x in st) or all(x in (0, -1) for x in st)):
                 ctx.check(rc)
             return Ps, dd, it, nb, ssq, ss, st
 
@@ -517,9 +520,14 @@ class Problem:
         Ps, dd, it, nb, ssq, ss, st = call(bl)
         out = []
         for i in range(R):
-            out.append({"status": int(st[i]), "P": Partition(int(dd[i]), Ps[i].reshape(n, n, order="F")), "iterations": int(it[i]),
-                        "nblocks": int(nb[i]), "sum_sq": int(ssq[i]), "sum_s": int(ss[i]),
-                        "blks": bl[i][:dd[i] * ssq[i]].reshape(dd[i], ssq[i]) if st[i] == 0 else None})
+            status, blks = int(st[i]), None
+            if status == 0:
+                if dd[i] * ssq[i] <= bl[i].size:
+                    blks = bl[i][:dd[i] * ssq[i]].reshape(dd[i], ssq[i])
+                else:  # the images pass ran another reduction than the sizes pass: its images were never written
+                    status = BAD_STATE
+            out.append({"status": status, "P": Partition(int(dd[i]), Ps[i].reshape(n, n, order="F")), "iterations": int(it[i]),
+                        "nblocks": int(nb[i]), "sum_sq": int(ssq[i]), "sum_s": int(ss[i]), "blks": blks})
         return out
 
 

@@ -1770,10 +1770,14 @@ __global__ void refine_label_kernel(int64_t len, const uint32_t* slot, uint32_t*
     // the last kernel of a refinement hands the counters (inserted, overflow flag, classes) to the host itself: a
     // store into pinned host memory instead of a separate 16-byte copy launch (~5 us + a launch gap per refinement)
     // ... and then the stamp: the host may go on as soon as it sees it (ctx_wait_word), the rest of this pass is behind it in the stream
-    if (host_counters && blockIdx.x == 0 && threadIdx.x < 64) {
-        if (threadIdx.x < 3) host_counters[threadIdx.x] = counters[threadIdx.x];
+    // (one thread writes all three and then the stamp: ctx_wait_word reads every counter as soon as the stamp lands, and
+    // only program order -- not the lockstep of a wave -- puts the counters before it)
+    if (host_counters && blockIdx.x == 0 && threadIdx.x == 0) {
+        host_counters[0] = counters[0];
+        host_counters[1] = counters[1];
+        host_counters[2] = counters[2];
         __threadfence_system();
-        if (threadIdx.x == 0) host_counters[3] = host_seq;
+        host_counters[3] = host_seq;
     }
     if (counters[1] || (expect_small && counters[0] > SMALL_K)) return;
     // four consecutive entries per thread and trip: one 16-byte load, four gathers in flight together, one 16-byte store (one

@@ -27,6 +27,7 @@ int admissible_subspace_impl(sdpsr_ctx* c, int64_t n, const double* CL, const do
     CHECK_CTX(c);
     const int hint = c->hint_symmetric_basis;  // one call only, whatever happens below
     c->hint_symmetric_basis = 0;
+    c->hint_used = hint;
     c->adm_dims.clear();
     if (!CL || !X0L || !P_out || !dim_out || n < 1 || r < 0 || (r > 0 && !U) || !(atol > 0))
         return ctx_fail(c, SDPSR_BAD_ARGUMENT, "bad arguments");
@@ -194,6 +195,7 @@ int admissible_subspace_impl(sdpsr_ctx* c, int64_t n, const double* CL, const do
                 if (jl2) launch_gather_i8_sym_packed(s, n, ld, T, Lp, key2, (int8_t*)Xp, current);
                 else launch_gather_i8(s, n, ld, T, L, key2, (int8_t*)Xp, current);
                 launch_gemm_tn_i8_sym(s, ld, ld, (const int8_t*)Xp, ld, (int32_t*)Cp, ld, T, ld * ld, ld * ld, zero_flag, c->num_cus, c->opts.square_kernel);
+                ++c->squares_launched;
                 tm.end();
                 tm.begin(SDPSR_T_REFINE);
                 SigSource qj;
@@ -232,7 +234,8 @@ int admissible_subspace_impl(sdpsr_ctx* c, int64_t n, const double* CL, const do
                     hv += 128;
                     // (inside sdpsr_jordan_reduce, on a guess that the input is closed: both verdicts go to words nobody else writes
                     // and are read by the reduction behind its next host waits, not here)
-                    const bool guess = it == 1 && !confirming && confirm_left > 0 && c->predict_closed && c->predict_n == n;
+                    // (no guess under SDPSR_FLAG_WAIT_FOR_EVERY_VERDICT: the control flow of rounds 1-4)
+                    const bool guess = it == 1 && !confirming && confirm_left > 0 && c->predict_closed && c->predict_n == n && early_ok;
                     const bool defer = guess && c->allow_deferred_verdict && c->pinned_small != nullptr;
                     if (defer) hv = c->pinned_small + 8;
                     if (launch_verify_no_split(s, qv, current, first, vref, hv)) {  // the verdict is stored straight into pinned host memory
@@ -240,7 +243,9 @@ int admissible_subspace_impl(sdpsr_ctx* c, int64_t n, const double* CL, const do
                         // built for) will be closed again: the confirm round -- a fresh square into its own buffers and its
                         // verify pass -- is enqueued behind the first verdict's kernels and both verdicts come back with
                         // one host wait instead of two.  A wrong guess costs the discarded square; the result is the same
-                        // either way (the first verdict decides first, exactly as without the guess).
+                        // either way (the first verdict decides first, exactly as without the guess).  The speculative square
+                        // draws the key the confirm round would draw; a square that does not serve as a confirm round gives its
+                        // key back, so that the call's later draws are those of a call that took no guess.
                         bool spec = false;
                         uint32_t* hv2 = hv + 16;
                         if (guess) {
@@ -251,6 +256,8 @@ int admissible_subspace_impl(sdpsr_ctx* c, int64_t n, const double* CL, const do
                                 const uint64_t key3 = next_key(c);
                                 launch_gather_i8_sym_packed(s, n, ld, T, Lp, key3, (int8_t*)Xs, current);
                                 launch_gemm_tn_i8_sym(s, ld, ld, (const int8_t*)Xs, ld, (int32_t*)Cs, ld, T, ld * ld, ld * ld, zero_flag, c->num_cus, c->opts.square_kernel);
+                                ++c->squares_launched;
+                                ++c->squares_speculative;
                                 SigSource q2 = qj;
                                 q2.kind = SIG_CHAN_I32;
                                 q2.C = Cs;
@@ -267,6 +274,7 @@ int admissible_subspace_impl(sdpsr_ctx* c, int64_t n, const double* CL, const do
                             HIP_TRY(c, hipGetLastError());
                             unchanged = hv[0] == 0;
                             spec_confirmed = spec && unchanged && hv2[0] == 0;
+                            if (spec && !spec_confirmed) --c->stream_counter;  // (a confirm round that follows redraws this key)
                         }
                     }
                 }
@@ -279,7 +287,10 @@ int admissible_subspace_impl(sdpsr_ctx* c, int64_t n, const double* CL, const do
                 tm.collect();
                 if (dj == current && confirm_left > 0) {  // extra independent draws before stopping
                     --confirm_left;
-                    if (spec_confirmed) break;  // the extra draw has been made and looked at already
+                    if (spec_confirmed) {  // the confirm round just scheduled is the speculative square, made and looked at already
+                        if (confirm_left == 0) break;
+                        --confirm_left;  // ... and it found nothing either: the next confirm round
+                    }
                     confirming = true;
                     continue;  // (same projected element, a fresh square: the projection did not refine either)
                 }
@@ -427,6 +438,7 @@ int admissible_subspace_impl(sdpsr_ctx* c, int64_t n, const double* CL, const do
                                    (double*)Cp, ld, 1, 0, 0, 0);
                 launch_sig_f64_rounded(s, n, ld, L, (const double*)Cp, atol, scale, sig);
             }
+            ++c->squares_launched;  // (one square of T channels, whichever mode)
             tm.end();
             tm.begin(SDPSR_T_REFINE);
             if (int_mode && labels_sym) {

@@ -162,6 +162,17 @@ extern "C" int sdpsr_profile_host_waits(sdpsr_ctx* c, uint64_t* out) {
     return SDPSR_OK;
 }
 
+extern "C" int sdpsr_profile_loop_counts(sdpsr_ctx* c, int32_t restart, uint64_t* out) {
+    CHECK_CTX(c);
+    if (!out || restart < 0 || restart > (int32_t)c->batch_children.size()) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "bad arguments");
+    const sdpsr_ctx* ci = restart == 0 ? c : c->batch_children[restart - 1];
+    out[0] = ci->stream_counter;
+    out[1] = ci->squares_launched;
+    out[2] = ci->squares_speculative;
+    out[3] = (uint64_t)ci->hint_used;
+    return SDPSR_OK;
+}
+
 extern "C" int sdpsr_profile_kernel(sdpsr_ctx* c, int kind, int64_t n, int64_t aux, int reps,
                                     double* ms_per_launch) {
     CHECK_CTX(c);

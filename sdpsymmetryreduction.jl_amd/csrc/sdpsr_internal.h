@@ -80,6 +80,10 @@ struct sdpsr_ctx {
     // the first iteration -- the next call of that order runs the confirm round speculatively behind the first verify pass
     bool predict_closed = false;
     int64_t predict_n = 0;
+    // what the loop has done on this ctx (sdpsr_profile_loop_counts): squares launched by admissible_subspace, of those the
+    // speculative ones, and the symmetric-basis hint bits its last run used
+    uint64_t squares_launched = 0, squares_speculative = 0;
+    int hint_used = 0;
     uint64_t host_waits = 0;                 // host waits for one of this ctx's streams (ctx_sync_stream); sdpsr_profile_host_waits
     uint32_t report_seq = 0;                 // stamps of the label passes' reports to pinned memory (ctx_wait_word)
     // sdpsr_jordan_reduce: the loop may leave the verdicts of its LAST verify passes (first iteration of an input predicted
