@@ -446,6 +446,12 @@ int sdpsr_gemm_tn_f64(sdpsr_ctx* c, int64_t m, int64_t n, int64_t k, const doubl
     double* Bp = (double*)ctx_buf(c, "g_bp", (size_t)kp * np * 8);
     double* Cp = (double*)ctx_buf(c, "g_cp", (size_t)mp * np * 8);
     if (st || !Ap || !Bp || !Cp) return st ? st : SDPSR_OUT_OF_MEMORY;
+    // host C: the whole ldc x n array travels back, so it starts as the caller's C -- rows m .. ldc - 1 are not
+    // the product's to write
+    if (mem != SDPSR_MEM_DEVICE && ldc > m) {
+        HIP_TRY(c, hipMemcpyAsync(dC, C, (size_t)ldc * n * 8, hipMemcpyHostToDevice, c->stream));
+        c->h2d_bytes += (size_t)ldc * n * 8;
+    }
     HIP_TRY(c, hipMemsetAsync(Ap, 0, (size_t)kp * mp * 8, c->stream));
     HIP_TRY(c, hipMemsetAsync(Bp, 0, (size_t)kp * np * 8, c->stream));
     HIP_TRY(c, hipMemcpy2DAsync(Ap, kp * 8, dA, lda * 8, k * 8, m, hipMemcpyDeviceToDevice, c->stream));

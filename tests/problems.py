@@ -251,6 +251,13 @@ def cycle_adjacency(m):
     return (np.minimum(d, m - d) == 1).astype(np.float64)
 
 
+def directed_cycle_adjacency(m):
+    """M[i, (i + 1) % m] = 1: the shift S of Z_m, whose powers S^0 .. S^(m-1) partition the m x m entries."""
+    M = np.zeros((m, m))
+    M[np.arange(m), (np.arange(m) + 1) % m] = 1.0
+    return M
+
+
 def theta_prime_product_problem(base_adj, base_labels, k, seed=0):
     """theta' SDP (test/sd_problems.jl:22-26 form) of the Cartesian product ``base [] K_k`` under a
     seeded vertex permutation, together with the canonical labels of the product scheme
@@ -265,3 +272,20 @@ def theta_prime_product_problem(base_adj, base_labels, k, seed=0):
     L, d = canonical_labels(L)
     C, A, b = theta_prime_problem(adj)
     return C, A, b, L, d
+
+
+def bench_instance(name, er7_labels):
+    """The N = 4096 / 4104 instances bench.py times, with the partition the reduction must reach.
+    ``er7_labels`` is the 57 x 57 ER(7) closure (golden fixture ``er7_P``).
+    Returns (C, A, b, labels, dim, block sizes, iterations of the default int8 loop)."""
+    if name == "closed_scheme":
+        L, d = synthetic_jordan_partition(4096, seed=1)
+        C, A, b = partition_as_sdp(L, seed=1)
+        return C, A, b, L, d, [1] * d, 1
+    if name == "theta_c32xk128":
+        C, A, b, L, d = theta_prime_product_problem(cycle_adjacency(32), symmetric_circulant_labels(32), 128, seed=1)
+        return C, A, b, L, d, [1] * d, 5
+    if name == "theta_er7xk72":
+        C, A, b, L, d = theta_prime_product_problem(er_graph_adjacency(7), np.asarray(er7_labels, dtype=np.int64), 72, seed=1)
+        return C, A, b, L, d, [2, 2, 2, 2, 3] * 2, 5
+    raise ValueError(name)

@@ -641,8 +641,10 @@ def test_admissible_without_constraints_and_bad_arguments(pkg, problems, oracle,
 
 @pytest.mark.gpu
 def test_admissible_nonsymmetric_labels_square_literally(pkg, oracle, gpu_ctx):
-    """Non-symmetric input: the random square is X*X as in src/partitions.jl:172 (the left operand
-    is gathered from the transposed labels), not the symmetric shortcut X'X of the Jordan case."""
+    """Non-symmetric C through admissible_subspace: the setup symmetrises it (src/partitions.jl:129-134),
+    so the loop's labels are symmetric here.  The loop on non-symmetric labels (X*X literally, the left
+    operand gathered from the transposed labels) is covered by test_gpu_squares.py, which hands it a
+    non-symmetric C_L directly."""
     rng = np.random.default_rng(5)
     for n in (9, 16):
         M = rng.integers(0, 3, size=(n, n))

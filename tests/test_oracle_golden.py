@@ -129,6 +129,24 @@ def test_synthetic_scheme_is_fixed_point(oracle, problems, golden):
         assert np.array_equal(P.matrix, Ls)
 
 
+@pytest.mark.parametrize("n", [16, 37, 64])
+def test_directed_cycle_closure_in_closed_form(oracle, problems, n):
+    """C = the directed n-cycle S, no constraints.  Through admissible_subspace(C, A, b) the setup symmetrises C
+    (src/partitions.jl:129-134), C_L = (S + S')/2, and the closure is the symmetric circulant scheme: n // 2 + 1
+    classes, label min((i - j) mod n, (j - i) mod n) + 1.  Handed to the loop as it is (C_L = S, X0_L = 0, no basis),
+    S stays non-symmetric: squares of circulants are circulants and generate every shift S^k, so the closure is all
+    n circulant classes, label ((i - j) mod n) + 1 (column 0 meets them in the order S^0, S^(n-1), ..., S^1)."""
+    S = problems.directed_cycle_adjacency(n)
+    i, j = np.indices((n, n))
+    P = oracle.admissible_subspace(S.ravel(order="F"), np.zeros((0, n * n)), np.zeros(0), rng=np.random.default_rng(n))
+    assert P.nparts == n // 2 + 1
+    assert np.array_equal(P.matrix, np.minimum((i - j) % n, (j - i) % n) + 1)
+    P = oracle.admissible_subspace(None, None, None, rng=np.random.default_rng(n),
+                                   setup=(n, np.zeros((n * n, 0)), S, np.zeros((n, n))))
+    assert P.nparts == n
+    assert np.array_equal(P.matrix, (i - j) % n + 1)
+
+
 def test_basis_image_fast_equals_literal(oracle, problems, golden):
     P = oracle.partition_from_labels(golden["er5_P"].astype(np.int64))
     Q = oracle.diagonalize(P, atol=oracle.RTOL_DEFAULT, rng=np.random.default_rng(1))
