@@ -333,6 +333,40 @@ int sdpsr_admissible_subspace_dense(sdpsr_ctx* ctx, int64_t n, int64_t m, const 
                                     uint32_t* P_out, int64_t* dim_out, int32_t* iters_out,
                                     double* phase_ms, int mem_out);
 
+/* ---- setup from a sparse constraint matrix, src/partitions.jl:117-142, src/utils.jl:58-66 ------------------
+   The setup stage of admissible_subspace (qr(A') at :124, C_L at :129-134, Krylov.craig's min-norm x0 and X0_L at
+   :137-142, projL of src/utils.jl:58-66) for an A given as CSR -- the form of every SDP a user builds (the reference's
+   own QAP relaxation, test/sd_problems.jl:63-92, is (2n+1) x n^4 with 2n + 1 + n^4 + 2 n^3 nonzeros).
+     rowptr[m + 1], colind[nnz], val[nnz], b[m], C[n^2]: host memory.  colind = the column-major linear index into the
+       n x n matrix (the reference's vec), index_base 0 or 1: with 1 a Julia caller passes sparse(A')'s colptr / rowval /
+       nzval unchanged (the CSC arrays of A' are the CSR arrays of A).  Unsorted columns, duplicates (summed, in input
+       order) and explicit zeros are accepted.  m = 0: L is the whole space.
+     A bad rowptr[0], a non-monotone rowptr, an index outside [0, n^2) after the base is subtracted or a non-finite
+     value: SDPSR_BAD_ARGUMENT before any kernel runs; n^2 x m doubles that do not fit the device: SDPSR_OUT_OF_MEMORY.
+     The ctx stays usable after either.
+   On the device: A's rows are densified into the columns of one n^2 x m buffer that becomes U in place; G = A A' (one
+   tall-skinny Gram kernel, any m) decides by a pivoted Cholesky on the host: every pivot's residual norm >= 1e-4 of
+   the largest row norm -> CholeskyQR2 (two Gram passes, two in-place triangular right-multiplications, two host
+   waits), else the pivoted MGS of sdpsr_admissible_subspace_dense (rank decided at 1e-12 of the largest row norm).
+   sdpsr_admissible_setup_csr: CL, X0L (n^2, column-major) and U (n^2 x r, column-major; capacity n^2 x m) in memory
+     space mem_out; *r_out = r; *hint_out = the bits of sdpsr_hint_symmetric_basis the library has proved (3 when every
+     row of A is a symmetric n x n matrix bit for bit -- every kernel of the stage does the same arithmetic for entry
+     (i, j) as for (j, i) --, else 0); *info_out = sdpsr_setup_path (may be NULL).
+   sdpsr_admissible_subspace_csr: the same stage, then the loop of sdpsr_admissible_subspace with those hint bits --
+     the CSR twin of sdpsr_admissible_subspace_dense.  P_out is in mem_out. */
+typedef enum sdpsr_setup_path {
+    SDPSR_SETUP_NO_CONSTRAINTS = 0, /* m = 0 */
+    SDPSR_SETUP_CHOLESKY_QR2 = 1,   /* rows clearly independent: CholeskyQR2 */
+    SDPSR_SETUP_MGS = 2             /* otherwise: pivoted modified Gram-Schmidt */
+} sdpsr_setup_path;
+int sdpsr_admissible_setup_csr(sdpsr_ctx* ctx, int64_t n, int64_t m, const int64_t* rowptr, const int64_t* colind,
+                               const double* val, int index_base, const double* b, const double* C, double atol,
+                               double* CL, double* X0L, double* U, int64_t* r_out, int* hint_out, int32_t* info_out,
+                               int mem_out);
+int sdpsr_admissible_subspace_csr(sdpsr_ctx* ctx, int64_t n, int64_t m, const int64_t* rowptr, const int64_t* colind,
+                                  const double* val, int index_base, const double* b, const double* C, double atol,
+                                  uint32_t* P_out, int64_t* dim_out, int32_t* iters_out, double* phase_ms, int mem_out);
+
 /* ---- desymmetrize(P) / unSymmetrize, src/partitions.jl:197-223, src/compat.jl:70 -------------- */
 /* WL-type refinement with products X*Y of two independent random elements until the dimension
    stalls: P (n x n labels) is refined in place, *dim updated, *iters (may be NULL) = rounds.

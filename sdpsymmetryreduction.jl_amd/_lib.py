@@ -17,6 +17,7 @@ MEM_HOST, MEM_DEVICE = 0, 1
 SQUARE_AUTO, SQUARE_I8, SQUARE_F32, SQUARE_F64 = 0, 1, 2, 3
 T_TOTAL, T_PROJECT, T_SQUARE, T_REFINE, T_EIGEN, T_ISO, T_IRRED, T_IMAGE, T_COUNT = range(9)
 ROUND_NEAREST, ROUND_TRUNC = 0, 1
+SETUP_NO_CONSTRAINTS, SETUP_CHOLESKY_QR2, SETUP_MGS = 0, 1, 2  # sdpsr_setup_path
 # sdpsr_opts.flags
 FLAG_SEPARATE_REFINEMENTS = 1 << 0
 FLAG_FRESH_IRREDUCIBLE_ELEMENT = 1 << 1
@@ -120,6 +121,9 @@ def load_library():
         "sdpsr_gemm_tn_f64": (C.c_int, [vp, i64, i64, i64, vp, i64, vp, i64, vp, i64, C.c_int]),
         "sdpsr_admissible_subspace": (C.c_int, [vp, i64, vp, vp, vp, i64, dbl, vp, pi64, pi32, vp, C.c_int]),
         "sdpsr_admissible_subspace_dense": (C.c_int, [vp, i64, i64, vp, vp, vp, dbl, vp, pi64, pi32, vp, C.c_int]),
+        "sdpsr_admissible_setup_csr": (C.c_int, [vp, i64, i64, vp, vp, vp, C.c_int, vp, vp, dbl, vp, vp, vp, pi64, C.POINTER(C.c_int),
+                                                 pi32, C.c_int]),
+        "sdpsr_admissible_subspace_csr": (C.c_int, [vp, i64, i64, vp, vp, vp, C.c_int, vp, vp, dbl, vp, pi64, pi32, vp, C.c_int]),
         "sdpsr_jordan_reduce": (C.c_int, [vp, i64, vp, vp, vp, i64, dbl, dbl, vp, pi64, pi32, pi32, pi64, pi64, vp, i64, vp, i64, vp, C.c_int]),
         "sdpsr_jordan_reduce_batch": (C.c_int, [vp, C.c_int32, vp, i64, vp, vp, vp, i64, dbl, dbl, vp, pi64, pi32, pi32, pi64, pi64, vp, vp, pi32,
                                                 C.c_int]),

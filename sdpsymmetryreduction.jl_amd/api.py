@@ -352,8 +352,9 @@ class Setup(tuple):
     (CL and X0L are exactly symmetric, as the reference's setup makes them).  ``hint`` is the bit
     mask for ``sdpsr_hint_symmetric_basis``."""
 
-    def __new__(cls, items, basis_symmetric=False, inputs_symmetric=False):
+    def __new__(cls, items, basis_symmetric=False, inputs_symmetric=False, info=None):
         t = super().__new__(cls, items)
+        t.info = info  # admissible_setup_csr: which orthogonalisation ran (_lib.SETUP_*); None for the host setup
         t.basis_symmetric = bool(basis_symmetric)
         t.inputs_symmetric = bool(inputs_symmetric)
         t.hint = (1 if basis_symmetric else 0) | (2 if inputs_symmetric else 0)
@@ -396,13 +397,151 @@ def _admissible_subspace_device_setup(C_, A, b, atol, ctx, verbose):
     return out
 
 
+# ---------------------------------------------------------------------------
+# setup from a sparse A (CSR), src/partitions.jl:117-142 on the device
+# ---------------------------------------------------------------------------
+def csr_arrays(A, len_, index_base=0):
+    """Canonical 0-based CSR arrays (rowptr, colind, val) -- int64, int64, float64 -- of the m x ``len_`` constraint
+    matrix ``A``: each row sorted by column, duplicates summed in input order, zeros dropped.  ``A`` is a SciPy sparse
+    matrix in any format, a dense 2-D array, or a tuple ``(rowptr, colind, val)`` of CSR arrays with ``index_base`` 0 or 1
+    (a Julia caller's ``sparse(A')`` colptr / rowval / nzval).  Malformed input raises ValueError."""
+    len_ = int(len_)
+    if isinstance(A, tuple):
+        if len(A) != 3:
+            raise ValueError("CSR input is a tuple (rowptr, colind, val)")
+        if index_base not in (0, 1):
+            raise ValueError("index_base must be 0 or 1")
+        rowptr = np.asarray(A[0])
+        colind = np.asarray(A[1])
+        val = np.asarray(A[2], dtype=np.float64).ravel()
+        if rowptr.ndim != 1 or rowptr.size < 1 or not np.issubdtype(rowptr.dtype, np.integer):
+            raise ValueError("rowptr must be a non-empty integer vector")
+        if colind.ndim != 1 or (colind.size and not np.issubdtype(colind.dtype, np.integer)):
+            raise ValueError("colind must be an integer vector")
+        rowptr = rowptr.astype(np.int64)
+        colind = colind.astype(np.int64)
+        if rowptr[0] != index_base:
+            raise ValueError(f"rowptr[0] = {rowptr[0]} != index_base {index_base}")
+        if np.any(np.diff(rowptr) < 0):
+            raise ValueError("rowptr is not monotone")
+        nnz = int(rowptr[-1] - index_base)
+        if colind.size != nnz or val.size != nnz:
+            raise ValueError(f"rowptr says {nnz} entries, colind has {colind.size}, val {val.size}")
+        m = rowptr.size - 1
+        rows = np.repeat(np.arange(m, dtype=np.int64), np.diff(rowptr))
+        cols = colind - index_base
+    elif hasattr(A, "tocsr"):  # SciPy: its compiled canonicalisation (O(nnz) per row sort, duplicates summed, zeros dropped)
+        if A.ndim != 2 or A.shape[1] != len_:
+            raise ValueError(f"A has shape {A.shape}, expected (m, {len_})")
+        Ac = A.tocsr(copy=True).astype(np.float64)
+        if not np.all(np.isfinite(Ac.data)):
+            raise ValueError("non-finite value in A")
+        Ac.sum_duplicates()
+        Ac.eliminate_zeros()
+        Ac.sort_indices()
+        if not np.all(np.isfinite(Ac.data)):
+            raise ValueError("duplicate entries sum to a non-finite value")
+        return (Ac.indptr.astype(np.int64), Ac.indices.astype(np.int64), np.ascontiguousarray(Ac.data, dtype=np.float64))
+    else:
+        Ad = np.asarray(A, dtype=np.float64)
+        if Ad.ndim != 2 or Ad.shape[1] != len_:
+            raise ValueError(f"A has shape {Ad.shape}, expected (m, {len_})")
+        m = Ad.shape[0]
+        rows, cols = np.nonzero(Ad)
+        rows, cols = rows.astype(np.int64), cols.astype(np.int64)
+        val = Ad[rows, cols]
+    if cols.size and (cols.min() < 0 or cols.max() >= len_):
+        raise ValueError(f"column index outside [0, {len_})")
+    if not np.all(np.isfinite(val)):
+        raise ValueError("non-finite value in A")
+    order = np.lexsort((cols, rows))  # stable: duplicates keep their input order
+    rows, cols, val = rows[order], cols[order], val[order]
+    if cols.size:
+        first = np.ones(cols.size, dtype=bool)
+        first[1:] = (rows[1:] != rows[:-1]) | (cols[1:] != cols[:-1])
+        starts = np.flatnonzero(first)
+        val = np.add.reduceat(val, starts)  # left to right within a run
+        rows, cols = rows[starts], cols[starts]
+        if not np.all(np.isfinite(val)):
+            raise ValueError("duplicate entries sum to a non-finite value")
+        keep = val != 0
+        rows, cols, val = rows[keep], cols[keep], val[keep]
+    rowptr = np.zeros(m + 1, dtype=np.int64)
+    np.cumsum(np.bincount(rows, minlength=m), out=rowptr[1:])
+    return rowptr, np.ascontiguousarray(cols, dtype=np.int64), np.ascontiguousarray(val, dtype=np.float64)
+
+
+def _csr_inputs(C_, A, b, index_base):
+    c = np.asarray(C_.todense()).reshape(-1) if hasattr(C_, "todense") else np.asarray(C_, dtype=np.float64).reshape(-1)
+    c = np.ascontiguousarray(c, dtype=np.float64)
+    n = math.isqrt(len(c))
+    if n * n != len(c):  # @assert n^2 == length(C), :118
+        raise ValueError("length(C) is not a perfect square")
+    rowptr, colind, val = csr_arrays(A, n * n, index_base)
+    m = rowptr.size - 1
+    bb = np.ascontiguousarray(np.asarray(b, dtype=np.float64).reshape(-1))
+    if bb.size != m:
+        raise ValueError(f"length(b) = {bb.size} != {m} rows of A")
+    if not np.all(np.isfinite(bb)):
+        raise ValueError("non-finite value in b")
+    return n, c, m, rowptr, colind, val, bb
+
+
+def admissible_setup_csr(C_, A, b, atol=RTOL_DEFAULT, ctx=None, index_base=0):
+    """Setup stage of ``admissible_subspace`` (src/partitions.jl:117-142) on the DEVICE from a sparse ``A``
+    (``sdpsr_admissible_setup_csr``): A travels as CSR, C_L, X0_L and the orthonormal basis U stay in device memory.
+    ``A``: anything ``csr_arrays`` takes.  Returns a ``Setup`` of torch CUDA tensors ``(n, CL, X0L, U)`` (U: n^2 x r,
+    column-major) with ``.hint`` (the symmetry bits the library proved) and ``.info`` (``_lib.SETUP_*``: which
+    orthogonalisation ran); it goes to ``admissible_subspace(setup=...)``, ``Problem(setup=...)`` and
+    ``jordan_reduce_batch(setup=...)`` as it is."""
+    import torch
+    n, c, m, rowptr, colind, val, bb = _csr_inputs(C_, A, b, index_base)  # (ValueError before any library call)
+    ctx = _ctx(ctx)
+    dev = torch.device("cuda", ctx.device)
+    CL = torch.empty(n * n, dtype=torch.float64, device=dev)
+    X0L = torch.empty(n * n, dtype=torch.float64, device=dev)
+    Ubuf = torch.empty((m, n * n), dtype=torch.float64, device=dev)  # U = Ubuf.t(): column-major n^2 x m
+    r = C.c_int64(0)
+    hint = C.c_int(0)
+    info = C.c_int32(0)
+    ctx.wait_for(CL)
+    ctx.check(ctx._lib.sdpsr_admissible_setup_csr(ctx._h, n, m, _ptr(rowptr), _ptr(colind), _ptr(val), 0, _ptr(bb), _ptr(c), float(atol),
+                                                  _ptr(CL), _ptr(X0L), _ptr(Ubuf) if m > 0 else None, C.byref(r), C.byref(hint),
+                                                  C.byref(info), L.MEM_DEVICE))
+    U = Ubuf.t()[:, :r.value]
+    return Setup((n, CL, X0L, U), bool(hint.value & 1), bool(hint.value & 2), info=int(info.value))
+
+
+def _admissible_subspace_csr(C_, A, b, atol, ctx, verbose):
+    """Whole ``admissible_subspace`` through ``sdpsr_admissible_subspace_csr``: A uploaded as CSR, the setup stage on
+    the device, then the loop."""
+    n, c, m, rowptr, colind, val, bb = _csr_inputs(C_, A, b, 0)
+    ctx = _ctx(ctx)
+    P = np.empty(n * n, dtype=np.uint32)
+    d = C.c_int64(0)
+    it = C.c_int32(0)
+    ms = (C.c_double * L.T_COUNT)()
+    ctx.check(ctx._lib.sdpsr_admissible_subspace_csr(ctx._h, n, m, _ptr(rowptr), _ptr(colind), _ptr(val), 0, _ptr(bb), _ptr(c), float(atol),
+                                                     _ptr(P), C.byref(d), C.byref(it), C.cast(ms, C.c_void_p), L.MEM_HOST))
+    if verbose:
+        print(f"[sdpsr] admissible subspace (CSR setup): dim {d.value} after {it.value} iterations, loop {ms[L.T_TOTAL]:.3f} ms")
+    out = Partition(d.value, P.reshape(n, n, order="F"))
+    out.iterations = it.value
+    out.phase_ms = list(ms)
+    out.dims = ctx.dimension_trajectory()
+    return out
+
+
 def admissible_subspace(C_, A, b, atol=RTOL_DEFAULT, ctx=None, verbose=False, setup=None,
-                        return_info=False, host_setup=False):
+                        return_info=False, host_setup=False, csr_setup=False):
     """``admissible_subspace(C, A, b; verbose, atol)`` (src/partitions.jl:77-190).
 
     By default the setup stage runs on the device too (dense copy of ``A``, at most 4 GiB);
     ``host_setup=True`` (or a precomputed ``setup``) uses the NumPy/SciPy setup, which is also the
-    path for very large sparse ``A``."""
+    path for very large sparse ``A``.  ``csr_setup=True`` (opt-in) sends ``A`` as CSR and runs the setup
+    stage on the device from it (``sdpsr_admissible_subspace_csr``): no dense copy of ``A`` anywhere."""
+    if setup is None and csr_setup and not host_setup:
+        return _admissible_subspace_csr(C_, A, b, atol, ctx, verbose)
     ctx = _ctx(ctx)
     if setup is None and not host_setup and A is not None:
         m_rows = A.shape[0]
@@ -457,10 +596,18 @@ class Problem:
         self.n, CL, X0L, U = setup
         self.r = U.shape[1]
         self.atol = atol
-        Uf = np.asfortranarray(U) if self.r else None
+        if _is_torch(CL):  # a device setup (admissible_setup_csr): read in place, copied device to device
+            ln = self.n * self.n
+            CL, X0L = CL.contiguous(), X0L.contiguous()
+            Uf = (U if U.stride() == (1, ln) else U.t().contiguous().t()) if self.r else None
+            mem = L.MEM_DEVICE
+            self.ctx.wait_for(CL, X0L, Uf if self.r else CL)
+        else:
+            Uf = np.asfortranarray(U) if self.r else None
+            mem = L.MEM_HOST
         h = C.c_void_p()
         self.ctx.check(self.ctx._lib.sdpsr_problem_create(self.ctx._h, self.n, _ptr(CL), _ptr(X0L), _ptr(Uf) if self.r else None, self.r,
-                                                          int(getattr(setup, "hint", 0)), L.MEM_HOST, C.byref(h)))
+                                                          int(getattr(setup, "hint", 0)), mem, C.byref(h)))
         self._h = h
 
     def close(self):

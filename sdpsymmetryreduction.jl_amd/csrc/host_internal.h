@@ -193,6 +193,13 @@ int refine_signatures(sdpsr_ctx* c, int64_t len, const uint64_t* sig, uint32_t* 
 int admissible_subspace_impl(sdpsr_ctx* c, int64_t n, const double* CL, const double* X0L, const double* U, int64_t r, double atol,
                              uint32_t* P_out, int64_t* dim_out, int32_t* iters_out, double* phase_ms, int mem, int mem_out,
                              bool final_sync, int* labels_sym_out);
+// loop.cpp: the setup stage of the dense entry in pieces, shared with the CSR entries (setup_csr.cpp)
+int setup_mgs(sdpsr_ctx* c, int64_t len, int64_t m, double* R, double* U, double* partial, int nblk, double* coef,
+              std::vector<std::vector<double>>& coeffs, std::vector<int64_t>& piv, int64_t* r_out);
+std::vector<double> min_norm_coefficients(int64_t r, const std::vector<int64_t>& piv, const std::vector<std::vector<double>>& coeffs,
+                                          const double* b);
+int setup_tail(sdpsr_ctx* c, int64_t n, int64_t r, const double* U, const std::vector<double>& y, double atol, double* v1, double* v2,
+               double* dCL, double* dX0, double* partial, int nblk, double* coef);
 // trusted_symmetric: the caller made the labels and knows; in_place (device labels only): no copy into ctx buffer
 // "bd_labels" -- P itself serves phase 2 (c->bd_labels_ext) until the caller ends that arrangement
 int block_diagonalize_impl(sdpsr_ctx* c, int64_t n, const uint32_t* P, int64_t d, double epsilon, int32_t* nblocks, int64_t* sum_sq,
@@ -277,6 +284,11 @@ void launch_fill_test_sig(hipStream_t s, int64_t len, int64_t nclasses, uint64_t
 size_t sytrd_workspace_doubles(int64_t n, int64_t ld);
 void launch_sytrd(sdpsr_ctx* c, int64_t n, double* A, int64_t ld, double* d, double* e, double* tau, double* ws);
 void launch_sytrd_symv_sweep(hipStream_t s, int64_t n, double* A, int64_t ld, double* d, double* e, double* tau, double* ws);
+// kernels_setup_csr.hip: the CSR setup stage (setup_csr.cpp)
+void launch_csr_densify(hipStream_t s, int64_t len, int64_t m, const int64_t* rowptr, const uint32_t* col, const double* val, double* W);
+size_t gram_tall_partial_doubles(int64_t len, int64_t m);
+void launch_gram_tall(hipStream_t s, int64_t len, int64_t m, const double* W, double* partials, double* host_G);
+void launch_apply_upper_inverse(hipStream_t s, int64_t len, int64_t m, double* W, const int32_t* piv, const double* Xrow);
 bool launch_small_syev(hipStream_t s, int64_t n, double* A, int64_t lda, double* w, double* Vtmp, int* info);
 
 }  // namespace sdpsr

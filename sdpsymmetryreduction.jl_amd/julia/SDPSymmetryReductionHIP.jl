@@ -119,20 +119,44 @@ function checksum(p::HIPPartition)
     return (out[1], out[2])
 end
 
-# ---- admissible_subspace: setup on the host (partitions.jl:117-142), loop on the device ----
+# ---- the setup stage (partitions.jl:117-142) of the entries below: C_L, X0_L, U and the hint bits ----
+# dense A: qr(A') on the host, as the reference does
+function _setup(C::AbstractVector{Float64}, A::AbstractMatrix{Float64}, b::AbstractVector{Float64}, atol)
+    n = isqrt(length(C)); @assert n^2 == length(C)
+    F = qr(A'); U = Matrix(F.Q)[:, 1:rank(A)]; proj(v) = U * (U' * v)
+    c = Vector(C); c .-= proj(c); SR._clamp_round!(c, atol=atol); SR._symmetrize!(c, n)
+    x0, _ = SR.Krylov.craig(A, b); SR._symmetrize!(x0, n); x0 = proj(x0); SR._clamp_round!(x0, atol=atol)
+    hint = 2 | (all(k -> (M = reshape(view(U, :, k), n, n); isapprox(M, M'; atol=1e-12, rtol=0)), 1:size(U, 2)) ? 1 : 0)
+    return n, c, x0, U, hint
+end
+# sparse A: on the device from CSR (sdpsr_admissible_setup_csr).  The CSC arrays of A' are the CSR arrays of A, so
+# sparse(A')'s colptr / rowval / nzval go in unchanged with index_base = 1.  No Q is formed: SPQR's Q of a sparse A'
+# lives in SPQR's row permutation, so Matrix(F.Q)[:, 1:rank(A)] is not a basis of rowspace(A) there.  The hint bits
+# are the ones the library proved.
+function _setup(C::AbstractVector{Float64}, A::SparseMatrixCSC{Float64}, b::AbstractVector{Float64}, atol)
+    n = isqrt(length(C)); @assert n^2 == length(C)
+    m = size(A, 1); @assert size(A, 2) == n^2 && length(b) == m
+    At = sparse(A')
+    c = Vector{Float64}(undef, n^2); x0 = Vector{Float64}(undef, n^2); U = Matrix{Float64}(undef, n^2, max(m, 1))
+    r = Ref{Int64}(0); hint = Ref{Cint}(0); info = Ref{Int32}(0); cx = ctx()
+    check(cx, ccall((:sdpsr_admissible_setup_csr, libsdpsr), Cint,
+                    (Ptr{Cvoid}, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Cint, Ptr{Float64}, Ptr{Float64}, Float64,
+                     Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Int64}, Ref{Cint}, Ref{Int32}, Cint),
+                    cx.handle, n, m, Vector{Int64}(At.colptr), Vector{Int64}(At.rowval), At.nzval, Cint(1), Vector{Float64}(b),
+                    Vector{Float64}(C), atol, c, x0, U, r, hint, info, MEM_HOST))
+    return n, c, x0, U[:, 1:r[]], Int(hint[])
+end
+
+# ---- admissible_subspace: setup on the host (partitions.jl:117-142; from CSR on the device for a sparse A), loop on
+# the device ----
 function SR.admissible_subspace(::Type{HIPPartition}, C::AbstractVector{T}, A::AbstractMatrix{T},
                                 b::AbstractVector{T}; verbose::Bool=false,
                                 atol=Base.rtoldefault(real(T))) where {T<:AbstractFloat}
-    n = isqrt(length(C)); @assert n^2 == length(C)
-    A′ = A'; F = qr(A′)
-    U = Matrix(F.Q)[:, 1:rank(A)]                      # orthonormal basis of rowspace(A)
-    proj(v) = U * (U' * v)
-    c = Vector(C); c .-= proj(c); SR._clamp_round!(c, atol=atol); SR._symmetrize!(c, n)
-    x0, _ = SR.Krylov.craig(A, b); SR._symmetrize!(x0, n); x0 = proj(x0); SR._clamp_round!(x0, atol=atol)
+    n, c, x0, U, hint = _setup(Vector{Float64}(C), A isa SparseMatrixCSC ? SparseMatrixCSC{Float64}(A) : Matrix{Float64}(A),
+                               Vector{Float64}(b), atol)
     P = Matrix{UInt32}(undef, n, n); d = Ref{Int64}(0); it = Ref{Int32}(0); cx = ctx()
     # symmetric basis matrices (the usual case): the projection step may work on the lower triangle
-    # (bit 1: c and x0 were symmetrised above)
-    hint = 2 | (all(k -> (M = reshape(view(U, :, k), n, n); isapprox(M, M'; atol=1e-12, rtol=0)), 1:size(U, 2)) ? 1 : 0)
+    # (bit 1: c and x0 were symmetrised)
     ccall((:sdpsr_hint_symmetric_basis, libsdpsr), Cint, (Ptr{Cvoid}, Cint), cx.handle, hint)
     check(cx, ccall((:sdpsr_admissible_subspace, libsdpsr), Cint,
                     (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Float64,
@@ -156,10 +180,7 @@ end
 # partition staying on the device; the images are fetched with sdpsr_block_images once their size is known ----
 function jordan_reduce(C::AbstractVector{Float64}, A::AbstractMatrix{Float64}, b::AbstractVector{Float64};
                        atol=Base.rtoldefault(Float64), epsilon=Base.rtoldefault(Float64))
-    n = isqrt(length(C)); @assert n^2 == length(C)
-    F = qr(A'); U = Matrix(F.Q)[:, 1:rank(A)]; proj(v) = U * (U' * v)
-    c = Vector(C); c .-= proj(c); SR._clamp_round!(c, atol=atol); SR._symmetrize!(c, n)
-    x0, _ = SR.Krylov.craig(A, b); SR._symmetrize!(x0, n); x0 = proj(x0); SR._clamp_round!(x0, atol=atol)
+    n, c, x0, U, _ = _setup(C, A, b, atol)
     P = Matrix{UInt32}(undef, n, n); d = Ref{Int64}(0); it = Ref{Int32}(0); cx = ctx()
     nb = Ref{Int32}(0); ssq = Ref{Int64}(0); ss = Ref{Int64}(0)
     check(cx, ccall((:sdpsr_jordan_reduce, libsdpsr), Cint,
@@ -247,15 +268,11 @@ end
 function jordan_reduce_batch(C::AbstractVector{Float64}, A::AbstractMatrix{Float64}, b::AbstractVector{Float64}, R::Integer;
                              seeds::Union{Nothing,Vector{UInt64}}=nothing, atol=Base.rtoldefault(Float64),
                              epsilon=Base.rtoldefault(Float64))
-    n = isqrt(length(C)); @assert n^2 == length(C)
-    F = qr(A'); U = Matrix(F.Q)[:, 1:rank(A)]; proj(v) = U * (U' * v)
-    c = Vector(C); c .-= proj(c); SR._clamp_round!(c, atol=atol); SR._symmetrize!(c, n)
-    x0, _ = SR.Krylov.craig(A, b); SR._symmetrize!(x0, n); x0 = proj(x0); SR._clamp_round!(x0, atol=atol)
+    n, c, x0, U, hint = _setup(C, A, b, atol)
     cx = ctx()
     Ps = [Matrix{UInt32}(undef, n, n) for _ in 1:R]
     pP = [pointer(P) for P in Ps]
     d = zeros(Int64, R); it = zeros(Int32, R); nb = zeros(Int32, R); ssq = zeros(Int64, R); ss = zeros(Int64, R); st = zeros(Int32, R)
-    hint = 2 | (all(k -> (M = reshape(view(U, :, k), n, n); isapprox(M, M'; atol=1e-12, rtol=0)), 1:size(U, 2)) ? 1 : 0)
     ccall((:sdpsr_hint_symmetric_basis, libsdpsr), Cint, (Ptr{Cvoid}, Cint), cx.handle, hint)
     GC.@preserve Ps begin
         ccall((:sdpsr_jordan_reduce_batch, libsdpsr), Cint,
@@ -282,11 +299,7 @@ mutable struct Problem
     ctx::Context
     function Problem(C::AbstractVector{Float64}, A::AbstractMatrix{Float64}, b::AbstractVector{Float64};
                      atol=Base.rtoldefault(Float64), cx::Context=ctx())
-        n = isqrt(length(C)); @assert n^2 == length(C)
-        F = qr(A'); U = Matrix(F.Q)[:, 1:rank(A)]; proj(v) = U * (U' * v)
-        c = Vector(C); c .-= proj(c); SR._clamp_round!(c, atol=atol); SR._symmetrize!(c, n)
-        x0, _ = SR.Krylov.craig(A, b); SR._symmetrize!(x0, n); x0 = proj(x0); SR._clamp_round!(x0, atol=atol)
-        hint = 2 | (all(k -> (M = reshape(view(U, :, k), n, n); isapprox(M, M'; atol=1e-12, rtol=0)), 1:size(U, 2)) ? 1 : 0)
+        n, c, x0, U, hint = _setup(C, A, b, atol)
         h = Ref{Ptr{Cvoid}}(C_NULL)
         check(cx, ccall((:sdpsr_problem_create, libsdpsr), Cint,
                         (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Cint, Cint, Ref{Ptr{Cvoid}}),
