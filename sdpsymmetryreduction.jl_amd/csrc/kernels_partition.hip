@@ -10,6 +10,7 @@
 // All of these are HBM-bound: one pass over n^2 entries each, 16-byte accesses per lane,
 // grid sized to a few blocks per CU with grid-stride loops.
 #include <cstdlib>
+#include <type_traits>
 #include "sdpsr_internal.h"
 
 namespace sdpsr {
@@ -343,6 +344,30 @@ void launch_unpad_copy(hipStream_t s, int64_t n, int64_t ld, const void* src, vo
 }
 
 // ---------------------------------------------------------------------------
+// Signature arithmetic shared by the sources below (Src*), whose signatures the insert pass of the refinement computes
+// itself, and the stand-alone kernels that keep a run-time shape (proj_apply_kernel: any r; sig_channels_kernel: any T).
+// A refinement may switch from one to the other in the middle of a call, so both must give the same bits: each
+// piece is written once, here or in the source's sig().
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ uint64_t finish_sig(uint32_t l, bool all_zero, uint64_t h) {
+    if (l == 0 && all_zero) return 0;
+    return h ? h : 1;
+}
+// (old label, code of the rounded projected value); the zero class: label 0 with code 0
+__device__ __forceinline__ uint64_t sig_label_key(uint32_t l, uint64_t kb) {
+    uint64_t h = 0;
+    if (l != 0 || kb != 0) {
+        h = sdpsr_sig_mix(sdpsr_sig_start(l), kb);
+        if (h == 0) h = 1;
+    }
+    return h;
+}
+// one mixing step of the channel values of a square: two 32-bit values per 64-bit word
+__device__ __forceinline__ uint64_t sig_mix_channels(uint64_t h, int32_t c0, int32_t c1) {
+    return sdpsr_sig_mix(h, (uint64_t)(uint32_t)c0 | ((uint64_t)(uint32_t)c1 << 32));
+}
+
+// ---------------------------------------------------------------------------
 // projection  y = x - U (U' x)
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ double block_reduce_sum(double v, double* sh) {
@@ -426,15 +451,7 @@ __global__ void proj_apply_kernel(int64_t len, int r, const double* __restrict__
         // signature: the injective code of the rounded value (sdpsr_hash.h) -- no division / ldexp; raw bits when not rounding
         const uint64_t kcode = do_round ? sdpsr_round_key(y, atol, scale) : (uint64_t)__double_as_longlong(y);
         if (yout) yout[e] = do_round ? sdpsr_clamp_round(y, atol, scale) : y;
-        if (sig) {
-            uint64_t kb = kcode;
-            uint64_t h = 0;
-            if (l != 0 || kb != 0) {
-                h = sdpsr_sig_mix(sdpsr_sig_start(l), kb);
-                if (h == 0) h = 1;
-            }
-            sig[e] = h;
-        }
+        if (sig) sig[e] = sig_label_key(l, kcode);
     }
 }
 
@@ -533,45 +550,9 @@ void launch_proj_coef_probe(hipStream_t s, int64_t len, int64_t n, int64_t r, co
     proj_coef_final_kernel<<<(unsigned)(2 * r), 256, 0, s>>>(nblk, partial, coef);
 }
 
-// proj_apply on the lower triangle, signatures packed (column j at offset j n - j (j - 1) / 2): the
-// stand-alone form of SrcProj<R> with packed = 1 (sort path / r > 4)
-__global__ void proj_apply_lower_kernel(int n, int r, const double* __restrict__ U, const uint32_t* __restrict__ L, int lab_packed,
-                                        uint64_t key, const double* __restrict__ coef, double atol, double scale,
-                                        uint64_t* __restrict__ sig) {
-    const int64_t len = (int64_t)n * n;
-    for (int j = blockIdx.x; j < n; j += gridDim.x) {
-        const int64_t poff = (int64_t)j * n - (int64_t)j * (j - 1) / 2 - j;
-        uint64_t* sj = sig + poff;
-        for (int i = j + threadIdx.x; i < n; i += blockDim.x) {
-            const int64_t e = i + (int64_t)j * n;
-            const uint32_t l = lab_packed ? L[poff + i] : L[e];
-            const double x = l ? sdpsr_class_uniform(key, l) : 0.0;
-            double p = 0;
-            for (int k = 0; k < r; ++k) p = fma(U[(int64_t)k * len + e], coef[k], p);
-            const uint64_t kb = sdpsr_round_key(x - p, atol, scale);
-            uint64_t h = 0;
-            if (l != 0 || kb != 0) {
-                h = sdpsr_sig_mix(sdpsr_sig_start(l), kb);
-                if (h == 0) h = 1;
-            }
-            sj[i] = h;
-        }
-    }
-}
-void launch_proj_apply_lower(hipStream_t s, int64_t n, int64_t r, const double* U, const uint32_t* L, int lab_packed, uint64_t key,
-                             const double* coef, double atol, double scale, uint64_t* sig) {
-    const int g = (int)(n < 256 * 8 ? n : 256 * 8);
-    proj_apply_lower_kernel<<<g, 256, 0, s>>>((int)n, (int)r, U, L, lab_packed, key, coef, atol, scale, sig);
-}
-
 // ---------------------------------------------------------------------------
 // signatures
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t finish_sig(uint32_t l, bool all_zero, uint64_t h) {
-    if (l == 0 && all_zero) return 0;
-    return h ? h : 1;
-}
-
 __global__ void sig_f64_kernel(int64_t len, const uint32_t* __restrict__ L,
                                const double* __restrict__ v, uint64_t* __restrict__ sig) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -584,36 +565,6 @@ __global__ void sig_f64_kernel(int64_t len, const uint32_t* __restrict__ L,
 void launch_sig_f64(hipStream_t s, int64_t len, const uint32_t* L, const double* v,
                     uint64_t* sig) {
     sig_f64_kernel<<<grid_for(len, 256), 256, 0, s>>>(len, L, v, sig);
-}
-
-// S = Part(a); S = refine!(S, Part(b)) in one pass: the canonical relabel of the value pairs
-// (src/partitions.jl:145-146); label 0 only where both values are +0.0
-__global__ void sig_f64_pair_kernel(int64_t len, const double* __restrict__ a, const double* __restrict__ b,
-                                    uint64_t* __restrict__ sig) {
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < len; e += stride) {
-        const uint64_t ka = (uint64_t)__double_as_longlong(a[e]);
-        const uint64_t kb = (uint64_t)__double_as_longlong(b[e]);
-        uint64_t h = sdpsr_sig_mix(sdpsr_sig_mix(sdpsr_sig_start(0u), ka), kb);
-        sig[e] = finish_sig(0u, ka == 0 && kb == 0, h);
-    }
-}
-// the pair signatures of the lower triangle, packed (column j at offset j n - j (j - 1) / 2)
-__global__ void sig_f64_pair_lower_kernel(int n, const double* __restrict__ a, const double* __restrict__ b,
-                                          uint64_t* __restrict__ sig) {
-    for (int j = blockIdx.x; j < n; j += gridDim.x) {
-        uint64_t* sj = sig + ((int64_t)j * n - (int64_t)j * (j - 1) / 2 - j);
-        for (int i = j + threadIdx.x; i < n; i += blockDim.x) {
-            const int64_t e = i + (int64_t)j * n;
-            const uint64_t ka = (uint64_t)__double_as_longlong(a[e]);
-            const uint64_t kb = (uint64_t)__double_as_longlong(b[e]);
-            const uint64_t h = sdpsr_sig_mix(sdpsr_sig_mix(sdpsr_sig_start(0u), ka), kb);
-            sj[i] = finish_sig(0u, ka == 0 && kb == 0, h);
-        }
-    }
-}
-void launch_sig_f64_pair(hipStream_t s, int64_t len, const double* a, const double* b, uint64_t* sig) {
-    sig_f64_pair_kernel<<<grid_for(len, 256), 256, 0, s>>>(len, a, b, sig);
 }
 
 // v is a padded ld x ld matrix; output sig is dense n x n
@@ -661,39 +612,32 @@ void launch_sig_u64(hipStream_t s, int64_t len, const uint64_t* k, uint64_t* sig
     sig_u64_kernel<<<grid_for(len, 256), 256, 0, s>>>(len, k, sig);
 }
 
-// grid (row chunks, columns): no 64-bit division per entry
+// The channel signatures for a run-time channel count T (SrcChan<CT, T> below has instances for T = 1, 2, 4, 8 only).
+// grid (row chunks, columns): no 64-bit division per entry.
+// packed: labels and products are symmetric, only the entries i >= j get a signature, written densely -- column j at
+// offset j n - j (j - 1) / 2, rows j .. n-1 (the refinement runs on n (n + 1) / 2 entries; first occurrences in
+// column-major order always sit in the lower triangle, so the canonical numbering is that of the full matrix);
+// lab_packed: the labels come packed the same way
 template <typename CT>
 __global__ void sig_channels_kernel(int64_t n, int64_t ld, int T, const uint32_t* __restrict__ L,
-                                    const CT* __restrict__ C, uint64_t* __restrict__ sig,
-                                    const uint32_t* __restrict__ nonsym_flag, int packed, int lab_packed) {
+                                    const CT* __restrict__ C, uint64_t* __restrict__ sig, int packed, int lab_packed) {
     const int64_t istride = (int64_t)gridDim.x * blockDim.x;
-    // lower != 0: labels and products are symmetric, only entries i >= j get a signature (the
-    // strict upper triangle gets the zero signature and is mirrored after the refinement; first
-    // occurrences in column-major order always sit in the lower triangle, so the canonical
-    // numbering is unchanged)
-    const bool lower = nonsym_flag && *nonsym_flag == 0u;
     for (int64_t j = blockIdx.y; j < n; j += gridDim.y) {
-        // packed != 0 (with lower): the signatures of the lower triangle are written densely,
-        // column j at offset j n - j (j - 1) / 2, rows j .. n-1 -- the refinement then runs on
-        // n (n + 1) / 2 entries in the same relative order; lab_packed: the labels come packed the same way
-        const bool pk = lower && packed;
-        const uint32_t* Lj = (pk && lab_packed) ? L + (j * n - j * (j - 1) / 2 - j) : L + j * n;
-        uint64_t* sj = pk ? sig + (j * n - j * (j - 1) / 2 - j) : sig + j * n;
+        const int64_t poff = j * n - j * (j - 1) / 2 - j;
+        const uint32_t* Lj = (packed && lab_packed) ? L + poff : L + j * n;
+        uint64_t* sj = packed ? sig + poff : sig + j * n;
         const CT* Cj = C + j * ld;
 #pragma unroll 2
         for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += istride) {
-            if (lower && i < j) {
-                if (!pk) sj[i] = 0ull;
-                continue;
-            }
+            if (packed && i < j) continue;
             const uint32_t l = Lj[i];
             uint64_t h = sdpsr_sig_start(l);
             bool allz = true;
-            for (int t = 0; t < T; t += 2) {  // two 32-bit channel values per 64-bit mixing step
+            for (int t = 0; t < T; t += 2) {
                 const int32_t c0 = (int32_t)Cj[(int64_t)t * ld * ld + i];  // exact: f32 channels hold integers < 2^24
                 const int32_t c1 = (t + 1 < T) ? (int32_t)Cj[(int64_t)(t + 1) * ld * ld + i] : 0;
                 allz = allz && (c0 == 0) && (c1 == 0);
-                h = sdpsr_sig_mix(h, (uint64_t)(uint32_t)c0 | ((uint64_t)(uint32_t)c1 << 32));
+                h = sig_mix_channels(h, c0, c1);
             }
             sj[i] = finish_sig(l, allz, h);
         }
@@ -710,18 +654,25 @@ static inline dim3 column_grid(int64_t n) {
     return dim3((unsigned)gx, (unsigned)gy);
 }
 void launch_sig_i32(hipStream_t s, int64_t n, int64_t ld, int T, const uint32_t* L,
-                    const int32_t* C, uint64_t* sig, const uint32_t* nonsym_flag, int packed, int lab_packed) {
-    sig_channels_kernel<int32_t><<<column_grid(n), 256, 0, s>>>(n, ld, T, L, C, sig, nonsym_flag, packed, lab_packed);
+                    const int32_t* C, uint64_t* sig, int packed, int lab_packed) {
+    sig_channels_kernel<int32_t><<<column_grid(n), 256, 0, s>>>(n, ld, T, L, C, sig, packed, lab_packed);
 }
 void launch_sig_f32(hipStream_t s, int64_t n, int64_t ld, int T, const uint32_t* L,
-                    const float* C, uint64_t* sig, const uint32_t* nonsym_flag, int packed, int lab_packed) {
-    sig_channels_kernel<float><<<column_grid(n), 256, 0, s>>>(n, ld, T, L, C, sig, nonsym_flag, packed, lab_packed);
+                    const float* C, uint64_t* sig, int packed, int lab_packed) {
+    sig_channels_kernel<float><<<column_grid(n), 256, 0, s>>>(n, ld, T, L, C, sig, packed, lab_packed);
 }
 
 // ---------------------------------------------------------------------------
 // Signature sources of the insert pass: the refinement either reads a signature array or computes
-// each signature from the data the matching sig_* / proj_apply kernel would have read -- the same
-// device functions, so the same bits -- and the 8 bytes per entry never travel through HBM.
+// each signature itself, and the 8 bytes per entry never travel through HBM.  A computed source is a
+// functor: fetch(i, j, e) loads what entry (i, j) -- number e of the source's numbering -- needs, sig(Raw)
+// is THE definition of its signature.  Everybody goes through that pair: the insert kernels, the
+// materialise kernel that writes the source out as an array (sort / bucket paths, a table that
+// overflowed, SDPSR_FLAG_REFINE_NO_FUSE: a refinement may go on with the array where it began with
+// the source), so both see the same bits.  with_source() maps a SigSource to its functor.
+// Beside the fetch batch every source names the shape of its insert kernel: kInsertPer entries per
+// thread and chunk, kLdsSlots entries of the workgroup's LDS table, and kMid: the source also has
+// the one-workgroup-per-CU kernel (refine_insert_mid_kernel).
 // ---------------------------------------------------------------------------
 // A source is either FLAT (signature of the linear index e) or walks the matrix by (row i, column j):
 // the insert kernel locates the first entry of a thread's chunk once (a division, or the inversion
@@ -750,6 +701,8 @@ struct IjWalk {
 struct SrcArray {
     static constexpr bool kIJ = false;
     static constexpr int kFetchBatch = 1;
+    static constexpr int kInsertPer = 16, kLdsSlots = 2048;
+    static constexpr bool kMid = true;
     const uint64_t* __restrict__ sig;
     __device__ __forceinline__ bool walks() const { return false; }
     __device__ __forceinline__ bool lower() const { return false; }
@@ -757,21 +710,20 @@ struct SrcArray {
     __device__ __forceinline__ uint64_t at(uint32_t, uint32_t, int64_t) const { return 0; }
     __device__ __forceinline__ uint64_t operator()(int64_t e) const { return __builtin_nontemporal_load(&sig[e]); }
 };
-struct SrcPair {  // sig_f64_pair_kernel; packed: the lower triangle column by column (a, b symmetric)
+// S = Part(a); S = refine!(S, Part(b)) in one pass: the canonical relabel of the value pairs
+// (src/partitions.jl:145-146); label 0 only where both values are +0.0.
+// packed: the lower triangle column by column (a, b symmetric); else flat, entry e of both
+struct SrcPair {
     static constexpr bool kIJ = true;
     static constexpr int kFetchBatch = 8;  // refine_insert_kernel: entries loaded before their signatures are formed
+    static constexpr int kInsertPer = 8, kLdsSlots = 1024;
+    static constexpr bool kMid = true;
     const double* __restrict__ a;
     const double* __restrict__ b;
     int n, packed;
-    __device__ __forceinline__ bool walks() const { return packed != 0; }
-    __device__ __forceinline__ bool lower() const { return true; }
-    __device__ __forceinline__ int order() const { return n; }
-    __device__ __forceinline__ uint64_t flat(int64_t e) const {
-        const uint64_t ka = (uint64_t)__double_as_longlong(__builtin_nontemporal_load(&a[e]));
-        const uint64_t kb = (uint64_t)__double_as_longlong(__builtin_nontemporal_load(&b[e]));
-        const uint64_t h = sdpsr_sig_mix(sdpsr_sig_mix(sdpsr_sig_start(0u), ka), kb);
-        return finish_sig(0u, ka == 0 && kb == 0, h);
-    }
+    __host__ __device__ __forceinline__ bool walks() const { return packed != 0; }
+    __host__ __device__ __forceinline__ bool lower() const { return true; }
+    __host__ __device__ __forceinline__ int order() const { return n; }
     // fetch / sig: the loads of an entry and the signature of what was loaded
     struct Raw {
         double a, b;
@@ -791,13 +743,15 @@ struct SrcPair {  // sig_f64_pair_kernel; packed: the lower triangle column by c
             packed_lower_ij(n, e, i, j);
             return at(i, j, e);
         }
-        return flat(e);
+        return at((uint32_t)e, 0u, e);  // flat: entry e of every operand
     }
 };
 template <int R>
-struct SrcProj {  // proj_apply_kernel with xin = nullptr, do_round = 1, sig only
+struct SrcProj {  // what proj_apply_kernel signs with xin = nullptr, do_round = 1, for r = R
     static constexpr bool kIJ = true;
     static constexpr int kFetchBatch = 1;
+    static constexpr int kInsertPer = 8, kLdsSlots = 1024;
+    static constexpr bool kMid = false;
     const double* __restrict__ U;
     const uint32_t* L;  // may alias the label output of the refinement (read before the entry's own write)
     const double* __restrict__ coef;
@@ -806,27 +760,9 @@ struct SrcProj {  // proj_apply_kernel with xin = nullptr, do_round = 1, sig onl
     double atol, scale;
     int n, packed;  // packed: the lower triangle column by column (symmetric labels and basis)
     int lab_packed;  // L is the packed lower triangle itself (label of packed entry e = L[e])
-    __device__ __forceinline__ bool walks() const { return packed != 0; }
-    __device__ __forceinline__ bool lower() const { return true; }
-    __device__ __forceinline__ int order() const { return n; }
-    __device__ __forceinline__ uint64_t flat(int64_t e) const { return flat(e, e); }
-    __device__ __forceinline__ uint64_t flat(int64_t e, int64_t el) const {
-        const uint32_t l = L[el];
-        double u[R > 0 ? R : 1];
-#pragma unroll
-        for (int k = 0; k < R; ++k) u[k] = __builtin_nontemporal_load(&U[(int64_t)k * len + e]);
-        const double x = l ? sdpsr_class_uniform(key, l) : 0.0;
-        double p = 0;
-#pragma unroll
-        for (int k = 0; k < R; ++k) p = fma(u[k], coef[k], p);
-        const uint64_t kb = sdpsr_round_key(x - p, atol, scale);
-        uint64_t h = 0;
-        if (l != 0 || kb != 0) {
-            h = sdpsr_sig_mix(sdpsr_sig_start(l), kb);
-            if (h == 0) h = 1;
-        }
-        return h;
-    }
+    __host__ __device__ __forceinline__ bool walks() const { return packed != 0; }
+    __host__ __device__ __forceinline__ bool lower() const { return true; }
+    __host__ __device__ __forceinline__ int order() const { return n; }
     struct Raw {
         uint32_t l;
         double u[R > 0 ? R : 1];
@@ -844,13 +780,7 @@ struct SrcProj {  // proj_apply_kernel with xin = nullptr, do_round = 1, sig onl
         double p = 0;
 #pragma unroll
         for (int k = 0; k < R; ++k) p = fma(r.u[k], coef[k], p);
-        const uint64_t kb = sdpsr_round_key(x - p, atol, scale);
-        uint64_t h = 0;
-        if (r.l != 0 || kb != 0) {
-            h = sdpsr_sig_mix(sdpsr_sig_start(r.l), kb);
-            if (h == 0) h = 1;
-        }
-        return h;
+        return sig_label_key(r.l, sdpsr_round_key(x - p, atol, scale));
     }
     __device__ __forceinline__ uint64_t at(uint32_t i, uint32_t j, int64_t e) const { return sig(fetch(i, j, e)); }
     __device__ __forceinline__ uint64_t operator()(int64_t e) const {
@@ -859,22 +789,24 @@ struct SrcProj {  // proj_apply_kernel with xin = nullptr, do_round = 1, sig onl
             packed_lower_ij(n, e, i, j);
             return at(i, j, e);
         }
-        return flat(e);
+        return at((uint32_t)e, 0u, e);  // flat: entry e of every operand
     }
 };
 template <typename CT, int T>
-struct SrcChan {  // sig_channels_kernel; packed: the lower triangle column by column
+struct SrcChan {  // (old label, T channel values of the square); packed: the lower triangle column by column
     static constexpr bool kIJ = true;
     static constexpr int kFetchBatch = T <= 2 ? 4 : 1;  // (measured at T = 2: 65 -> 58 us; all 8 with three workgroups per CU: 64 us; wider entries not measured)
+    static constexpr int kInsertPer = T <= 4 ? 8 : 4, kLdsSlots = 1024;
+    static constexpr bool kMid = std::is_same<CT, int32_t>::value && T == 2;
     int n;
     int64_t ld;
     const uint32_t* L;
     const CT* __restrict__ C;
     int packed;
     int lab_packed;  // (with packed) L is the packed lower triangle itself
-    __device__ __forceinline__ bool walks() const { return true; }  // C is ld-strided: (i, j) needed either way
-    __device__ __forceinline__ bool lower() const { return packed != 0; }
-    __device__ __forceinline__ int order() const { return n; }
+    __host__ __device__ __forceinline__ bool walks() const { return true; }  // C is ld-strided: (i, j) needed either way
+    __host__ __device__ __forceinline__ bool lower() const { return packed != 0; }
+    __host__ __device__ __forceinline__ int order() const { return n; }
     struct Raw {
         uint32_t l;
         CT c[T];
@@ -897,7 +829,7 @@ struct SrcChan {  // sig_channels_kernel; packed: the lower triangle column by c
 #pragma unroll
         for (int t = 0; t < T; t += 2) {
             allz = allz && (c[t] == 0) && (c[t + 1] == 0);
-            h = sdpsr_sig_mix(h, (uint64_t)(uint32_t)c[t] | ((uint64_t)(uint32_t)c[t + 1] << 32));
+            h = sig_mix_channels(h, c[t], c[t + 1]);
         }
         return finish_sig(r.l, allz, h);
     }
@@ -918,6 +850,8 @@ template <int R, int T>  // T = 2 or 4 channels
 struct SrcJoint {
     static constexpr bool kIJ = true;
     static constexpr int kFetchBatch = 1;  // (2: 79 -> 99 us, 8: 114 us for SrcJoint<2, 2>)
+    static constexpr int kInsertPer = 8, kLdsSlots = 1024;
+    static constexpr bool kMid = false;
     const double* __restrict__ U;
     const uint32_t* L;
     const double* __restrict__ coef;
@@ -926,9 +860,9 @@ struct SrcJoint {
     const int32_t* __restrict__ C;  // T channels, ld x ld each
     int64_t ld;
     int n, lab_packed;
-    __device__ __forceinline__ bool walks() const { return true; }
-    __device__ __forceinline__ bool lower() const { return true; }
-    __device__ __forceinline__ int order() const { return n; }
+    __host__ __device__ __forceinline__ bool walks() const { return true; }
+    __host__ __device__ __forceinline__ bool lower() const { return true; }
+    __host__ __device__ __forceinline__ int order() const { return n; }
     struct Raw {
         uint32_t l;
         double u[R > 0 ? R : 1];
@@ -956,7 +890,7 @@ struct SrcJoint {
         bool allz = kb == 0;
 #pragma unroll
         for (int t = 0; t < T; t += 2) {
-            h = sdpsr_sig_mix(h, (uint64_t)(uint32_t)r.c[t] | ((uint64_t)(uint32_t)r.c[t + 1] << 32));
+            h = sig_mix_channels(h, r.c[t], r.c[t + 1]);
             allz = allz && r.c[t] == 0 && r.c[t + 1] == 0;
         }
         return finish_sig(r.l, allz, h);
@@ -1899,12 +1833,8 @@ refine_label_sym_kernel(int64_t n, const uint32_t* slot, uint32_t* labels_out,
     if (sym_tile_pass<VEC4>(n, slot, labels_out, MapSlotLabel{tab_lab}, tile)) counters[3] = 1u;
 }
 
-// Which sources have the one-workgroup-per-CU kernel (each costs two more instantiations of a large kernel; the ones the
-// loop of admissible_subspace runs on the benchmark shapes and the array source)
-template <class SRC> struct MidSource { static constexpr bool value = false; };
-template <> struct MidSource<SrcArray> { static constexpr bool value = true; };
-template <> struct MidSource<SrcPair> { static constexpr bool value = true; };
-template <> struct MidSource<SrcChan<int32_t, 2>> { static constexpr bool value = true; };
+// Which sources have the one-workgroup-per-CU kernel (SRC::kMid; each costs two more instantiations of a large kernel):
+// the ones the loop of admissible_subspace runs on the benchmark shapes and the array source.
 // (Measured and not kept: the joint source.  SrcJoint<2, 2> with its raw entries prefetched spills (107 us per launch at
 // N = 4104), without the prefetch it takes 78 - 88 + 8 us against 71 + 18 for the 256-thread kernel.  The channel source gains
 // only with the deferral in the kernel: ER(7) x K_72 is not vertex-transitive, and its large classes that the first
@@ -1912,6 +1842,7 @@ template <> struct MidSource<SrcChan<int32_t, 2>> { static constexpr bool value 
 
 template <class SRC>
 bool mid_set_attributes_kind() {
+    static_assert(SRC::kMid, "");
     bool ok = true;
     ok &= hipSuccess == hipFuncSetAttribute(reinterpret_cast<const void*>(&refine_insert_mid_kernel<SRC, MID_PER>),
                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)MID_LDS_BYTES);
@@ -1964,10 +1895,11 @@ static void launch_insert_mid(hipStream_t s, int64_t len, const SRC& src, uint32
 // SLOTS: entries of the workgroup's LDS table (16 bytes each): 2048 -> four workgroups per CU,
 // 1024 -> up to eight (the computed sources are bound by their hash arithmetic and by the
 // barriers between the phases of a chunk: more resident workgroups overlap those phases)
-template <class SRC, int PER, int SLOTS = 1024>
+template <class SRC>
 static void launch_insert(hipStream_t s, int g_chunks_cap, int64_t len, const SRC& src, uint32_t* slot, const RefineWs& ws,
                           size_t cap) {
-    if constexpr (MidSource<SRC>::value) {
+    constexpr int PER = SRC::kInsertPer, SLOTS = SRC::kLdsSlots;
+    if constexpr (SRC::kMid) {
         if (ws.mid) {
             launch_insert_mid<SRC>(s, len, src, slot, ws, cap);
             return;
@@ -2016,46 +1948,6 @@ static void launch_insert(hipStream_t s, int g_chunks_cap, int64_t len, const SR
         hipFree(dbg);
     }
 #endif
-}
-
-template <typename CT>
-static bool launch_insert_chan(hipStream_t s, int gcap, int64_t len, const SigSource& q, uint32_t* slot, const RefineWs& ws,
-                               size_t cap) {
-    const CT* C = (const CT*)q.C;
-    switch (q.T) {
-        case 1: launch_insert<SrcChan<CT, 1>, 8>(s, gcap, len, SrcChan<CT, 1>{(int)q.n, q.ld, q.L, C, q.packed, q.lab_packed}, slot, ws, cap); return true;
-        case 2: launch_insert<SrcChan<CT, 2>, 8>(s, gcap, len, SrcChan<CT, 2>{(int)q.n, q.ld, q.L, C, q.packed, q.lab_packed}, slot, ws, cap); return true;
-        case 4: launch_insert<SrcChan<CT, 4>, 8>(s, gcap, len, SrcChan<CT, 4>{(int)q.n, q.ld, q.L, C, q.packed, q.lab_packed}, slot, ws, cap); return true;
-        case 8: launch_insert<SrcChan<CT, 8>, 4>(s, gcap, len, SrcChan<CT, 8>{(int)q.n, q.ld, q.L, C, q.packed, q.lab_packed}, slot, ws, cap); return true;
-        default: return false;
-    }
-}
-
-// stand-alone form of SrcJoint (sort path); T = 2 or 4 channels
-__global__ void sig_joint_lower_kernel(int n, int64_t ld, int r, int T, const double* __restrict__ U, const uint32_t* __restrict__ L,
-                                       int lab_packed, uint64_t key, const double* __restrict__ coef, double atol, double scale,
-                                       const int32_t* __restrict__ C, uint64_t* __restrict__ sig) {
-    const int64_t len = (int64_t)n * n;
-    for (int j = blockIdx.x; j < n; j += gridDim.x) {
-        const int64_t poff = (int64_t)j * n - (int64_t)j * (j - 1) / 2 - j;
-        for (int i = j + threadIdx.x; i < n; i += blockDim.x) {
-            const int64_t e = i + (int64_t)j * n;
-            const uint32_t l = lab_packed ? L[poff + i] : L[e];
-            const double x = l ? sdpsr_class_uniform(key, l) : 0.0;
-            double p = 0;
-            for (int k = 0; k < r; ++k) p = fma(U[(int64_t)k * len + e], coef[k], p);
-            const uint64_t kb = sdpsr_round_key(x - p, atol, scale);
-            const int32_t* Cij = C + (int64_t)j * ld + i;
-            uint64_t h = sdpsr_sig_mix(sdpsr_sig_start(l), kb);
-            bool allz = kb == 0;
-            for (int t = 0; t < T; t += 2) {
-                const int32_t c0 = Cij[(int64_t)t * ld * ld], c1 = Cij[(int64_t)(t + 1) * ld * ld];
-                h = sdpsr_sig_mix(h, (uint64_t)(uint32_t)c0 | ((uint64_t)(uint32_t)c1 << 32));
-                allz = allz && c0 == 0 && c1 == 0;
-            }
-            sig[poff + i] = finish_sig(l, allz, h);
-        }
-    }
 }
 
 // ---------------------------------------------------------------------------
@@ -2270,52 +2162,108 @@ bool launch_verify_no_split(hipStream_t s, const SigSource& q, int64_t d, const 
     return true;
 }
 
-bool sig_source_fusable(const SigSource& q) {
+// f(std::integral_constant<int, v>) for the v of the list that equals x; false when none does
+template <int... Vs, class F>
+static bool with_constant(int x, F&& f) {
+    return ((x == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...);
+}
+
+// THE map from a SigSource to its functor: f(src) with the Src* instance of q.  false (f not called) when q's shape has
+// no instance -- a projection onto more than four basis matrices, a channel count other than 1, 2, 4, 8, a joint source
+// that is not packed: such a source is not fusable and is written out by the stand-alone kernel of its run-time shape
+// (launch_sig_materialize).  Every instance named here gets an insert kernel and a materialise kernel.
+template <class F>
+static bool with_source(const SigSource& q, F&& f) {
+    const int n = (int)q.n;
     switch (q.kind) {
-        case SIG_JOINT_I32: return q.r >= 0 && q.r <= 4 && (q.T == 2 || q.T == 4) && q.packed;
-        case SIG_ARRAY: return true;
-        case SIG_PAIR: return true;
-        case SIG_PROJ: return q.r >= 0 && q.r <= 4;
+        case SIG_ARRAY: f(SrcArray{q.sig}); return true;
+        case SIG_PAIR: f(SrcPair{q.a, q.b, n, q.packed}); return true;
+        case SIG_PROJ:
+            return with_constant<0, 1, 2, 3, 4>(q.r, [&](auto R) {
+                f(SrcProj<decltype(R)::value>{q.U, q.L, q.coef, q.n * q.n, q.key, q.atol, q.scale, n, q.packed, q.lab_packed});
+            });
         case SIG_CHAN_I32:
-        case SIG_CHAN_F32: return q.T == 1 || q.T == 2 || q.T == 4 || q.T == 8;
+            return with_constant<1, 2, 4, 8>(q.T, [&](auto T) {
+                f(SrcChan<int32_t, decltype(T)::value>{n, q.ld, q.L, (const int32_t*)q.C, q.packed, q.lab_packed});
+            });
+        case SIG_CHAN_F32:
+            return with_constant<1, 2, 4, 8>(q.T, [&](auto T) {
+                f(SrcChan<float, decltype(T)::value>{n, q.ld, q.L, (const float*)q.C, q.packed, q.lab_packed});
+            });
+        case SIG_JOINT_I32: {
+            bool found = false;
+            if (q.packed)
+                with_constant<0, 1, 2, 3, 4>(q.r, [&](auto R) {
+                    found = with_constant<2, 4>(q.T, [&](auto T) {
+                        f(SrcJoint<decltype(R)::value, decltype(T)::value>{q.U, q.L, q.coef, q.key, q.atol, q.scale, (const int32_t*)q.C,
+                                                                           q.ld, n, q.lab_packed});
+                    });
+                });
+            return found;
+        }
         default: return false;
     }
 }
 
-// the signature array of a computed source (sort path, or a source the insert kernel has no
-// instance for): the stand-alone kernels
-void launch_sig_materialize(hipStream_t s, int64_t len, const SigSource& q, uint64_t* sig) {
-    switch (q.kind) {
-        case SIG_PAIR:
-            if (q.packed) sig_f64_pair_lower_kernel<<<(int)(q.n < 2048 ? q.n : 2048), 256, 0, s>>>((int)q.n, q.a, q.b, sig);
-            else launch_sig_f64_pair(s, len, q.a, q.b, sig);
-            break;
-        case SIG_PROJ:
-            if (q.packed) launch_proj_apply_lower(s, q.n, q.r, q.U, q.L, q.lab_packed, q.key, q.coef, q.atol, q.scale, sig);
-            else launch_proj_apply(s, len, q.r, q.U, q.L, q.key, nullptr, q.coef, q.atol, q.scale, 1, nullptr, sig);
-            break;
-        case SIG_JOINT_I32:
-            sig_joint_lower_kernel<<<(int)(q.n < 2048 ? q.n : 2048), 256, 0, s>>>((int)q.n, q.ld, q.r, q.T, q.U, q.L, q.lab_packed, q.key, q.coef,
-                                                                                 q.atol, q.scale, (const int32_t*)q.C, sig);
-            break;
-        case SIG_CHAN_I32: launch_sig_i32(s, q.n, q.ld, q.T, q.L, (const int32_t*)q.C, sig, q.zero_flag, q.packed, q.lab_packed); break;
-        case SIG_CHAN_F32: launch_sig_f32(s, q.n, q.ld, q.T, q.L, (const float*)q.C, sig, q.zero_flag, q.packed, q.lab_packed); break;
-        default: break;
-    }
+bool sig_source_fusable(const SigSource& q) {
+    return with_source(q, [](const auto&) {});
 }
 
 // does launch_refine run the one-workgroup-per-CU insert kernel for this source (RefineWs::mid)?
 bool refine_mid_supports(const SigSource& q) {
+    bool mid = false;
+    with_source(q, [&](const auto& src) { mid = std::decay_t<decltype(src)>::kMid; });
+    return mid;
+}
+
+// A computed source written out as an array, by the source's own fetch / sig.  A source that walks the matrix: columns
+// over workgroups, the rows of a column -- i >= j on the packed lower triangle -- over threads; entry (i, j) is number
+// off(j) + i of the source's numbering (packed: column j starts at j n - j (j - 1) / 2).  A flat one: a grid-stride loop.
+template <class SRC>
+__global__ void __launch_bounds__(256)
+sig_materialize_kernel(int64_t len, const SRC src, uint64_t* __restrict__ sig) {
+    if (!src.walks()) {  // uniform
+        const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+        for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < len; e += stride) sig[e] = src(e);
+        return;
+    }
+    const int n = src.order();
+    const bool low = src.lower();
+    for (int j = blockIdx.x; j < n; j += gridDim.x) {
+        const int64_t off = (int64_t)j * n - (low ? (int64_t)j * (j - 1) / 2 + j : 0);
+        for (int i = (low ? j : 0) + threadIdx.x; i < n; i += blockDim.x)
+            sig[off + i] = src.sig(src.fetch((uint32_t)i, (uint32_t)j, off + i));
+    }
+}
+
+// The signature array of a computed source: sort / bucket paths, a table that overflowed, SDPSR_FLAG_REFINE_NO_FUSE, or
+// a shape without a functor instance -- those have a stand-alone kernel: proj_apply_kernel (any r, full matrix) and
+// sig_channels_kernel (any T).  false: nothing can write this source out.
+bool launch_sig_materialize(hipStream_t s, int64_t len, const SigSource& q, uint64_t* sig) {
+    if (q.kind == SIG_ARRAY) return false;
+    const bool done = with_source(q, [&](const auto& src) {
+        using SRC = std::decay_t<decltype(src)>;
+        if constexpr (SRC::kIJ) {
+            const int g = src.walks() ? (int)(q.n < 2048 ? q.n : 2048) : grid_for(len, 256);
+            sig_materialize_kernel<SRC><<<g, 256, 0, s>>>(len, src, sig);
+        }
+    });
+    if (done) return true;
     switch (q.kind) {
-        case SIG_ARRAY:
-        case SIG_PAIR: return true;
-        case SIG_CHAN_I32: return q.T == 2;
+        case SIG_PROJ:
+            if (q.packed) return false;  // (the loop runs the packed projection for r <= 4 only)
+            launch_proj_apply(s, len, q.r, q.U, q.L, q.key, nullptr, q.coef, q.atol, q.scale, 1, nullptr, sig);
+            return true;
+        case SIG_CHAN_I32: launch_sig_i32(s, q.n, q.ld, q.T, q.L, (const int32_t*)q.C, sig, q.packed, q.lab_packed); return true;
+        case SIG_CHAN_F32: launch_sig_f32(s, q.n, q.ld, q.T, q.L, (const float*)q.C, sig, q.packed, q.lab_packed); return true;
         default: return false;
     }
 }
 
-void launch_refine(hipStream_t s, int64_t len, const SigSource& q, uint32_t* slot, uint32_t* labels_out,
+// false: the source has no insert kernel (not sig_source_fusable), nothing was launched
+bool launch_refine(hipStream_t s, int64_t len, const SigSource& q, uint32_t* slot, uint32_t* labels_out,
                    const RefineWs& ws, int64_t sym_n) {
+    if (!sig_source_fusable(q)) return false;
     const size_t cap = (size_t)1 << ws.log2cap;
     refine_clear_kernel<<<grid_for((int64_t)cap, 256), 256, 0, s>>>((int64_t)cap, ws.tab, ws.counters);
     const int64_t nblk = (len + REFINE_BLOCK - 1) / REFINE_BLOCK;
@@ -2323,53 +2271,7 @@ void launch_refine(hipStream_t s, int64_t len, const SigSource& q, uint32_t* slo
     // work) launch exactly one round of resident workgroups -- a fifth per CU would run alone
     const int per_cu = (ws.log2cap <= 16) ? 4 : 5;  // many classes: bound by the global table, a few more workgroups help
     const int gcap = 256 * per_cu;
-    switch (q.kind) {
-        case SIG_PAIR: launch_insert<SrcPair, 8>(s, gcap, len, SrcPair{q.a, q.b, (int)q.n, q.packed}, slot, ws, cap); break;
-        case SIG_PROJ:
-            switch (q.r) {
-                case 0: launch_insert<SrcProj<0>, 8>(s, gcap, len, SrcProj<0>{q.U, q.L, q.coef, q.packed ? q.n * q.n : len, q.key, q.atol, q.scale, (int)q.n, q.packed, q.lab_packed}, slot, ws, cap); break;
-                case 1: launch_insert<SrcProj<1>, 8>(s, gcap, len, SrcProj<1>{q.U, q.L, q.coef, q.packed ? q.n * q.n : len, q.key, q.atol, q.scale, (int)q.n, q.packed, q.lab_packed}, slot, ws, cap); break;
-                case 2: launch_insert<SrcProj<2>, 8>(s, gcap, len, SrcProj<2>{q.U, q.L, q.coef, q.packed ? q.n * q.n : len, q.key, q.atol, q.scale, (int)q.n, q.packed, q.lab_packed}, slot, ws, cap); break;
-                case 3: launch_insert<SrcProj<3>, 8>(s, gcap, len, SrcProj<3>{q.U, q.L, q.coef, q.packed ? q.n * q.n : len, q.key, q.atol, q.scale, (int)q.n, q.packed, q.lab_packed}, slot, ws, cap); break;
-                default: launch_insert<SrcProj<4>, 8>(s, gcap, len, SrcProj<4>{q.U, q.L, q.coef, q.packed ? q.n * q.n : len, q.key, q.atol, q.scale, (int)q.n, q.packed, q.lab_packed}, slot, ws, cap); break;
-            }
-            break;
-        case SIG_JOINT_I32: {
-            const int32_t* Cj = (const int32_t*)q.C;
-#define SDPSR_JOINT_CASE(RR, TT)                                                                                                   \
-    launch_insert<SrcJoint<RR, TT>, 8>(s, gcap, len, SrcJoint<RR, TT>{q.U, q.L, q.coef, q.key, q.atol, q.scale, Cj, q.ld, (int)q.n, \
-                                                                      q.lab_packed}, slot, ws, cap)
-            const int rr = q.r < 0 ? 0 : (q.r > 4 ? 4 : q.r);
-            if (q.T == 2) {
-                switch (rr) {
-                    case 0: SDPSR_JOINT_CASE(0, 2); break;
-                    case 1: SDPSR_JOINT_CASE(1, 2); break;
-                    case 2: SDPSR_JOINT_CASE(2, 2); break;
-                    case 3: SDPSR_JOINT_CASE(3, 2); break;
-                    default: SDPSR_JOINT_CASE(4, 2); break;
-                }
-            } else {
-                switch (rr) {
-                    case 0: SDPSR_JOINT_CASE(0, 4); break;
-                    case 1: SDPSR_JOINT_CASE(1, 4); break;
-                    case 2: SDPSR_JOINT_CASE(2, 4); break;
-                    case 3: SDPSR_JOINT_CASE(3, 4); break;
-                    default: SDPSR_JOINT_CASE(4, 4); break;
-                }
-            }
-#undef SDPSR_JOINT_CASE
-            break;
-        }
-        case SIG_CHAN_I32: launch_insert_chan<int32_t>(s, gcap, len, q, slot, ws, cap); break;
-        case SIG_CHAN_F32: launch_insert_chan<float>(s, gcap, len, q, slot, ws, cap); break;
-        default:
-            if (ws.mid) {
-                launch_insert_mid<SrcArray>(s, len, SrcArray{q.sig}, slot, ws, cap);
-            } else {
-                launch_insert<SrcArray, 16, 2048>(s, gcap, len, SrcArray{q.sig}, slot, ws, cap);
-            }
-            break;
-    }
+    with_source(q, [&](const auto& src) { launch_insert(s, gcap, len, src, slot, ws, cap); });
     const int g2 = (int)(nblk < 256 * 8 ? nblk : 256 * 8);
     // ws.expect_small: the host predicts <= SMALL_K classes (from the previous refinement) and
     // launches the one-workgroup ranking only; it checks counters[0] afterwards and repeats the
@@ -2395,6 +2297,7 @@ void launch_refine(hipStream_t s, int64_t len, const SigSource& q, uint32_t* slo
     } else {
         refine_label_kernel<<<grid_for(len, 256), 256, 0, s>>>(len, slot, labels_out, ws.tab_lab, ws.counters, ws.expect_small, ws.host_counters, ws.host_seq);
     }
+    return true;
 }
 
 // ---------------------------------------------------------------------------

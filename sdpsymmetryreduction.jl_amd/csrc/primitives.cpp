@@ -22,20 +22,20 @@ namespace sdpsr {
 // and the verdict rides back with the counters (same synchronisation): *sym_out = 1 if symmetric.
 // src: where the signatures come from (sdpsr_internal.h: SigSource).  A computed source is
 // evaluated inside the insert kernel; it is written out as an array (src.sig: len entries of
-// scratch) only for the sort path or when the insert kernel has no instance for it.
+// scratch) for the sort / bucket paths, after a table overflow, under SDPSR_FLAG_REFINE_NO_FUSE,
+// or when the insert kernel has no instance for its shape.
 int refine_signatures(sdpsr_ctx* c, int64_t len, const SigSource& src_in, uint32_t* labels,
                       int64_t* nparts, int64_t sym_n, uint32_t* symflag_dev, int* sym_out, bool early) {
     SigSource src = src_in;
     auto materialize = [&]() -> bool {
         if (src.kind == SIG_ARRAY) return true;
-        if (!src.sig) return false;
-        launch_sig_materialize(c->stream, len, src, src.sig);
+        if (!src.sig || !launch_sig_materialize(c->stream, len, src, src.sig)) return false;
         src.kind = SIG_ARRAY;
         return true;
     };
     const bool no_fuse = (c->opts.flags & SDPSR_FLAG_REFINE_NO_FUSE) != 0;  // always through the array
     if ((no_fuse || !sig_source_fusable(src)) && !materialize())
-        return ctx_fail(c, SDPSR_BAD_ARGUMENT, "refine: signature source needs scratch");
+        return ctx_fail(c, SDPSR_BAD_ARGUMENT, "refine: signature source needs scratch and a kernel for its shape");
     // slots of the insert pass: in place for an array source (nothing reads the old labels), a
     // scratch array for a computed source (it may read the old labels from `labels` on a repeated pass)
     uint32_t* slot = (src.kind == SIG_ARRAY) ? labels : (uint32_t*)ctx_buf(c, "ref_slots", (size_t)len * 4);
@@ -133,7 +133,8 @@ int refine_signatures(sdpsr_ctx* c, int64_t len, const SigSource& src_in, uint32
         if (!h) return ctx_fail(c, SDPSR_OUT_OF_MEMORY, "pinned staging");
         ws.host_counters = sym_fused ? nullptr : h;  // the plain label pass stores the counters into the pinned buffer itself
         ws.host_seq = ++c->report_seq ? c->report_seq : ++c->report_seq;
-        launch_refine(c->stream, len, src, slot, labels, ws, sym_fused ? sym_n : 0);
+        if (!launch_refine(c->stream, len, src, slot, labels, ws, sym_fused ? sym_n : 0))
+            return ctx_fail(c, SDPSR_BAD_ARGUMENT, "refine: no insert kernel for this signature source");
         if (!ws.host_counters) HIP_TRY(c, hipMemcpyAsync(h, ws.counters, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         if (sym_n > 0 && symflag_dev && !sym_fused) {
             launch_check_symmetric(c->stream, sym_n, labels, symflag_dev);  // flag = 1 if NOT symmetric

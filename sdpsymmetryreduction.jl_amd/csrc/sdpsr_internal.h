@@ -203,25 +203,23 @@ void launch_proj_coef_lower(hipStream_t s, int64_t n, int64_t r, const double* U
                             uint64_t key, double* partial, int nblk, double* coef);
 void launch_proj_coef_probe(hipStream_t s, int64_t len, int64_t n, int64_t r, const double* U, const uint32_t* L, uint64_t key,
                             double* partial, int nblk, double* coef);
-void launch_proj_apply_lower(hipStream_t s, int64_t n, int64_t r, const double* U, const uint32_t* L, int lab_packed, uint64_t key,
-                             const double* coef, double atol, double scale, uint64_t* sig);
 void launch_proj_apply(hipStream_t s, int64_t len, int64_t r, const double* U, const uint32_t* L,
                        uint64_t key, const double* xin, const double* coef, double atol,
                        double scale, int do_round, double* yout, uint64_t* sig);
 
 // signatures.  sig = 0 <=> (L == 0 and key == 0).  L may be nullptr (all zero labels).
 void launch_sig_f64(hipStream_t s, int64_t len, const uint32_t* L, const double* v, uint64_t* sig);
-void launch_sig_f64_pair(hipStream_t s, int64_t len, const double* a, const double* b, uint64_t* sig);
 void launch_sig_f64_rounded(hipStream_t s, int64_t n, int64_t ld, const uint32_t* L,
                             const double* v, double atol, double scale, uint64_t* sig);
 void launch_sig_u32(hipStream_t s, int64_t len, const uint32_t* L, const uint32_t* k,
                     uint64_t* sig);
 void launch_sig_u64(hipStream_t s, int64_t len, const uint64_t* k, uint64_t* sig);
-// T channels of int32 / f32 squares, padded ld, C[t] at C + t*ld*ld
+// T channels of int32 / f32 squares, padded ld, C[t] at C + t*ld*ld; packed: the lower triangle only, written densely
+// (column j at offset j n - j (j - 1) / 2); lab_packed: L is packed the same way
 void launch_sig_i32(hipStream_t s, int64_t n, int64_t ld, int T, const uint32_t* L,
-                    const int32_t* C, uint64_t* sig, const uint32_t* nonsym_flag = nullptr, int packed = 0, int lab_packed = 0);
+                    const int32_t* C, uint64_t* sig, int packed = 0, int lab_packed = 0);
 void launch_sig_f32(hipStream_t s, int64_t n, int64_t ld, int T, const uint32_t* L,
-                    const float* C, uint64_t* sig, const uint32_t* nonsym_flag = nullptr, int packed = 0, int lab_packed = 0);
+                    const float* C, uint64_t* sig, int packed = 0, int lab_packed = 0);
 
 // canonical relabel of signatures (hash table + first-occurrence ranking).
 // Workspace layout is owned by the caller (see refine_workspace_bytes).
@@ -252,24 +250,25 @@ size_t refine_block_entries();
 size_t refine_counters_bytes();
 uint32_t refine_small_k();
 // Where the insert pass takes its signatures from: an array (SIG_ARRAY), or computed on the fly
-// from the data the matching signature kernel reads (the signatures never travel through HBM).
-// `sig` is the array (SIG_ARRAY) or len entries of scratch for the paths that need one (sort).
+// (the signatures never travel through HBM).  Each kind is defined by one functor of
+// kernels_partition.hip (SrcPair, SrcProj<r>, SrcChan<CT, T>, SrcJoint<r, T>).
+// `sig` is the array (SIG_ARRAY) or len entries of scratch for the paths that need one
+// (launch_sig_materialize: sort / bucket, an overflowed table, a shape without a functor instance).
 enum { SIG_ARRAY = 0, SIG_PAIR = 1, SIG_PROJ = 2, SIG_CHAN_I32 = 3, SIG_CHAN_F32 = 4, SIG_JOINT_I32 = 5 };  // JOINT: SIG_PROJ and SIG_CHAN_I32 fields together (packed)
 struct SigSource {
     int kind = SIG_ARRAY;
     uint64_t* sig = nullptr;
-    const double *a = nullptr, *b = nullptr;                      // SIG_PAIR (launch_sig_f64_pair)
-    const double *U = nullptr, *coef = nullptr;                   // SIG_PROJ (launch_proj_apply, rounded, sig only)
+    const double *a = nullptr, *b = nullptr;                      // SIG_PAIR: bit patterns of (a[e], b[e])
+    const double *U = nullptr, *coef = nullptr;                   // SIG_PROJ: rounded x - U coef, x drawn from L and key; U: r matrices of n x n
     const uint32_t* L = nullptr;                                  // old labels (SIG_PROJ, SIG_CHAN_*)
     int r = 0;
     uint64_t key = 0;
     double atol = 0, scale = 1;
-    int64_t n = 0, ld = 0;                                        // SIG_CHAN_* (launch_sig_i32 / launch_sig_f32)
+    int64_t n = 0, ld = 0;                                        // matrix order (SIG_PROJ, SIG_CHAN_*, SIG_JOINT_I32; SIG_PAIR when packed); ld: SIG_CHAN_* / JOINT: T channels of ld x ld in C
     int T = 0;
     const void* C = nullptr;
     int packed = 0;                                               // lower triangle only, densely packed (symmetric labels; SIG_PROJ: and symmetric basis, needs n)
     int lab_packed = 0;                                           // (with packed) L is the packed lower triangle itself: label of packed entry e = L[e]
-    const uint32_t* zero_flag = nullptr;                          // device constant 0 when packed (the kernels' "lower" flag)
 };
 bool sig_source_fusable(const SigSource& q);
 uint32_t refine_first_cap();
@@ -278,12 +277,12 @@ size_t uconst_ref_bytes(int64_t d, int64_t r);
 bool launch_basis_constant_on_classes(hipStream_t s, int64_t n, int64_t r, const double* U, const uint32_t* Lp, int64_t d,
                                       const uint32_t* first_idx, double atol, double scale, void* ref, uint32_t* flag);
 bool launch_verify_no_split(hipStream_t s, const SigSource& q, int64_t d, const uint32_t* first_idx, void* ref, uint32_t* flag);
-void launch_sig_materialize(hipStream_t s, int64_t len, const SigSource& q, uint64_t* sig);
+bool launch_sig_materialize(hipStream_t s, int64_t len, const SigSource& q, uint64_t* sig);  // false: nothing writes this source out
 // slot: len entries of scratch; labels_out may alias q.L (it is written only by a pass that succeeded)
 // sym_n > 0 (and len == sym_n^2): the label pass also checks the new labels for symmetry, counters[3] = 1 if NOT symmetric
 bool refine_mid_supports(const SigSource& q);  // RefineWs::mid is honoured for this source
-void launch_refine(hipStream_t s, int64_t len, const SigSource& q, uint32_t* slot, uint32_t* labels_out,
-                   const RefineWs& ws, int64_t sym_n = 0);
+bool launch_refine(hipStream_t s, int64_t len, const SigSource& q, uint32_t* slot, uint32_t* labels_out,
+                   const RefineWs& ws, int64_t sym_n = 0);  // false: q is not sig_source_fusable
 
 // kernels_refine_sort.hip: radix-sort relabel for the many-classes regime
 size_t refine_bucketed_workspace_bytes(int64_t len);

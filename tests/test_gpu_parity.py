@@ -1802,3 +1802,68 @@ def test_problem_handle_uploads_once(pkg, problems, golden):
         assert rc != 0 and all(s != 0 for s in st)
         with pytest.raises(ValueError):
             pkg.Problem(setup=setup, ctx=ctx).reduce_batch(2, seeds=[1, 2, 3])
+
+
+# ------------------------------------------------ signature sources: the array path against the fused path
+SIG_INSTANCES = ["petersen", "er7", "esc16j", "closed256", "er7_as_sdp", "open256"]
+
+
+@pytest.fixture(scope="module")
+def sig_instances(pkg, problems, golden):
+    """name -> (setup, expected partition).  The golden problems (esc16j: r > 4, the projection keeps the full matrix and goes
+    through proj_apply_kernel, then the channel source) and the three instances of test_gpu_loop_contract.py: circ256 and er7
+    wrapped as SDPs (closed, everything symmetric: the joint iteration on packed labels; N = 57 is ragged) and theta' of
+    C_16 [] K_16 (open: dimension trajectory 6, 10, 18, 18)."""
+    out = {}
+    for name in ("petersen", "er7", "esc16j"):
+        out[name] = (pkg.admissible_setup(*_problem(problems, name)), golden[f"{name}_P"])
+    out["closed256"] = (pkg.admissible_setup(*problems.partition_as_sdp(golden["circ256_P"].astype(np.int64), seed=1)), golden["circ256_P"])
+    out["er7_as_sdp"] = (pkg.admissible_setup(*problems.partition_as_sdp(golden["er7_P"].astype(np.int64), seed=1)), golden["er7_P"])
+    Cv, A, b, Le, dopen = problems.theta_prime_product_problem(problems.cycle_adjacency(16), problems.symmetric_circulant_labels(16), 16, seed=1)
+    out["open256"] = (pkg.admissible_setup(Cv, A, b), Le)
+    assert out["closed256"][0][0] == out["open256"][0][0] == 256 and out["er7_as_sdp"][0][0] == 57
+    return out
+
+
+def _loop_run(pkg, setup, channels, flags=0, refine_path="auto"):
+    # int8 squares; one confirm round, as the default pair has: a stop is believed after two squares that split nothing
+    with pkg.Context(seed=7, square_mode=pkg.SQUARE_I8, channels=channels, confirm_rounds=1, flags=flags, refine_path=refine_path) as ctx:
+        P = pkg.admissible_subspace(None, None, None, ctx=ctx, setup=setup)
+    return np.array(P.matrix), list(P.dims), P.iterations
+
+
+@pytest.mark.parametrize("channels", [2, 3, 4])
+@pytest.mark.parametrize("name", SIG_INSTANCES)
+def test_signature_array_path_equals_fused_path(pkg, sig_instances, name, channels):
+    """A computed signature source (pair, projection, channels, joint) is defined once, by its functor in
+    kernels_partition.hip; the insert pass evaluates it entry by entry, and SDPSR_FLAG_REFINE_NO_FUSE writes it out as an array
+    first (the materialise kernel, or the stand-alone kernel of a run-time shape: 3 channels, r > 4) and refines that.  Same
+    seed and same control flow, so the same keys and the same signatures either way: labels BIT-IDENTICAL, and the same
+    dimension after every iteration and the same iteration count -- in the default loop (joint iteration on packed labels), with
+    the labels unpacked after every step, and with the reference's two refinements per iteration.  Every result is the golden /
+    generating partition."""
+    setup, expect = sig_instances[name]
+    F = pkg._lib
+    for flags in (0, F.FLAG_UNPACK_EVERY_STEP, F.FLAG_SEPARATE_REFINEMENTS):
+        fused = _loop_run(pkg, setup, channels, flags)
+        array = _loop_run(pkg, setup, channels, flags | F.FLAG_REFINE_NO_FUSE)
+        assert np.array_equal(fused[0], expect), (name, channels, flags)
+        assert np.array_equal(array[0], fused[0]), (name, channels, flags)
+        assert array[1] == fused[1], (name, channels, flags, array[1], fused[1])
+        assert array[2] == fused[2], (name, channels, flags, array[2], fused[2])
+        assert fused[1][-1] == int(expect.max())
+
+
+@pytest.mark.parametrize("channels", [2, 3, 4])
+@pytest.mark.parametrize("name", SIG_INSTANCES)
+def test_forced_relabel_paths_read_the_same_signatures(pkg, sig_instances, name, channels):
+    """refine_path = "sort" / "bucket" (forced at any size) always go through the written-out signatures of the loop's sources:
+    labels bit-identical to refine_path = "auto" and the same final dimension.  (Their control flow differs -- the radix sort
+    leaves no class representatives, so no compare shortcut -- and the trajectory is not compared.)"""
+    setup, expect = sig_instances[name]
+    auto = _loop_run(pkg, setup, channels)
+    assert np.array_equal(auto[0], expect), (name, channels)
+    for path in ("sort", "bucket"):
+        got = _loop_run(pkg, setup, channels, refine_path=path)
+        assert np.array_equal(got[0], auto[0]), (name, channels, path)
+        assert got[1][-1] == auto[1][-1] == int(expect.max()), (name, channels, path, got[1], auto[1])
