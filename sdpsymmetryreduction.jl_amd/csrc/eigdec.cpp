@@ -551,9 +551,10 @@ int dense_diagonalize(sdpsr_ctx* c, int64_t n, const uint32_t* L, const ElemGen*
 
 // C = A' B for skinny outputs: the 128 x 128 output tiling alone would occupy a handful of
 // CUs, so K is split over the batch dimension of the same MFMA kernel and the partial tiles are
-// summed in fixed order.  Requires ldc == m (dense C) -- true for every caller.
+// summed in fixed order.  Requires ldc == m (dense C) -- true for every caller.  `partials` names the ctx buffer of
+// the partial tiles: a caller whose products run on the side stream beside the main stream's passes its own.
 int gemm_tn_splitk(sdpsr_ctx* c, int64_t m, int64_t n, int64_t k, const double* A, int64_t lda, const double* B,
-                   int64_t ldb, double* C, int64_t ldc) {
+                   int64_t ldb, double* C, int64_t ldc, const char* partials) {
     const int64_t tiles = (m / 128) * (n / 128);
     // K is split over Z workgroups per output tile: the largest divisor of the K-tile count that keeps
     // >= 128 of K per workgroup and the launch within ~one workgroup per CU (any divisor, not only
@@ -568,7 +569,7 @@ int gemm_tn_splitk(sdpsr_ctx* c, int64_t m, int64_t n, int64_t k, const double* 
         launch_gemm_tn_f64(c->stream, m, n, k, A, lda, B, ldb, C, ldc, 1, 0, 0, 0);
         return SDPSR_OK;
     }
-    double* P = (double*)ctx_buf(c, "splitk_partials", (size_t)Z * m * n * 8);
+    double* P = (double*)ctx_buf(c, partials, (size_t)Z * m * n * 8);
     if (!P) return SDPSR_OUT_OF_MEMORY;
     const int64_t kz = k / Z;
     launch_gemm_tn_f64(c->stream, m, n, kz, A, lda, B, ldb, P, m, Z, kz, kz, m * n);

@@ -17,12 +17,9 @@ namespace sdpsr {
 size_t sytrd_workspace_doubles(int64_t n, int64_t ld);
 void launch_sytrd(sdpsr_ctx* c, int64_t n, double* A, int64_t ld, double* d, double* e, double* tau, double* ws);
 bool launch_small_syev(hipStream_t s, int64_t n, double* A, int64_t lda, double* w, double* Vtmp, int* info);
-void launch_splitk_reduce(hipStream_t s, int64_t len, int Z, int64_t stride, const double* P, double* C);
 void launch_bt_extract_panel(hipStream_t s, int64_t n, int64_t ld, const double* A, int64_t j0, int64_t r0, double* Vp,
                              double* VpT);
 void launch_bt_larft(hipStream_t s, const double* G, const double* tau, int64_t nblk, int64_t n, double* T);
-void launch_gemm_tn_f64_sub(hipStream_t s, int64_t m, int64_t n, int64_t k, const double* A, int64_t lda, const double* B,
-                            int64_t ldb, double* C, int64_t ldc);
 // kernels_stedc.hip: divide and conquer for the tridiagonal problem
 size_t stedc_workspace_bytes(int64_t ld);
 size_t stedc_descriptors(int64_t ld, std::vector<int>& out);
@@ -30,32 +27,6 @@ void* stedc_descriptor_slot(void* ws, int64_t ld);
 bool launch_stedc(hipStream_t s, int64_t n, int64_t ld, const double* d, const double* e, double* w, double* Z, double* W1, double* W2,
                   void* ws);
 void launch_stedc_check(hipStream_t s, int64_t n, const double* a, const double* b, int pre, int* info);
-
-// C (m x n, dense: ldc == m) = A' B with the K range split over workgroups when the output alone
-// would leave most CUs idle; partial tiles are summed in fixed order.
-static int bt_gemm_splitk(sdpsr_ctx* c, int64_t m, int64_t n, int64_t k, const double* A, int64_t lda, const double* B,
-                          int64_t ldb, double* C) {
-    const int64_t tiles = (m / 128) * (n / 128);
-    // K is split over Z workgroups per output tile: the largest divisor of the K-tile count that keeps
-    // >= 128 of K per workgroup and the launch within ~one workgroup per CU (any divisor, not only
-    // powers of two: ld = 4224 = 33 * 128 at N = 4104 has 264 = 8 * 33 K-tiles)
-    int Z = 1;
-    {
-        const int64_t kt = k / 16;
-        for (int64_t z = 1; z <= kt && tiles * z <= 256; ++z)
-            if (kt % z == 0 && k / z >= 128) Z = (int)z;
-    }
-    if (Z == 1) {
-        launch_gemm_tn_f64(c->stream, m, n, k, A, lda, B, ldb, C, m, 1, 0, 0, 0);
-        return SDPSR_OK;
-    }
-    double* P = (double*)ctx_buf(c, "bt_partials", (size_t)Z * m * n * 8);
-    if (!P) return SDPSR_OUT_OF_MEMORY;
-    const int64_t kz = k / Z;
-    launch_gemm_tn_f64(c->stream, m, n, kz, A, lda, B, ldb, P, m, Z, kz, kz, m * n);
-    launch_splitk_reduce(c->stream, m * n, Z, m * n, P, C);
-    return SDPSR_OK;
-}
 
 // Z <- Q Z with Q = H_0 ... H_{n-2} from the tridiagonalisation (reflectors below the subdiagonal of
 // A, tau): compact-WY blocks of 128 reflectors, last block first, every product on the fp64
@@ -78,7 +49,7 @@ static int backtransform_prepare(sdpsr_ctx* c, int64_t n, const double* A, int64
         const int64_t j0 = 128 * b, r0 = j0, m = ld - r0;
         double* Vp = VpAll + b * ld * 128;
         launch_bt_extract_panel(s, n, ld, A, j0, r0, Vp, VpTAll + b * ld * 128);
-        int st = bt_gemm_splitk(c, 128, 128, m, Vp + r0, ld, Vp + r0, ld, G + b * 128 * 128);  // G_b = V'V
+        int st = gemm_tn_splitk(c, 128, 128, m, Vp + r0, ld, Vp + r0, ld, G + b * 128 * 128, 128, "bt_partials");  // G_b = V'V
         if (st) return st;
     }
     launch_bt_larft(s, G, tau, nblk, n, T);
@@ -99,7 +70,7 @@ static int backtransform_apply(sdpsr_ctx* c, int64_t n, int64_t ld, double* Z) {
     if (!VpAll || !XAll || !W) return SDPSR_OUT_OF_MEMORY;
     for (int64_t b = nblk - 1; b >= 0; --b) {  // the blocks applied last first
         const int64_t r0 = 128 * b, m = ld - r0;
-        int st = bt_gemm_splitk(c, 128, ld, m, VpAll + b * ld * 128 + r0, ld, Z + r0, ld, W);  // W = V' Z
+        int st = gemm_tn_splitk(c, 128, ld, m, VpAll + b * ld * 128 + r0, ld, Z + r0, ld, W, 128, "bt_partials");  // W = V' Z
         if (st) return st;
         launch_gemm_tn_f64_sub(s, m, ld, 128, XAll + b * ld * 128 + r0 * 128, 128, W, 128, Z + r0, ld);  // Z -= (V T) W
     }

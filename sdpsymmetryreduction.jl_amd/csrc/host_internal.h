@@ -242,7 +242,7 @@ int driver_fallback(sdpsr_ctx* c, const std::string& why);
 int dense_diagonalize(sdpsr_ctx* c, int64_t n, const uint32_t* L, const ElemGen* gen, double atol, EigInfo& info,
                       std::vector<int32_t>& sizes, int64_t& S1, int64_t& S, PhaseTimer& tm, int64_t expect_dim = -1);
 int gemm_tn_splitk(sdpsr_ctx* c, int64_t m, int64_t n, int64_t k, const double* A, int64_t lda, const double* B, int64_t ldb,
-                   double* C, int64_t ldc);
+                   double* C, int64_t ldc, const char* partials = "splitk_partials");
 // host_C (optional, pinned host memory, mp x np like C): filled by the product itself when the exact-shape kernel
 // runs; *host_filled says whether it did (the padded split-K path does not)
 int gram_tn(sdpsr_ctx* c, int64_t ma, int64_t nb, int64_t k, const double* A, int64_t lda, const double* B, int64_t ldb, double* C,

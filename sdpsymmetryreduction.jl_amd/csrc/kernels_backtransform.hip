@@ -2,7 +2,7 @@
 // eigenvectors of the tridiagonal T (third phase of eigen(A), src/eigen_decomposition.jl:246;
 // LAPACK dormtr).  Q = H_0 H_1 ... H_{n-2} is applied in blocks of 128 reflectors in compact-WY
 // form, Q_b = I - V_b T_b V_b', last block first, and every O(n^3) step is a product on the fp64
-// matrix cores (gemm_tn_dma_kernel<f64>, kernels_gemm.hip):
+// matrix cores (gemm_tn_dma_kernel<F64, CMODE, 128>, kernels_gemm.hip):
 //     G   = V_b' V_b                  Gram matrix of the panel            (split-K)
 //     T_b = larft(G, tau)             one workgroup, LDS
 //     X   = (V_b T_b)' as rows        128 x m, one small product

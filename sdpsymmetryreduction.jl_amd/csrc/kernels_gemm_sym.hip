@@ -23,47 +23,37 @@
 //
 // Exact integers (int32 accumulation of int8 products, |sum| <= 2^14 ld): the order in which K is consumed is free.
 #include "sdpsr_internal.h"
+#include "mfma_tile.h"
 
 namespace sdpsr {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v16i __attribute__((ext_vector_type(16)));
-typedef __attribute__((address_space(3))) void lds_void_t;
+typedef MfmaTile<KIND_I8> I8Tile;
 
-// 16 bytes per lane global -> LDS, lane-linear at the wave-uniform LDS byte address `lds_dst` (see glds16 in
-// kernels_gemm.hip for why this is inline asm and how it is ordered: explicit counted waits + barriers below)
-__device__ __forceinline__ void glds16_u(const void* gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(gsrc), "s"(lds_dst)
-                 : "memory");
-}
-
-// Source-side XOR swizzle of the 16-byte chunks of an LDS row (slot p of row r holds global chunk p ^ swz(r)) that
-// makes the ds_read_b128 fragment reads conflict-free (lane groups {0-3,12-15,20-27}, {4-11,16-19,28-31} of the b128
-// banking, MI355X_MICROARCH.md): rows of 128 bytes alternate between the two halves of the 64 banks, so the 8 rows of a
-// group with the same parity need 8 different slots; rows of 64 bytes repeat every 4 rows, the 4 rows of a group with
-// the same r mod 4 have (r >> 2) in {0,3,5,6} or {1,2,4,7} and need 4 different slots.
-template <int KB> __device__ __forceinline__ int sym_swz(int r) {
-    if constexpr (KB == 128) return (r >> 1) & 7;
-    else return ((r >> 3) ^ (r >> 2)) & 3;
-}
-
-// Diagonal macro-tile: the 36 blocks (r, c), c <= r, of its 8 x 8 grid of 32 x 32 blocks, dealt to four waves.
-// fr[]: the row blocks a wave reads (a fragment serves as either MFMA operand: both are cut the same way);
-// tr[] / tc[]: positions in fr[] of the row / column block of the wave's nine accumulators.
-struct DiagRole {
-    int nf;
+// What one wave does in one job: the fragments it reads per K-group and the 32 x 32 blocks it accumulates.
+// fr[x]: row block (units of 32 rows) of fragment x inside the wave's part of a panel; fragments x < na come from the
+// wave's row panel, the others from its column panel (a fragment serves as either MFMA operand: both are cut the same
+// way).  Accumulator t multiplies the fragments tr[t] (rows of C) and tc[t] (columns of C) and lands at block
+// (fr[tr[t]], fr[tc[t]]) of the wave's part.  wrows / wcols: rows / columns of the wave's part per step of the wave grid
+// (wi = wave & 1, wj = wave >> 1); 0 x 0: a diagonal macro-tile, a single panel that every wave reads from its start.
+struct SymRole {
+    int wrows, wcols;
+    int nf, na;
     int fr[7];
+    int nacc;
     int tr[9];
     int tc[9];
 };
-__device__ constexpr DiagRole kDiagRoles[4] = {
-    {6, {3, 4, 5, 0, 1, 2, 0}, {0, 0, 0, 1, 1, 1, 2, 2, 2}, {3, 4, 5, 3, 4, 5, 3, 4, 5}},  // rows 3-5 x columns 0-2
-    {7, {6, 7, 0, 1, 2, 3, 4}, {0, 0, 0, 1, 1, 1, 0, 1, 1}, {2, 3, 4, 2, 3, 4, 5, 5, 6}},  // rows 6-7 x columns 0-2, (6,3) (7,3) (7,4)
-    {5, {0, 1, 2, 3, 4, 0, 0}, {0, 1, 1, 2, 2, 2, 3, 4, 4}, {0, 0, 1, 0, 1, 2, 3, 3, 4}},  // triangle of rows 0-2, (3,3) (4,3) (4,4)
-    {5, {3, 4, 5, 6, 7, 0, 0}, {2, 2, 2, 3, 3, 3, 4, 4, 4}, {0, 1, 2, 1, 2, 3, 2, 3, 4}},  // (5,3..5) (6,4..6) (7,5..7)
+enum { ROLE_FULL = 4, ROLE_QUARTER = 5 };
+__device__ constexpr SymRole kSymRoles[6] = {
+    // diagonal macro-tile: the 36 blocks (r, c), c <= r, of its 8 x 8 grid of 32 x 32 blocks, dealt nine to a wave
+    {0, 0, 6, 6, {3, 4, 5, 0, 1, 2, 0}, 9, {0, 0, 0, 1, 1, 1, 2, 2, 2}, {3, 4, 5, 3, 4, 5, 3, 4, 5}},  // rows 3-5 x columns 0-2
+    {0, 0, 7, 7, {6, 7, 0, 1, 2, 3, 4}, 9, {0, 0, 0, 1, 1, 1, 0, 1, 1}, {2, 3, 4, 2, 3, 4, 5, 5, 6}},  // rows 6-7 x columns 0-2, (6,3) (7,3) (7,4)
+    {0, 0, 5, 5, {0, 1, 2, 3, 4, 0, 0}, 9, {0, 1, 1, 2, 2, 2, 3, 4, 4}, {0, 0, 1, 0, 1, 2, 3, 3, 4}},  // triangle of rows 0-2, (3,3) (4,3) (4,4)
+    {0, 0, 5, 5, {3, 4, 5, 6, 7, 0, 0}, 9, {2, 2, 2, 3, 3, 3, 4, 4, 4}, {0, 1, 2, 1, 2, 3, 2, 3, 4}},  // (5,3..5) (6,4..6) (7,5..7)
+    // full macro-tile (256 x 256): the wave's 128 x 64 part, rows from panel A, columns from panel B
+    {128, 64, 6, 4, {0, 1, 2, 3, 0, 1, 0}, 8, {0, 1, 2, 3, 0, 1, 2, 3, 0}, {4, 4, 4, 4, 5, 5, 5, 5, 0}},
+    // quarter tile (128 x 128): the wave's 64 x 32 part
+    {64, 32, 3, 2, {0, 1, 0, 0, 0, 0, 0}, 2, {0, 1, 0, 0, 0, 0, 0, 0, 0}, {2, 2, 0, 0, 0, 0, 0, 0, 0}},
 };
 
 struct SymSquareArgs {
@@ -93,28 +83,27 @@ template <int KB> struct SymCfg {
 // what a wave needs to walk K for one job
 struct SymLane {
     unsigned lds0;  // LDS byte address of the ring
-    int wave, lane_off, r32, h;
+    int wave, lane, lane_off;  // lane_off: the lane's row inside a 32-row block, in bytes
 };
 
-// One job of one wave: ROLE -1 = its 128 x 64 part of a full macro-tile (rows from panel A, columns from panel B),
-// ROLE -2 = its 64 x 32 part of a 128 x 128 "quarter" tile (the ragged last 128 rows / columns of a matrix whose order
-// is an odd multiple of 128: panels of 128 rows, half the DMA instructions),
-// ROLE 0..3 = nine blocks of a diagonal macro-tile (waves 0-3: the tile of panel A, waves 4-7: that of panel B).
-// Every wave of the workgroup passes the same nk + 1 barriers whatever its role.
+// One job of one wave: ROLE_FULL = its part of a full macro-tile, ROLE_QUARTER = its part of a 128 x 128 "quarter" tile
+// (the ragged last 128 rows / columns of a matrix whose order is an odd multiple of 128: panels of 128 rows, half the
+// DMA instructions), ROLE 0..3 = nine blocks of a diagonal macro-tile (waves 0-3: the tile of panel A, waves 4-7: that
+// of panel B).  Every wave of the workgroup passes the same nk + 1 barriers whatever its role.
 template <int KB, int ROLE, bool LATE>
 __device__ __forceinline__ void sym_job(const SymLane& L, const char* smem, const int8_t* pA, const int8_t* pB, int32_t* Cout, int64_t ldc,
-                                        int nk, const int (&soff)[ROLE == -2 ? 1 : SymCfg<KB>::IPW], const int (&coff)[SymCfg<KB>::NQ]) {
+                                        int nk, const int (&soff)[ROLE == ROLE_QUARTER ? 1 : SymCfg<KB>::IPW], const int (&coff)[SymCfg<KB>::NQ]) {
     typedef SymCfg<KB> CF;
-    constexpr bool QUARTER = ROLE == -2;
-    constexpr int NACC = QUARTER ? 2 : (ROLE < 0 ? 8 : 9);
+    constexpr SymRole R = kSymRoles[ROLE];
+    constexpr bool QUARTER = ROLE == ROLE_QUARTER;
     constexpr int NIS = QUARTER ? 1 : CF::IPW;  // DMA instructions per wave, panel and stage
     const int wave = L.wave;
     const int wi = wave & 1, wj = wave >> 1;
-    v16i acc[NACC];
+    I8Tile::acc_t acc[R.nacc];
 #pragma unroll
-    for (int t = 0; t < NACC; ++t)
+    for (int t = 0; t < R.nacc; ++t)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0;
+        for (int r = 0; r < I8Tile::NR; ++r) acc[t][r] = 0;
 
     auto issue = [&](int slot, int kt) {
         const unsigned dst = L.lds0 + (unsigned)(slot * CF::STAGE + wave * NIS * 1024);
@@ -122,67 +111,33 @@ __device__ __forceinline__ void sym_job(const SymLane& L, const char* smem, cons
         const char* gb = reinterpret_cast<const char*>(pB) + (int64_t)kt * KB;
 #pragma unroll
         for (int s = 0; s < NIS; ++s) {
-            glds16_u(ga + soff[s], dst + s * 1024);
-            glds16_u(gb + soff[s], dst + CF::OPB + s * 1024);
+            glds16(ga + soff[s], dst + s * 1024);
+            glds16(gb + soff[s], dst + CF::OPB + s * 1024);
         }
     };
 #pragma unroll
     for (int st = 0; st < CF::D; ++st)
         if (st < nk) issue(st, st);
 
-    // fragments of one 32-byte K-group and the MFMAs on them, by role
-    constexpr int NFR = QUARTER ? 3 : (ROLE < 0 ? 6 : kDiagRoles[ROLE < 0 ? 0 : ROLE].nf);
-    auto load = [&](uint4 (&F)[NFR], const char* sA, const char* sB, int q) {
-        if constexpr (QUARTER) {
+    // fragments of one 32-byte K-group and the MFMAs on them
+    typedef I8Tile::frag_t frag_t;
+    auto load = [&](frag_t (&F)[R.nf], const char* sA, const char* sB, int q) {
+        const char* rows = R.wrows ? sA + wi * R.wrows * KB : (wave < 4 ? sA : sB);
+        const char* cols = sB + wj * R.wcols * KB;
 #pragma unroll
-            for (int t = 0; t < 2; ++t) F[t] = *reinterpret_cast<const uint4*>(sA + (wi * 64 + t * 32) * KB + L.lane_off + coff[q]);
-            F[2] = *reinterpret_cast<const uint4*>(sB + (wj * 32) * KB + L.lane_off + coff[q]);
-        } else if constexpr (ROLE < 0) {
-#pragma unroll
-            for (int t = 0; t < 4; ++t) F[t] = *reinterpret_cast<const uint4*>(sA + (wi * 128 + t * 32) * KB + L.lane_off + coff[q]);
-#pragma unroll
-            for (int t = 0; t < 2; ++t) F[4 + t] = *reinterpret_cast<const uint4*>(sB + (wj * 64 + t * 32) * KB + L.lane_off + coff[q]);
-        } else {
-            constexpr DiagRole R = kDiagRoles[ROLE < 0 ? 0 : ROLE];
-            const char* sP = (wave < 4) ? sA : sB;
-#pragma unroll
-            for (int x = 0; x < R.nf; ++x) F[x] = *reinterpret_cast<const uint4*>(sP + R.fr[x] * 32 * KB + L.lane_off + coff[q]);
-        }
+        for (int x = 0; x < R.nf; ++x)
+            F[x] = *reinterpret_cast<const frag_t*>((x < R.na ? rows : cols) + R.fr[x] * 32 * KB + L.lane_off + coff[q]);
     };
-    auto mma = [&](const uint4 (&F)[NFR]) {
-        if constexpr (QUARTER) {
+    auto mma = [&](const frag_t (&F)[R.nf]) {
 #pragma unroll
-            for (int ti = 0; ti < 2; ++ti) {
-                v4i av = {(int)F[2].x, (int)F[2].y, (int)F[2].z, (int)F[2].w};
-                v4i bv = {(int)F[ti].x, (int)F[ti].y, (int)F[ti].z, (int)F[ti].w};
-                acc[ti] = __builtin_amdgcn_mfma_i32_32x32x32_i8(av, bv, acc[ti], 0, 0, 0);
-            }
-        } else if constexpr (ROLE < 0) {
-#pragma unroll
-            for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-                for (int ti = 0; ti < 4; ++ti) {
-                    v4i av = {(int)F[4 + tj].x, (int)F[4 + tj].y, (int)F[4 + tj].z, (int)F[4 + tj].w};
-                    v4i bv = {(int)F[ti].x, (int)F[ti].y, (int)F[ti].z, (int)F[ti].w};
-                    acc[tj * 4 + ti] = __builtin_amdgcn_mfma_i32_32x32x32_i8(av, bv, acc[tj * 4 + ti], 0, 0, 0);
-                }
-        } else {
-            constexpr DiagRole R = kDiagRoles[ROLE < 0 ? 0 : ROLE];
-#pragma unroll
-            for (int t = 0; t < 9; ++t) {
-                const uint4 fa = F[R.tc[t]], fb = F[R.tr[t]];
-                v4i av = {(int)fa.x, (int)fa.y, (int)fa.z, (int)fa.w};
-                v4i bv = {(int)fb.x, (int)fb.y, (int)fb.z, (int)fb.w};
-                acc[t] = __builtin_amdgcn_mfma_i32_32x32x32_i8(av, bv, acc[t], 0, 0, 0);
-            }
-        }
+        for (int t = 0; t < R.nacc; ++t) I8Tile::step(F[R.tc[t]], F[R.tr[t]], acc[t]);
     };
 
     // The two waves of a SIMD (w and w + 4) walk K half a stage apart: waves 4-7 ("late") keep the fragments of a
     // stage's last K-group in registers across the barrier and multiply them right behind it, while waves 0-3 wait for
     // their first reads of the new stage.
     constexpr bool late = LATE;
-    uint4 Fc[NFR];  // the late group's carried fragments
+    frag_t Fc[R.nf];  // the late group's carried fragments
     for (int kt = 0; kt < nk; ++kt) {
         // stage kt has landed once at most the D - 1 younger stages of this wave are outstanding
         if (kt + CF::D - 1 < nk) {
@@ -199,7 +154,7 @@ __device__ __forceinline__ void sym_job(const SymLane& L, const char* smem, cons
         if constexpr (!late) {
 #pragma unroll
             for (int q = 0; q < CF::NQ; ++q) {
-                uint4 F[NFR];
+                frag_t F[R.nf];
                 load(F, sA, sB, q);
                 mma(F);
             }
@@ -207,7 +162,7 @@ __device__ __forceinline__ void sym_job(const SymLane& L, const char* smem, cons
             if (kt > 0) mma(Fc);
 #pragma unroll
             for (int q = 0; q < CF::NQ - 1; ++q) {
-                uint4 F[NFR];
+                frag_t F[R.nf];
                 load(F, sA, sB, q);
                 mma(F);
             }
@@ -219,33 +174,10 @@ __device__ __forceinline__ void sym_job(const SymLane& L, const char* smem, cons
     }
     __syncthreads();  // the ring is free for the next job's first stages
 
-    // ---- results: D[jj][ii], ii = lane & 31, jj = (reg & 3) + 8 (reg >> 2) + 4 h ----
     if (!Cout) return;
-    if constexpr (QUARTER) {
 #pragma unroll
-        for (int ti = 0; ti < 2; ++ti) {
-            int32_t* Ct = Cout + (wi * 64 + ti * 32 + L.r32) + (int64_t)(wj * 32 + 4 * L.h) * ldc;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) Ct[(int64_t)((r & 3) + 8 * (r >> 2)) * ldc] = acc[ti][r];
-        }
-    } else if constexpr (ROLE < 0) {
-#pragma unroll
-        for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-            for (int ti = 0; ti < 4; ++ti) {
-                int32_t* Ct = Cout + (wi * 128 + ti * 32 + L.r32) + (int64_t)(wj * 64 + tj * 32 + 4 * L.h) * ldc;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) Ct[(int64_t)((r & 3) + 8 * (r >> 2)) * ldc] = acc[tj * 4 + ti][r];
-            }
-    } else {
-        constexpr DiagRole R = kDiagRoles[ROLE < 0 ? 0 : ROLE];
-#pragma unroll
-        for (int t = 0; t < 9; ++t) {
-            int32_t* Ct = Cout + (R.fr[R.tr[t]] * 32 + L.r32) + (int64_t)(R.fr[R.tc[t]] * 32 + 4 * L.h) * ldc;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) Ct[(int64_t)((r & 3) + 8 * (r >> 2)) * ldc] = acc[t][r];
-        }
-    }
+    for (int t = 0; t < R.nacc; ++t)
+        mfma_store<KIND_I8>(acc[t], Cout, ldc, wi * R.wrows + R.fr[R.tr[t]] * 32, wj * R.wcols + R.fr[R.tc[t]] * 32, L.lane);
 }
 
 template <int KB>
@@ -256,10 +188,9 @@ __global__ void __launch_bounds__(SYM_NT) i8_symsquare_kernel(SymSquareArgs a) {
     const int lane = tid & 63;
     SymLane L;
     L.wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    L.r32 = lane & 31;
-    L.h = lane >> 5;
-    L.lds0 = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(lds_void_t*)smem);
-    L.lane_off = L.r32 * KB;
+    L.lane = lane;
+    L.lds0 = lds_address(smem);
+    L.lane_off = I8Tile::row(lane) * KB;
     const int wave = L.wave;
 
     const bool sym = a.nonsym_flag && *a.nonsym_flag == 0u;  // uniform
@@ -278,33 +209,27 @@ __global__ void __launch_bounds__(SYM_NT) i8_symsquare_kernel(SymSquareArgs a) {
 #pragma unroll
     for (int s = 0; s < CF::IPW; ++s) {
         const int r = (wave * CF::IPW + s) * CF::RPI + lane / CF::CH;
-        const int c = (lane % CF::CH) ^ sym_swz<KB>(r);
+        const int c = (lane % CF::CH) ^ dma_swz<KB>(r);
         soff[s] = r * (int)a.ldx + c * 16;
     }
     int soffq[1];  // quarter tiles: this wave's 16 rows of a 128-row panel
     {
         const int r = wave * CF::RPI + lane / CF::CH;
-        soffq[0] = r * (int)a.ldx + ((lane % CF::CH) ^ sym_swz<KB>(r)) * 16;
+        soffq[0] = r * (int)a.ldx + ((lane % CF::CH) ^ dma_swz<KB>(r)) * 16;
     }
-    // fragment reads: row r32 of a 32-row block, chunk 2 q + h, un-swizzled
+    // fragment reads: the lane's row of a 32-row block, its chunk of K-group q, un-swizzled
     int coff[CF::NQ];
 #pragma unroll
-    for (int q = 0; q < CF::NQ; ++q) coff[q] = ((2 * q + L.h) ^ sym_swz<KB>(L.r32)) << 4;
+    for (int q = 0; q < CF::NQ; ++q) coff[q] = (I8Tile::chunk(q, I8Tile::grp(lane)) ^ dma_swz<KB>(I8Tile::row(lane))) << 4;
 
     for (int job = blockIdx.x; job < NJ; job += gridDim.x) {
         if (job < NF) {
-            // workgroup b sits on XCD b % 8: every XCD gets one contiguous run of the tile sequence (neighbours in
-            // the run share operand panels through that XCD's L2); the last NF % 8 jobs keep their number
-            const int per = NF >> 3;
-            const int f = (job < 8 * per) ? (job & 7) * per + (job >> 3) : job;
+            const int f = xcd_run(job, NF);
             int c, I, J;
             if (sym) {
                 c = f / tri;
-                const int t = f - c * tri;  // strictly lower macro-tiles, row-major: (I, J), J < I, I = 1 .. m - 1
-                I = (int)((1.0f + sqrtf(1.0f + 8.0f * (float)t)) * 0.5f);
-                while (I * (I - 1) / 2 > t) --I;
-                while ((I + 1) * I / 2 <= t) ++I;
-                J = t - I * (I - 1) / 2;
+                tri_decode(f - c * tri, I, J);  // strictly lower macro-tiles, row-major: (I, J), J < I, I = 1 .. m - 1
+                ++I;
             } else {
                 c = f / (m * m);
                 const int t = f - c * m * m;
@@ -314,8 +239,8 @@ __global__ void __launch_bounds__(SYM_NT) i8_symsquare_kernel(SymSquareArgs a) {
             const int8_t* pA = a.X + (int64_t)c * a.strideX + (int64_t)I * 256 * a.ldx;
             const int8_t* pB = a.X + (int64_t)c * a.strideX + (int64_t)J * 256 * a.ldx;
             int32_t* cA = a.C + (int64_t)c * a.strideC + (int64_t)I * 256 + (int64_t)J * 256 * a.ldc;
-            if (wave < 4) sym_job<KB, -1, false>(L, smem, pA, pB, cA, a.ldc, nk, soff, coff);
-            else sym_job<KB, -1, true>(L, smem, pA, pB, cA, a.ldc, nk, soff, coff);
+            if (wave < 4) sym_job<KB, ROLE_FULL, false>(L, smem, pA, pB, cA, a.ldc, nk, soff, coff);
+            else sym_job<KB, ROLE_FULL, true>(L, smem, pA, pB, cA, a.ldc, nk, soff, coff);
         } else if (job >= NF + ND) {
             // quarter tile of the ragged border: unit row 2 m x unit column u (u <= 2 m), or -- full squares only --
             // unit row u - (2 m + 1) x unit column 2 m
@@ -325,8 +250,8 @@ __global__ void __launch_bounds__(SYM_NT) i8_symsquare_kernel(SymSquareArgs a) {
             const int8_t* pA = a.X + (int64_t)c * a.strideX + (int64_t)ur * 128 * a.ldx;
             const int8_t* pB = a.X + (int64_t)c * a.strideX + (int64_t)uc * 128 * a.ldx;
             int32_t* cQ = a.C + (int64_t)c * a.strideC + (int64_t)ur * 128 + (int64_t)uc * 128 * a.ldc;
-            if (wave < 4) sym_job<KB, -2, false>(L, smem, pA, pB, cQ, a.ldc, nk, soffq, coff);
-            else sym_job<KB, -2, true>(L, smem, pA, pB, cQ, a.ldc, nk, soffq, coff);
+            if (wave < 4) sym_job<KB, ROLE_QUARTER, false>(L, smem, pA, pB, cQ, a.ldc, nk, soffq, coff);
+            else sym_job<KB, ROLE_QUARTER, true>(L, smem, pA, pB, cQ, a.ldc, nk, soffq, coff);
         } else {
             const int d1 = 2 * (job - NF), d2 = d1 + 1;
             const int c1 = d1 / m, I1 = d1 - c1 * m;

@@ -653,9 +653,6 @@ dc_finish_kernel(int n, int ld, const double* __restrict__ D, const double* __re
         for (int i = threadIdx.x; i < n; i += DC_THREADS) w[i] = D[i] * sc;
 }
 
-void launch_gemm_tn_f64(hipStream_t s, int64_t m, int64_t n, int64_t k, const double* A, int64_t lda, const double* B, int64_t ldb, double* C,
-                        int64_t ldc, int batch, int64_t strideA, int64_t strideB, int64_t strideC);
-
 size_t stedc_workspace_bytes(int64_t ld) {
     // doubles: D, Dn, E, scale(8), dl, wz, dfval, lam, mu, zhat, rho, sd, sz (13 ld) + rotc (2 ld); ints: ndorig, dforig, Kidx, so, f0, f1, p0,
     // runoff (2 ld) (9 ld) + meta (4 ld) + rotab (2 ld); descriptors

@@ -566,7 +566,7 @@ typedef double sy_v4d __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void sy_lds_void_t;
 typedef const __attribute__((address_space(1))) void sy_gbl_void_t;
 
-// 16-byte-per-lane global -> LDS DMA through inline asm (see glds16 in kernels_gemm.hip: the
+// 16-byte-per-lane global -> LDS DMA through inline asm (see glds16 in mfma_tile.h: the
 // builtin makes the compiler drain the VM counter in front of every LDS read, which would void the
 // counted waits below)
 __device__ __forceinline__ void sy_glds16(const void* gsrc, const void* lds_dst_generic) {

@@ -403,6 +403,9 @@ void launch_gemm_tn_f32(hipStream_t s, int64_t m, int64_t n, int64_t k, const fl
 void launch_gemm_tn_f64(hipStream_t s, int64_t m, int64_t n, int64_t k, const double* A,
                         int64_t lda, const double* B, int64_t ldb, double* C, int64_t ldc,
                         int batch, int64_t strideA, int64_t strideB, int64_t strideC);
+// C -= A' * B
+void launch_gemm_tn_f64_sub(hipStream_t s, int64_t m, int64_t n, int64_t k, const double* A, int64_t lda, const double* B,
+                            int64_t ldb, double* C, int64_t ldc);
 
 // ---------------------------------------------------------------------------
 // kernels_blockdiag.hip

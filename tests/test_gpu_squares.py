@@ -5,7 +5,8 @@ for fp64 on real data, and closed-form partitions for the loop in its fp32 / fp6
 Branches, from launch_gemm() and launch_i8_symsquare().  Every ABI entry pads its operands (K to 128 int8, 32 floats
 or 16 doubles per K-tile of 128 bytes, 16-byte aligned rows), so the LDS-DMA kernels always run:
   * int8 / fp32 with m, n multiples of 256 and >= 1024 workgroups of 256 x 256 (full: (m/256)(n/256) per channel;
-    lower triangle: t2 (t2 + 1) / 2 with t2 = m/256) -> gemm_tn_dma256_kernel, otherwise gemm_tn_dma_kernel (128 x 128);
+    lower triangle: t2 (t2 + 1) / 2 with t2 = m/256) -> gemm_tn_dma_kernel<KIND, 0, 256>, otherwise
+    gemm_tn_dma_kernel<KIND, CMODE, 128> ("dma128" below);
   * full grids are XCD-swizzled when gm % 8 == 0 and gm gn % 8 == 0 (gm = m / tile, gn = n / tile); lower-triangle
     grids deal the ntri = gm (gm + 1) / 2 tiles in 8 runs of ntri / 8, the last ntri % 8 keep their own number;
   * sdpsr_square_i8_symmetric with square_kernel != 1 takes the persistent i8_symsquare_kernel when
@@ -13,23 +14,23 @@ or 16 doubles per K-tile of 128 bytes, 16-byte aligned rows), so the LDS-DMA ker
 
   entry point                       shape                      ld / grid                    branch
   sdpsr_square_i8 / _f32            n = 1100                   1152, 9 x 9                  dma128, unswizzled
-                                    n = 8192, 8100             8192, 32 x 32 (256-tiles)    dma256<I8/F32> full, swizzled
+                                    n = 8192, 8100             8192, 32 x 32 (256-tiles)    gemm_tn_dma_kernel<I8/F32, 0, 256> full, swizzled
                                     n = 8200                   8320, 65 x 65                dma128, unswizzled, 4225 wgs
   sdpsr_square_f32                  n = 4096, +-vmax constant  4096, 32 x 32                dma128, swizzled, sums 2^24
   sdpsr_square_f64                  n = 1024 / 1100 / 8192     8 x 8 / 9 x 9 / 64 x 64      dma128 swz / unswz / swz large
   sdpsr_gemm_tn_f64                 (1024, 640, 777)           8 x 5, K 777 -> 784          dma128 swizzled, gm != gn
                                     (1000, 1500, 300)          8 x 12, K 300 -> 304         dma128 swizzled, gm != gn
                                     (1000, 1016, 333), lda 345, ldb 340, ldc 1009  8 x 8   leading dimensions
-  sdpsr_square_i8_symmetric, sk 1   (4096, 8), (8192, 2)       136 x 8, 528 x 2 triangles   dma256<I8> lower
+  sdpsr_square_i8_symmetric, sk 1   (4096, 8), (8192, 2)       136 x 8, 528 x 2 triangles   gemm_tn_dma_kernel<I8, 0, 256> lower
                            , sk 1   (4096, 2)                  gm 32: 528 = 8 x 66 tiles    dma128 lower, all renumbered
                            , sk 1   (4104, 3)                  4224, gm 33: 561 = 8 x 70 + 1  dma128 lower, 1 keeps its number
                            , sk 0   (8192, 2), (4096, 8)       1024 jobs on 256 CUs         persistent i8_symsquare_kernel
-  loop fp32, closed_scheme N 4096   channels 0 (2) / 8         272 / 1088 lower tiles       dma128 lower / dma256<F32> lower
+  loop fp32, closed_scheme N 4096   channels 0 (2) / 8         272 / 1088 lower tiles       dma128 lower / gemm_tn_dma_kernel<F32, 0, 256> lower
   loop fp32, theta_er7xk72 N 4104   channels 0 / 8             4224: not a multiple of 256  dma128 lower
   loop fp64, both                   4096 / 4224                32 x 32 / 33 x 33            dma128<F64> swizzled / unswizzled
   loop non-symmetric (int8, fp32)   n = 300, 1100              384 / 1152: 3 x 3 / 9 x 9    dma128 full, batch stride
                                     n = 4096, channels 0 (2)   32 x 32 x 2                  dma128 full, swizzled
-                                    n = 4096, channels 4       16 x 16 x 4 = 1024 256-tiles dma256<I8/F32> full, batch stride
+                                    n = 4096, channels 4       16 x 16 x 4 = 1024 256-tiles gemm_tn_dma_kernel<I8/F32, 0, 256> full, batch stride
 
 Checking cost: a full fp64 host product up to about 0.3 TFLOP in all; beyond that (n >= 8100, batches of 8, the
 ragged 4104 x 3) an exact O(n^2) check: Freivalds with 3 random integer vectors plus every row and column at a
@@ -106,7 +107,7 @@ def _square(lib, ctx, fn, X, in_dt, out_dt):
 # ------------------------------------------------------------------ int8 and fp32 full squares
 @pytest.mark.parametrize("n", [1100, 8192, 8100, 8200])
 def test_square_i8_every_launch(pkg, gpu_ctx, n):
-    """sdpsr_square_i8: n = 1100 dma128 unswizzled (gm 9); 8192 / 8100 gemm_tn_dma256_kernel<I8> full, swizzled, 8100
+    """sdpsr_square_i8: n = 1100 dma128 unswizzled (gm 9); 8192 / 8100 gemm_tn_dma_kernel<I8, 0, 256> full, swizzled, 8100
     with a zero-padded border; 8200 dma128 gm 65 unswizzled, large grid.  Full int8 range; at 8192 also the all -128
     matrix (every sum n * 16384 = 2^27, the largest magnitude)."""
     lib = pkg.load_library()
@@ -123,7 +124,7 @@ def test_square_i8_every_launch(pkg, gpu_ctx, n):
 def test_square_f32_every_launch(pkg, gpu_ctx, n):
     """sdpsr_square_f32 on integers in [-vmax, vmax], vmax = floor(sqrt(2^24 / n)) (the loop's rule, loop.cpp): every
     sum is an integer <= 2^24, exact in fp32.  n = 1100 dma128 unswizzled (gm 9); 8192 / 8100
-    gemm_tn_dma256_kernel<F32> full, swizzled (8100 padded); 8200 dma128 gm 65 unswizzled."""
+    gemm_tn_dma_kernel<F32, 0, 256> full, swizzled (8100 padded); 8200 dma128 gm 65 unswizzled."""
     lib = pkg.load_library()
     vmax = int(np.floor(np.sqrt(2 ** 24 / n)))
     X = _sym_int(np.random.default_rng(n), n, vmax, np.float32)
@@ -202,7 +203,7 @@ def test_gemm_tn_f64_shapes(pkg, gpu_ctx, m, n, k, lda, ldb, ldc):
 ])
 def test_square_i8_symmetric_every_launch(pkg, kernel, n, batch):
     """sdpsr_square_i8_symmetric (lower-triangle tiles, upper mirrored).  square_kernel 1: (4096, 8) and (8192, 2)
-    gemm_tn_dma256_kernel<I8> lower-triangle mapping; (4096, 2) dma128 lower, 528 tiles all renumbered; (4104, 3)
+    gemm_tn_dma_kernel<I8, 0, 256> lower-triangle mapping; (4096, 2) dma128 lower, 528 tiles all renumbered; (4104, 3)
     dma128 lower, gm 33, the last of 561 tiles keeps its number.  Default kernel: (8192, 2) (the bench's N = 8192
     shape) and (4096, 8) persistent i8_symsquare_kernel, 1024 jobs.  Batches of 8 carry one all -128 matrix."""
     lib = pkg.load_library()
@@ -232,7 +233,7 @@ def bench_case(request, pkg, problems, golden):
 def test_bench_instances_every_square_mode(pkg, bench_case, mode, channels):
     """The bench instances in the fp32 and fp64 square modes must reach the generator's partition bit for bit
     (README: P.matrix is the same in all three modes).  closed_scheme, N = 4096: fp32 with 2 channels squares in
-    dma128 lower tiles, with 8 channels in gemm_tn_dma256_kernel<F32> lower tiles (vmax = 64: sums up to 2^24);
+    dma128 lower tiles, with 8 channels in gemm_tn_dma_kernel<F32, 0, 256> lower tiles (vmax = 64: sums up to 2^24);
     fp64 in dma128 swizzled.  theta_er7xk72, N = 4104 (ld 4224): dma128 lower / unswizzled fp64.  closed_scheme is
     closed: one iteration in every mode."""
     name, setup, L, d, iters = bench_case
@@ -253,7 +254,7 @@ def test_nonsymmetric_loop_closes_the_directed_cycle(pkg, problems, mode, n, cha
     non-symmetric, so every square is X X literally (left operand from the transposed labels, full -- not
     lower-triangle -- batched squares), and the closure is all n circulant classes, label ((i - j) mod n) + 1
     (pinned against the oracle in test_oracle_golden.py).  n = 300 / 1100: dma128 3 x 3 / 9 x 9; n = 4096,
-    2 channels: dma128 32 x 32 swizzled; 4 channels: gemm_tn_dma256_kernel<I8/F32> full with batch stride."""
+    2 channels: dma128 32 x 32 swizzled; 4 channels: gemm_tn_dma_kernel<I8/F32, 0, 256> full with batch stride."""
     S = problems.directed_cycle_adjacency(n)
     setup = (n, S.ravel(order="F"), np.zeros(n * n), np.zeros((n * n, 0), order="F"))
     sq = {"i8": pkg.SQUARE_I8, "f32": pkg.SQUARE_F32}[mode]
