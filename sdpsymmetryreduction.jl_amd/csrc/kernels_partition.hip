@@ -2476,22 +2476,28 @@ void launch_transpose_labels(hipStream_t s, int64_t n, const uint32_t* L, uint32
 // PMat[e, i] = 1[L[e] == i], i.e. the columns of A (m x n^2, column-major) summed per class.
 // One wave per chunk of entries: lanes own the rows of A (m <= 64 per pass), the per-class
 // accumulators sit in LDS, entries are walked in order (fixed summation order); chunk partials
-// are added in chunk order by the second kernel.
+// are added in chunk order by the second kernel.  A label beyond d has no accumulator: its entry
+// is skipped (counted like label 0) and the flag raised, as fill_f64_kernel does.
 // ---------------------------------------------------------------------------
 __global__ void __launch_bounds__(64)
 reduce_columns_kernel(int64_t len, int64_t chunk, int m, int d, const uint32_t* __restrict__ L,
-                      const double* __restrict__ A, double* __restrict__ partial) {
+                      const double* __restrict__ A, double* __restrict__ partial, uint32_t* __restrict__ bad_flag) {
     extern __shared__ __attribute__((aligned(16))) double s_bins[];  // [(d + 1)][mw]
     const int lane = threadIdx.x;
     const int64_t e0 = (int64_t)blockIdx.x * chunk;
     int64_t e1 = e0 + chunk;
     if (e1 > len) e1 = len;
+    bool bad = false;
     for (int r0 = 0; r0 < m; r0 += 64) {
         const int mw = (m - r0 < 64) ? m - r0 : 64;
         for (int t = lane; t < (d + 1) * mw; t += 64) s_bins[t] = 0.0;
         __syncthreads();
         for (int64_t eb = e0; eb < e1; eb += 64) {
-            const uint32_t mylab = (eb + lane < e1) ? L[eb + lane] : 0u;
+            uint32_t mylab = (eb + lane < e1) ? L[eb + lane] : 0u;
+            if (mylab > (uint32_t)d) {  // never index s_bins past its (d + 1) rows
+                bad = true;
+                mylab = 0u;
+            }
             const int lim = (int)((e1 - eb < 64) ? e1 - eb : 64);
             for (int u = 0; u < lim; ++u) {
                 const uint32_t lb = __shfl(mylab, u, 64);
@@ -2505,6 +2511,7 @@ reduce_columns_kernel(int64_t len, int64_t chunk, int m, int d, const uint32_t* 
         }
         __syncthreads();
     }
+    if (bad) *bad_flag = 1u;
 }
 __global__ void reduce_columns_final_kernel(int64_t nchunks, int m, int d, const double* __restrict__ partial,
                                             double* __restrict__ out) {
@@ -2533,13 +2540,13 @@ int64_t reduce_columns_chunk(int64_t len, int64_t m, int64_t d) {
     return chunk;
 }
 bool launch_reduce_columns(hipStream_t s, int64_t len, int64_t m, int64_t d, const uint32_t* L, const double* A,
-                           double* partial, double* out) {
+                           double* partial, double* out, uint32_t* bad_flag) {
     const int mw = (int)(m < 64 ? m : 64);
     const size_t lds = (size_t)(d + 1) * mw * 8;
     if (lds > 60 * 1024) return false;
     const int64_t chunk = reduce_columns_chunk(len, m, d);
     const int64_t nch = (len + chunk - 1) / chunk;
-    reduce_columns_kernel<<<(unsigned)nch, 64, lds, s>>>(len, chunk, (int)m, (int)d, L, A, partial);
+    reduce_columns_kernel<<<(unsigned)nch, 64, lds, s>>>(len, chunk, (int)m, (int)d, L, A, partial, bad_flag);
     reduce_columns_final_kernel<<<(unsigned)((m * d + 255) / 256), 256, 0, s>>>(nch, (int)m, (int)d, partial, out);
     return true;
 }

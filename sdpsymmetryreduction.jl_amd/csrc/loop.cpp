@@ -674,11 +674,18 @@ int sdpsr_reduce_constraints(sdpsr_ctx* c, int64_t len, const uint32_t* labels, 
     double* dO = out_dev(c, "red_out", out, (size_t)m * d, mem, &st);
     const int64_t chunk = reduce_columns_chunk(len, m, d);
     double* part = (double*)ctx_buf(c, "red_part", (size_t)((len + chunk - 1) / chunk) * d * m * 8);
-    if (st || !part) return st ? st : SDPSR_OUT_OF_MEMORY;
-    if (!launch_reduce_columns(c->stream, len, m, d, dL, dA, part, dO))
+    // labels beyond d never index the accumulators (the kernel skips the entry and raises the flag)
+    uint32_t* flag = (uint32_t*)ctx_buf(c, "prim_flag", 64);
+    if (st || !part || !flag || !c->pinned_small) return st ? st : SDPSR_OUT_OF_MEMORY;
+    HIP_TRY(c, hipMemsetAsync(flag, 0, 4, c->stream));
+    if (!launch_reduce_columns(c->stream, len, m, d, dL, dA, part, dO, flag))
         return ctx_fail(c, SDPSR_BAD_ARGUMENT, "dim(P) * min(m, 64) too large for the LDS accumulators");
     HIP_TRY(c, hipGetLastError());
-    return out_finish(c, out, dO, (size_t)m * d, mem);
+    HIP_TRY(c, hipMemcpyAsync(c->pinned_small, flag, 4, hipMemcpyDeviceToHost, c->stream));
+    st = out_finish(c, out, dO, (size_t)m * d, mem);
+    if (st) return st;
+    if (c->pinned_small[0]) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "reduce_constraints: a label exceeds d = dim(P)");
+    return SDPSR_OK;
 }
 
 // Setup stage for dense problems on the device, src/partitions.jl:117-142:

@@ -305,7 +305,7 @@ void launch_transpose_labels(hipStream_t s, int64_t n, const uint32_t* L, uint32
 void launch_labels_checksum(hipStream_t s, int64_t len, const uint32_t* L, uint64_t* partial, uint64_t* out);
 int64_t reduce_columns_chunk(int64_t len, int64_t m, int64_t d);
 bool launch_reduce_columns(hipStream_t s, int64_t len, int64_t m, int64_t d, const uint32_t* L, const double* A,
-                           double* partial, double* out);
+                           double* partial, double* out, uint32_t* bad_flag);
 // kernels_module.hip / setup-stage helpers used across api.cpp
 void launch_symmetrize(hipStream_t s, int64_t m, int64_t ld, double* B);
 void launch_tall_times_small(hipStream_t s, int64_t n, int64_t ldi, const double* In, int kk, const double* S,

@@ -198,6 +198,55 @@ def kron_with_complete(base_labels, k, seed=0):
     return canonical_labels(permute_labels(L, seed))
 
 
+def sym_full_labels(s):
+    """s x s labels in which every unordered pair {p, q} is its own class: s(s+1)/2 classes, the algebra of ALL
+    symmetric s x s matrices -- one block of size s."""
+    p, q = np.indices((s, s))
+    lo, hi = np.minimum(p, q), np.maximum(p, q)
+    return hi * (hi + 1) // 2 + lo + 1
+
+
+def direct_sum_labels(parts):
+    """Direct sum of Sym(s) (x) I_k over ``parts`` = [(s, k), ...]: k diagonal copies of ``sym_full_labels(s)``
+    carrying the SAME labels (one block of size s, multiplicity k), label ranges disjoint between parts, label 0
+    everywhere off the diagonal blocks.  Not permuted, not canonicalised."""
+    n = sum(s * k for s, k in parts)
+    L = np.zeros((n, n), dtype=np.int64)
+    o, base = 0, 0
+    for s, k in parts:
+        B = sym_full_labels(s) + base
+        for _ in range(k):
+            L[o:o + s, o:o + s] = B
+            o += s
+        base += s * (s + 1) // 2
+    return L
+
+
+# name -> block sizes (sorted) of the instances of ``known_blocks_instance``
+KNOWN_BLOCKS = {"K17": [17, 17], "K2": [2, 2], "K40": [40, 40], "DS": [1, 2, 5, 17]}
+
+
+def known_blocks_instance(name):
+    """Partitions whose block sizes are known by construction, permuted (fixed seed) and canonicalised.
+    K17: Sym(17) (x) {I, J-I}_4, n = 68, d = 306, classes of 4..24 entries.
+    K2:  Sym(2) (x) {I, J-I}_100, n = 200, d = 6, classes of 100, 200, 9 900 and 19 800 entries.
+    K40: Sym(40) (x) {I, J-I}_3, n = 120, d = 1640.
+    DS:  Sym(1) (x) I_1 + Sym(2) (x) I_3 + Sym(5) (x) I_7 + Sym(17) (x) I_2, n = 76, d = 172, one class of a single
+         entry, label 0 off the diagonal blocks.
+    Returns (labels int64 n x n canonical, dim, sorted block sizes)."""
+    if name == "K17":
+        L, d = kron_with_complete(sym_full_labels(17), 4, seed=17)
+    elif name == "K2":
+        L, d = kron_with_complete(sym_full_labels(2), 100, seed=2)
+    elif name == "K40":
+        L, d = kron_with_complete(sym_full_labels(40), 3, seed=40)
+    elif name == "DS":
+        L, d = canonical_labels(permute_labels(direct_sum_labels([(1, 1), (2, 3), (5, 7), (17, 2)]), 76))
+    else:
+        raise ValueError(name)
+    return L, d, list(KNOWN_BLOCKS[name])
+
+
 def partition_as_sdp(L, seed=0):
     """Wrap a partition as an SDP (C = sum_i c_i 1[P==i], A = one trace row, b=[1])
     so that ``admissible_subspace`` must recover (the closure of) it."""

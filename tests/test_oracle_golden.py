@@ -147,6 +147,32 @@ def test_directed_cycle_closure_in_closed_form(oracle, problems, n):
     assert np.array_equal(P.matrix, (i - j) % n + 1)
 
 
+@pytest.mark.parametrize("name,n,dim", [("K17", 68, 306), ("K2", 200, 6), ("K40", 120, 1640), ("DS", 76, 172)])
+def test_known_blocks_instances(oracle, problems, name, n, dim):
+    """The instances whose blocks are known by construction (tests/problems.py, known_blocks_instance): the oracle's
+    blockDiagonalize returns exactly the constructed block sizes, and the spectrum invariant holds."""
+    L, d, blocks = problems.known_blocks_instance(name)
+    assert L.shape == (n, n) and d == dim == int(L.max())
+    assert np.array_equal(L, L.T)
+    assert sum(s * (s + 1) // 2 for s in blocks) == d
+    counts = np.bincount(L.ravel(), minlength=d + 1)[1:]
+    assert counts.min() >= 1
+    if name == "K2":  # 3 and 5 chunks of 4096 entries, the last one ragged
+        assert sorted(set(counts.tolist())) == [100, 200, 9900, 19800]
+    if name == "DS":  # one class of a single entry; most entries carry label 0
+        assert int((counts == 1).sum()) == 1 and int((L == 0).sum()) > n * n // 2
+    else:
+        assert int((L == 0).sum()) == 0
+    P = oracle.Partition(d, L)
+    assert oracle.sort_unique(P) == P  # canonical
+    sizes, blks, _ = oracle.block_diagonalize(P, rng=np.random.default_rng(5))
+    assert sorted(sizes) == blocks
+    x = np.random.default_rng(8).random(d)
+    full, blk = oracle.spectrum_invariant(P, blks, x)
+    assert len(full) == len(blk)
+    assert np.allclose(full, blk, rtol=1e-6, atol=1e-9)
+
+
 def test_basis_image_fast_equals_literal(oracle, problems, golden):
     P = oracle.partition_from_labels(golden["er5_P"].astype(np.int64))
     Q = oracle.diagonalize(P, atol=oracle.RTOL_DEFAULT, rng=np.random.default_rng(1))
