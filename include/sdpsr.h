@@ -376,9 +376,28 @@ int sdpsr_desymmetrize(sdpsr_ctx* ctx, int64_t n, uint32_t* P, int64_t* dim, int
 /* ---- reduced-SDP assembly, README.md:57-60, test/sd_problems.jl:32-37 ------------------------- */
 /* out = A * PMat with PMat = hcat(vec(P.matrix .== i) for i = 1:d): the columns of A summed per
    class.  A: m x len column-major (dense), labels: len, out: m x d column-major.  C' * PMat is the
-   m = 1 case.  Sparse A stays with the caller (one sparse-times-indicator product). */
+   m = 1 case.  The accumulators live in LDS: (d + 1) * min(m, 64) doubles must fit 60 KiB, else SDPSR_BAD_ARGUMENT; a
+   sparse A, or a larger d, goes to sdpsr_reduce_constraints_csr. */
 int sdpsr_reduce_constraints(sdpsr_ctx* ctx, int64_t len, const uint32_t* labels, int64_t d, int64_t m,
                              const double* A, double* out, int mem);
+/* The same product for a sparse A given as CSR and any d: newA = A * PMat, newC = C' * PMat (README.md:57-60,
+   test/sd_problems.jl:32-37,113-118, docs/src/examples/ReduceAndSolveJuMP.jl:42-51) without a dense copy of A anywhere.
+     rowptr[m + 1], colind[nnz], val[nnz]: host memory, exactly the conventions of sdpsr_admissible_setup_csr (colind =
+       column-major linear index into [0, len), index_base 0 or 1 -- with 1 a Julia caller passes sparse(A')'s colptr /
+       rowval / nzval unchanged; unsorted columns, duplicates (summed, in input order) and explicit zeros are accepted)
+       and the same validation: malformed CSR is SDPSR_BAD_ARGUMENT before any kernel runs.
+     labels[len] with values 0 .. d (0: no column) and out (m x d column-major) live in the memory space `mem`.
+   out[r, i - 1] = the sum of val over the entries of row r whose column carries label i; a pair (r, i) without such an
+   entry gets exactly 0.0 -- every element of out is written.  C' * PMat is the m = 1 case; m = 0 and nnz = 0 are legal.
+   Any 1 <= d <= len: nothing but out itself grows with d.  An output or workspace (28 bytes per non-zero) that does not
+   fit the device: SDPSR_OUT_OF_MEMORY.  The entries are indexed with 32 bits: nnz >= 2^32 is SDPSR_BAD_ARGUMENT.  A label
+   > d: SDPSR_BAD_ARGUMENT ("a label exceeds d"), found by a flag -- such a label never indexes anything.  The ctx stays
+   usable after each of these.
+   REPRODUCIBLE BITS: the entries of a (row, class) pair are added in an order that depends on the inputs alone (no
+   floating-point atomics; DESIGN.md "A * PMat from a sparse A"), so equal calls return equal bits on any ctx. */
+int sdpsr_reduce_constraints_csr(sdpsr_ctx* ctx, int64_t len, const uint32_t* labels, int64_t d, int64_t m,
+                                 const int64_t* rowptr, const int64_t* colind, const double* val, int index_base,
+                                 double* out, int mem);
 
 /* ---- blockDiagonalize, src/compat.jl:46-68 ---------------------------------- */
 /* Phase 1 = diagonalize(Float64, P; atol=epsilon) (src/diagonalize.jl:25-40) +

@@ -12,4 +12,5 @@ from .api import (BlockDiagonalization, Context, DimensionMismatch, InvalidDecom
                   LabelOverflow, NotConverged, NumericalInconsistency, Partition, SdpsrError,
                   admissible_setup, admissible_setup_csr, admissible_subspace, csr_arrays, blockDiagonalize, default_context, desymmetrize, unSymmetrize,
                   diagonalize, dim, eigen_decomposition, jordan_reduce_batch, Problem, eigen_decomposition_batched, fill, partition_checksum, randomize, reduce_constraints,
+                  reduce_constraints_csr,
                   refine, relabel_keys)

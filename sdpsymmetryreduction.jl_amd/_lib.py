@@ -134,6 +134,7 @@ def load_library():
         "sdpsr_batch_block_sizes": (C.c_int, [vp, C.c_int32, vp]),
         "sdpsr_transfer_bytes": (C.c_int, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "sdpsr_reduce_constraints": (C.c_int, [vp, i64, vp, i64, i64, vp, vp, C.c_int]),
+        "sdpsr_reduce_constraints_csr": (C.c_int, [vp, i64, vp, i64, i64, vp, vp, vp, C.c_int, vp, C.c_int]),
         "sdpsr_desymmetrize": (C.c_int, [vp, i64, vp, pi64, pi32, C.c_int]),
         "sdpsr_block_diagonalize": (C.c_int, [vp, i64, vp, i64, dbl, pi32, pi64, pi64, vp, C.c_int]),
         "sdpsr_block_sizes": (C.c_int, [vp, vp]),

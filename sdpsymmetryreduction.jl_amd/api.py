@@ -693,7 +693,9 @@ def jordan_reduce_batch(C_, A, b, restarts=2, seeds=None, atol=RTOL_DEFAULT, eps
 
 def reduce_constraints(P, A, ctx=None):
     """``A * PMat`` with ``PMat = hcat([vec(P.matrix .== i) for i = 1:dim(P)]...)``
-    (README.md:57-60, test/sd_problems.jl:32-37); ``A`` dense m x n^2 (or a vector: C' * PMat)."""
+    (README.md:57-60, test/sd_problems.jl:32-37); ``A`` dense m x n^2 (or a vector: C' * PMat).  A sparse ``A`` is
+    densified here, and the accumulators must fit the LDS ((dim(P) + 1) * min(m, 64) doubles in 60 KiB):
+    ``reduce_constraints_csr`` takes a sparse ``A`` as it is, for any dim(P)."""
     ctx = _ctx(ctx)
     A = np.asarray(_dense(A), dtype=np.float64)
     vec = A.ndim == 1
@@ -704,6 +706,44 @@ def reduce_constraints(P, A, ctx=None):
     Af = np.asfortranarray(A2)
     out = np.zeros((m, P.nparts), order="F")
     ctx.check(ctx._lib.sdpsr_reduce_constraints(ctx._h, ln, _ptr(lab), P.nparts, m, _ptr(Af), _ptr(out), L.MEM_HOST))
+    return out[0] if vec else out
+
+
+def reduce_constraints_csr(P, A, ctx=None, index_base=0):
+    """``A * PMat`` (README.md:57-60, test/sd_problems.jl:32-37,113-118) from a sparse ``A``, for any dim(P)
+    (``sdpsr_reduce_constraints_csr``): A travels as CSR and is never densified.  ``A``: anything ``csr_arrays`` takes
+    -- SciPy sparse, dense 2-D, or ``(rowptr, colind, val)`` with ``index_base`` -- with n^2 columns; returns an
+    m x dim(P) NumPy array.  A 1-D array or a SciPy-sparse vector (n^2 x 1, or 1-D) means ``C' * PMat``: a vector of
+    length dim(P) comes back.  Malformed input raises ValueError before any library call.  Equal inputs give equal bits."""
+    ln = int(P.shape[0]) * int(P.shape[1])
+    vec = False
+    if not isinstance(A, tuple):
+        if hasattr(A, "tocsr"):
+            if A.ndim == 1:
+                vec, A = True, A.reshape(1, -1)
+            elif A.shape[1] == 1 and ln != 1:
+                vec, A = True, A.T
+        else:
+            A = np.asarray(A, dtype=np.float64)
+            if A.ndim == 1:
+                vec, A = True, A.reshape(1, -1)
+    rowptr, colind, val = csr_arrays(A, ln, index_base)  # (ValueError before any library call)
+    m, d = rowptr.size - 1, int(P.nparts)
+    if not 1 <= d <= ln:
+        raise ValueError(f"dim(P) = {d} outside [1, {ln}]")
+    ctx = _ctx(ctx)
+    lab, mem = _labels_arg(P)
+    if mem == L.MEM_DEVICE:
+        import torch
+        t_out = torch.empty(m * d, dtype=torch.float64, device=lab.device)
+        ctx.wait_for(lab, t_out)
+        ctx.check(ctx._lib.sdpsr_reduce_constraints_csr(ctx._h, ln, _ptr(lab), d, m, _ptr(rowptr), _ptr(colind), _ptr(val), 0,
+                                                        _ptr(t_out), mem))
+        out = t_out.cpu().numpy().reshape(m, d, order="F")
+    else:
+        out = np.zeros((m, d), order="F")
+        ctx.check(ctx._lib.sdpsr_reduce_constraints_csr(ctx._h, ln, _ptr(lab), d, m, _ptr(rowptr), _ptr(colind), _ptr(val), 0,
+                                                        _ptr(out), mem))
     return out[0] if vec else out
 
 

@@ -291,6 +291,22 @@ void launch_gram_tall(hipStream_t s, int64_t len, int64_t m, const double* W, do
 void launch_apply_upper_inverse(hipStream_t s, int64_t len, int64_t m, double* W, const int32_t* piv, const double* Xrow);
 bool launch_small_syev(hipStream_t s, int64_t n, double* A, int64_t lda, double* w, double* Vtmp, int* info);
 
+// setup_csr.cpp: what a CSR input means, for every entry that takes one (the setup entries, sdpsr_reduce_constraints_csr).
+// Validates (SDPSR_BAD_ARGUMENT with a message, before any kernel) and brings the rows into canonical form.
+struct CanonCsr {
+    std::vector<int64_t> rowptr;  // m + 1, 0-based
+    std::vector<uint32_t> col;    // sorted per row, no duplicates
+    std::vector<double> val;      // no zeros
+};
+int canonicalize_csr(sdpsr_ctx* c, int64_t len, int64_t m, const int64_t* rowptr, const int64_t* colind, const double* val, int base,
+                     CanonCsr& out);
+// kernels_reduce_csr.hip: A * PMat from canonical CSR (reduce_csr.cpp)
+void launch_labels_exceed(hipStream_t s, int64_t len, const uint32_t* L, int64_t d, uint32_t* flag);
+void launch_csr_entry_labels(hipStream_t s, int64_t nnz, const uint32_t* col, const uint32_t* L, int64_t d, uint32_t* key);
+size_t csr_class_sums_carry_bytes(int64_t nnz);
+void launch_csr_class_sums(hipStream_t s, int64_t nnz, int64_t m, const int64_t* rowptr, const uint32_t* key_sorted,
+                           const uint32_t* idx_sorted, const double* val, void* carry, double* out);
+
 }  // namespace sdpsr
 
 #define CHECK_CTX(c) \

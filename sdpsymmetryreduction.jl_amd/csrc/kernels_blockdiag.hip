@@ -1593,23 +1593,14 @@ rx_scatter_kernel(int64_t len, const uint32_t* __restrict__ keys, const uint32_t
         }
 }
 
-int sort_entries_by_label(sdpsr_ctx* c, int64_t len, int64_t d, const uint32_t* L,
-                          uint32_t** ent_out, int64_t** class_ptr_host) {
-    hipStream_t s = c->stream;
-    if (len >= (int64_t(1) << 32)) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "sort_entries_by_label: len >= 2^32");
+size_t radix_sort_hist_words(int64_t len) { return (size_t)16 * (size_t)((len + RX_CH - 1) / RX_CH); }
+
+void launch_radix_sort_pairs(hipStream_t s, int64_t len, int bits, const uint32_t* keys, uint32_t* kA, uint32_t* kB, uint32_t* vA,
+                             uint32_t* vB, uint32_t* hist) {
     const uint32_t G = (uint32_t)((len + RX_CH - 1) / RX_CH);
-    uint32_t* kA = (uint32_t*)ctx_buf(c, "bi_key_a", len * sizeof(uint32_t));
-    uint32_t* kB = (uint32_t*)ctx_buf(c, "bi_key_out", len * sizeof(uint32_t));
-    uint32_t* vA = (uint32_t*)ctx_buf(c, "bi_idx_in", len * sizeof(uint32_t));
-    uint32_t* vB = (uint32_t*)ctx_buf(c, "bi_idx_out", len * sizeof(uint32_t));
-    uint32_t* hist = (uint32_t*)ctx_buf(c, "bi_sort_tmp", (size_t)16 * G * sizeof(uint32_t));
-    int64_t* cstart = (int64_t*)ctx_buf(c, "bi_cstart", (d + 2) * sizeof(int64_t));
-    if (!kA || !kB || !vA || !vB || !hist || !cstart) return SDPSR_OUT_OF_MEMORY;
-    int bits = 1;
-    while (((int64_t)1 << bits) <= d) ++bits;
     const int passes = (bits + 3) / 4;
-    // pass p reads (kin, vin) and writes (kout, vout); the first pass reads the labels themselves with the index as the value
-    const uint32_t* kin = L;
+    // pass p reads (kin, vin) and writes (kout, vout); the first pass reads the keys themselves with the index as the value
+    const uint32_t* kin = keys;
     const uint32_t* vin = nullptr;
     uint32_t* kout = (passes & 1) ? kB : kA;  // so that the last pass ends in (kB, vB)
     uint32_t* vout = (passes & 1) ? vB : vA;
@@ -1622,8 +1613,24 @@ int sort_entries_by_label(sdpsr_ctx* c, int64_t len, int64_t d, const uint32_t* 
         kout = (kout == kA) ? kB : kA;
         vout = (vout == vA) ? vB : vA;
     }
-    const uint32_t* key_sorted = kin;
-    uint32_t* idx_sorted = const_cast<uint32_t*>(vin);
+}
+
+int sort_entries_by_label(sdpsr_ctx* c, int64_t len, int64_t d, const uint32_t* L,
+                          uint32_t** ent_out, int64_t** class_ptr_host) {
+    hipStream_t s = c->stream;
+    if (len >= (int64_t(1) << 32)) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "sort_entries_by_label: len >= 2^32");
+    uint32_t* kA = (uint32_t*)ctx_buf(c, "bi_key_a", len * sizeof(uint32_t));
+    uint32_t* kB = (uint32_t*)ctx_buf(c, "bi_key_out", len * sizeof(uint32_t));
+    uint32_t* vA = (uint32_t*)ctx_buf(c, "bi_idx_in", len * sizeof(uint32_t));
+    uint32_t* vB = (uint32_t*)ctx_buf(c, "bi_idx_out", len * sizeof(uint32_t));
+    uint32_t* hist = (uint32_t*)ctx_buf(c, "bi_sort_tmp", radix_sort_hist_words(len) * sizeof(uint32_t));
+    int64_t* cstart = (int64_t*)ctx_buf(c, "bi_cstart", (d + 2) * sizeof(int64_t));
+    if (!kA || !kB || !vA || !vB || !hist || !cstart) return SDPSR_OUT_OF_MEMORY;
+    int bits = 1;
+    while (((int64_t)1 << bits) <= d) ++bits;
+    launch_radix_sort_pairs(s, len, bits, L, kA, kB, vA, vB, hist);
+    const uint32_t* key_sorted = kB;
+    uint32_t* idx_sorted = vB;
     HIP_TRY(c, hipMemsetAsync(cstart, 0xFF, (d + 2) * sizeof(int64_t), s));  // -1 = class absent
     class_starts_kernel<<<grid_for(len, 256), 256, 0, s>>>(len, key_sorted, cstart);
     int64_t* h = (int64_t*)malloc((d + 2) * sizeof(int64_t));  // handed to the caller, who frees it

@@ -474,6 +474,12 @@ bool launch_basis_image_commutative(hipStream_t s, int64_t n, int64_t d, int64_t
                                     double atol, double tol, double* ws, double* out, uint32_t* flag);
 void launch_transpose_to_rowmajor(hipStream_t s, int64_t n, int64_t S1, const double* Qcm,
                                   double* Qrm);
+// Stable LSD radix sort of the pairs (keys[e], e), e < len < 2^32, by the low `bits` bits of the key (4 bits per pass; the
+// keys must not exceed them).  kA / kB / vA / vB: len words each, hist: radix_sort_hist_words(len).  The sorted keys and
+// indices end in (kB, vB).  No atomics on the way: the order is a function of the keys alone.
+size_t radix_sort_hist_words(int64_t len);
+void launch_radix_sort_pairs(hipStream_t s, int64_t len, int bits, const uint32_t* keys, uint32_t* kA, uint32_t* kB, uint32_t* vA,
+                             uint32_t* vB, uint32_t* hist);
 // stable sort of entries by label (label 0 dropped): ent sorted, hist[d+1]
 int sort_entries_by_label(sdpsr_ctx* c, int64_t len, int64_t d, const uint32_t* L,
                           uint32_t** ent_out, int64_t** class_ptr_host);

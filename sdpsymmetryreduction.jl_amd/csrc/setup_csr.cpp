@@ -13,20 +13,10 @@
 
 using namespace sdpsr;
 
-namespace {
-
-struct CanonCsr {
-    std::vector<int64_t> rowptr;  // m + 1, 0-based
-    std::vector<uint32_t> col;    // sorted per row, no duplicates
-    std::vector<double> val;      // no zeros
-    bool symmetric = true;        // every row is a symmetric n x n matrix, bit for bit
-};
-
 // Validation + canonical form: sort each row by column (stable: duplicates keep their input order), sum duplicates in
-// that order, drop zeros; then the exact symmetry test (entry (i, j) present with the same bits as (j, i)).
-int canonicalize_csr(sdpsr_ctx* c, int64_t n, int64_t m, const int64_t* rowptr, const int64_t* colind, const double* val, int base,
-                     CanonCsr& out) {
-    const int64_t len = n * n;
+// that order, drop zeros.  Shared with the reduced-SDP assembly (reduce_csr.cpp): one definition of what a CSR input means.
+int sdpsr::canonicalize_csr(sdpsr_ctx* c, int64_t len, int64_t m, const int64_t* rowptr, const int64_t* colind, const double* val,
+                            int base, CanonCsr& out) {
     if (base != 0 && base != 1) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "index_base must be 0 or 1");
     if (m == 0) {
         out.rowptr.assign(1, 0);
@@ -77,8 +67,15 @@ int canonicalize_csr(sdpsr_ctx* c, int64_t n, int64_t m, const int64_t* rowptr, 
         }
         out.rowptr[i + 1] = (int64_t)out.col.size();
     }
-    // symmetry: the transposed position of every entry is present with the same bits
-    for (int64_t i = 0; i < m && out.symmetric; ++i) {
+    return SDPSR_OK;
+}
+
+namespace {
+
+// every row is a symmetric n x n matrix, bit for bit: the transposed position of every entry is present with the same bits
+bool csr_rows_symmetric(const CanonCsr& out, int64_t n) {
+    const int64_t m = (int64_t)out.rowptr.size() - 1;
+    for (int64_t i = 0; i < m; ++i) {
         const uint32_t* c0 = out.col.data() + out.rowptr[i];
         const uint32_t* c1 = out.col.data() + out.rowptr[i + 1];
         for (const uint32_t* p = c0; p < c1; ++p) {
@@ -88,12 +85,11 @@ int canonicalize_csr(sdpsr_ctx* c, int64_t n, int64_t m, const int64_t* rowptr, 
             const uint32_t* f = std::lower_bound(c0, c1, t);
             if (f == c1 || *f != t ||
                 std::memcmp(&out.val[f - out.col.data()], &out.val[p - out.col.data()], sizeof(double)) != 0) {
-                out.symmetric = false;
-                break;
+                return false;
             }
         }
     }
-    return SDPSR_OK;
+    return true;
 }
 
 // Cholesky of a symmetric m x m matrix G (column-major) into an upper-triangular R (row-major, G[perm][:, perm] = R'R).
@@ -161,8 +157,9 @@ int setup_csr_impl(sdpsr_ctx* c, int64_t n, int64_t m, const int64_t* rowptr, co
     if (st) return st;
     if (m > 0x7FFFFFFF) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "m too large");
     CanonCsr A;
-    st = canonicalize_csr(c, n, m, rowptr, colind, val, base, A);
+    st = canonicalize_csr(c, len, m, rowptr, colind, val, base, A);
     if (st) return st;
+    const bool symmetric = csr_rows_symmetric(A, n);
     for (int64_t i = 0; i < m; ++i)
         if (!std::isfinite(b[i])) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "non-finite b");
     hipStream_t s = c->stream;
@@ -202,7 +199,7 @@ int setup_csr_impl(sdpsr_ctx* c, int64_t n, int64_t m, const int64_t* rowptr, co
         }
         c->h2d_bytes += (size_t)(m + 1) * 8 + (size_t)nnz * 12;
     }
-    o.hint = A.symmetric ? 3 : 0;
+    o.hint = symmetric ? 3 : 0;
     std::vector<std::vector<double>> coeffs;  // coeffs[i][j]: coefficient of U's column j in row i (as setup_mgs has them)
     std::vector<int64_t> piv;
     int64_t r = 0;

@@ -176,6 +176,20 @@ function SR.admissible_subspace(::Type{HIPPartition}, C::AbstractVector{T}, A::A
     return HIPPartition(d[], P)
 end
 
+# ---- reduced-SDP assembly from a sparse A (README.md:57-60, test/sd_problems.jl:32-37,113-118):
+# newA = reduce_constraints(P, A), newC = reduce_constraints(P, sparse(C')) in place of A * PMat with
+# PMat = hcat(vec(P.matrix .== i) for i = 1:dim(P)).  sparse(A')'s colptr / rowval / nzval are the CSR arrays of A and go
+# in unchanged with index_base = 1 (sdpsr_reduce_constraints_csr).  WRITTEN BLIND like the rest of this file: never run.
+function reduce_constraints(P::HIPPartition, A::SparseMatrixCSC)
+    m = size(A, 1); d = Int64(P.nparts); len = length(P.matrix); @assert size(A, 2) == len
+    At = sparse(SparseMatrixCSC{Float64}(A)')
+    out = Matrix{Float64}(undef, m, d); cx = ctx()
+    check(cx, ccall((:sdpsr_reduce_constraints_csr, libsdpsr), Cint,
+                    (Ptr{Cvoid}, Int64, Ptr{UInt32}, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Cint, Ptr{Float64}, Cint),
+                    cx.handle, len, P.matrix, d, m, Vector{Int64}(At.colptr), Vector{Int64}(At.rowval), At.nzval, Cint(1), out, MEM_HOST))
+    return out
+end
+
 # ---- the whole reduction in ONE call (sdpsr_jordan_reduce): admissible_subspace + blockDiagonalize with the
 # partition staying on the device; the images are fetched with sdpsr_block_images once their size is known ----
 function jordan_reduce(C::AbstractVector{Float64}, A::AbstractMatrix{Float64}, b::AbstractVector{Float64};
