@@ -78,7 +78,6 @@ inline int ceil_log2(uint64_t x) {
     return l;
 }
 
-
 double round_scale(const sdpsr_ctx* c, double atol);
 bool label_overflows(const sdpsr_ctx* c, uint64_t value);
 int label_overflow_fail(sdpsr_ctx* c, const char* where, uint64_t value);
@@ -180,6 +179,37 @@ struct TotalEvents {
     TotalEvents& operator=(const TotalEvents&) = delete;
 };
 
+// ---- the words of c->pinned and c->pinned_small that kernels (and small copies) report into: one table for the loop (loop.cpp), the
+// refinement (primitives.cpp) and the reduction's deferred verdicts (reduce.cpp).  uint32 words [first, first + count); no two regions share a
+// word, and the symmetry probe's r doubles, the only variable-length report, start behind them all: (char*)c->pinned + PINNED_FIXED_BYTES
+struct PinnedWords { size_t first, count; };
+constexpr PinnedWords PINNED_REFINE{0, 4};  // the refinement's counters as its label pass stores them:
+enum { REFINE_INSERTED = 0, REFINE_OVERFLOW = 1, REFINE_CLASSES = 2, REFINE_STAMP = 3 };  // (STAMP: the report's sequence number; the fused symmetry verdict when the counters are copied)
+constexpr PinnedWords PINNED_SYMMETRY{8, 1};          // != 0: the new labels are NOT symmetric
+constexpr PinnedWords PINNED_VERIFY{128, 1};          // != 0: an entry differs from its class representative (verify pass)
+constexpr PinnedWords PINNED_SPECULATIVE{144, 1};     // the same for the speculative confirm round
+constexpr PinnedWords PINNED_BASIS_CONSTANT{192, 1};  // != 0: some U_k is not constant on the classes
+constexpr PinnedWords PINNED_SAMPLE{224, 4};          // sample of the signatures: non-zero, distinct, seen once, seen twice
+constexpr size_t PINNED_FIXED_BYTES = 1024;
+constexpr PinnedWords PINNED_SMALL_FLAG{0, 1};                   // c->pinned_small (256 B): the flag of the one-shot entries ("a label exceeds d", symmetry)
+constexpr PinnedWords PINNED_SMALL_DEFERRED_VERIFY{8, 1};        // sdpsr_jordan_reduce: the two verdicts the loop left unread (c->deferred_verdict)
+constexpr PinnedWords PINNED_SMALL_DEFERRED_SPECULATIVE{24, 1};
+constexpr bool pinned_words_disjoint(std::initializer_list<PinnedWords> w, size_t bytes) {
+    for (const PinnedWords* a = w.begin(); a != w.end(); ++a) {
+        if (a->count == 0 || (a->first + a->count) * 4 > bytes) return false;
+        for (const PinnedWords* b = w.begin(); b != a; ++b)
+            if (a->first < b->first + b->count && b->first < a->first + a->count) return false;
+    }
+    return true;
+}
+static_assert(pinned_words_disjoint({PINNED_REFINE, PINNED_SYMMETRY, PINNED_VERIFY, PINNED_SPECULATIVE, PINNED_BASIS_CONSTANT, PINNED_SAMPLE}, PINNED_FIXED_BYTES) &&
+              PINNED_FIXED_BYTES % sizeof(double) == 0, "two reports share a word of c->pinned, or one reaches into the symmetry probe's doubles");
+static_assert(pinned_words_disjoint({PINNED_SMALL_FLAG, PINNED_SMALL_DEFERRED_VERIFY, PINNED_SMALL_DEFERRED_SPECULATIVE}, 256), "two reports share a word of c->pinned_small");
+inline uint32_t* pinned_report(sdpsr_ctx* c, PinnedWords w) {  // the pinned words of one report (nullptr: no pinned buffer)
+    uint32_t* p = (uint32_t*)ctx_pinned(c, PINNED_FIXED_BYTES);
+    return p ? p + w.first : nullptr;
+}
+
 // canonical refinement of a signature source / array (primitives.cpp)
 // early: return as soon as the label pass has REPORTED the class count (ctx_wait_word) -- the pass itself is still running; only
 // for a caller that goes on in stream order and waits for the stream before its own return
@@ -193,7 +223,7 @@ int refine_signatures(sdpsr_ctx* c, int64_t len, const uint64_t* sig, uint32_t* 
 int admissible_subspace_impl(sdpsr_ctx* c, int64_t n, const double* CL, const double* X0L, const double* U, int64_t r, double atol,
                              uint32_t* P_out, int64_t* dim_out, int32_t* iters_out, double* phase_ms, int mem, int mem_out,
                              bool final_sync, int* labels_sym_out);
-// loop.cpp: the setup stage of the dense entry in pieces, shared with the CSR entries (setup_csr.cpp)
+// setup_dense.cpp: the setup stage of the dense entry in pieces, shared with the CSR entries (setup_csr.cpp)
 int setup_mgs(sdpsr_ctx* c, int64_t len, int64_t m, double* R, double* U, double* partial, int nblk, double* coef,
               std::vector<std::vector<double>>& coeffs, std::vector<int64_t>& piv, int64_t* r_out);
 std::vector<double> min_norm_coefficients(int64_t r, const std::vector<int64_t>& piv, const std::vector<std::vector<double>>& coeffs,
@@ -214,7 +244,6 @@ struct EigInfo {
     // (false after extra coupling elements: the decisive block may come from any of them)
     bool t_valid = false;
 };
-
 
 // Source of "generic elements" for the dense driver: the label gather (gen == nullptr,
 // randomize!(A, P)) or a compressed representation B = W' A W of it (module-compression driver).

@@ -3,13 +3,7 @@
 // source that the loop shares with them.  Reference: src/partitions.jl:24-75, src/utils.jl:34-66.
 #include <algorithm>
 #include <cmath>
-#include <complex>
 #include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <chrono>
-#include <functional>
-#include <numeric>
 
 #include "host_internal.h"
 
@@ -72,33 +66,34 @@ int refine_signatures(sdpsr_ctx* c, int64_t len, const SigSource& src_in, uint32
             void* wsp = ctx_buf(c, "ref_sort_ws", wsb);
             uint32_t* counters = (uint32_t*)ctx_buf(c, "ref_counters", refine_counters_bytes());
             uint32_t* firsts = (uint32_t*)ctx_buf(c, "ref_first", (size_t)refine_first_cap() * 4);
-            uint32_t* h = (uint32_t*)ctx_pinned(c, 64);
+            uint32_t* h = pinned_report(c, PINNED_REFINE);
+            uint32_t* hsym = pinned_report(c, PINNED_SYMMETRY);
             if (!wsp || !counters || !firsts || !h) return SDPSR_OUT_OF_MEMORY;
             if (!materialize()) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "refine: signature source needs scratch");
             const uint32_t seq = ++c->report_seq ? c->report_seq : ++c->report_seq;  // (never 0: the pinned words start as zeros)
             if (cub ? !launch_refine_sorted(c->stream, len, src.sig, labels, wsp, wsb, counters)
                     : !launch_refine_bucketed(c->stream, len, src.sig, labels, wsp, wsb, counters, firsts, refine_first_cap(), h, seq))
                 return ctx_fail(c, SDPSR_HIP_ERROR, "sorted / bucketed refinement failed");
-            if (cub) HIP_TRY(c, hipMemcpyAsync(h, counters, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));  // (the grouping's label pass stores them itself)
+            if (cub) HIP_TRY(c, hipMemcpyAsync(h, counters, PINNED_REFINE.count * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));  // (the grouping's label pass stores them itself)
             if (sym_n > 0 && symflag_dev) {
                 launch_check_symmetric(c->stream, sym_n, labels, symflag_dev);
-                HIP_TRY(c, hipMemcpyAsync(h + 8, symflag_dev, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+                HIP_TRY(c, hipMemcpyAsync(hsym, symflag_dev, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
             }
             // (early: the caller only needs the label pass's report and waits for the stream itself before it returns)
-            if (early && !cub && !(sym_n > 0 && symflag_dev)) HIP_TRY(c, ctx_wait_word(c, c->stream, h + 3, seq));
+            if (early && !cub && !(sym_n > 0 && symflag_dev)) HIP_TRY(c, ctx_wait_word(c, c->stream, h + REFINE_STAMP, seq));
             else HIP_TRY(c, ctx_sync_stream(c, c->stream));
             HIP_TRY(c, hipGetLastError());
-            if (h[1]) {
+            if (h[REFINE_OVERFLOW]) {
                 // a bucket the grouping could not resolve (signatures that do not spread over its sub-passes): the radix sort
                 // has no such case.  (The grouping reads the signature ARRAY, never the old labels: nothing to restore.)
                 if (cub) return ctx_fail(c, SDPSR_HIP_ERROR, "sorted refinement reported a failure");
                 cub_fallback = true;
                 continue;
             }
-            if (sym_n > 0 && symflag_dev && sym_out) *sym_out = h[8] ? 0 : 1;
-            *nparts = h[2];
-            c->table_log2_hint = std::min(full, std::max(12, ceil_log2((uint64_t)h[2] * 8 + 1)));
-            if (!cub && h[2] <= refine_first_cap()) c->first_idx_labels = labels;  // "ref_first" describes these labels
+            if (sym_n > 0 && symflag_dev && sym_out) *sym_out = *hsym ? 0 : 1;
+            *nparts = h[REFINE_CLASSES];
+            c->table_log2_hint = std::min(full, std::max(12, ceil_log2((uint64_t)h[REFINE_CLASSES] * 8 + 1)));
+            if (!cub && h[REFINE_CLASSES] <= refine_first_cap()) c->first_idx_labels = labels;  // "ref_first" describes these labels
             return SDPSR_OK;
         }
         // Up to ~5000 classes (array source and the loop's computed sources): one workgroup per CU with every signature in LDS (refine_insert_mid_kernel; built for
@@ -129,29 +124,30 @@ int refine_signatures(sdpsr_ctx* c, int64_t len, const SigSource& src_in, uint32
         // hint 12 <=> last dim <= 512; a table grown after an overflow in this call holds more than 0.75 * 2^12 classes
         ws.expect_small = (!mispredicted && !sampled && c->table_log2_hint <= 12 && log2cap <= 12) ? 1 : 0;
         const bool sym_fused = sym_n > 0 && sym_n * sym_n == len;  // verdict in counters[3], same read-back
-        uint32_t* h = (uint32_t*)ctx_pinned(c, 64);
+        uint32_t* h = pinned_report(c, PINNED_REFINE);
+        uint32_t* hsym = pinned_report(c, PINNED_SYMMETRY);
         if (!h) return ctx_fail(c, SDPSR_OUT_OF_MEMORY, "pinned staging");
         ws.host_counters = sym_fused ? nullptr : h;  // the plain label pass stores the counters into the pinned buffer itself
         ws.host_seq = ++c->report_seq ? c->report_seq : ++c->report_seq;
         if (!launch_refine(c->stream, len, src, slot, labels, ws, sym_fused ? sym_n : 0))
             return ctx_fail(c, SDPSR_BAD_ARGUMENT, "refine: no insert kernel for this signature source");
-        if (!ws.host_counters) HIP_TRY(c, hipMemcpyAsync(h, ws.counters, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        if (!ws.host_counters) HIP_TRY(c, hipMemcpyAsync(h, ws.counters, PINNED_REFINE.count * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         if (sym_n > 0 && symflag_dev && !sym_fused) {
             launch_check_symmetric(c->stream, sym_n, labels, symflag_dev);  // flag = 1 if NOT symmetric
-            HIP_TRY(c, hipMemcpyAsync(h + 8, symflag_dev, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(hsym, symflag_dev, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         }
-        if (early && ws.host_counters && !(sym_n > 0 && symflag_dev)) HIP_TRY(c, ctx_wait_word(c, c->stream, h + 3, ws.host_seq));
+        if (early && ws.host_counters && !(sym_n > 0 && symflag_dev)) HIP_TRY(c, ctx_wait_word(c, c->stream, h + REFINE_STAMP, ws.host_seq));
         else HIP_TRY(c, ctx_sync_stream(c, c->stream));
-        if (sym_fused) h[8] = h[3];
-        if (sym_n > 0 && (symflag_dev || sym_fused) && sym_out) *sym_out = h[8] ? 0 : 1;
+        if (sym_fused) *hsym = h[REFINE_STAMP];  // (counters copied, not reported: the word carries the fused verdict)
+        if (sym_n > 0 && (symflag_dev || sym_fused) && sym_out) *sym_out = *hsym ? 0 : 1;
         HIP_TRY(c, hipGetLastError());
-        if (!h[1] && ws.expect_small && h[0] > refine_small_k()) {  // more classes than predicted: general ranking
+        if (!h[REFINE_OVERFLOW] && ws.expect_small && h[REFINE_INSERTED] > refine_small_k()) {  // more classes than predicted: general ranking
             mispredicted = true;
             // the count is exact now: the size the hint would have asked for (a 2^12 table three quarters full probes long chains)
-            log2cap = std::min(full, std::max(log2cap, ceil_log2((uint64_t)h[0] * 8 + 1)));
+            log2cap = std::min(full, std::max(log2cap, ceil_log2((uint64_t)h[REFINE_INSERTED] * 8 + 1)));
             continue;
         }
-        if (h[1]) {  // table too small for this many classes
+        if (h[REFINE_OVERFLOW]) {  // table too small for this many classes
             if (log2cap >= full) return ctx_fail(c, SDPSR_HIP_ERROR, "refine hash table overflow at full size");
             if (len < (int64_t(1) << 16)) {  // small inputs: the full-size table is a few hundred KB
                 log2cap = full;
@@ -170,9 +166,8 @@ int refine_signatures(sdpsr_ctx* c, int64_t len, const SigSource& src_in, uint32
             }
             slot = labels;  // array source: the slots go in place, nothing reads the old labels any more
             void* sws = ctx_buf(c, "ref_sample", refine_sample_workspace_bytes());
-            uint32_t* hs = (uint32_t*)ctx_pinned(c, 1024);
+            uint32_t* hs = pinned_report(c, PINNED_SAMPLE);  // its own pinned words
             if (!sws || !hs) return SDPSR_OUT_OF_MEMORY;
-            hs += 224;  // its own pinned words (counters at 0, verify verdict at 128, basis verdict at 192)
             const int64_t m = launch_refine_sample(c->stream, len, src.sig, sws, hs);
             if (m <= 0) return ctx_fail(c, SDPSR_HIP_ERROR, "refine: sample launch failed");
             HIP_TRY(c, ctx_sync_stream(c, c->stream));
@@ -194,9 +189,9 @@ int refine_signatures(sdpsr_ctx* c, int64_t len, const SigSource& src_in, uint32
             log2cap = std::min(full, std::max(log2cap + 2, ceil_log2((uint64_t)(est * 3.0) + 1)));
             continue;
         }
-        *nparts = h[2];
-        c->table_log2_hint = std::min(full, std::max(12, ceil_log2((uint64_t)h[2] * 8 + 1)));
-        if (h[2] <= refine_first_cap()) c->first_idx_labels = labels;  // "ref_first" describes these labels
+        *nparts = h[REFINE_CLASSES];
+        c->table_log2_hint = std::min(full, std::max(12, ceil_log2((uint64_t)h[REFINE_CLASSES] * 8 + 1)));
+        if (h[REFINE_CLASSES] <= refine_first_cap()) c->first_idx_labels = labels;  // "ref_first" describes these labels
         return SDPSR_OK;
     }
 }

@@ -39,7 +39,7 @@ int jordan_reduce_impl(sdpsr_ctx* c, int64_t n, const double* CL, const double* 
     c->bd_labels_ext = nullptr;
     double pm_a[SDPSR_T_COUNT] = {}, pm_b[SDPSR_T_COUNT] = {}, pm_i[SDPSR_T_COUNT] = {};
     int labels_sym = 0;
-    c->deferred_verdict = nullptr;
+    c->deferred_verdict = false;
     c->allow_deferred_verdict = !(c->opts.flags & SDPSR_FLAG_WAIT_FOR_EVERY_VERDICT);  // (the loop's last verdicts may ride on this reduction's later host waits, see sdpsr_internal.h)
     st = admissible_subspace_impl(c, n, CL, X0L, U, r, atol, L, dim_out, iters_out, phase_ms ? pm_a : nullptr, mem_in, SDPSR_MEM_DEVICE,
                                   /*final_sync=*/false, &labels_sym);
@@ -93,11 +93,12 @@ int jordan_reduce_impl(sdpsr_ctx* c, int64_t n, const double* CL, const double* 
         // The stream has been waited for: the verdicts the loop left unread are in.  A violated one means the loop stopped on a
         // partition that one more step would have refined -- whatever blockDiagonalize made of it (a failure included) is void;
         // the reduction is done again, this time reading the verdicts where they arise.
-        const volatile uint32_t* dv = c->deferred_verdict;
-        c->deferred_verdict = nullptr;
-        if (dv[0] != 0 || dv[16] != 0) {
+        const volatile uint32_t* ps = c->pinned_small;
+        const uint32_t dv = ps[PINNED_SMALL_DEFERRED_VERIFY.first], dv_spec = ps[PINNED_SMALL_DEFERRED_SPECULATIVE.first];
+        c->deferred_verdict = false;
+        if (dv != 0 || dv_spec != 0) {
             c->predict_closed = false;
-            if (dbg_on()) fprintf(stderr, "[sdpsr] jordan_reduce: the input was not closed after all (deferred verdicts %u %u): reduction repeated\n", dv[0], dv[16]);
+            if (dbg_on()) fprintf(stderr, "[sdpsr] jordan_reduce: the input was not closed after all (deferred verdicts %u %u): reduction repeated\n", dv, dv_spec);
             // the repeat makes the draws of a call that took no guess, with the caller's hint
             c->stream_counter = stream_at_entry;
             c->hint_symmetric_basis = hint_at_entry;

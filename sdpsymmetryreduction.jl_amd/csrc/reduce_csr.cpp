@@ -8,6 +8,32 @@ using namespace sdpsr;
 
 extern "C" {
 
+// A * PMat (README.md:57-60)
+int sdpsr_reduce_constraints(sdpsr_ctx* c, int64_t len, const uint32_t* labels, int64_t d, int64_t m, const double* A,
+                             double* out, int mem) {
+    CHECK_CTX(c);
+    if (!labels || !A || !out || d < 1 || m < 1) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "bad arguments");
+    int st = check_len(c, len);
+    if (st) return st;
+    const uint32_t* dL = in_dev(c, "prim_in_a", labels, len, mem, &st);
+    const double* dA = in_dev(c, "red_a", A, (size_t)len * m, mem, &st);
+    double* dO = out_dev(c, "red_out", out, (size_t)m * d, mem, &st);
+    const int64_t chunk = reduce_columns_chunk(len, m, d);
+    double* part = (double*)ctx_buf(c, "red_part", (size_t)((len + chunk - 1) / chunk) * d * m * 8);
+    // labels beyond d never index the accumulators (the kernel skips the entry and raises the flag)
+    uint32_t* flag = (uint32_t*)ctx_buf(c, "prim_flag", 64);
+    if (st || !part || !flag || !c->pinned_small) return st ? st : SDPSR_OUT_OF_MEMORY;
+    HIP_TRY(c, hipMemsetAsync(flag, 0, 4, c->stream));
+    if (!launch_reduce_columns(c->stream, len, m, d, dL, dA, part, dO, flag))
+        return ctx_fail(c, SDPSR_BAD_ARGUMENT, "dim(P) * min(m, 64) too large for the LDS accumulators");
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(c->pinned_small, flag, 4, hipMemcpyDeviceToHost, c->stream));
+    st = out_finish(c, out, dO, (size_t)m * d, mem);
+    if (st) return st;
+    if (c->pinned_small[0]) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "reduce_constraints: a label exceeds d = dim(P)");
+    return SDPSR_OK;
+}
+
 int sdpsr_reduce_constraints_csr(sdpsr_ctx* c, int64_t len, const uint32_t* labels, int64_t d, int64_t m, const int64_t* rowptr,
                                  const int64_t* colind, const double* val, int index_base, double* out, int mem) {
     CHECK_CTX(c);

@@ -91,7 +91,7 @@ struct sdpsr_ctx {
     // order and reads them behind its next host waits (reduce.cpp) -- one host wait less per reduction.  Violated verdicts
     // discard everything and the reduction is repeated without the guess.
     bool allow_deferred_verdict = false;
-    const volatile uint32_t* deferred_verdict = nullptr;  // words [0] and [16] must be 0
+    bool deferred_verdict = false;  // both wait in c->pinned_small (host_internal.h: PINNED_SMALL_DEFERRED_*) and must be 0
 };
 
 // sdpsr_problem_create: the loop's inputs, device-resident, shared (read-only) by every reduction / restart that names them

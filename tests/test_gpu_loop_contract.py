@@ -302,3 +302,35 @@ def test_restored_confirm_rounds_keep_the_oracle_trajectory(pkg, oracle, inst):
     assert len(dims) == r["iterations"] + 1 and dims[-1] == r["dim"]
     assert dims[1:] == trace, (dims, trace)
     assert r["draws"] == f["draws"] and r["squares"] - r["spec"] == f["squares"] and dims == f["traj"]
+
+
+def _loop_paths_tool():
+    """tools/record_loop_paths.py: the table's rows and the one way a row is run, shared with the recorder."""
+    import importlib.util
+    import pathlib
+    path = pathlib.Path(__file__).resolve().parents[1] / "tools" / "record_loop_paths.py"
+    spec = importlib.util.spec_from_file_location("record_loop_paths", path)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_every_loop_path_matches_the_recorded_table(pkg, inst):
+    """Every path of the loop at once: instance x square mode x one flag x hint x channels, plus the confirmed and the wrong
+    speculation (tools/record_loop_paths.py).  Each row -- dim, iterations, dimension trajectory, draws, squares, speculative
+    squares, host waits, CRC32 of the labels -- equals tests/golden/loop_paths.json, recorded once from the csrc of the commit
+    the file names; a combination the library rejects has no row there and is rejected here too."""
+    import json
+    tool = _loop_paths_tool()
+    with open(tool.GOLDEN) as f:
+        recorded = json.load(f)
+    assert recorded["seed"] == tool.SEED == SEED
+    rows = tool.rows()
+    assert set(recorded["rows"]) <= {row[0] for row in rows}
+    assert len(recorded["rows"]) >= 100  # (the table really is there: 134 rows less the rejected combinations)
+    bad = []
+    for row in rows:
+        got, want = tool.run_row(pkg, inst, row), recorded["rows"].get(row[0])
+        if got != want:
+            bad.append((row[0], got, want))
+    assert not bad, bad
