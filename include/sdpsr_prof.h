@@ -57,6 +57,19 @@ int sdpsr_profile_band_reduce(sdpsr_ctx* ctx, int64_t n, int b, double* A_host, 
    host), out[2] = milliseconds spent building.  A caller that alternates between a few orders pays the build once per
    order. */
 int sdpsr_profile_sytrd_graphs(sdpsr_ctx* ctx, double* out);
+/* The loop's label passes on caller-made inputs (tests).  The packed lower triangle Lp_host of symmetric labels <= d of order n (column j at
+   offset j n - j (j - 1) / 2) goes through the packed channel gather in its plain and in its label-writing form, Lfull_host (the mirrored n x n
+   labels) through the full-matrix gather, all with the same key.  X_plain, X_writing, X_full: T * ld * ld bytes each (T = 1, 2 or 4, ld = n
+   rounded up to 128), padding included; every byte no kernel wrote is 0x5A.  L_inout: n * n + guard words, uploaded as given, written by the
+   writing form (leading dimension n), downloaded again. */
+int sdpsr_profile_gather_packed(sdpsr_ctx* ctx, int64_t n, int T, int64_t d, uint64_t key, const uint32_t* Lp_host, const uint32_t* Lfull_host,
+                                int8_t* X_plain, int8_t* X_writing, int8_t* X_full, uint32_t* L_inout, int64_t guard);
+/* The verify pass "does any entry of the packed triangle differ from the representative of its class?".  first_idx_host: the packed index of
+   the representative of class l at [l - 1]; C_host: T (2 or 4) int32 channels of ld x ld.  mode 0: channels alone; 1: joint with one basis
+   matrix U_host (n x n) and its coefficient coef; 2: "is U_host constant on the classes" (C_host unused).  out[0] = verdict word (0: no entry
+   differs), out[1] = the class count up to which the pass is a single launch. */
+int sdpsr_profile_verify(sdpsr_ctx* ctx, int64_t n, int T, int64_t d, int mode, const uint32_t* Lp_host, const uint32_t* first_idx_host,
+                         const int32_t* C_host, const double* U_host, double coef, uint64_t key, double atol, uint32_t* out);
 
 #ifdef __cplusplus
 }

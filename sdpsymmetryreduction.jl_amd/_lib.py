@@ -187,5 +187,10 @@ def load_prof_library():
     lib.sdpsr_profile_loop_counts.argtypes = [vp, C.c_int32, C.POINTER(C.c_uint64)]
     lib.sdpsr_profile_sytrd_graphs.restype = C.c_int
     lib.sdpsr_profile_sytrd_graphs.argtypes = [vp, C.POINTER(C.c_double)]
+    lib.sdpsr_profile_gather_packed.restype = C.c_int
+    lib.sdpsr_profile_gather_packed.argtypes = [vp, i64, C.c_int, i64, C.c_uint64, vp, vp, vp, vp, vp, vp, i64]
+    lib.sdpsr_profile_verify.restype = C.c_int
+    lib.sdpsr_profile_verify.argtypes = [vp, i64, C.c_int, i64, C.c_int, vp, vp, vp, vp, C.c_double, C.c_uint64, C.c_double,
+                                         C.POINTER(C.c_uint32)]
     _prof = lib
     return lib

@@ -169,11 +169,16 @@ __device__ __forceinline__ void bytes_4x4_transpose(uint32_t a, uint32_t b, uint
     o[3] = __builtin_amdgcn_perm(cd_hi, ab_hi, 0x07060302u);
 }
 
-template <int T>
+// WRITE_L: the kernel also forms the full label matrix Lfull (n x n, leading dimension n) from the labels it has just read -- the work of
+// unpack_symmetric_labels_kernel without its pass over Lp.  The lower tile is stored as read, the mirrored one through the SAME LDS tile in a phase
+// of its own before the channel bytes are staged (a second tile would halve the resident workgroups); diagonal tiles hold every entry of the tile
+// by symmetry and are stored whole.  Nothing is stored at or beyond row / column n.
+template <int T, bool WRITE_L>
 __global__ void __launch_bounds__(256)
-gather_i8_sym_packed_kernel(int n, int64_t ld, const uint32_t* __restrict__ Lp, uint64_t key, int8_t* __restrict__ X, int dlut) {
+gather_i8_sym_packed_kernel(int n, int64_t ld, const uint32_t* __restrict__ Lp, uint64_t key, int8_t* __restrict__ X, int dlut,
+                            uint32_t* __restrict__ Lfull) {
     __shared__ uint32_t lut[GATHER_LUT + 1];
-    __shared__ uint32_t tile[64][65];  // [column][row]: channel bytes of element (i0 + row, j0 + column)
+    __shared__ uint32_t tile[64][65];  // [column][row]: channel bytes of element (i0 + row, j0 + column) (WRITE_L: its label first)
     const int bi = blockIdx.x, bj = blockIdx.y;
     if (bi < bj) return;
     if (dlut > 0) {
@@ -190,6 +195,23 @@ gather_i8_sym_packed_kernel(int n, int64_t ld, const uint32_t* __restrict__ Lp, 
         if (i < n && j < n) {
             const int hi = i > j ? i : j, lo = i > j ? j : i;  // (diagonal tiles: the upper half by symmetry)
             lab[q] = Lp[(int64_t)lo * n - (int64_t)lo * (lo - 1) / 2 + (hi - lo)];
+        }
+    }
+    if (WRITE_L) {
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            const int i = i0 + tx, j = j0 + ty + 4 * q;
+            if (i < n && j < n) Lfull[(int64_t)i + (int64_t)j * n] = lab[q];
+            if (bi != bj) tile[ty + 4 * q][tx] = lab[q];
+        }
+        if (bi != bj) {  // (uniform in the workgroup)
+            __syncthreads();
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {  // destination: row j0 + tx, column i0 + c  (= entry (i0 + c, j0 + tx))
+                const int c = ty + 4 * q, rr = j0 + tx, cc = i0 + c;
+                if (rr < n && cc < n) Lfull[(int64_t)rr + (int64_t)cc * n] = tile[tx][c];
+            }
+            __syncthreads();  // the tile is staged again below
         }
     }
 #pragma unroll
@@ -225,17 +247,24 @@ gather_i8_sym_packed_kernel(int n, int64_t ld, const uint32_t* __restrict__ Lp, 
             *reinterpret_cast<uint4*>(X + (int64_t)t * ld * ld + r0 + c0 * ld) = make_uint4(w[t][0], w[t][1], w[t][2], w[t][3]);
     }
 }
+// Lfull != nullptr: the full n x n label matrix is written as well (leading dimension n)
 void launch_gather_i8_sym_packed(hipStream_t s, int64_t n, int64_t ld, int T, const uint32_t* Lp, uint64_t key, int8_t* X,
-                                 int64_t dmax) {
+                                 int64_t dmax, uint32_t* Lfull) {
     const int dlut = (dmax > 0 && dmax <= GATHER_LUT) ? (int)dmax : 0;
     const unsigned t = (unsigned)(ld / 64);  // ld is a multiple of 128
     dim3 g(t, t);
+#define SDPSR_GATHER_PACKED_CASE(TT)                                                                                    \
+    case TT:                                                                                                            \
+        if (Lfull) gather_i8_sym_packed_kernel<TT, true><<<g, 256, 0, s>>>((int)n, ld, Lp, key, X, dlut, Lfull);        \
+        else gather_i8_sym_packed_kernel<TT, false><<<g, 256, 0, s>>>((int)n, ld, Lp, key, X, dlut, nullptr);           \
+        break;
     switch (T) {
-        case 1: gather_i8_sym_packed_kernel<1><<<g, 256, 0, s>>>((int)n, ld, Lp, key, X, dlut); break;
-        case 2: gather_i8_sym_packed_kernel<2><<<g, 256, 0, s>>>((int)n, ld, Lp, key, X, dlut); break;
-        case 4: gather_i8_sym_packed_kernel<4><<<g, 256, 0, s>>>((int)n, ld, Lp, key, X, dlut); break;
+        SDPSR_GATHER_PACKED_CASE(1)
+        SDPSR_GATHER_PACKED_CASE(2)
+        SDPSR_GATHER_PACKED_CASE(4)
         default: break;
     }
+#undef SDPSR_GATHER_PACKED_CASE
 }
 
 __global__ void gather_f32_kernel(int64_t n, int64_t ld, int T, int vmax,
@@ -1966,13 +1995,15 @@ struct VerifyRef {  // one per class: the step's values at the class representat
     uint64_t ybits;  // code of the rounded projected value there (sdpsr_round_key)
     int32_t c[4];    // channel products there
 };
+// Up to this many classes the compare pass builds the table of representatives itself, in LDS, in a prologue of every workgroup (8 KiB: the
+// kernel's occupancy stays where it is): no launch of its own for the table, no gather from global memory per entry.  More classes: the table
+// kernel and the compare pass as two launches.  The same cap serves the basis check below (<= 4 codes of 8 bytes per class).
+constexpr int VERIFY_LDS_CAP = 256;
+int verify_lds_cap() { return VERIFY_LDS_CAP; }
 template <int R, int T, bool JOINT>
-__global__ void verify_ref_kernel(int n, int64_t ld, int d, const uint32_t* __restrict__ first_idx, const double* __restrict__ U,
-                                  uint64_t key, const double* __restrict__ coef, double atol, double scale,
-                                  const int32_t* __restrict__ C, VerifyRef* __restrict__ ref, uint32_t* __restrict__ flag) {
-    const int cls = blockIdx.x * blockDim.x + threadIdx.x;
-    if (cls == 0) flag[0] = 0u;  // the verdict of the compare pass that follows in stream order
-    if (cls >= d) return;
+__device__ __forceinline__ VerifyRef verify_ref_of(int cls, int n, int64_t ld, const uint32_t* __restrict__ first_idx, const double* __restrict__ U,
+                                                   uint64_t key, const double* __restrict__ coef, double atol, double scale,
+                                                   const int32_t* __restrict__ C) {
     uint32_t i, j;
     packed_lower_ij(n, (int64_t)first_idx[cls], i, j);
     const int64_t ef = (int64_t)i + (int64_t)j * n;
@@ -1988,13 +2019,30 @@ __global__ void verify_ref_kernel(int n, int64_t ld, int d, const uint32_t* __re
     }
 #pragma unroll
     for (int t = 0; t < 4; ++t) r.c[t] = t < T ? C[(int64_t)t * ld * ld + (int64_t)j * ld + i] : 0;
-    ref[cls] = r;
+    return r;
 }
 template <int R, int T, bool JOINT>
+__global__ void verify_ref_kernel(int n, int64_t ld, int d, const uint32_t* __restrict__ first_idx, const double* __restrict__ U,
+                                  uint64_t key, const double* __restrict__ coef, double atol, double scale,
+                                  const int32_t* __restrict__ C, VerifyRef* __restrict__ ref, uint32_t* __restrict__ flag) {
+    const int cls = blockIdx.x * blockDim.x + threadIdx.x;
+    if (cls == 0) flag[0] = 0u;  // the verdict of the compare pass that follows in stream order
+    if (cls >= d) return;
+    ref[cls] = verify_ref_of<R, T, JOINT>(cls, n, ld, first_idx, U, key, coef, atol, scale, C);
+}
+// LDSREF (d <= VERIFY_LDS_CAP): the table is built here from first_idx (ref unused) and nobody zeroes flag[0] on the device -- a workgroup
+// could set the word before another one clears it: the launcher stores the 0 from the host before it enqueues the pass.
+template <int R, int T, bool JOINT, bool LDSREF>
 __global__ void __launch_bounds__(256)
 verify_lower_kernel(int n, int64_t ld, const uint32_t* __restrict__ Lp, const double* __restrict__ U, const double* __restrict__ coef,
                     double atol, double scale, const int32_t* __restrict__ C, const VerifyRef* __restrict__ ref,
-                    uint32_t* __restrict__ flag) {
+                    uint32_t* __restrict__ flag, int d, const uint32_t* __restrict__ first_idx, uint64_t key) {
+    __shared__ VerifyRef sref[LDSREF ? VERIFY_LDS_CAP : 1];
+    if (LDSREF) {
+        for (int cls = threadIdx.x; cls < d; cls += blockDim.x)
+            sref[cls] = verify_ref_of<R, T, JOINT>(cls, n, ld, first_idx, U, key, coef, atol, scale, C);
+        __syncthreads();
+    }
     bool bad = false;
     double cf[R > 0 ? R : 1];
 #pragma unroll
@@ -2030,7 +2078,11 @@ verify_lower_kernel(int n, int64_t ld, const uint32_t* __restrict__ Lp, const do
                 r[b].x = 0;
                 r[b].ybits = 0;
                 r[b].c[0] = r[b].c[1] = r[b].c[2] = r[b].c[3] = 0;
-                if (l[b]) r[b] = ref[l[b] - 1];  // label 0 (and the slots past the column): the zero class stays together only while every value is zero
+                // label 0 (and the slots past the column): the zero class stays together only while every value is zero
+                if (l[b]) {
+                    if (LDSREF) r[b] = sref[l[b] - 1];
+                    else r[b] = ref[l[b] - 1];
+                }
             }
 #pragma unroll
             for (int b = 0; b < VB; ++b) {
@@ -2049,14 +2101,21 @@ verify_lower_kernel(int n, int64_t ld, const uint32_t* __restrict__ Lp, const do
     if (bad) flag[0] = 1u;
 }
 
+// flag: a word of pinned host memory whose last verdict has been read (the one-launch form clears it from the host)
 template <int R, int T, bool JOINT>
 static void launch_verify_rt(hipStream_t s, const SigSource& q, int64_t d, const uint32_t* first_idx, void* ref, uint32_t* flag) {
     const int n = (int)q.n;
+    const int g = n < 256 * 8 ? n : 256 * 8;
+    if (d <= VERIFY_LDS_CAP) {
+        *(volatile uint32_t*)flag = 0u;
+        verify_lower_kernel<R, T, JOINT, true><<<g, 256, 0, s>>>(n, q.ld, q.L, q.U, q.coef, q.atol, q.scale, (const int32_t*)q.C, nullptr, flag,
+                                                                (int)d, first_idx, q.key);
+        return;
+    }
     verify_ref_kernel<R, T, JOINT><<<(unsigned)((d + 255) / 256), 256, 0, s>>>(n, q.ld, (int)d, first_idx, q.U, q.key, q.coef, q.atol, q.scale,
                                                                              (const int32_t*)q.C, (VerifyRef*)ref, flag);
-    const int g = n < 256 * 8 ? n : 256 * 8;
-    verify_lower_kernel<R, T, JOINT><<<g, 256, 0, s>>>(n, q.ld, q.L, q.U, q.coef, q.atol, q.scale, (const int32_t*)q.C,
-                                                      (const VerifyRef*)ref, flag);
+    verify_lower_kernel<R, T, JOINT, false><<<g, 256, 0, s>>>(n, q.ld, q.L, q.U, q.coef, q.atol, q.scale, (const int32_t*)q.C,
+                                                             (const VerifyRef*)ref, flag, (int)d, first_idx, q.key);
 }
 size_t verify_ref_bytes(int64_t d) { return (size_t)(d > 0 ? d : 1) * sizeof(VerifyRef); }
 
@@ -2067,11 +2126,8 @@ size_t verify_ref_bytes(int64_t d) { return (size_t)(d > 0 ? d : 1) * sizeof(Ver
 // entry of the packed lower triangle with those at the class representative (first_idx, as the verify pass); label 0
 // (structural zeros) needs U_k = 0.  flag[0] = 1 <=> some U_k is NOT constant on some class.
 template <int R>
-__global__ void uconst_ref_kernel(int n, int d, const uint32_t* __restrict__ first_idx, const double* __restrict__ U, double atol, double scale,
-                                  uint64_t* __restrict__ ref, uint32_t* __restrict__ flag) {
-    const int cls = blockIdx.x * blockDim.x + threadIdx.x;
-    if (cls == 0) flag[0] = 0u;
-    if (cls >= d) return;
+__device__ __forceinline__ void uconst_ref_of(int cls, int n, const uint32_t* __restrict__ first_idx, const double* __restrict__ U, double atol,
+                                              double scale, uint64_t* ref) {
     uint32_t i, j;
     packed_lower_ij(n, (int64_t)first_idx[cls], i, j);
     const int64_t ef = (int64_t)i + (int64_t)j * n;
@@ -2079,9 +2135,23 @@ __global__ void uconst_ref_kernel(int n, int d, const uint32_t* __restrict__ fir
     for (int k = 0; k < R; ++k) ref[(int64_t)cls * R + k] = sdpsr_round_key(U[(int64_t)k * n * n + ef], atol, scale);
 }
 template <int R>
+__global__ void uconst_ref_kernel(int n, int d, const uint32_t* __restrict__ first_idx, const double* __restrict__ U, double atol, double scale,
+                                  uint64_t* __restrict__ ref, uint32_t* __restrict__ flag) {
+    const int cls = blockIdx.x * blockDim.x + threadIdx.x;
+    if (cls == 0) flag[0] = 0u;
+    if (cls >= d) return;
+    uconst_ref_of<R>(cls, n, first_idx, U, atol, scale, ref);
+}
+// LDSREF: as verify_lower_kernel (the codes of d <= VERIFY_LDS_CAP classes from first_idx into LDS; flag[0] cleared by the launcher)
+template <int R, bool LDSREF>
 __global__ void __launch_bounds__(256)
 uconst_check_kernel(int n, const uint32_t* __restrict__ Lp, const double* __restrict__ U, double atol, double scale,
-                    const uint64_t* __restrict__ ref, uint32_t* __restrict__ flag) {
+                    const uint64_t* __restrict__ ref, uint32_t* __restrict__ flag, int d, const uint32_t* __restrict__ first_idx) {
+    __shared__ uint64_t sref[LDSREF ? VERIFY_LDS_CAP * R : 1];
+    if (LDSREF) {
+        for (int cls = threadIdx.x; cls < d; cls += blockDim.x) uconst_ref_of<R>(cls, n, first_idx, U, atol, scale, sref);
+        __syncthreads();
+    }
     bool bad = false;
     const int64_t nn = (int64_t)n * n;
     const uint64_t zero_code = sdpsr_round_key(0.0, atol, scale);
@@ -2105,7 +2175,13 @@ uconst_check_kernel(int n, const uint32_t* __restrict__ Lp, const double* __rest
 #pragma unroll
             for (int b = 0; b < VB; ++b)
 #pragma unroll
-                for (int k = 0; k < R; ++k) rc[b][k] = l[b] ? ref[(int64_t)(l[b] - 1) * R + k] : zero_code;
+                for (int k = 0; k < R; ++k) {
+                    rc[b][k] = zero_code;
+                    if (l[b]) {
+                        if (LDSREF) rc[b][k] = sref[(l[b] - 1) * R + k];
+                        else rc[b][k] = ref[(int64_t)(l[b] - 1) * R + k];
+                    }
+                }
 #pragma unroll
             for (int b = 0; b < VB; ++b)
 #pragma unroll
@@ -2116,16 +2192,23 @@ uconst_check_kernel(int n, const uint32_t* __restrict__ Lp, const double* __rest
 }
 size_t uconst_ref_bytes(int64_t d, int64_t r) { return (size_t)(d > 0 ? d : 1) * (size_t)(r > 0 ? r : 1) * 8; }
 // symmetric basis matrices U_k (n x n, column-major, r <= 4 of them), packed labels Lp of d <= REFINE_FIRST_CAP classes
-// with their representatives first_idx; flag: a word the device can write (pinned host memory)
+// with their representatives first_idx; flag: a word of pinned host memory whose last verdict has been read (d <= VERIFY_LDS_CAP: one launch,
+// the word is cleared from the host)
 bool launch_basis_constant_on_classes(hipStream_t s, int64_t n, int64_t r, const double* U, const uint32_t* Lp, int64_t d,
                                       const uint32_t* first_idx, double atol, double scale, void* ref, uint32_t* flag) {
     if (r < 1 || r > 4 || d < 1 || d > (int64_t)REFINE_FIRST_CAP) return false;
     const unsigned gr = (unsigned)((d + 255) / 256);
     const int g = n < 256 * 8 ? (int)n : 256 * 8;
-#define SDPSR_UCONST_CASE(RR)                                                                                          \
-    case RR:                                                                                                           \
-        uconst_ref_kernel<RR><<<gr, 256, 0, s>>>((int)n, (int)d, first_idx, U, atol, scale, (uint64_t*)ref, flag);      \
-        uconst_check_kernel<RR><<<g, 256, 0, s>>>((int)n, Lp, U, atol, scale, (const uint64_t*)ref, flag);              \
+    const bool lds = d <= VERIFY_LDS_CAP;
+    if (lds) *(volatile uint32_t*)flag = 0u;
+#define SDPSR_UCONST_CASE(RR)                                                                                                                  \
+    case RR:                                                                                                                                   \
+        if (lds) {                                                                                                                             \
+            uconst_check_kernel<RR, true><<<g, 256, 0, s>>>((int)n, Lp, U, atol, scale, nullptr, flag, (int)d, first_idx);                      \
+        } else {                                                                                                                               \
+            uconst_ref_kernel<RR><<<gr, 256, 0, s>>>((int)n, (int)d, first_idx, U, atol, scale, (uint64_t*)ref, flag);                          \
+            uconst_check_kernel<RR, false><<<g, 256, 0, s>>>((int)n, Lp, U, atol, scale, (const uint64_t*)ref, flag, (int)d, first_idx);        \
+        }                                                                                                                                      \
         break;
     switch (r) {
         SDPSR_UCONST_CASE(1)

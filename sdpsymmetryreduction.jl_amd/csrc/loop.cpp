@@ -7,8 +7,11 @@ using namespace sdpsr;
 
 namespace {  // ---- the admissible_subspace loop, src/partitions.jl:145-185 ----
 // Which label array is current.  Symmetric labels live as the packed lower triangle Lp (column j at offset j n - j (j - 1) / 2) between the
-// refinements of the int8 loop: every consumer there reads the packed form (the channel gather mirrors it tile by tile), the full matrix L is formed
-// once at the end -- or whenever a step needs it (non-symmetric basis, other square modes).  Only the methods below write the two validity bits.
+// refinements of the int8 loop: every consumer there reads the packed form (the channel gather mirrors it tile by tile).  The full matrix L is
+// formed by the channel gather of a round that is expected not to refine (a confirm round, the speculative square of a guess): that kernel holds
+// every tile in both orientations anyway, and when the round's verdict is "unchanged" L is the call's output as it stands.  A refinement
+// invalidates it; the unpack pass forms it where no such gather ran (no confirm rounds), or whenever a step needs it (non-symmetric basis, other
+// square modes).  Only the methods below write the two validity bits.
 class LoopLabels {
 public:
     uint32_t* L = nullptr;   // the full matrix (the call's output)
@@ -21,13 +24,19 @@ public:
         if (!full_valid) launch_unpack_symmetric_labels(c->stream, n, Lp, L);
         full_valid = true;
     }
-    void packed_is_current() { packed_valid = true, full_valid = false; }  // (a verify pass found the packed labels final)
+    // where a gather of the packed labels should write the full matrix too (nullptr: it is current already); the caller enqueues that gather
+    uint32_t* full_from_gather() {
+        if (full_valid || !packed_valid) return nullptr;
+        full_valid = true;
+        return L;
+    }
+    void packed_refined() { packed_valid = true, full_valid = false; }
     // symmetric by construction: refine the n (n + 1) / 2 entries of the packed lower triangle (same relative order, same canonical numbering; in
     // place when the labels were packed); the full matrix is formed right away only where the loop does not keep packed labels (the joint iteration
     // runs with keep_packed alone: nothing to form there)
     int refine_packed(const SigSource& src, int64_t* d) {
         const int st = refine_signatures(c, n * (n + 1) / 2, src, Lp, d, 0, nullptr, nullptr, early_ok);  // (early report: what follows is stream-ordered)
-        packed_is_current();
+        packed_refined();
         if (!st && !keep_packed) need_full();
         return st;
     }
@@ -110,8 +119,9 @@ struct Loop {
     }
     // The symmetric int8 square of a fresh random element of S: X from the packed or the full labels, X'X = X X on the lower-triangle tiles only (X
     // is symmetric, the product exact).
-    void launch_square(bool from_packed, uint64_t key, void* X, void* C, int64_t dim) {
-        if (from_packed) launch_gather_i8_sym_packed(s, n, ld, T, lab.Lp, key, (int8_t*)X, dim);
+    // write_full (packed labels only): the gather forms the full label matrix as well, unless it is current (LoopLabels).
+    void launch_square(bool from_packed, uint64_t key, void* X, void* C, int64_t dim, bool write_full = false) {
+        if (from_packed) launch_gather_i8_sym_packed(s, n, ld, T, lab.Lp, key, (int8_t*)X, dim, write_full ? lab.full_from_gather() : nullptr);
         else launch_gather_i8(s, n, ld, T, lab.L, key, (int8_t*)X, dim);
         launch_gemm_tn_i8_sym(s, ld, ld, (const int8_t*)X, ld, (int32_t*)C, ld, T, ld * ld, ld * ld, zero_flag, c->num_cus, c->opts.square_kernel);
         ++c->squares_launched;
@@ -137,10 +147,12 @@ struct Loop {
     // question "does any entry differ from the representative of its class?" (one streaming compare pass, kernels_partition.hip verify_*); only a yes
     // runs the insert / rank / label passes.  A confirm round re-checks the channels only: its projected element is the one the previous round has
     // cleared.
+    bool verify_applies(bool confirming, bool from_packed) const {
+        return (it == 1 || confirming) && from_packed && c->first_idx_labels == lab.Lp && current >= 1 && current <= (int64_t)refine_first_cap() &&
+               !(c->opts.flags & SDPSR_FLAG_NO_VERIFY_SHORTCUT);
+    }
     int verify_round(const SigSource& qj, bool confirming, bool from_packed, Verdict* v) {
-        if (!((it == 1 || confirming) && from_packed && c->first_idx_labels == lab.Lp && current >= 1 && current <= (int64_t)refine_first_cap() &&
-              !(c->opts.flags & SDPSR_FLAG_NO_VERIFY_SHORTCUT)))
-            return SDPSR_OK;
+        if (!verify_applies(confirming, from_packed)) return SDPSR_OK;
         SigSource qv = qj;
         if (confirming) qv.kind = SIG_CHAN_I32;
         void* vref = ctx_buf(c, "adm_vref", verify_ref_bytes(current));
@@ -166,7 +178,7 @@ struct Loop {
             void* Cs = ctx_buf(c, "adm_ci32_spec", (size_t)T * ld * ld * 4);
             void* vref2 = ctx_buf(c, "adm_vref2", verify_ref_bytes(current));
             if (Xs && Cs && vref2) {
-                launch_square(true, next_key(c), Xs, Cs, current);
+                launch_square(true, next_key(c), Xs, Cs, current, /*write_full=*/true);  // (expected to be the call's last gather)
                 ++c->squares_speculative;
                 SigSource q2 = qj;
                 q2.kind = SIG_CHAN_I32, q2.C = Cs;
@@ -212,14 +224,15 @@ struct Loop {
             tm.begin(SDPSR_T_SQUARE);
             const uint64_t key2 = next_key(c);
             const bool jl2 = lab.packed();
-            launch_square(jl2, key2, Xp, Cp, current);
+            // a confirm round that the verify pass will judge is expected to leave the labels as they are: its gather writes the full matrix
+            launch_square(jl2, key2, Xp, Cp, current, /*write_full=*/confirming && verify_applies(confirming, jl2));
             tm.end();
             tm.begin(SDPSR_T_REFINE);
             const SigSource qj = joint_source(jl2);
             Verdict v;
             st = verify_round(qj, confirming, jl2, &v);
             if (st) return st;
-            if (v.unchanged) dj = current, lab.packed_is_current();  // labels, class representatives and table hints stay as they are
+            if (v.unchanged) dj = current;  // labels (packed, and full where a gather has written them), class representatives and table hints stay as they are
             else st = lab.refine_packed(qj, &dj);
             tm.end();
             if (st) return st;
@@ -363,8 +376,8 @@ struct Loop {
 }  // namespace
 
 namespace sdpsr {
-// mem_in: where CL / X0L / U live; mem_out: where P_out lives.  final_sync = false (sdpsr_jordan_reduce): return with the last launches (the unpack
-// of the packed labels) still in flight on ctx's stream -- the caller keeps enqueueing; *labels_sym_out = 1 if the labels written are symmetric by
+// mem_in: where CL / X0L / U live; mem_out: where P_out lives.  final_sync = false (sdpsr_jordan_reduce): return with the last launches (the
+// gather or the unpack that forms the full labels) still in flight on ctx's stream -- the caller keeps enqueueing; *labels_sym_out = 1 if the labels written are symmetric by
 // construction.
 int admissible_subspace_impl(sdpsr_ctx* c, int64_t n, const double* CL, const double* X0L, const double* U, int64_t r, double atol,
                              uint32_t* P_out, int64_t* dim_out, int32_t* iters_out, double* phase_ms, int mem, int mem_out,

@@ -173,6 +173,87 @@ extern "C" int sdpsr_profile_loop_counts(sdpsr_ctx* c, int32_t restart, uint64_t
     return SDPSR_OK;
 }
 
+// The loop's label passes on caller-made inputs (tests/test_gpu_label_passes.py).  Gather: the packed triangle Lp (order n, labels <= d) through
+// the plain and the label-writing form of the packed channel gather, and the mirrored full labels Lfull through the full-matrix gather; the three
+// X (T channels of ld x ld, ld = n rounded up to 128; every buffer filled with 0x5A first, so padding nobody wrote shows) come back with the full
+// matrix the writing form made.  L_inout: n * n + guard words, uploaded as they are (the test's fill) and downloaded after the kernel.
+extern "C" int sdpsr_profile_gather_packed(sdpsr_ctx* c, int64_t n, int T, int64_t d, uint64_t key, const uint32_t* Lp_host, const uint32_t* Lfull_host,
+                                           int8_t* X_plain, int8_t* X_writing, int8_t* X_full, uint32_t* L_inout, int64_t guard) {
+    CHECK_CTX(c);
+    if (!Lp_host || !Lfull_host || !X_plain || !X_writing || !X_full || !L_inout || n < 1 || n > 8192 || guard < 0 || (T != 1 && T != 2 && T != 4))
+        return ctx_fail(c, SDPSR_BAD_ARGUMENT, "bad arguments");
+    hipStream_t s = c->stream;
+    const int64_t ld = round_up(n, 128), np = n * (n + 1) / 2;
+    const size_t xb = (size_t)T * ld * ld;
+    uint32_t* Lp = (uint32_t*)ctx_buf(c, "prof_lp", (size_t)np * 4);
+    uint32_t* Lf = (uint32_t*)ctx_buf(c, "prof_lfull", (size_t)n * n * 4);
+    uint32_t* Lw = (uint32_t*)ctx_buf(c, "prof_lwritten", (size_t)(n * n + guard) * 4);
+    int8_t* X = (int8_t*)ctx_buf(c, "prof_gx", 3 * xb);
+    if (!Lp || !Lf || !Lw || !X) return SDPSR_OUT_OF_MEMORY;
+    HIP_TRY(c, hipMemcpyAsync(Lp, Lp_host, (size_t)np * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(Lf, Lfull_host, (size_t)n * n * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(Lw, L_inout, (size_t)(n * n + guard) * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemsetAsync(X, 0x5A, 3 * xb, s));
+    launch_gather_i8_sym_packed(s, n, ld, T, Lp, key, X, d);
+    launch_gather_i8_sym_packed(s, n, ld, T, Lp, key, X + xb, d, Lw);
+    launch_gather_i8(s, n, ld, T, Lf, key, X + 2 * xb, d);
+    HIP_TRY(c, hipMemcpyAsync(X_plain, X, xb, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(X_writing, X + xb, xb, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(X_full, X + 2 * xb, xb, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(L_inout, Lw, (size_t)(n * n + guard) * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, hipGetLastError());
+    return SDPSR_OK;
+}
+
+// Verify: "does any entry of the packed triangle differ from the representative of its class?" on caller-made inputs.  Lp: packed labels <= d,
+// first_idx: the d packed indices of the representatives, C_host: T (2 or 4) int32 channels of ld x ld.  mode 0: the channels alone; 1: joint
+// with the one basis matrix U_host (n x n) and coefficient coef (the class draws come from key); 2: the basis check "is U constant on the
+// classes" (C_host unused).  out[0] = the verdict word (it holds 0xDEAD before the pass is enqueued: the pass has to clear it),
+// out[1] = the class count up to which the pass is one launch.
+extern "C" int sdpsr_profile_verify(sdpsr_ctx* c, int64_t n, int T, int64_t d, int mode, const uint32_t* Lp_host, const uint32_t* first_idx_host,
+                                    const int32_t* C_host, const double* U_host, double coef, uint64_t key, double atol, uint32_t* out) {
+    CHECK_CTX(c);
+    if (!Lp_host || !first_idx_host || !out || n < 1 || n > 8192 || d < 1 || d > (int64_t)refine_first_cap() || mode < 0 || mode > 2 ||
+        (mode != 2 && (!C_host || (T != 2 && T != 4))) || (mode != 0 && !U_host) || !(atol > 0))
+        return ctx_fail(c, SDPSR_BAD_ARGUMENT, "bad arguments");
+    hipStream_t s = c->stream;
+    const int64_t ld = round_up(n, 128), np = n * (n + 1) / 2;
+    const size_t cb = (size_t)(mode == 2 ? 1 : T) * ld * ld * 4;
+    uint32_t* Lp = (uint32_t*)ctx_buf(c, "prof_lp", (size_t)np * 4);
+    uint32_t* first = (uint32_t*)ctx_buf(c, "prof_first", (size_t)d * 4);
+    int32_t* Cd = (int32_t*)ctx_buf(c, "prof_vc", cb);
+    double* Ud = (double*)ctx_buf(c, "prof_vu", (size_t)(n * n + 1) * 8);  // + the coefficient
+    void* ref = ctx_buf(c, "prof_vref", std::max(verify_ref_bytes(d), uconst_ref_bytes(d, 1)));
+    uint32_t* hv = pinned_report(c, PINNED_VERIFY);
+    if (!Lp || !first || !Cd || !Ud || !ref || !hv) return SDPSR_OUT_OF_MEMORY;
+    HIP_TRY(c, hipMemcpyAsync(Lp, Lp_host, (size_t)np * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(first, first_idx_host, (size_t)d * 4, hipMemcpyHostToDevice, s));
+    if (mode != 2) HIP_TRY(c, hipMemcpyAsync(Cd, C_host, cb, hipMemcpyHostToDevice, s));
+    if (mode != 0) {
+        HIP_TRY(c, hipMemcpyAsync(Ud, U_host, (size_t)n * n * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(Ud + n * n, &coef, 8, hipMemcpyHostToDevice, s));
+    }
+    HIP_TRY(c, hipStreamSynchronize(s));  // (coef is a stack variable; and nothing may be in flight on the verdict word)
+    hv[0] = 0xDEADu;
+    const double scale = round_scale(c, atol);
+    bool ran;
+    if (mode == 2) {
+        ran = launch_basis_constant_on_classes(s, n, 1, Ud, Lp, d, first, atol, scale, ref, hv);
+    } else {
+        SigSource q;
+        q.kind = mode == 1 ? SIG_JOINT_I32 : SIG_CHAN_I32, q.U = Ud, q.coef = Ud + n * n, q.r = mode == 1 ? 1 : 0, q.key = key, q.atol = atol, q.scale = scale;
+        q.n = n, q.ld = ld, q.T = T, q.C = Cd, q.L = Lp, q.packed = 1, q.lab_packed = 1;
+        ran = launch_verify_no_split(s, q, d, first, ref, hv);
+    }
+    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, hipGetLastError());
+    if (!ran) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "no verify pass for this shape");
+    out[0] = ((const volatile uint32_t*)hv)[0];
+    out[1] = (uint32_t)verify_lds_cap();
+    return SDPSR_OK;
+}
+
 extern "C" int sdpsr_profile_kernel(sdpsr_ctx* c, int kind, int64_t n, int64_t aux, int reps,
                                     double* ms_per_launch) {
     CHECK_CTX(c);

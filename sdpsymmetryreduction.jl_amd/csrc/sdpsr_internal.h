@@ -197,8 +197,9 @@ void launch_proj_coef(hipStream_t s, int64_t len, int64_t r, const double* U, co
                       uint64_t key, const double* xin, double* partial, int nblk, double* coef);
 // y[e] = x[e] - sum_k U[e,k] coef[k]; optional outputs: yout (rounded value, fp64),
 // sig (signature chained on L).  x as above.
+// Lfull != nullptr: the kernel also writes the full n x n label matrix (leading dimension n) that the packed triangle describes
 void launch_gather_i8_sym_packed(hipStream_t s, int64_t n, int64_t ld, int T, const uint32_t* Lp, uint64_t key, int8_t* X,
-                                 int64_t dmax);
+                                 int64_t dmax, uint32_t* Lfull = nullptr);
 void launch_proj_coef_lower(hipStream_t s, int64_t n, int64_t r, const double* U, const uint32_t* L, int lab_packed,
                             uint64_t key, double* partial, int nblk, double* coef);
 void launch_proj_coef_probe(hipStream_t s, int64_t len, int64_t n, int64_t r, const double* U, const uint32_t* L, uint64_t key,
@@ -274,6 +275,10 @@ bool sig_source_fusable(const SigSource& q);
 uint32_t refine_first_cap();
 size_t verify_ref_bytes(int64_t d);
 size_t uconst_ref_bytes(int64_t d, int64_t r);
+// The two checks below are ONE launch up to verify_lds_cap() classes (the table of representatives is built in LDS by every workgroup, `ref` is
+// not touched) and then clear flag[0] with a store from the HOST before they enqueue the pass: `flag` is pinned host memory, and the verdict of
+// the previous pass on that word has been read.  More classes: table kernel (which clears the word on the device) + compare pass.
+int verify_lds_cap();
 bool launch_basis_constant_on_classes(hipStream_t s, int64_t n, int64_t r, const double* U, const uint32_t* Lp, int64_t d,
                                       const uint32_t* first_idx, double atol, double scale, void* ref, uint32_t* flag);
 bool launch_verify_no_split(hipStream_t s, const SigSource& q, int64_t d, const uint32_t* first_idx, void* ref, uint32_t* flag);
