@@ -6,10 +6,24 @@
 // Householder tridiagonalisation with the reflectors accumulated, implicit-shift QL on the
 // tridiagonal matrix, eigenvalues ascending -- the textbook dense method (what LAPACK's dsteqr path
 // does), ~10 w^3 flop: 0.4 Mflop at w = 34.
+//
+// Two norm-wise rules keep it sound on inputs of exact low rank (block-constant matrices: kron(ones, C), u u'),
+// whose trailing blocks are rounding noise that is itself of low rank and shrinks level by level:
+//   drop rule       a column whose norm below the diagonal is <= 1e-30 max|A| counts as reduced (tau = 0): dropping it
+//                   perturbs A by <= 1e-30 |A| per column, n 1e-30 |A| << eps |A| in all.  Above that threshold the
+//                   reflector norm is formed from the squares, or dlarfg-style from x / max|x| where the squares leave
+//                   [1e-280, 1e280], so that H = I - tau v v' stays orthogonal when the squares would underflow.
+//   deflation rule  once an eigenvalue has taken 30 QL iterations (half the cap; Wilkinson shifts need 2 - 3), QL splits
+//                   at e[m] when |e[m]| <= eps |T| (|T| = max |entry|) as well as by the local test
+//                   |e[m]| <= eps (|d[m]| + |d[m+1]|): zeroing it perturbs T by <= eps |T|, the backward error of the
+//                   whole method.  The local test alone never fires in a noise tail with |e| ~ 10 |d|.
+// Neither rule changes a bit of the result where the local test and the plain squares suffice.
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
+#include <cstdint>
 #include <cstring>
+#include <limits>
 #include <numeric>
 #include <vector>
 
@@ -72,18 +86,31 @@ int host_syev(int n, const double* A, int lda, double* w, double* Z, int ldz) {
     for (int j = 0; j < n; ++j)
         for (int i = 0; i < n; ++i) a[(size_t)i + (size_t)j * n] = 0.5 * (A[(size_t)i + (size_t)j * lda] + A[(size_t)j + (size_t)i * lda]);
     auto at = [&](int i, int j) -> double& { return a[(size_t)i + (size_t)j * n]; };
+    double amax = 0.0;  // max |A|, for the drop rule
+    for (double t : a) amax = std::max(amax, std::fabs(t));
     // --- tridiagonalisation: H_k = I - tau_k v_k v_k', v_k = (1, x) kept below the subdiagonal of column k
     for (int k = 0; k + 2 < n; ++k) {
         const int m = n - k - 1;  // order of the trailing block
         double* x = &at(k + 1, k);
-        const double xn2 = dot(m - 1, x + 1, x + 1);
-        if (xn2 == 0.0) {
-            e[k] = x[0];
+        const double alpha = x[0];
+        const double xn2 = dot(m - 1, x + 1, x + 1), nrm2 = alpha * alpha + xn2;
+        double xnrm = std::sqrt(xn2), nrm = std::sqrt(nrm2);  // |x[1:]| and |x|
+        if (!(nrm2 > 1e-280 && nrm2 < 1e280) && !std::isnan(nrm2)) {  // the squares may have under- or overflowed
+            double mx = 0.0;
+            for (int i = 0; i < m; ++i) mx = std::max(mx, std::fabs(x[i]));
+            if (mx > 0.0 && mx <= std::numeric_limits<double>::max()) {
+                double s = 0.0;
+                for (int i = 1; i < m; ++i) s += (x[i] / mx) * (x[i] / mx);
+                xnrm = mx * std::sqrt(s);
+                nrm = mx * std::sqrt(s + (alpha / mx) * (alpha / mx));
+            }
+        }
+        if (xnrm == 0.0 || nrm <= 1e-30 * amax) {  // reduced already, or negligible against |A|: the drop rule
+            e[k] = alpha;
             tau[k] = 0.0;
             continue;
         }
-        const double alpha = x[0];
-        const double beta = -std::copysign(std::sqrt(alpha * alpha + xn2), alpha);
+        const double beta = -std::copysign(nrm, alpha);
         tau[k] = (beta - alpha) / beta;
         const double sc = 1.0 / (alpha - beta);
         v[0] = 1.0;
@@ -119,6 +146,9 @@ int host_syev(int n, const double* A, int lda, double* w, double* Z, int ldz) {
     // applied ONE STEP LATE (generation order is kept): the out-of-order core runs the vector work of
     // rotation k in the shadow of the chain of rotation k + 1.
     const double eps = 2.220446049250313e-16;
+    double tnorm = 0.0;  // max |T|, for the norm-wise deflation rule
+    for (int i = 0; i < n; ++i) tnorm = std::max(tnorm, std::max(std::fabs(d[i]), std::fabs(e[i])));
+    const double esmall = eps * tnorm;
     int held_i = -1;  // the one rotation generated but not yet applied
     double held_c = 1, held_s = 0;
     auto apply_held = [&]() {
@@ -130,7 +160,7 @@ int host_syev(int n, const double* A, int lda, double* w, double* Z, int ldz) {
         for (;;) {
             int m = l;
             for (; m + 1 < n; ++m)
-                if (std::fabs(e[m]) <= eps * (std::fabs(d[m]) + std::fabs(d[m + 1]))) break;
+                if (std::fabs(e[m]) <= eps * (std::fabs(d[m]) + std::fabs(d[m + 1])) || (iter >= 30 && std::fabs(e[m]) <= esmall)) break;
             if (m == l) break;
             if (++iter > 60) return l + 1;
             double g = (d[l + 1] - d[l]) / (2.0 * e[l]);
