@@ -12,7 +12,8 @@
  * Conventions
  *  - all matrices column-major, n x n unless stated; "len" = number of entries
  *    scanned in column-major linear order (the only order the reference uses);
- *  - labels are uint32: 0 = structurally-zero class (not counted), 1..dim;
+ *  - labels are uint32: 0 = structurally-zero class (not counted), 1..dim; a ctx told so with
+ *    sdpsr_set_label_width reads and writes them as uint16 / uint8 instead (the reference's Partition{T});
  *  - every array argument lives in the memory space named by `mem`
  *    (SDPSR_MEM_HOST: caller-owned host memory, copied by the library;
  *     SDPSR_MEM_DEVICE: device pointers on ctx's device, used in place);
@@ -49,7 +50,8 @@ typedef enum sdpsr_status {
     SDPSR_NUMERICAL_INCONSISTENCY = 2,
     /* DimensionMismatch from check_block_sizes, src/diagonalize.jl:1-11 */
     SDPSR_DIMENSION_MISMATCH = 3,
-    /* Julia's InexactError on label overflow (src/partitions.jl:29,63).  Only with sdpsr_opts.label_bits = 8 / 16 / 32
+    /* Julia's InexactError on label overflow (src/partitions.jl:29,63).  At the interface: a partition that does not fit the
+       width set with sdpsr_set_label_width, sdpsr_labels_convert (see there).  Inside the algorithms only with sdpsr_opts.label_bits = 8 / 16 / 32
        (the width of the reference's label type T): sdpsr_partition_from_* when the class count exceeds typemax(T);
        sdpsr_refine when the largest pair code l1 + l2 (dim(P1) + 1) does (exactly the reference's condition);
        sdpsr_admissible_subspace when dim(S) after a refinement does -- a NECESSARY condition of the reference's
@@ -228,6 +230,30 @@ int sdpsr_set_seed(sdpsr_ctx* ctx, uint64_t seed);
    dims[k] = dim(S) at the end of iteration k; *count = iterations + 1 (also when capacity is smaller; at most
    `capacity` entries are written).  Host arrays. */
 int sdpsr_dimension_trajectory(sdpsr_ctx* ctx, int64_t* dims, int32_t capacity, int32_t* count);
+
+/* ---- label width: Partition{T <: Integer}, src/partitions.jl:6-11 (admissible_subspace defaults to UInt16, :84) ----
+   width, in bits, of every label array this ctx's entry points read or write, in EITHER memory space:
+   32 (default) | 16 | 8.  The prototypes keep uint32_t*; with 16 / 8 the caller passes uint16_t* / uint8_t* cast.
+   Applies to calls made after it; restarts of a batch call inherit it.  Governed: `labels` of sdpsr_partition_from_f64 / _u32 /
+   _u64 (their `in` stays as declared: keys, not labels), sdpsr_partition_checksum, sdpsr_fill, sdpsr_randomize,
+   sdpsr_reduce_constraints / _csr; p1, p2 of sdpsr_refine; P of sdpsr_desymmetrize, sdpsr_block_diagonalize / _complex (and its
+   P_desym), sdpsr_eigen_decomposition / _batched; P_out of sdpsr_admissible_subspace / _dense / _csr, sdpsr_jordan_reduce /
+   _batch, sdpsr_problem_reduce / _batch.
+   The label VALUES are those of the 32-bit interface: an array at width B equals the 32-bit array cast to B (same checksum).
+   OUTPUT OVERFLOW: an entry point that would deliver a partition of more than 2^B - 1 classes -- the reference's InexactError
+   of Partition{T} -- returns SDPSR_LABEL_OVERFLOW with the class count (*nparts, *d1, *dim, *dim_out, *d_desym) set and the
+   label output untouched; sdpsr_jordan_reduce / sdpsr_problem_reduce stop behind the loop then, the batch entries report it
+   in status[i].  The count is known on the host before any label is delivered: no kernel decides this.
+   DEVICE MEMORY at 16 / 8: the work runs on the ctx's own uint32 buffer and the result is narrowed into the caller's array by
+   one streaming pass; the in-place arrangements of width 32 (P_out serving blockDiagonalize directly, desymmetrize and refine
+   on the caller's buffer) do not apply.  sdpsr_transfer_bytes counts what crosses: len * B / 8 per label array.
+   Independent of sdpsr_opts.label_bits, which emulates the reference's overflow INSIDE the algorithms. */
+int sdpsr_set_label_width(sdpsr_ctx* ctx, int bits); /* other values: SDPSR_BAD_ARGUMENT, width unchanged */
+int sdpsr_label_width(sdpsr_ctx* ctx);               /* 8 / 16 / 32 */
+/* element-wise conversion of a label array between two widths (8 / 16 / 32 each), on the device; `in` and `out` in memory space
+   mem, must not overlap.  Narrowing a value that does not fit: SDPSR_LABEL_OVERFLOW (contents of out then unspecified, nothing
+   outside out[0, len) written).  Independent of the ctx's own width. */
+int sdpsr_labels_convert(sdpsr_ctx* ctx, int64_t len, const void* in, int in_bits, void* out, int out_bits, int mem);
 
 /* ---- AbstractPartition contract (primitives) ------------------------------- */
 /* Partition{T}(M::AbstractMatrix) float ctor, src/partitions.jl:24-35: classes of
@@ -490,7 +516,10 @@ int sdpsr_problem_reduce_batch(sdpsr_ctx* ctx, const sdpsr_problem* problem, int
                                int64_t* sum_sq, int64_t* sum_s, double* const* blks, const int64_t* blks_capacity,
                                int32_t* status, int mem_out);
 /* Bytes ctx (and the restarts' ctxs inside it) has moved host -> device / device -> host since its creation: what a
-   caller of the host-array interface pays on PCIe (tests: a 4-restart batch uploads what one call uploads). */
+   caller of the host-array interface pays on PCIe (tests: a 4-restart batch uploads what one call uploads).  A label array
+   counts len * B / 8 bytes at label width B (sdpsr_set_label_width).  Since the label widths were added the host label upload
+   of sdpsr_block_diagonalize and the label upload / P_desym download of sdpsr_block_diagonalize_complex are counted too, at
+   every width (they crossed uncounted before). */
 int sdpsr_transfer_bytes(sdpsr_ctx* ctx, uint64_t* h2d, uint64_t* d2h);
 
 /* ---- blockDiagonalize(P; complex = true), src/compat.jl:26-32,46-68 with T = ComplexF64 ---------

@@ -7,6 +7,8 @@ import ctypes as C
 import os
 import re
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsdpsr_hip.so")
 PROF_LIB_PATH = os.path.join(_HERE, "libsdpsr_prof.so")  # measurement entry points, not the product
@@ -37,6 +39,18 @@ FLAG_SYTRD_ONE_LAUNCH = 1 << 14
 FLAG_WAIT_FOR_EVERY_VERDICT = 1 << 15
 BASIS_IMAGE_KERNELS = {"auto": 0, "two_stage": 1, "outer": 2, "chunk": 3}
 REFINE_PATHS = {"auto": 0, "hash": 1, "sort": 2, "bucket": 3, "no_mid": 4, "mid_no_first": 6}
+
+# sdpsr_set_label_width: the element type of a label array at each interface width (the reference's Partition{T})
+LABEL_DTYPES = {8: np.dtype(np.uint8), 16: np.dtype(np.uint16), 32: np.dtype(np.uint32)}
+
+
+def label_dtype(bits):
+    """numpy dtype of a label array at interface width ``bits`` (8, 16 or 32)."""
+    try:
+        return LABEL_DTYPES[int(bits)]
+    except KeyError:
+        raise ValueError(f"label width must be 8, 16 or 32, not {bits!r}") from None
+
 
 STATUS = {
     0: "OK", 1: "INVALID_DECOMPOSITION_FIELD", 2: "NUMERICAL_INCONSISTENCY", 3: "DIMENSION_MISMATCH",
@@ -147,6 +161,9 @@ def load_library():
         "sdpsr_eigen_decomposition_batched": (C.c_int, [vp, i64, vp, i64, dbl, i64, vp, vp, vp, vp, C.c_int]),
         "sdpsr_syev_f64": (C.c_int, [vp, i64, vp, vp, vp, C.c_int]),
         "sdpsr_hint_symmetric_basis": (C.c_int, [vp, C.c_int]),
+        "sdpsr_set_label_width": (C.c_int, [vp, C.c_int]),
+        "sdpsr_label_width": (C.c_int, [vp]),
+        "sdpsr_labels_convert": (C.c_int, [vp, i64, vp, C.c_int, vp, C.c_int, C.c_int]),
     }
     missing = [s for s in declared_symbols() if not hasattr(lib, s)]
     if missing:

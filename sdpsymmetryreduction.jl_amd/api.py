@@ -52,6 +52,12 @@ _EXC = {1: InvalidDecompositionField, 2: NumericalInconsistency, 3: DimensionMis
         4: LabelOverflow, 9: NotConverged}
 
 
+def _torch_label_dtype(bits):
+    """torch dtype of a device-resident label array at ``bits`` bits per label (32: int32, the uint32 bit pattern)."""
+    import torch
+    return {8: torch.uint8, 16: getattr(torch, "uint16", torch.int16), 32: torch.int32}[int(bits)]
+
+
 def _is_torch(x):
     return hasattr(x, "data_ptr") and hasattr(x, "is_cuda")
 
@@ -69,10 +75,13 @@ class Context:
 
     def __init__(self, device=0, seed=0, square_mode=L.SQUARE_AUTO, channels=0, max_iters=0,
                  confirm_rounds=0, eig_driver=0, flags=0, round_mode="nearest", basis_image_kernel="auto",
-                 refine_path="auto", label_bits=0, insert_wgs_per_cu=0, square_kernel=0):
+                 refine_path="auto", label_bits=0, insert_wgs_per_cu=0, square_kernel=0, label_width=32):
         """``flags``: OR of ``_lib.FLAG_*``; ``round_mode``: "nearest" (default) or "trunc" (the
         reference's ``unsafe_round``, src/utils.jl:49-53); ``label_bits``: 0, or the width of the
-        reference's label type ``T`` in ``Partition{T}`` to get ``LabelOverflow`` where it would throw."""
+        reference's label type ``T`` in ``Partition{T}`` to get ``LabelOverflow`` where it would throw
+        inside the algorithms; ``label_width``: 32, 16 or 8 -- the element width of every label array this
+        context passes to or receives from the library (``sdpsr_set_label_width``; ``Partition.matrix``
+        then comes back as ``label_dtype``)."""
         self._lib = L.load_library()
         o = L.Opts()
         o.struct_size = C.sizeof(L.Opts)
@@ -94,6 +103,33 @@ class Context:
             raise SdpsrError(f"sdpsr_create failed: {L.STATUS.get(st, st)} (is a GPU visible?)")
         self._h = h
         self.device = device
+        self._label_width = 32
+        if int(label_width) != 32:
+            try:
+                self.label_width = label_width
+            except Exception:
+                self.close()
+                raise
+
+    @property
+    def label_width(self):
+        """Bits of a label at this context's interface: 32 (default), 16 or 8 (``sdpsr_label_width``)."""
+        return self._label_width
+
+    @label_width.setter
+    def label_width(self, bits):
+        L.label_dtype(bits)  # ValueError for anything but 8 / 16 / 32
+        self.check(self._lib.sdpsr_set_label_width(self._h, int(bits)))
+        self._label_width = int(self._lib.sdpsr_label_width(self._h))
+
+    @property
+    def label_dtype(self):
+        """NumPy dtype of the label arrays of this context (``np.uint8`` / ``np.uint16`` / ``np.uint32``)."""
+        return L.label_dtype(self._label_width)
+
+    def torch_label_dtype(self):
+        """torch dtype of a device-resident label array of this context (32 bits: int32, the uint32 bit pattern)."""
+        return _torch_label_dtype(self._label_width)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -176,6 +212,17 @@ def _f(a, dtype):
     return np.ascontiguousarray(a.ravel(order="F"))
 
 
+def _lab(matrix, ctx):
+    """Column-major flat host labels at the context's width; a label that does not fit is the reference's InexactError."""
+    a = np.asarray(matrix)
+    dt = ctx.label_dtype
+    if a.dtype != dt and a.size and (a.max() > np.iinfo(dt).max or a.min() < 0):
+        exc = LabelOverflow(f"a label does not fit {dt.name} (the context's label_width is {ctx.label_width})")
+        exc.status = 4
+        raise exc
+    return _f(a, dt)
+
+
 class Partition:
     """``Partition`` (src/partitions.jl:6-17): ``matrix`` holds labels 0..nparts."""
 
@@ -190,7 +237,7 @@ class Partition:
         M = np.asarray(M)
         shape = M.shape
         n = C.c_int64(0)
-        out = np.empty(M.size, dtype=np.uint32)
+        out = np.empty(M.size, dtype=ctx.label_dtype)
         if np.issubdtype(M.dtype, np.floating):
             flat = _f(M, np.float64)
             ctx.check(ctx._lib.sdpsr_partition_from_f64(ctx._h, flat.size, _ptr(flat), _ptr(out), C.byref(n), L.MEM_HOST))
@@ -227,8 +274,8 @@ def refine(P1, P2, ctx=None):
     """``refine!(P1, P2)`` (src/partitions.jl:62-66); P1 is updated and returned."""
     ctx = _ctx(ctx)
     assert P1.shape == P2.shape
-    a = _f(P1.matrix, np.uint32).copy()
-    b = _f(P2.matrix, np.uint32)
+    a = _lab(P1.matrix, ctx).copy()
+    b = _lab(P2.matrix, ctx)
     d1 = C.c_int64(P1.nparts)
     ctx.check(ctx._lib.sdpsr_refine(ctx._h, a.size, _ptr(a), C.byref(d1), _ptr(b), P2.nparts, L.MEM_HOST))
     P1.matrix = a.reshape(P1.shape, order="F")
@@ -242,11 +289,12 @@ def partition_checksum(P, ctx=None):
     ``P`` is a Partition or a flat torch/NumPy array of column-major labels."""
     ctx = _ctx(ctx)
     if isinstance(P, Partition):
-        lab, mem = _labels_arg(P)
+        lab, mem = _labels_arg(P, ctx)
     elif _is_torch(P):
+        _check_torch_labels(P, ctx)
         lab, mem = P.contiguous().view(-1), (L.MEM_DEVICE if P.is_cuda else L.MEM_HOST)
     else:
-        lab, mem = np.ascontiguousarray(P, dtype=np.uint32).ravel(), L.MEM_HOST
+        lab, mem = np.ascontiguousarray(_lab(np.asarray(P).ravel(), ctx)), L.MEM_HOST
     n_entries = lab.numel() if _is_torch(lab) else lab.size
     ctx.wait_for(lab)
     out = (C.c_uint64 * 2)()
@@ -256,13 +304,13 @@ def partition_checksum(P, ctx=None):
 
 def relabel_keys(keys, ctx=None):
     """Canonical relabel (first-occurrence order, 0 stays 0) of a flat torch CUDA int64 tensor of
-    arbitrary 64-bit keys, on the device: ``sdpsr_partition_from_u64``.  Returns (labels int32 CUDA
-    tensor, nparts) -- the ``relabel`` callback of ``parallel.agree_partition`` on a GPU."""
+    arbitrary 64-bit keys, on the device: ``sdpsr_partition_from_u64``.  Returns (labels CUDA tensor -- int32 at the
+    default label width --, nparts) -- the ``relabel`` callback of ``parallel.agree_partition`` on a GPU."""
     import torch
     ctx = _ctx(ctx)
     keys = keys.contiguous().view(-1)
     assert keys.is_cuda and keys.dtype == torch.int64
-    out = torch.empty(keys.numel(), dtype=torch.int32, device=keys.device)
+    out = torch.empty(keys.numel(), dtype=ctx.torch_label_dtype(), device=keys.device)
     n = C.c_int64(0)
     ctx.wait_for(keys)
     ctx.check(ctx._lib.sdpsr_partition_from_u64(ctx._h, keys.numel(), _ptr(keys), _ptr(out), C.byref(n), L.MEM_DEVICE))
@@ -275,7 +323,7 @@ def fill(P, values, ctx=None):
     values = np.ascontiguousarray(values, dtype=np.float64)
     if len(values) != P.nparts:  # @assert length(values) == dim(P), :69
         raise ValueError("length(values) != dim(P)")
-    lab = _f(P.matrix, np.uint32)
+    lab = _lab(P.matrix, ctx)
     out = np.empty(lab.size, dtype=np.float64)
     ctx.check(ctx._lib.sdpsr_fill(ctx._h, lab.size, _ptr(lab), _ptr(values), P.nparts, _ptr(out), L.MEM_HOST))
     return out.reshape(P.shape, order="F")
@@ -284,7 +332,7 @@ def fill(P, values, ctx=None):
 def randomize(P, ctx=None):
     """``randomize(P)`` (src/abstract_part.jl:97-110)."""
     ctx = _ctx(ctx)
-    lab = _f(P.matrix, np.uint32)
+    lab = _lab(P.matrix, ctx)
     out = np.empty(lab.size, dtype=np.float64)
     ctx.check(ctx._lib.sdpsr_randomize(ctx._h, lab.size, _ptr(lab), _ptr(out), L.MEM_HOST))
     return out.reshape(P.shape, order="F")
@@ -382,7 +430,7 @@ def _admissible_subspace_device_setup(C_, A, b, atol, ctx, verbose):
     Ad = np.asfortranarray(_dense(A), dtype=np.float64)
     m = Ad.shape[0]
     bb = np.ascontiguousarray(b, dtype=np.float64)
-    P = np.empty(n * n, dtype=np.uint32)
+    P = np.empty(n * n, dtype=ctx.label_dtype)
     d = C.c_int64(0)
     it = C.c_int32(0)
     ms = (C.c_double * L.T_COUNT)()
@@ -517,7 +565,7 @@ def _admissible_subspace_csr(C_, A, b, atol, ctx, verbose):
     the device, then the loop."""
     n, c, m, rowptr, colind, val, bb = _csr_inputs(C_, A, b, 0)
     ctx = _ctx(ctx)
-    P = np.empty(n * n, dtype=np.uint32)
+    P = np.empty(n * n, dtype=ctx.label_dtype)
     d = C.c_int64(0)
     it = C.c_int32(0)
     ms = (C.c_double * L.T_COUNT)()
@@ -556,10 +604,10 @@ def admissible_subspace(C_, A, b, atol=RTOL_DEFAULT, ctx=None, verbose=False, se
     r = U.shape[1]
     if on_dev:
         import torch
-        P = torch.empty(n * n, dtype=torch.int32, device=CL.device)  # uint32 bit pattern
+        P = torch.empty(n * n, dtype=ctx.torch_label_dtype(), device=CL.device)  # (32 bits: the uint32 bit pattern)
     else:
         U = np.asfortranarray(U, dtype=np.float64)
-        P = np.empty(n * n, dtype=np.uint32)
+        P = np.empty(n * n, dtype=ctx.label_dtype)
     d = C.c_int64(0)
     it = C.c_int32(0)
     ms = (C.c_double * L.T_COUNT)()
@@ -642,9 +690,10 @@ class Problem:
         if len(seeds) != R:
             raise ValueError(f"{len(seeds)} seeds for {R} restarts")
         sd = (C.c_uint64 * R)(*[int(x) & (2 ** 64 - 1) for x in seeds])
+        label_dt = L.label_dtype(getattr(ctx, "label_width", 32))  # (a context-like object without a width: the ABI's default)
 
         def call(blk_arrays):
-            Ps = [np.zeros(n * n, dtype=np.uint32) for _ in range(R)]
+            Ps = [np.zeros(n * n, dtype=label_dt) for _ in range(R)]
             pP = (C.c_void_p * R)(*[a.ctypes.data for a in Ps])
             dd, it, nb = (C.c_int64 * R)(), (C.c_int32 * R)(), (C.c_int32 * R)()
             ssq, ss = (C.c_int64 * R)(), (C.c_int64 * R)()
@@ -701,7 +750,7 @@ def reduce_constraints(P, A, ctx=None):
     vec = A.ndim == 1
     A2 = A.reshape(1, -1) if vec else A
     m, ln = A2.shape
-    lab = _f(P.matrix, np.uint32)
+    lab = _lab(P.matrix, ctx)
     assert ln == lab.size
     Af = np.asfortranarray(A2)
     out = np.zeros((m, P.nparts), order="F")
@@ -732,7 +781,7 @@ def reduce_constraints_csr(P, A, ctx=None, index_base=0):
     if not 1 <= d <= ln:
         raise ValueError(f"dim(P) = {d} outside [1, {ln}]")
     ctx = _ctx(ctx)
-    lab, mem = _labels_arg(P)
+    lab, mem = _labels_arg(P, ctx)
     if mem == L.MEM_DEVICE:
         import torch
         t_out = torch.empty(m * d, dtype=torch.float64, device=lab.device)
@@ -751,7 +800,7 @@ def desymmetrize(P, ctx=None):
     """``desymmetrize(P)`` (src/partitions.jl:197-223); returns a new Partition."""
     ctx = _ctx(ctx)
     n = P.shape[0]
-    lab = _f(P.matrix, np.uint32).copy()
+    lab = _lab(P.matrix, ctx).copy()
     d = C.c_int64(P.nparts)
     it = C.c_int32(0)
     ctx.check(ctx._lib.sdpsr_desymmetrize(ctx._h, n, _ptr(lab), C.byref(d), C.byref(it), L.MEM_HOST))
@@ -770,13 +819,45 @@ BlockDiagonalization = namedtuple("BlockDiagonalization", ["blkSizes", "blks", "
 ComplexBlockDiagonalization = namedtuple("ComplexBlockDiagonalization", ["blkSizes", "blks", "Q_hat", "partition"])
 
 
-def _labels_arg(P):
+def _check_torch_labels(t, ctx):
+    if t.element_size() * 8 != ctx.label_width or t.dtype.is_floating_point:
+        raise TypeError(f"a torch label array of this context has {ctx.label_width}-bit integer elements "
+                        f"({ctx.torch_label_dtype()}), not {t.dtype}: convert with labels_convert")
+
+
+def _labels_arg(P, ctx=None):
+    ctx = _ctx(ctx)
     m = P.matrix
     if _is_torch(m):
+        _check_torch_labels(m, ctx)
         # stored as the transposed view of a flat column-major buffer (see admissible_subspace)
         flat = m.t().contiguous().view(-1)
         return flat, L.MEM_DEVICE
-    return _f(m, np.uint32), L.MEM_HOST
+    return _lab(m, ctx), L.MEM_HOST
+
+
+def labels_convert(a, bits, ctx=None):
+    """Element-wise conversion of a label array to ``bits`` = 8, 16 or 32 bits per label on the device
+    (``sdpsr_labels_convert``): a NumPy array of uint8 / uint16 / uint32 (copied by the library) or a torch CUDA tensor
+    with 1-, 2- or 4-byte integer elements (converted where it lies).  Returns a new array of the same kind and shape;
+    raises ``LabelOverflow`` when a value does not fit.  Independent of the context's own ``label_width``."""
+    ctx = _ctx(ctx)
+    out_dt = L.label_dtype(bits)
+    if _is_torch(a):
+        import torch
+        if a.dtype.is_floating_point or a.element_size() not in (1, 2, 4) or not a.is_cuda:
+            raise TypeError("labels_convert takes a CUDA tensor of 1-, 2- or 4-byte integers")
+        src = a.contiguous()
+        out = torch.empty(src.shape, dtype=_torch_label_dtype(bits), device=src.device)
+        ctx.wait_for(src, out)
+        ctx.check(ctx._lib.sdpsr_labels_convert(ctx._h, src.numel(), _ptr(src), src.element_size() * 8, _ptr(out), int(bits), L.MEM_DEVICE))
+        return out
+    src = np.ascontiguousarray(a)
+    if src.dtype not in L.LABEL_DTYPES.values():
+        raise TypeError("labels_convert takes uint8, uint16 or uint32 labels")
+    out = np.empty(src.shape, dtype=out_dt)
+    ctx.check(ctx._lib.sdpsr_labels_convert(ctx._h, src.size, _ptr(src), src.dtype.itemsize * 8, _ptr(out), int(bits), L.MEM_HOST))
+    return out
 
 
 def blockDiagonalize(P, verbose=False, epsilon=RTOL_DEFAULT, complex=False, ctx=None, retries=0):
@@ -795,7 +876,7 @@ def blockDiagonalize(P, verbose=False, epsilon=RTOL_DEFAULT, complex=False, ctx=
             if verbose:
                 print(f"[sdpsr] blockDiagonalize attempt {attempt + 1} failed ({type(e).__name__}); retrying")
     n = P.shape[0]
-    lab, mem = _labels_arg(P)
+    lab, mem = _labels_arg(P, ctx)
     ctx.wait_for(lab)
     nb = C.c_int32(0)
     ssq = C.c_int64(0)
@@ -839,8 +920,8 @@ def _block_diagonalize_complex(P, verbose, epsilon, ctx, retries):
         except (NumericalInconsistency, DimensionMismatch):
             pass
     n = P.shape[0]
-    lab = _f(np.asarray(P.matrix.cpu() if _is_torch(P.matrix) else P.matrix), np.uint32)
-    Pd = np.empty(n * n, dtype=np.uint32)
+    lab = _lab(np.asarray(P.matrix.cpu() if _is_torch(P.matrix) else P.matrix), ctx)
+    Pd = np.empty(n * n, dtype=ctx.label_dtype)
     dd = C.c_int64(0)
     nb = C.c_int32(0)
     ssq = C.c_int64(0)
@@ -878,7 +959,7 @@ def diagonalize(P, atol=None, ctx=None):
     n = P.shape[0]
     atol = 1e-12 * n if atol is None else atol
     ctx = _ctx(ctx)
-    lab, mem = _labels_arg(P)
+    lab, mem = _labels_arg(P, ctx)
     ctx.wait_for(lab)
     nb = C.c_int32(0)
     ssq = C.c_int64(0)
@@ -905,7 +986,7 @@ def eigen_decomposition(P, atol=None, ctx=None):
     n = P.shape[0]
     atol = 1e-12 * n if atol is None else atol
     ctx = _ctx(ctx)
-    lab, mem = _labels_arg(P)
+    lab, mem = _labels_arg(P, ctx)
     ctx.wait_for(lab)
     ne = C.c_int32(0)
     nc = C.c_int32(0)
@@ -922,7 +1003,7 @@ def eigen_decomposition_batched(P, count, atol=None, values=None, ctx=None, rais
     n = P.shape[0]
     atol = 1e-12 * n if atol is None else atol
     ctx = _ctx(ctx)
-    lab, mem = _labels_arg(P)
+    lab, mem = _labels_arg(P, ctx)
     ctx.wait_for(lab)
     vals = None
     if values is not None:

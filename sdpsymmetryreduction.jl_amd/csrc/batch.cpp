@@ -141,6 +141,7 @@ int jordan_reduce_batch_impl(sdpsr_ctx* c, int32_t R, const uint64_t* seeds, int
         sdpsr_ctx* ci = ctxs[i];
         if (seeds) sdpsr_set_seed(ci, seeds[i]);
         ci->hint_symmetric_basis = hint;
+        ci->label_width = c->label_width;  // the restarts write their P_out at the width of the ctx the caller holds
         status[i] = SDPSR_OK;
         Fiber& f = sched.fibers[i];
         f.sched = &sched;

@@ -16,7 +16,7 @@ using namespace sdpsr;
 
 namespace sdpsr {
 int block_diagonalize_impl(sdpsr_ctx* c, int64_t n, const uint32_t* P, int64_t d, double epsilon, int32_t* nblocks, int64_t* sum_sq,
-                           int64_t* sum_s, double* phase_ms, int mem, bool trusted_symmetric, bool final_sync, bool in_place) {
+                           int64_t* sum_s, double* phase_ms, int mem, bool trusted_symmetric, bool final_sync, bool in_place, bool labels_are_u32) {
     CHECK_CTX(c);
     if (!P || n < 1 || d < 0 || !(epsilon > 0)) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "bad arguments");
     const int64_t len = n * n;
@@ -28,14 +28,19 @@ int block_diagonalize_impl(sdpsr_ctx* c, int64_t n, const uint32_t* P, int64_t d
     PhaseTimer tm(c, phase_ms != nullptr);
     TotalEvents ev_total(phase_ms != nullptr, s);
     // keep a device copy of the labels for phase 2 (or, in_place, the caller's device buffer itself)
-    in_place = in_place && mem == SDPSR_MEM_DEVICE;
+    // (narrow labels -- the public entry only; sdpsr_jordan_reduce hands over its own uint32 labels -- are widened into the ctx's copy)
+    const bool narrow = !labels_are_u32 && c->label_width != 32;
+    in_place = in_place && mem == SDPSR_MEM_DEVICE && !narrow;
     uint32_t* L = in_place ? const_cast<uint32_t*>(P) : (uint32_t*)ctx_buf(c, "bd_labels", len * 4);
     if (!L) return SDPSR_OUT_OF_MEMORY;
     c->bd_labels_ext = in_place ? P : nullptr;
     c->bd_sym_labels = nullptr;
     c->bd_sym_epoch = 0;
     c->bd_trusted_symmetric = (trusted_symmetric && mem == SDPSR_MEM_DEVICE && P == L) ? L : nullptr;
-    if (mem == SDPSR_MEM_DEVICE) {
+    if (narrow) {
+        st = labels_fetch(c, L, P, (size_t)len, mem);
+        if (st) return st;
+    } else if (mem == SDPSR_MEM_DEVICE) {
         if (P != L) {
             // copy and symmetry check of the same tiles in one pass; the verdict ("bd_symflag"[0] ==
             // epoch <=> not symmetric) is read back by the driver with its first synchronisation
@@ -50,6 +55,7 @@ int block_diagonalize_impl(sdpsr_ctx* c, int64_t n, const uint32_t* P, int64_t d
         }
     } else {
         HIP_TRY(c, hipMemcpyAsync(L, P, len * 4, hipMemcpyHostToDevice, s));
+        c->h2d_bytes += (size_t)len * 4;
     }
     dbg_mark(c, "block_diagonalize: entered, labels copied");
     const double atol = epsilon;  // diagonalize(T, P; atol=epsilon), src/compat.jl:53
@@ -104,7 +110,7 @@ extern "C" {
 int sdpsr_block_diagonalize(sdpsr_ctx* c, int64_t n, const uint32_t* P, int64_t d, double epsilon,
                             int32_t* nblocks, int64_t* sum_sq, int64_t* sum_s, double* phase_ms,
                             int mem) {
-    return block_diagonalize_impl(c, n, P, d, epsilon, nblocks, sum_sq, sum_s, phase_ms, mem, false, true);
+    return block_diagonalize_impl(c, n, P, d, epsilon, nblocks, sum_sq, sum_s, phase_ms, mem, false, true, false, /*labels_are_u32=*/false);
 }
 
 }  // extern "C"

@@ -159,10 +159,15 @@ int sdpsr_block_diagonalize_complex(sdpsr_ctx* c, int64_t n, const uint32_t* P, 
     // diagonalize(ComplexF64, P) desymmetrizes first (src/diagonalize.jl:26-28)
     uint32_t* L = (uint32_t*)ctx_buf(c, "bdc_labels", len * 4);
     if (!L) return SDPSR_OUT_OF_MEMORY;
-    HIP_TRY(c, hipMemcpyAsync(L, P, len * 4, mem == SDPSR_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
-    int64_t dd = d;
-    int st = sdpsr_desymmetrize(c, n, L, &dd, nullptr, SDPSR_MEM_DEVICE);
+    int st = labels_fetch(c, L, P, (size_t)len, mem);  // (width 32: the plain copy; narrow labels are widened into the ctx's copy)
     if (st) return st;
+    int64_t dd = d;
+    st = desymmetrize_device(c, n, L, &dd, nullptr);
+    if (st) return st;
+    if (P_desym && label_width_overflows(c, (uint64_t)dd)) {  // the desymmetrized partition cannot be delivered (P_desym untouched)
+        if (d_desym) *d_desym = dd;
+        return label_width_fail(c, "blockDiagonalize(complex): desymmetrize", (uint64_t)dd);
+    }
     const double atol = epsilon;
     double* Hr = (double*)ctx_buf(c, "bdc_hr", len * 8);
     double* Hi = (double*)ctx_buf(c, "bdc_hi", len * 8);
@@ -250,8 +255,9 @@ int sdpsr_block_diagonalize_complex(sdpsr_ctx* c, int64_t n, const uint32_t* P, 
     if (small) launch_cx_irreducible(s, n, Hr, Hi, Vr, Vi, ddesc, (int)S1, atol, Qhat);
     else launch_cx_irreducible_general(s, n, Hr, Hi, Vr, Vi, ddesc, (int)S1, atol, Qhat);
     HIP_TRY(c, hipGetLastError());
-    if (P_desym) HIP_TRY(c, hipMemcpyAsync(P_desym, L, len * 4, mem == SDPSR_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+    if (P_desym && (st = labels_deliver(c, P_desym, L, (size_t)len, mem)) != SDPSR_OK) return st;
     HIP_TRY(c, ctx_sync_stream(c, s));
+    if (P_desym && (st = labels_delivered(c)) != SDPSR_OK) return st;
     c->bdc_n = n;
     c->bdc_d = dd;
     c->bdc_sizes = sizes;

@@ -609,7 +609,7 @@ int sdpsr_eigen_decomposition(sdpsr_ctx* c, int64_t n, const uint32_t* P, int64_
     c->bd_sym_labels = nullptr;
     c->bd_trusted_symmetric = nullptr;
     c->bd_labels_ext = nullptr;
-    const uint32_t* L = in_dev(c, "bd_labels", P, (size_t)n * n, mem, &st);
+    const uint32_t* L = labels_in_dev(c, "bd_labels", P, (size_t)n * n, mem, &st);
     if (st) return st;
     c->bd_valid = false;
     EigInfo info;
@@ -637,7 +637,7 @@ int sdpsr_eigen_decomposition_batched(sdpsr_ctx* c, int64_t n, const uint32_t* P
     c->bd_sym_labels = nullptr;
     c->bd_trusted_symmetric = nullptr;
     c->bd_labels_ext = nullptr;
-    const uint32_t* L = in_dev(c, "bd_labels", P, (size_t)n * n, mem, &st);
+    const uint32_t* L = labels_in_dev(c, "bd_labels", P, (size_t)n * n, mem, &st);
     if (st) return st;
     c->bd_valid = false;
     std::vector<int32_t> h_st(count, 0), h_ne(count, 0), h_nc(count, 0);

@@ -65,6 +65,29 @@ int out_finish(sdpsr_ctx* c, T* host, const T* dev, size_t count, int mem) {
     return SDPSR_OK;
 }
 
+// ---- label arrays at the ctx's interface width (sdpsr_set_label_width; labels.cpp) ----
+// At width 32 the three templates above under another name: same buffers, same bytes counted.  At 16 / 8 the named buffer is
+// ALWAYS the ctx's own uint32 array, in both memory spaces: an input is widened into it (host arrays: count * B / 8 bytes
+// uploaded into the staging buffer "lab_stage" first), an output is formed in it and narrowed into the caller's array by
+// labels_out_finish (host arrays: narrowed into "lab_stage", count * B / 8 bytes copied out).
+const uint32_t* labels_in_dev(sdpsr_ctx* c, const char* name, const uint32_t* p, size_t count, int mem, int* st);
+uint32_t* labels_out_dev(sdpsr_ctx* c, const char* name, uint32_t* p, size_t count, int mem, int* st);
+int labels_out_finish(sdpsr_ctx* c, uint32_t* p, const uint32_t* dev, size_t count, int mem);
+// the pieces, for the entries that copy labels by hand: the caller's array (ctx's width, memory space mem) into / from a uint32
+// device array, stream-ordered, no host wait; labels_delivered checks the narrowing pass's flag once the stream has been waited for
+int labels_fetch(sdpsr_ctx* c, uint32_t* dst32, const uint32_t* p, size_t count, int mem);
+int labels_deliver(sdpsr_ctx* c, uint32_t* p, const uint32_t* src32, size_t count, int mem);
+int labels_delivered(sdpsr_ctx* c);
+// a partition of `classes` classes cannot be delivered at the ctx's width (the reference's InexactError of Partition{T}, src/partitions.jl:29):
+// decided on the host from the count, before any label is written
+bool label_width_overflows(const sdpsr_ctx* c, uint64_t classes);
+int label_width_fail(sdpsr_ctx* c, const char* where, uint64_t classes);
+// kernels_labels.hip
+void launch_labels_narrow(hipStream_t s, int64_t len, const uint32_t* in, void* out, int bits, uint32_t* flag, int num_cus);
+void launch_labels_widen(hipStream_t s, int64_t len, const void* in, int bits, uint32_t* out, int num_cus);
+// loop.cpp: sdpsr_desymmetrize on uint32 device labels, in place
+int desymmetrize_device(sdpsr_ctx* c, int64_t n, uint32_t* L, int64_t* dim, int32_t* iters);
+
 inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
 bool ctx_ensure_side(sdpsr_ctx* c);
@@ -194,6 +217,7 @@ constexpr size_t PINNED_FIXED_BYTES = 1024;
 constexpr PinnedWords PINNED_SMALL_FLAG{0, 1};                   // c->pinned_small (256 B): the flag of the one-shot entries ("a label exceeds d", symmetry)
 constexpr PinnedWords PINNED_SMALL_DEFERRED_VERIFY{8, 1};        // sdpsr_jordan_reduce: the two verdicts the loop left unread (c->deferred_verdict)
 constexpr PinnedWords PINNED_SMALL_DEFERRED_SPECULATIVE{24, 1};
+constexpr PinnedWords PINNED_SMALL_NARROW{40, 1};                // != 0: a label did not fit the narrow type (kernels_labels.hip); cleared by the host before each pass
 constexpr bool pinned_words_disjoint(std::initializer_list<PinnedWords> w, size_t bytes) {
     for (const PinnedWords* a = w.begin(); a != w.end(); ++a) {
         if (a->count == 0 || (a->first + a->count) * 4 > bytes) return false;
@@ -204,7 +228,7 @@ constexpr bool pinned_words_disjoint(std::initializer_list<PinnedWords> w, size_
 }
 static_assert(pinned_words_disjoint({PINNED_REFINE, PINNED_SYMMETRY, PINNED_VERIFY, PINNED_SPECULATIVE, PINNED_BASIS_CONSTANT, PINNED_SAMPLE}, PINNED_FIXED_BYTES) &&
               PINNED_FIXED_BYTES % sizeof(double) == 0, "two reports share a word of c->pinned, or one reaches into the symmetry probe's doubles");
-static_assert(pinned_words_disjoint({PINNED_SMALL_FLAG, PINNED_SMALL_DEFERRED_VERIFY, PINNED_SMALL_DEFERRED_SPECULATIVE}, 256), "two reports share a word of c->pinned_small");
+static_assert(pinned_words_disjoint({PINNED_SMALL_FLAG, PINNED_SMALL_DEFERRED_VERIFY, PINNED_SMALL_DEFERRED_SPECULATIVE, PINNED_SMALL_NARROW}, 256), "two reports share a word of c->pinned_small");
 inline uint32_t* pinned_report(sdpsr_ctx* c, PinnedWords w) {  // the pinned words of one report (nullptr: no pinned buffer)
     uint32_t* p = (uint32_t*)ctx_pinned(c, PINNED_FIXED_BYTES);
     return p ? p + w.first : nullptr;
@@ -233,7 +257,8 @@ int setup_tail(sdpsr_ctx* c, int64_t n, int64_t r, const double* U, const std::v
 // trusted_symmetric: the caller made the labels and knows; in_place (device labels only): no copy into ctx buffer
 // "bd_labels" -- P itself serves phase 2 (c->bd_labels_ext) until the caller ends that arrangement
 int block_diagonalize_impl(sdpsr_ctx* c, int64_t n, const uint32_t* P, int64_t d, double epsilon, int32_t* nblocks, int64_t* sum_sq,
-                           int64_t* sum_s, double* phase_ms, int mem, bool trusted_symmetric, bool final_sync, bool in_place = false);
+                           int64_t* sum_s, double* phase_ms, int mem, bool trusted_symmetric, bool final_sync, bool in_place = false,
+                           bool labels_are_u32 = true);  // false (the public entry): P has the ctx's label width
 
 // ---- blockDiagonalize: host pieces and drivers (eigdec.cpp, compress.cpp) ----
 struct EigInfo {

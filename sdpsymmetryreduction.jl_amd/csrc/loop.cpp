@@ -484,7 +484,17 @@ extern "C" {
 int sdpsr_admissible_subspace(sdpsr_ctx* c, int64_t n, const double* CL, const double* X0L,
                               const double* U, int64_t r, double atol, uint32_t* P_out,
                               int64_t* dim_out, int32_t* iters_out, double* phase_ms, int mem) {
-    return admissible_subspace_impl(c, n, CL, X0L, U, r, atol, P_out, dim_out, iters_out, phase_ms, mem, mem, true, nullptr);
+    if (!c || c->label_width == 32 || !P_out || !dim_out || n < 1)
+        return admissible_subspace_impl(c, n, CL, X0L, U, r, atol, P_out, dim_out, iters_out, phase_ms, mem, mem, true, nullptr);
+    // narrow labels: the loop works on the ctx's uint32 buffer; the result is narrowed into the caller's array once dim(S) is known to fit
+    CHECK_CTX(c);
+    uint32_t* L = (uint32_t*)ctx_buf(c, "adm_labels", (size_t)n * n * 4);
+    if (!L) return SDPSR_OUT_OF_MEMORY;
+    const int st = admissible_subspace_impl(c, n, CL, X0L, U, r, atol, L, dim_out, iters_out, phase_ms, mem, SDPSR_MEM_DEVICE, true, nullptr);
+    if (st && st != SDPSR_NOT_CONVERGED) return st;
+    if (label_width_overflows(c, (uint64_t)*dim_out)) return label_width_fail(c, "admissible_subspace", (uint64_t)*dim_out);  // (P_out untouched)
+    const int st_out = labels_out_finish(c, P_out, L, (size_t)n * n, mem);
+    return st_out ? st_out : st;
 }
 
 // desymmetrize, src/partitions.jl:197-223
@@ -494,9 +504,21 @@ int sdpsr_desymmetrize(sdpsr_ctx* c, int64_t n, uint32_t* P, int64_t* dim, int32
     const int64_t len = n * n;
     int st = check_len(c, len);
     if (st) return st;
-    hipStream_t s = c->stream;
-    uint32_t* L = (mem == SDPSR_MEM_DEVICE) ? P : (uint32_t*)in_dev(c, "adm_labels", (const uint32_t*)P, len, mem, &st);
+    // (device memory at width 32: refined in place; a narrow P is widened into the ctx's buffer and receives the result from there)
+    uint32_t* L = (mem == SDPSR_MEM_DEVICE && c->label_width == 32) ? P : (uint32_t*)labels_in_dev(c, "adm_labels", (const uint32_t*)P, len, mem, &st);
     if (st) return st;
+    st = desymmetrize_device(c, n, L, dim, iters);
+    if (st) return st;
+    if (label_width_overflows(c, (uint64_t)*dim)) return label_width_fail(c, "desymmetrize", (uint64_t)*dim);  // (P untouched)
+    return labels_out_finish(c, P, L, len, mem);
+}
+}  // extern "C"
+
+// the rounds of desymmetrize on uint32 device labels, in place; returns with the stream waited for (the last refinement's verdict)
+int sdpsr::desymmetrize_device(sdpsr_ctx* c, int64_t n, uint32_t* L, int64_t* dim, int32_t* iters) {
+    const int64_t len = n * n;
+    int st = SDPSR_OK;
+    hipStream_t s = c->stream;
     const int T = c->opts.channels;
     const int64_t ld = round_up(n, 128);
     uint32_t* Lt = (uint32_t*)ctx_buf(c, "des_lt", len * 4);
@@ -529,6 +551,5 @@ int sdpsr_desymmetrize(sdpsr_ctx* c, int64_t n, uint32_t* P, int64_t* dim, int32
     }
     *dim = current;
     if (iters) *iters = it;
-    return out_finish(c, P, L, len, mem);
+    return SDPSR_OK;
 }
-}  // extern "C"

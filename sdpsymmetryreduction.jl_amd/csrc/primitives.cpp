@@ -218,14 +218,15 @@ int sdpsr_partition_from_f64(sdpsr_ctx* c, int64_t len, const double* M, uint32_
     int st = check_len(c, len);
     if (st) return st;
     const double* dM = in_dev(c, "prim_in_a", M, len, mem, &st);
-    uint32_t* dL = out_dev(c, "prim_out", labels, len, mem, &st);
+    uint32_t* dL = labels_out_dev(c, "prim_out", labels, len, mem, &st);
     uint64_t* sig = (uint64_t*)ctx_buf(c, "sig", len * 8);
     if (st || !sig) return st ? st : SDPSR_OUT_OF_MEMORY;
     launch_sig_f64(c->stream, len, nullptr, dM, sig);
     st = refine_signatures(c, len, sig, dL, nparts);
     if (st) return st;
     if (label_overflows(c, (uint64_t)*nparts)) return label_overflow_fail(c, "Partition{T}(M)", (uint64_t)*nparts);
-    return out_finish(c, labels, dL, len, mem);
+    if (label_width_overflows(c, (uint64_t)*nparts)) return label_width_fail(c, "Partition{T}(M)", (uint64_t)*nparts);  // (labels untouched)
+    return labels_out_finish(c, labels, dL, len, mem);
 }
 
 int sdpsr_partition_from_u32(sdpsr_ctx* c, int64_t len, const uint32_t* in, uint32_t* labels,
@@ -235,14 +236,15 @@ int sdpsr_partition_from_u32(sdpsr_ctx* c, int64_t len, const uint32_t* in, uint
     int st = check_len(c, len);
     if (st) return st;
     const uint32_t* dI = in_dev(c, "prim_in_a", in, len, mem, &st);
-    uint32_t* dL = out_dev(c, "prim_out", labels, len, mem, &st);
+    uint32_t* dL = labels_out_dev(c, "prim_out", labels, len, mem, &st);
     uint64_t* sig = (uint64_t*)ctx_buf(c, "sig", len * 8);
     if (st || !sig) return st ? st : SDPSR_OUT_OF_MEMORY;
     launch_sig_u32(c->stream, len, nullptr, dI, sig);
     st = refine_signatures(c, len, sig, dL, nparts);
     if (st) return st;
     if (label_overflows(c, (uint64_t)*nparts)) return label_overflow_fail(c, "Partition{T}(M)", (uint64_t)*nparts);
-    return out_finish(c, labels, dL, len, mem);
+    if (label_width_overflows(c, (uint64_t)*nparts)) return label_width_fail(c, "Partition{T}(M)", (uint64_t)*nparts);  // (labels untouched)
+    return labels_out_finish(c, labels, dL, len, mem);
 }
 
 int sdpsr_partition_from_u64(sdpsr_ctx* c, int64_t len, const uint64_t* in, uint32_t* labels, int64_t* nparts, int mem) {
@@ -251,14 +253,15 @@ int sdpsr_partition_from_u64(sdpsr_ctx* c, int64_t len, const uint64_t* in, uint
     int st = check_len(c, len);
     if (st) return st;
     const uint64_t* dI = in_dev(c, "prim_in_a", in, len, mem, &st);
-    uint32_t* dL = out_dev(c, "prim_out", labels, len, mem, &st);
+    uint32_t* dL = labels_out_dev(c, "prim_out", labels, len, mem, &st);
     uint64_t* sig = (uint64_t*)ctx_buf(c, "sig", len * 8);
     if (st || !sig) return st ? st : SDPSR_OUT_OF_MEMORY;
     launch_sig_u64(c->stream, len, dI, sig);
     st = refine_signatures(c, len, sig, dL, nparts);
     if (st) return st;
     if (label_overflows(c, (uint64_t)*nparts)) return label_overflow_fail(c, "Partition{T}(M)", (uint64_t)*nparts);
-    return out_finish(c, labels, dL, len, mem);
+    if (label_width_overflows(c, (uint64_t)*nparts)) return label_width_fail(c, "Partition{T}(M)", (uint64_t)*nparts);  // (labels untouched)
+    return labels_out_finish(c, labels, dL, len, mem);
 }
 
 int sdpsr_refine(sdpsr_ctx* c, int64_t len, uint32_t* p1, int64_t* d1, const uint32_t* p2,
@@ -268,9 +271,10 @@ int sdpsr_refine(sdpsr_ctx* c, int64_t len, uint32_t* p1, int64_t* d1, const uin
     if (!p1 || !p2 || !d1) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "null pointer");
     int st = check_len(c, len);
     if (st) return st;
-    const uint32_t* d1in = in_dev(c, "prim_in_a", (const uint32_t*)p1, len, mem, &st);
-    const uint32_t* d2in = in_dev(c, "prim_in_b", p2, len, mem, &st);
-    uint32_t* dL = (mem == SDPSR_MEM_DEVICE) ? p1 : (uint32_t*)ctx_buf(c, "prim_out", len * 4);
+    const uint32_t* d1in = labels_in_dev(c, "prim_in_a", (const uint32_t*)p1, len, mem, &st);
+    const uint32_t* d2in = labels_in_dev(c, "prim_in_b", p2, len, mem, &st);
+    // (device memory at width 32: refined in place in p1; a narrow p1 receives the result from the ctx's buffer)
+    uint32_t* dL = (mem == SDPSR_MEM_DEVICE && c->label_width == 32) ? p1 : (uint32_t*)ctx_buf(c, "prim_out", len * 4);
     uint64_t* sig = (uint64_t*)ctx_buf(c, "sig", len * 8);
     if (st || !sig || !dL) return st ? st : SDPSR_OUT_OF_MEMORY;
     if (c->opts.label_bits) {
@@ -288,7 +292,8 @@ int sdpsr_refine(sdpsr_ctx* c, int64_t len, uint32_t* p1, int64_t* d1, const uin
     launch_sig_u32(c->stream, len, d1in, d2in, sig);
     st = refine_signatures(c, len, sig, dL, d1);
     if (st) return st;
-    return out_finish(c, p1, dL, len, mem);
+    if (label_width_overflows(c, (uint64_t)*d1)) return label_width_fail(c, "refine!", (uint64_t)*d1);  // (p1 untouched)
+    return labels_out_finish(c, p1, dL, len, mem);
 }
 
 int sdpsr_partition_checksum(sdpsr_ctx* c, int64_t len, const uint32_t* labels, uint64_t* out, int mem) {
@@ -296,7 +301,7 @@ int sdpsr_partition_checksum(sdpsr_ctx* c, int64_t len, const uint32_t* labels, 
     if (!labels || !out) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "null pointer");
     int st = check_len(c, len);
     if (st) return st;
-    const uint32_t* dL = in_dev(c, "chk_labels", labels, (size_t)len, mem, &st);
+    const uint32_t* dL = labels_in_dev(c, "chk_labels", labels, (size_t)len, mem, &st);
     uint64_t* scratch = (uint64_t*)ctx_buf(c, "chk_scratch", (size_t)(2 * 2048 + 2) * 8);
     if (st || !scratch) return st ? st : SDPSR_OUT_OF_MEMORY;
     launch_labels_checksum(c->stream, len, dL, scratch, scratch + 2 * 2048);
@@ -310,7 +315,7 @@ int sdpsr_fill(sdpsr_ctx* c, int64_t len, const uint32_t* labels, const double* 
     if (!labels || !M || (d > 0 && !values)) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "null pointer");
     int st = check_len(c, len);
     if (st) return st;
-    const uint32_t* dL = in_dev(c, "prim_in_a", labels, len, mem, &st);
+    const uint32_t* dL = labels_in_dev(c, "prim_in_a", labels, len, mem, &st);
     const double* dV = in_dev(c, "prim_in_b", values, (size_t)std::max<int64_t>(d, 1), mem, &st);
     double* dM = out_dev(c, "prim_out", M, len, mem, &st);
     if (st) return st;
@@ -332,7 +337,7 @@ int sdpsr_randomize(sdpsr_ctx* c, int64_t len, const uint32_t* labels, double* M
     if (!labels || !M) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "null pointer");
     int st = check_len(c, len);
     if (st) return st;
-    const uint32_t* dL = in_dev(c, "prim_in_a", labels, len, mem, &st);
+    const uint32_t* dL = labels_in_dev(c, "prim_in_a", labels, len, mem, &st);
     double* dM = out_dev(c, "prim_out", M, len, mem, &st);
     if (st) return st;
     launch_randomize_f64(c->stream, len, dL, next_key(c), dM);

@@ -31,7 +31,8 @@ int jordan_reduce_impl(sdpsr_ctx* c, int64_t n, const double* CL, const double* 
     const int hint_at_entry = c->hint_symmetric_basis;
     // the partition is formed where blockDiagonalize reads its labels: in the caller's device buffer P_out when there
     // is one (no copy at all), else in the ctx buffer "bd_labels"
-    const bool in_place = mem == SDPSR_MEM_DEVICE && P_out != nullptr;
+    // (narrow labels, sdpsr_set_label_width: the ctx buffer too; P_out receives the narrowed result once dim(S) is known to fit)
+    const bool in_place = mem == SDPSR_MEM_DEVICE && P_out != nullptr && c->label_width == 32;
     uint32_t* L = in_place ? P_out : (uint32_t*)ctx_buf(c, "bd_labels", (size_t)len * 4);
     if (!L) return SDPSR_OUT_OF_MEMORY;
     c->bd_valid = false;
@@ -46,20 +47,24 @@ int jordan_reduce_impl(sdpsr_ctx* c, int64_t n, const double* CL, const double* 
     c->allow_deferred_verdict = false;
     const int st_loop = st;
     if (st && st != SDPSR_NOT_CONVERGED) return st;
-    if (P_out && !in_place) {  // stream-ordered; complete when the call returns (it ends with a synchronisation on every path)
-        HIP_TRY(c, hipMemcpyAsync(P_out, L, (size_t)len * 4, mem == SDPSR_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
-        if (mem != SDPSR_MEM_DEVICE) c->d2h_bytes += (size_t)len * 4;
+    // more classes than the ctx's label width holds (the reference's InexactError of Partition{T}): the reduction stops behind the loop,
+    // P_out untouched -- reported below, once the stream has been waited for and the loop's deferred verdicts are in
+    const bool overflow = P_out && label_width_overflows(c, (uint64_t)*dim_out);
+    if (P_out && !in_place && !overflow) {  // stream-ordered; complete when the call returns (it ends with a synchronisation on every path)
+        st = labels_deliver(c, P_out, L, (size_t)len, mem);
+        if (st) return st;
     }
     const int64_t d = *dim_out;
     int32_t nb = 0;
     int64_t S = 0, S1 = 0;
-    st = block_diagonalize_impl(c, n, L, d, epsilon, &nb, &S, &S1, phase_ms ? pm_b : nullptr, SDPSR_MEM_DEVICE, labels_sym != 0,
-                                /*final_sync=*/false, in_place);
+    st = overflow ? SDPSR_OK
+                  : block_diagonalize_impl(c, n, L, d, epsilon, &nb, &S, &S1, phase_ms ? pm_b : nullptr, SDPSR_MEM_DEVICE, labels_sym != 0,
+                                           /*final_sync=*/false, in_place);
     if (nblocks) *nblocks = nb;
     if (sum_sq) *sum_sq = S;
     if (sum_s) *sum_s = S1;
     bool images_done = false;
-    if (st == SDPSR_OK && blks && d * S <= blks_capacity && (!Q_hat || n * S1 <= qhat_capacity)) {
+    if (st == SDPSR_OK && !overflow && blks && d * S <= blks_capacity && (!Q_hat || n * S1 <= qhat_capacity)) {
         st = sdpsr_block_images(c, blks, (Q_hat && n * S1 <= qhat_capacity) ? Q_hat : nullptr, phase_ms ? pm_i : nullptr, mem);  // ends synchronised
         images_done = st == SDPSR_OK;
     }
@@ -119,6 +124,8 @@ int jordan_reduce_impl(sdpsr_ctx* c, int64_t n, const double* CL, const double* 
     if (phase_ms) {
         for (int i = 0; i < SDPSR_T_COUNT; ++i) phase_ms[i] = pm_a[i] + pm_b[i] + pm_i[i];
     }
+    if (overflow && st == SDPSR_OK) return label_width_fail(c, "jordan_reduce: admissible_subspace", (uint64_t)d);
+    if (st == SDPSR_OK && P_out && !in_place) st = labels_delivered(c);  // (the narrowing pass's own flag: dim(S) fits, so do the labels)
     return st ? st : st_loop;
 }
 }  // namespace sdpsr

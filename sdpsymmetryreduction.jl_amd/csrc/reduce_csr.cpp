@@ -15,7 +15,7 @@ int sdpsr_reduce_constraints(sdpsr_ctx* c, int64_t len, const uint32_t* labels, 
     if (!labels || !A || !out || d < 1 || m < 1) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "bad arguments");
     int st = check_len(c, len);
     if (st) return st;
-    const uint32_t* dL = in_dev(c, "prim_in_a", labels, len, mem, &st);
+    const uint32_t* dL = labels_in_dev(c, "prim_in_a", labels, len, mem, &st);
     const double* dA = in_dev(c, "red_a", A, (size_t)len * m, mem, &st);
     double* dO = out_dev(c, "red_out", out, (size_t)m * d, mem, &st);
     const int64_t chunk = reduce_columns_chunk(len, m, d);
@@ -50,7 +50,7 @@ int sdpsr_reduce_constraints_csr(sdpsr_ctx* c, int64_t len, const uint32_t* labe
         return ctx_fail(c, SDPSR_BAD_ARGUMENT, "nnz >= 2^32: the entries of A are indexed with 32 bits");
     if (m == 0) return SDPSR_OK;  // an empty result
     hipStream_t s = c->stream;
-    const uint32_t* dL = in_dev(c, "prim_in_a", labels, len, mem, &st);
+    const uint32_t* dL = labels_in_dev(c, "prim_in_a", labels, len, mem, &st);
     double* dO = out_dev(c, "red_out", out, (size_t)m * d, mem, &st);
     uint32_t* flag = (uint32_t*)ctx_buf(c, "prim_flag", 64);
     if (st || !dO || !flag || !c->pinned_small) return st ? st : SDPSR_OUT_OF_MEMORY;

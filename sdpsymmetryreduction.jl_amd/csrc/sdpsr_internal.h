@@ -30,6 +30,7 @@ struct sdpsr_ctx {
     uint64_t seed = 0;
     uint64_t stream_counter = 0;  // fresh RNG stream per randomize call
     sdpsr_opts opts{};
+    int label_width = 32;  // sdpsr_set_label_width: bits of every label array that crosses the interface (labels.cpp); inside, labels are uint32
     hipStream_t stream = nullptr;
     hipStream_t side_stream = nullptr;  // lazily created: work that overlaps a one-workgroup kernel
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_wait = nullptr;

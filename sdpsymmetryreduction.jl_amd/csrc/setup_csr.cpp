@@ -315,13 +315,15 @@ int sdpsr_admissible_subspace_csr(sdpsr_ctx* c, int64_t n, int64_t m, const int6
     int st = setup_csr_impl(c, n, m, rowptr, colind, val, index_base, b, C, atol, o);
     if (st) return st;
     const int64_t len = n * n;
-    uint32_t* dP = (mem_out == SDPSR_MEM_DEVICE) ? P_out : (uint32_t*)ctx_buf(c, "adm_labels", (size_t)len * 4);
+    int st_buf = SDPSR_OK;
+    uint32_t* dP = labels_out_dev(c, "adm_labels", P_out, (size_t)len, mem_out, &st_buf);
     if (!dP) return SDPSR_OUT_OF_MEMORY;
     c->hint_symmetric_basis = o.hint;  // proved above: symmetric rows, position-independent arithmetic
-    st = sdpsr_admissible_subspace(c, n, o.CL, o.X0, o.U, o.r, atol, dP, dim_out, iters_out, phase_ms, SDPSR_MEM_DEVICE);
+    st = admissible_subspace_impl(c, n, o.CL, o.X0, o.U, o.r, atol, dP, dim_out, iters_out, phase_ms, SDPSR_MEM_DEVICE, SDPSR_MEM_DEVICE, true, nullptr);  // (dP: uint32 labels)
     if (st && st != SDPSR_NOT_CONVERGED) return st;
     const int st_loop = st;
-    st = out_finish(c, P_out, dP, len, mem_out);
+    if (label_width_overflows(c, (uint64_t)*dim_out)) return label_width_fail(c, "admissible_subspace", (uint64_t)*dim_out);  // (P_out untouched)
+    st = labels_out_finish(c, P_out, dP, len, mem_out);
     return st ? st : st_loop;
 }
 

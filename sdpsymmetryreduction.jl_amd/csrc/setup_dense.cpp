@@ -127,7 +127,7 @@ int sdpsr_admissible_subspace_dense(sdpsr_ctx* c, int64_t n, int64_t m, const do
                                     int mem_out) {
     CHECK_CTX(c);
     c->hint_symmetric_basis = 0;  // hints describe caller-made CL / X0L / U; here the library makes them itself
-    if (!C || !A || !b || n < 1 || m < 0 || !(atol > 0)) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "bad arguments");
+    if (!C || !A || !b || !P_out || !dim_out || n < 1 || m < 0 || !(atol > 0)) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "bad arguments");
     const int64_t len = n * n;
     int st = check_len(c, len);
     if (st) return st;
@@ -155,12 +155,14 @@ int sdpsr_admissible_subspace_dense(sdpsr_ctx* c, int64_t n, int64_t m, const do
     st = setup_tail(c, n, r, U, min_norm_coefficients(r, piv, coeffs, b), atol, v1, v2, dCL, dX0, partial, nblk, coef);
     if (st) return st;
     // the loop, device-resident inputs
-    uint32_t* dP = (mem_out == SDPSR_MEM_DEVICE) ? P_out : (uint32_t*)ctx_buf(c, "adm_labels", (size_t)len * 4);
+    int st_buf = SDPSR_OK;
+    uint32_t* dP = labels_out_dev(c, "adm_labels", P_out, (size_t)len, mem_out, &st_buf);
     if (!dP) return SDPSR_OUT_OF_MEMORY;
-    st = sdpsr_admissible_subspace(c, n, dCL, dX0, U, r, atol, dP, dim_out, iters_out, phase_ms, SDPSR_MEM_DEVICE);
+    st = admissible_subspace_impl(c, n, dCL, dX0, U, r, atol, dP, dim_out, iters_out, phase_ms, SDPSR_MEM_DEVICE, SDPSR_MEM_DEVICE, true, nullptr);  // (dP: uint32 labels)
     if (st && st != SDPSR_NOT_CONVERGED) return st;
     const int st_loop = st;
-    st = out_finish(c, P_out, dP, len, mem_out);
+    if (label_width_overflows(c, (uint64_t)*dim_out)) return label_width_fail(c, "admissible_subspace", (uint64_t)*dim_out);  // (P_out untouched)
+    st = labels_out_finish(c, P_out, dP, len, mem_out);
     return st ? st : st_loop;
 }
 }  // extern "C"

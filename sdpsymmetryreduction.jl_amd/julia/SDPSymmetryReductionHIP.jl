@@ -67,54 +67,69 @@ function check(c::Context, st::Cint)
 end
 
 # ---- the partition backend (AbstractPartition contract, abstract_part.jl:7-16) ----------
-mutable struct HIPPartition <: SR.AbstractPartition
+# HIPPartition{T} mirrors Partition{T <: Integer} (partitions.jl:6-11) for the label types the library reads and writes as they
+# are: T = UInt8, UInt16 (the reference's default in admissible_subspace, partitions.jl:84) or UInt32.  The ctx is told the
+# width before every call that passes labels (sdpsr_set_label_width, 8 * sizeof(T)) and P.matrix goes in WITHOUT a widened
+# copy; a partition with more than typemax(T) classes is the reference's InexactError (status 4, output untouched).
+const LabelT = Union{UInt8,UInt16,UInt32}
+mutable struct HIPPartition{T<:LabelT} <: SR.AbstractPartition
     nparts::Int
-    matrix::Matrix{UInt32}
+    matrix::Matrix{T}
+end
+HIPPartition(nparts::Integer, matrix::Matrix{T}) where {T<:LabelT} = HIPPartition{T}(Int(nparts), matrix)
+labeltype(::HIPPartition{T}) where {T} = T
+labeltype(::Type{HIPPartition{T}}) where {T} = T
+labeltype(::Type{HIPPartition}) = UInt32
+function width!(c::Context, ::Type{T}) where {T<:LabelT}
+    st = ccall((:sdpsr_set_label_width, libsdpsr), Cint, (Ptr{Cvoid}, Cint), c.handle, 8 * sizeof(T))
+    st == 0 || throw(StatusError(st, "sdpsr_set_label_width"))
+    return c
 end
 SR.dim(p::HIPPartition) = p.nparts
 Base.size(p::HIPPartition, args...) = size(p.matrix, args...)
 Base.:(==)(p::HIPPartition, q::HIPPartition) = p.nparts == q.nparts && p.matrix == q.matrix
 
-function HIPPartition(M::AbstractMatrix{<:AbstractFloat})               # partitions.jl:24-35
-    Md = Matrix{Float64}(M); out = Matrix{UInt32}(undef, size(M)); n = Ref{Int64}(0)
-    c = ctx()
+HIPPartition(M::AbstractMatrix{<:Real}) = HIPPartition{UInt32}(M)
+function HIPPartition{T}(M::AbstractMatrix{<:AbstractFloat}) where {T<:LabelT}   # partitions.jl:24-35
+    Md = Matrix{Float64}(M); out = Matrix{T}(undef, size(M)); n = Ref{Int64}(0)
+    c = width!(ctx(), T)
     check(c, ccall((:sdpsr_partition_from_f64, libsdpsr), Cint,
-                   (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{UInt32}, Ref{Int64}, Cint),
+                   (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Cvoid}, Ref{Int64}, Cint),
                    c.handle, length(Md), Md, out, n, MEM_HOST))
     return HIPPartition(n[], out)
 end
-function HIPPartition(M::AbstractMatrix{<:Integer})                      # partitions.jl:37-60
-    Mi = Matrix{UInt32}(M); out = similar(Mi); n = Ref{Int64}(0)
-    c = ctx()
+function HIPPartition{T}(M::AbstractMatrix{<:Integer}) where {T<:LabelT}         # partitions.jl:37-60
+    Mi = Matrix{UInt32}(M); out = Matrix{T}(undef, size(M)); n = Ref{Int64}(0)   # (the entries are keys: they stay UInt32)
+    c = width!(ctx(), T)
     check(c, ccall((:sdpsr_partition_from_u32, libsdpsr), Cint,
-                   (Ptr{Cvoid}, Int64, Ptr{UInt32}, Ptr{UInt32}, Ref{Int64}, Cint),
+                   (Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ref{Int64}, Cint),
                    c.handle, length(Mi), Mi, out, n, MEM_HOST))
     return HIPPartition(n[], out)
 end
-function SR.refine!(p::HIPPartition, q::HIPPartition)                   # partitions.jl:62-66
-    d = Ref{Int64}(p.nparts); c = ctx()
+function SR.refine!(p::HIPPartition{T}, q::HIPPartition{T}) where {T}   # partitions.jl:62-66
+    d = Ref{Int64}(p.nparts); c = width!(ctx(), T)
     check(c, ccall((:sdpsr_refine, libsdpsr), Cint,
-                   (Ptr{Cvoid}, Int64, Ptr{UInt32}, Ref{Int64}, Ptr{UInt32}, Int64, Cint),
+                   (Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ref{Int64}, Ptr{Cvoid}, Int64, Cint),
                    c.handle, length(p.matrix), p.matrix, d, q.matrix, q.nparts, MEM_HOST))
     p.nparts = d[]
     return p
 end
 function Base.fill!(M::AbstractMatrix{Float64}, p::HIPPartition; values::AbstractVector) # :68-75
     @assert length(values) == SR.dim(p)
-    v = Vector{Float64}(values); c = ctx()
+    v = Vector{Float64}(values); c = width!(ctx(), labeltype(p))
     check(c, ccall((:sdpsr_fill, libsdpsr), Cint,
-                   (Ptr{Cvoid}, Int64, Ptr{UInt32}, Ptr{Float64}, Int64, Ptr{Float64}, Cint),
+                   (Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Cint),
                    c.handle, length(p.matrix), p.matrix, v, length(v), M, MEM_HOST))
     return M
 end
-SR._constraints(p::HIPPartition) = SR._constraints(SR.Partition{UInt32}(p.nparts, p.matrix))
+SR._constraints(p::HIPPartition{T}) where {T} = SR._constraints(SR.Partition{T}(p.nparts, p.matrix))
 
 # 128-bit checksum of the canonical labels: a probabilistic `==` (partitions.jl:16-17) that lets
 # independent restarts on several GPUs agree without exchanging the n x n label matrices
 function checksum(p::HIPPartition)
-    out = zeros(UInt64, 2); c = ctx()
+    out = zeros(UInt64, 2); c = width!(ctx(), labeltype(p))
     check(c, ccall((:sdpsr_partition_checksum, libsdpsr), Cint,
-                   (Ptr{Cvoid}, Int64, Ptr{UInt32}, Ptr{UInt64}, Cint),
+                   (Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{UInt64}, Cint),
                    c.handle, length(p.matrix), p.matrix, out, MEM_HOST))
     return (out[1], out[2])
 end
@@ -149,18 +164,19 @@ end
 
 # ---- admissible_subspace: setup on the host (partitions.jl:117-142; from CSR on the device for a sparse A), loop on
 # the device ----
-function SR.admissible_subspace(::Type{HIPPartition}, C::AbstractVector{T}, A::AbstractMatrix{T},
+function SR.admissible_subspace(::Type{PT}, C::AbstractVector{T}, A::AbstractMatrix{T},
                                 b::AbstractVector{T}; verbose::Bool=false,
-                                atol=Base.rtoldefault(real(T))) where {T<:AbstractFloat}
+                                atol=Base.rtoldefault(real(T))) where {T<:AbstractFloat,PT<:HIPPartition}
+    LT = labeltype(PT)   # HIPPartition{UInt16} etc.; plain HIPPartition: UInt32
     n, c, x0, U, hint = _setup(Vector{Float64}(C), A isa SparseMatrixCSC ? SparseMatrixCSC{Float64}(A) : Matrix{Float64}(A),
                                Vector{Float64}(b), atol)
-    P = Matrix{UInt32}(undef, n, n); d = Ref{Int64}(0); it = Ref{Int32}(0); cx = ctx()
+    P = Matrix{LT}(undef, n, n); d = Ref{Int64}(0); it = Ref{Int32}(0); cx = width!(ctx(), LT)
     # symmetric basis matrices (the usual case): the projection step may work on the lower triangle
     # (bit 1: c and x0 were symmetrised)
     ccall((:sdpsr_hint_symmetric_basis, libsdpsr), Cint, (Ptr{Cvoid}, Cint), cx.handle, hint)
     check(cx, ccall((:sdpsr_admissible_subspace, libsdpsr), Cint,
                     (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Float64,
-                     Ptr{UInt32}, Ref{Int64}, Ref{Int32}, Ptr{Float64}, Cint),
+                     Ptr{Cvoid}, Ref{Int64}, Ref{Int32}, Ptr{Float64}, Cint),
                     cx.handle, n, c, x0, U, size(U, 2), atol, P, d, it, C_NULL, MEM_HOST))
     if verbose  # the reference's log lines (partitions.jl:150,156,187-188) from the dimension trajectory
         cnt = Ref{Int32}(0)
@@ -183,9 +199,9 @@ end
 function reduce_constraints(P::HIPPartition, A::SparseMatrixCSC)
     m = size(A, 1); d = Int64(P.nparts); len = length(P.matrix); @assert size(A, 2) == len
     At = sparse(SparseMatrixCSC{Float64}(A)')
-    out = Matrix{Float64}(undef, m, d); cx = ctx()
+    out = Matrix{Float64}(undef, m, d); cx = width!(ctx(), labeltype(P))
     check(cx, ccall((:sdpsr_reduce_constraints_csr, libsdpsr), Cint,
-                    (Ptr{Cvoid}, Int64, Ptr{UInt32}, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Cint, Ptr{Float64}, Cint),
+                    (Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Cint, Ptr{Float64}, Cint),
                     cx.handle, len, P.matrix, d, m, Vector{Int64}(At.colptr), Vector{Int64}(At.rowval), At.nzval, Cint(1), out, MEM_HOST))
     return out
 end
@@ -193,12 +209,12 @@ end
 # ---- the whole reduction in ONE call (sdpsr_jordan_reduce): admissible_subspace + blockDiagonalize with the
 # partition staying on the device; the images are fetched with sdpsr_block_images once their size is known ----
 function jordan_reduce(C::AbstractVector{Float64}, A::AbstractMatrix{Float64}, b::AbstractVector{Float64};
-                       atol=Base.rtoldefault(Float64), epsilon=Base.rtoldefault(Float64))
+                       atol=Base.rtoldefault(Float64), epsilon=Base.rtoldefault(Float64), labels::Type{LT}=UInt32) where {LT<:LabelT}
     n, c, x0, U, _ = _setup(C, A, b, atol)
-    P = Matrix{UInt32}(undef, n, n); d = Ref{Int64}(0); it = Ref{Int32}(0); cx = ctx()
+    P = Matrix{LT}(undef, n, n); d = Ref{Int64}(0); it = Ref{Int32}(0); cx = width!(ctx(), LT)
     nb = Ref{Int32}(0); ssq = Ref{Int64}(0); ss = Ref{Int64}(0)
     check(cx, ccall((:sdpsr_jordan_reduce, libsdpsr), Cint,
-                    (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Float64, Float64, Ptr{UInt32}, Ref{Int64},
+                    (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Float64, Float64, Ptr{Cvoid}, Ref{Int64},
                      Ref{Int32}, Ref{Int32}, Ref{Int64}, Ref{Int64}, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Cint),
                     cx.handle, n, c, x0, U, size(U, 2), atol, epsilon, P, d, it, nb, ssq, ss, C_NULL, 0, C_NULL, 0, C_NULL, MEM_HOST))
     sizes = Vector{Int32}(undef, nb[])
@@ -212,10 +228,10 @@ end
 # ---- blockDiagonalize(Float64, P) (compat.jl:46-68) -------------------------------------
 function SR.blockDiagonalize(::Type{Float64}, P::HIPPartition, verbose=true;
                              epsilon=Base.rtoldefault(Float64))
-    n = size(P, 1); cx = ctx()
+    n = size(P, 1); cx = width!(ctx(), labeltype(P))
     nb = Ref{Int32}(0); ssq = Ref{Int64}(0); ss = Ref{Int64}(0)
     check(cx, ccall((:sdpsr_block_diagonalize, libsdpsr), Cint,
-                    (Ptr{Cvoid}, Int64, Ptr{UInt32}, Int64, Float64, Ref{Int32}, Ref{Int64}, Ref{Int64},
+                    (Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Float64, Ref{Int32}, Ref{Int64}, Ref{Int64},
                      Ptr{Float64}, Cint),
                     cx.handle, n, P.matrix, P.nparts, epsilon, nb, ssq, ss, C_NULL, MEM_HOST))
     sizes = Vector{Int32}(undef, nb[])
@@ -236,10 +252,10 @@ end
 
 # ---- diagonalize(Float64, P) (diagonalize.jl:25-40): Q_hat itself ---------------------------
 function SR.diagonalize(::Type{Float64}, P::HIPPartition; verbose=false, atol=1e-12 * size(P, 1))
-    n = size(P, 1); cx = ctx()
+    n = size(P, 1); cx = width!(ctx(), labeltype(P))
     nb = Ref{Int32}(0); ssq = Ref{Int64}(0); ss = Ref{Int64}(0)
     st = ccall((:sdpsr_block_diagonalize, libsdpsr), Cint,
-               (Ptr{Cvoid}, Int64, Ptr{UInt32}, Int64, Float64, Ref{Int32}, Ref{Int64}, Ref{Int64}, Ptr{Float64}, Cint),
+               (Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Float64, Ref{Int32}, Ref{Int64}, Ref{Int64}, Ptr{Float64}, Cint),
                cx.handle, n, P.matrix, P.nparts, atol, nb, ssq, ss, C_NULL, MEM_HOST)
     st == 3 || check(cx, st)   # check_block_sizes belongs to blockDiagonalize (compat.jl:60), not to diagonalize
     sizes = Vector{Int32}(undef, nb[])
@@ -253,11 +269,11 @@ end
 # ---- blockDiagonalize(ComplexF64, P) (compat.jl:26-32,54-57; n <= 3072 in this library version) ---
 function SR.blockDiagonalize(::Type{ComplexF64}, P::HIPPartition, verbose=true;
                              epsilon=Base.rtoldefault(Float64))
-    n = size(P, 1); cx = ctx()
-    Pd = Matrix{UInt32}(undef, n, n); dd = Ref{Int64}(0)
+    n = size(P, 1); cx = width!(ctx(), labeltype(P))
+    Pd = Matrix{labeltype(P)}(undef, n, n); dd = Ref{Int64}(0)
     nb = Ref{Int32}(0); ssq = Ref{Int64}(0); ss = Ref{Int64}(0)
     check(cx, ccall((:sdpsr_block_diagonalize_complex, libsdpsr), Cint,
-                    (Ptr{Cvoid}, Int64, Ptr{UInt32}, Int64, Float64, Ptr{UInt32}, Ref{Int64}, Ref{Int32}, Ref{Int64},
+                    (Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Float64, Ptr{Cvoid}, Ref{Int64}, Ref{Int32}, Ref{Int64},
                      Ref{Int64}, Cint),
                     cx.handle, n, P.matrix, P.nparts, epsilon, Pd, dd, nb, ssq, ss, MEM_HOST))
     sizes = Vector{Int32}(undef, nb[])
@@ -281,17 +297,17 @@ end
 # (images: call jordan_reduce / blockDiagonalize on the partition of the first restart whose status is 0) ----
 function jordan_reduce_batch(C::AbstractVector{Float64}, A::AbstractMatrix{Float64}, b::AbstractVector{Float64}, R::Integer;
                              seeds::Union{Nothing,Vector{UInt64}}=nothing, atol=Base.rtoldefault(Float64),
-                             epsilon=Base.rtoldefault(Float64))
+                             epsilon=Base.rtoldefault(Float64), labels::Type{LT}=UInt32) where {LT<:LabelT}
     n, c, x0, U, hint = _setup(C, A, b, atol)
-    cx = ctx()
-    Ps = [Matrix{UInt32}(undef, n, n) for _ in 1:R]
-    pP = [pointer(P) for P in Ps]
+    cx = width!(ctx(), LT)
+    Ps = [Matrix{LT}(undef, n, n) for _ in 1:R]
+    pP = Ptr{Cvoid}[pointer(P) for P in Ps]
     d = zeros(Int64, R); it = zeros(Int32, R); nb = zeros(Int32, R); ssq = zeros(Int64, R); ss = zeros(Int64, R); st = zeros(Int32, R)
     ccall((:sdpsr_hint_symmetric_basis, libsdpsr), Cint, (Ptr{Cvoid}, Cint), cx.handle, hint)
     GC.@preserve Ps begin
         ccall((:sdpsr_jordan_reduce_batch, libsdpsr), Cint,
               (Ptr{Cvoid}, Int32, Ptr{UInt64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Float64, Float64,
-               Ptr{Ptr{UInt32}}, Ptr{Int64}, Ptr{Int32}, Ptr{Int32}, Ptr{Int64}, Ptr{Int64}, Ptr{Ptr{Float64}}, Ptr{Int64},
+               Ptr{Ptr{Cvoid}}, Ptr{Int64}, Ptr{Int32}, Ptr{Int32}, Ptr{Int64}, Ptr{Int64}, Ptr{Ptr{Float64}}, Ptr{Int64},
                Ptr{Int32}, Cint),
               cx.handle, R, seeds === nothing ? C_NULL : seeds, n, c, x0, U, size(U, 2), atol, epsilon, pP, d, it, nb, ssq, ss,
               C_NULL, C_NULL, st, MEM_HOST)
@@ -325,14 +341,14 @@ mutable struct Problem
 end
 
 function reduce_batch(p::Problem, R::Integer; seeds::Union{Nothing,Vector{UInt64}}=nothing, atol=Base.rtoldefault(Float64),
-                      epsilon=Base.rtoldefault(Float64))
-    n = p.n; cx = p.ctx
-    Ps = [Matrix{UInt32}(undef, n, n) for _ in 1:R]
-    pP = [pointer(P) for P in Ps]
+                      epsilon=Base.rtoldefault(Float64), labels::Type{LT}=UInt32) where {LT<:LabelT}
+    n = p.n; cx = width!(p.ctx, LT)
+    Ps = [Matrix{LT}(undef, n, n) for _ in 1:R]
+    pP = Ptr{Cvoid}[pointer(P) for P in Ps]
     d = zeros(Int64, R); it = zeros(Int32, R); nb = zeros(Int32, R); ssq = zeros(Int64, R); ss = zeros(Int64, R)
     st = fill(Int32(-1), R)
     rc = GC.@preserve Ps ccall((:sdpsr_problem_reduce_batch, libsdpsr), Cint,
-              (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{UInt64}, Float64, Float64, Ptr{Ptr{UInt32}}, Ptr{Int64}, Ptr{Int32}, Ptr{Int32},
+              (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{UInt64}, Float64, Float64, Ptr{Ptr{Cvoid}}, Ptr{Int64}, Ptr{Int32}, Ptr{Int32},
                Ptr{Int64}, Ptr{Int64}, Ptr{Ptr{Float64}}, Ptr{Int64}, Ptr{Int32}, Cint),
               cx.handle, p.handle, R, seeds === nothing ? C_NULL : seeds, atol, epsilon, pP, d, it, nb, ssq, ss, C_NULL, C_NULL, st, MEM_HOST)
     (rc != 0 && all(x -> x <= 0, st)) && check(cx, rc)   # a failure before the restarts started
@@ -342,10 +358,10 @@ end
 
 # ---- test/numerical_issues.jl:85-94 in one call: `count` runs of eigen_decomposition on all CUs ----
 function eigen_decomposition_batched(P::HIPPartition, count::Integer; atol=1e-12 * size(P, 1))
-    n = size(P, 1); cx = ctx()
+    n = size(P, 1); cx = width!(ctx(), labeltype(P))
     st = Vector{Int32}(undef, count); ne = similar(st); nc = similar(st)
     check(cx, ccall((:sdpsr_eigen_decomposition_batched, libsdpsr), Cint,
-                    (Ptr{Cvoid}, Int64, Ptr{UInt32}, Int64, Float64, Int64, Ptr{Float64}, Ptr{Int32}, Ptr{Int32},
+                    (Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Float64, Int64, Ptr{Float64}, Ptr{Int32}, Ptr{Int32},
                      Ptr{Int32}, Cint),
                     cx.handle, n, P.matrix, P.nparts, atol, count, C_NULL, st, ne, nc, MEM_HOST))
     return (status=st, neig=ne, nclasses=nc)
