@@ -2,36 +2,25 @@
 // then basis_image (:42-89).  Entry points sdpsr_block_diagonalize / _block_sizes / _q_hat / _block_images.
 #include <algorithm>
 #include <cmath>
-#include <complex>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <chrono>
-#include <functional>
-#include <numeric>
 
 #include "host_internal.h"
 
 using namespace sdpsr;
 
 namespace sdpsr {
-int block_diagonalize_impl(sdpsr_ctx* c, int64_t n, const uint32_t* P, int64_t d, double epsilon, int32_t* nblocks, int64_t* sum_sq,
-                           int64_t* sum_s, double* phase_ms, int mem, bool trusted_symmetric, bool final_sync, bool in_place, bool labels_are_u32) {
-    CHECK_CTX(c);
-    if (!P || n < 1 || d < 0 || !(epsilon > 0)) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "bad arguments");
-    const int64_t len = n * n;
-    int st = check_len(c, len);
-    if (st) return st;
+// keep a device copy of the labels for phase 2 (or, in_place, the caller's device buffer itself)
+// (narrow labels -- the public entry only; sdpsr_jordan_reduce hands over its own uint32 labels -- are widened into the ctx's copy)
+static int keep_labels(sdpsr_ctx* c, int64_t n, const uint32_t* P, int mem, bool trusted_symmetric, bool in_place, bool labels_are_u32,
+                       uint32_t*& L) {
     hipStream_t s = c->stream;
-    c->bd_valid = false;
-    c->bd_q_valid = false;
-    PhaseTimer tm(c, phase_ms != nullptr);
-    TotalEvents ev_total(phase_ms != nullptr, s);
-    // keep a device copy of the labels for phase 2 (or, in_place, the caller's device buffer itself)
-    // (narrow labels -- the public entry only; sdpsr_jordan_reduce hands over its own uint32 labels -- are widened into the ctx's copy)
+    const int64_t len = n * n;
+    int st = SDPSR_OK;
     const bool narrow = !labels_are_u32 && c->label_width != 32;
     in_place = in_place && mem == SDPSR_MEM_DEVICE && !narrow;
-    uint32_t* L = in_place ? const_cast<uint32_t*>(P) : (uint32_t*)ctx_buf(c, "bd_labels", len * 4);
+    L = in_place ? const_cast<uint32_t*>(P) : (uint32_t*)ctx_buf(c, "bd_labels", len * 4);
     if (!L) return SDPSR_OUT_OF_MEMORY;
     c->bd_labels_ext = in_place ? P : nullptr;
     c->bd_sym_labels = nullptr;
@@ -57,6 +46,36 @@ int block_diagonalize_impl(sdpsr_ctx* c, int64_t n, const uint32_t* P, int64_t d
         HIP_TRY(c, hipMemcpyAsync(L, P, len * 4, hipMemcpyHostToDevice, s));
         c->h2d_bytes += (size_t)len * 4;
     }
+    return SDPSR_OK;
+}
+
+// check_block_sizes (src/diagonalize.jl:1-11)
+static int check_block_sizes(sdpsr_ctx* c, const std::vector<int32_t>& sizes, int64_t d) {
+    int64_t final_dim = 0;
+    for (int32_t sz : sizes) final_dim += (int64_t)sz * (sz + 1) / 2;
+    if (final_dim == d) return SDPSR_OK;
+    std::string szs;
+    for (int32_t sz : sizes) szs += std::to_string(sz) + " ";
+    return ctx_fail(c, SDPSR_DIMENSION_MISMATCH,
+                    "final_dim=" + std::to_string(final_dim) + " block_sizes=[" + szs + "] expected dim(P)=" +
+                        std::to_string(d) + " (rounding error: try another epsilon or try again; or the algebra is not block-diagonalizable over the reals)");
+}
+
+int block_diagonalize_impl(sdpsr_ctx* c, int64_t n, const uint32_t* P, int64_t d, double epsilon, int32_t* nblocks, int64_t* sum_sq,
+                           int64_t* sum_s, double* phase_ms, int mem, bool trusted_symmetric, bool final_sync, bool in_place, bool labels_are_u32) {
+    CHECK_CTX(c);
+    if (!P || n < 1 || d < 0 || !(epsilon > 0)) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "bad arguments");
+    const int64_t len = n * n;
+    int st = check_len(c, len);
+    if (st) return st;
+    hipStream_t s = c->stream;
+    c->bd_valid = false;
+    c->bd_q_valid = false;
+    PhaseTimer tm(c, phase_ms != nullptr);
+    TotalEvents ev_total(phase_ms != nullptr, s);
+    uint32_t* L = nullptr;
+    st = keep_labels(c, n, P, mem, trusted_symmetric, in_place, labels_are_u32, L);
+    if (st) return st;
     dbg_mark(c, "block_diagonalize: entered, labels copied");
     const double atol = epsilon;  // diagonalize(T, P; atol=epsilon), src/compat.jl:53
     EigInfo info;
@@ -73,9 +92,6 @@ int block_diagonalize_impl(sdpsr_ctx* c, int64_t n, const uint32_t* P, int64_t d
     }
 
     dbg_mark(c, "block_diagonalize: diagonalize done");
-    // check_block_sizes (src/diagonalize.jl:1-11)
-    int64_t final_dim = 0;
-    for (int32_t sz : sizes) final_dim += (int64_t)sz * (sz + 1) / 2;
     c->bd_n = n;
     c->bd_d = d;
     c->bd_sizes = sizes;
@@ -93,15 +109,202 @@ int block_diagonalize_impl(sdpsr_ctx* c, int64_t n, const uint32_t* P, int64_t d
     } else if (final_sync) {
         HIP_TRY(c, ctx_sync_stream(c, s));
     }
-    if (final_dim != d) {
-        std::string szs;
-        for (int32_t sz : sizes) szs += std::to_string(sz) + " ";
-        return ctx_fail(c, SDPSR_DIMENSION_MISMATCH,
-                        "final_dim=" + std::to_string(final_dim) + " block_sizes=[" + szs + "] expected dim(P)=" +
-                            std::to_string(d) + " (rounding error: try another epsilon or try again; or the algebra is not block-diagonalizable over the reals)");
-    }
+    st = check_block_sizes(c, sizes, d);
+    if (st) return st;
     c->bd_valid = true;
     return SDPSR_OK;
+}
+
+// basis_image (src/diagonalize.jl:42-89) as routes over one state: two shortcuts that check themselves, then one of three
+// kernels for the projection formula
+struct BasisImage {
+    enum Shortcut { FALL_THROUGH, DONE, DONE_SYNCED };  // DONE_SYNCED: the verdict's host wait was the last thing on the stream
+    enum Route { TWO_STAGE, OUTER, CHUNK };
+    sdpsr_ctx* c;
+    hipStream_t s;
+    int64_t n, d, S1, S, len;
+    uint32_t* L;
+    double *Qrm = nullptr, *out = nullptr;
+    double atol;  // basis_image default atol (src/diagonalize.jl:67)
+    BlockLayout lay;
+    // sources of asynchronous uploads (chunk)
+    std::vector<int32_t> desc;
+    std::vector<int64_t> chunk_ptr, cb, ce;
+
+    explicit BasisImage(sdpsr_ctx* ctx)
+        : c(ctx), s(ctx->stream), n(ctx->bd_n), d(ctx->bd_d), S1(ctx->bd_sum_s), S(ctx->bd_sum_sq), len(ctx->bd_n * ctx->bd_n),
+          L(ctx->bd_labels_ext ? const_cast<uint32_t*>(ctx->bd_labels_ext) : (uint32_t*)ctx_buf(ctx, "bd_labels", (size_t)ctx->bd_n * ctx->bd_n * 4)),
+          atol(1e-12 * (double)ctx->bd_n), lay(block_layout(ctx->bd_sizes)) {}
+
+    bool shortcuts_allowed() const { return c->opts.basis_image_kernel == 0 && !(c->opts.flags & SDPSR_FLAG_FULL_BASIS_IMAGE) && d >= 1 && n >= 64; }
+    uint32_t* verdict_words(size_t count);
+    int shortcut_commutative(Shortcut& r);
+    int shortcut_blocks(Shortcut& r);
+    Route route() const;
+    int two_stage();
+    int outer(const uint32_t* ent, const std::vector<int64_t>& class_ptr);
+    int chunk(const uint32_t* ent, const std::vector<int64_t>& class_ptr);
+    int run(bool& done_synced);
+};
+
+// per-column / per-block verdicts, stored by the check kernel straight into pinned host memory: its own words, behind
+// (not inside) the fixed reports at the start of the buffer; [0] = number of failures, [1 + k] = failure of column / block k
+uint32_t* BasisImage::verdict_words(size_t count) {
+    uint32_t* hv = (uint32_t*)ctx_pinned(c, PINNED_BASIS_IMAGE_VERDICTS.first * 4 + (count + 1) * 4);
+    return hv ? hv + PINNED_BASIS_IMAGE_VERDICTS.first : nullptr;
+}
+
+// commutative case (every block 1 x 1): the images are eigenvalues, lambda_ik = q_k'(1[P==i] x) for x = sum_k q_k
+// -- one vector's class sums -- with a randomized self-check; the projection formula runs if the check
+// fails (kernels_blockdiag.hip, launch_basis_image_commutative) and always under SDPSR_FLAG_FULL_BASIS_IMAGE
+int BasisImage::shortcut_commutative(Shortcut& r) {
+    r = FALL_THROUGH;
+    if (S != S1 || !shortcuts_allowed()) return SDPSR_OK;
+    double* ws = (double*)ctx_buf(c, "bi_comm_ws", basis_image_commutative_workspace_doubles(n, d) * 8);
+    uint32_t* hv = verdict_words((size_t)S1);
+    if (!ws || !hv) return SDPSR_OUT_OF_MEMORY;
+    if (!launch_basis_image_commutative(s, n, d, S1, L, Qrm, next_key(c), atol, 2e-10, ws, out, hv)) return SDPSR_OK;
+    HIP_TRY(c, ctx_sync_stream(c, s));
+    HIP_TRY(c, hipGetLastError());
+    const uint32_t nbad = hv[0];
+    if (nbad == 0) r = DONE_SYNCED;
+    if (nbad == 0 || nbad > 8) {
+        if (nbad && dbg_on()) fprintf(stderr, "[sdpsr] basis_image: invariance check failed for %u columns, projection formula instead\n", nbad);
+        return SDPSR_OK;
+    }
+    // a few columns failed (the eigenvectors of a pair of close eigenvalues): the projection formula for
+    // those columns only, two per extra class-sum pass
+    std::vector<int> badk;
+    for (int64_t k2 = 0; k2 < S1; ++k2)
+        if (hv[1 + k2]) badk.push_back((int)k2);
+    bool done = true;
+    for (size_t q = 0; q < badk.size() && done; q += 2)
+        done = launch_basis_image_fix_pair(s, n, d, S1, L, Qrm, badk[q], badk[q + 1 < badk.size() ? q + 1 : q], atol, ws, out);
+    if (dbg_on()) fprintf(stderr, "[sdpsr] basis_image: invariance check failed for %u column(s), projection formula for those\n", nbad);
+    if (done) r = DONE;
+    return SDPSR_OK;
+}
+
+// blocks up to 3 x 3 (non-commutative algebras with small blocks: ER(q) (x) K_k): the images from FOUR vectors' class
+// sums with a per-block check (kernels_blockdiag.hip, launch_basis_image_blocks); blocks that fail get the projection
+// formula, one block per extra pair of passes; many failures: the two-stage kernels for everything
+int BasisImage::shortcut_blocks(Shortcut& r) {
+    r = FALL_THROUGH;
+    if (S == S1 || !shortcuts_allowed() || lay.nb > 4096 || lay.max_size > 3) return SDPSR_OK;
+    const int nb = lay.nb;
+    int32_t* d_cs = (int32_t*)ctx_buf(c, "bi_colsz", (size_t)2 * nb * 4);
+    int64_t* d_off = (int64_t*)ctx_buf(c, "bi_off", (size_t)nb * 8);
+    double* ws = (double*)ctx_buf(c, "bi_comm_ws", basis_image_blocks_workspace_doubles(n, d) * 8);
+    uint32_t* hv = verdict_words((size_t)nb);
+    if (!d_cs || !d_off || !ws || !hv) return SDPSR_OUT_OF_MEMORY;
+    int st = h2d_sync(c, d_cs, lay.colsz.data(), (size_t)2 * nb * 4);
+    if (!st) st = h2d_sync(c, d_off, lay.off.data(), (size_t)nb * 8);
+    if (st) return st;
+    if (!launch_basis_image_blocks(s, n, d, S1, S, nb, d_cs, d_cs + nb, d_off, L, Qrm, next_key(c), -1, atol, 2e-10, ws, out, hv)) return SDPSR_OK;
+    HIP_TRY(c, ctx_sync_stream(c, s));
+    HIP_TRY(c, hipGetLastError());
+    const uint32_t nbad = hv[0];
+    if (nbad == 0) {
+        r = DONE_SYNCED;
+        return SDPSR_OK;
+    }
+    bool done = nbad <= 4;
+    for (int k2 = 0; k2 < nb && done; ++k2)
+        if (hv[1 + k2]) done = launch_basis_image_blocks(s, n, d, S1, S, nb, d_cs, d_cs + nb, d_off, L, Qrm, 0, k2, atol, 2e-10, ws, out, nullptr);
+    if (dbg_on()) fprintf(stderr, "[sdpsr] basis_image: invariance check failed for %u block(s)%s\n", nbad, done ? ", projection formula for those" : ", two-stage kernels instead");
+    if (done) r = DONE;
+    return SDPSR_OK;
+}
+
+// opts.basis_image_kernel = 1 two_stage | 2 outer | 3 chunk forces one of the three kernels (tests: the
+// automatic choice reaches `outer` / `chunk` only for shapes far beyond the test sizes)
+BasisImage::Route BasisImage::route() const {
+    const int force = c->opts.basis_image_kernel;
+    const bool f_outer = force == 2, f_chunk = force == 3;
+    if (basis_image_two_stage_fits(n, d, S1) && !f_outer && !f_chunk) return TWO_STAGE;
+    // many small classes (average class below 4096 entries) and blocks up to 256: outer-product
+    // kernel, one workgroup per (class, block), every output written once, no partial sums
+    if (lay.max_size <= 256 && d > 0 && (len / d < 4096 || f_outer) && !f_chunk && d <= 0x7FFFFFFF && lay.nb <= 65535) return OUTER;
+    return CHUNK;
+}
+
+// two-stage form (class sums per row, then the s_k x s_k dots)
+int BasisImage::two_stage() {
+    desc = pair_descriptor(c->bd_sizes, S);
+    int32_t* d_desc = (int32_t*)ctx_buf(c, "bi_desc", (size_t)2 * S * 4);
+    double* Tb = (double*)ctx_buf(c, "bi_T", (size_t)d * n * S1 * 8);
+    if (!d_desc || !Tb) return SDPSR_OUT_OF_MEMORY;
+    const int st = h2d_sync(c, d_desc, desc.data(), (size_t)2 * S * 4);
+    if (st) return st;
+    launch_basis_image_two_stage(s, n, d, S1, S, L, Qrm, Tb, d_desc, d_desc + S, atol, out);
+    return SDPSR_OK;
+}
+
+int BasisImage::outer(const uint32_t* ent, const std::vector<int64_t>& class_ptr) {
+    const int nb = lay.nb;
+    int32_t* d_col = (int32_t*)ctx_buf(c, "bi_col", (size_t)nb * 4);
+    int32_t* d_sz = (int32_t*)ctx_buf(c, "bi_sz", (size_t)nb * 4);
+    int64_t* d_off = (int64_t*)ctx_buf(c, "bi_off", (size_t)nb * 8);
+    int64_t* d_cls = (int64_t*)ctx_buf(c, "bi_cls_ptr", (size_t)(d + 2) * 8);
+    if (!d_col || !d_sz || !d_off || !d_cls) return SDPSR_OUT_OF_MEMORY;
+    int st = h2d_sync(c, d_col, lay.col(), (size_t)nb * 4);
+    if (!st) st = h2d_sync(c, d_sz, lay.size(), (size_t)nb * 4);
+    if (!st) st = h2d_sync(c, d_off, lay.off.data(), (size_t)nb * 8);
+    if (!st) st = h2d_sync(c, d_cls, class_ptr.data(), (size_t)(d + 2) * 8);
+    if (st) return st;
+    launch_basis_image_outer(s, n, d, S1, S, nb, lay.max_size, Qrm, ent, d_cls, d_col, d_sz, d_off, atol, out);
+    return SDPSR_OK;
+}
+
+// chunks of 4096 entries of a class + output descriptors; the uploads are asynchronous, from vectors of the state
+int BasisImage::chunk(const uint32_t* ent, const std::vector<int64_t>& class_ptr) {
+    const int64_t CH = 4096;
+    chunk_ptr.assign(d + 1, 0);
+    for (int64_t i = 1; i <= d; ++i) {
+        chunk_ptr[i - 1] = (int64_t)cb.size();
+        for (int64_t p = class_ptr[i]; p < class_ptr[i + 1]; p += CH) {
+            cb.push_back(p);
+            ce.push_back(std::min(p + CH, class_ptr[i + 1]));
+        }
+    }
+    chunk_ptr[d] = (int64_t)cb.size();
+    desc = pair_descriptor(c->bd_sizes, S);
+    const int64_t nch = (int64_t)cb.size();
+    int64_t* d_chunk_ptr = (int64_t*)ctx_buf(c, "bi_chunk_ptr", (d + 1) * 8);
+    int64_t* d_cb = (int64_t*)ctx_buf(c, "bi_cb", std::max<int64_t>(nch, 1) * 8);
+    int64_t* d_ce = (int64_t*)ctx_buf(c, "bi_ce", std::max<int64_t>(nch, 1) * 8);
+    int32_t* d_dA = (int32_t*)ctx_buf(c, "bi_da", std::max<int64_t>(S, 1) * 4);
+    int32_t* d_dB = (int32_t*)ctx_buf(c, "bi_db", std::max<int64_t>(S, 1) * 4);
+    double* partial = (double*)ctx_buf(c, "bi_partial", (size_t)std::max<int64_t>(nch * S, 1) * 8);
+    if (!d_chunk_ptr || !d_cb || !d_ce || !d_dA || !d_dB || !partial) return SDPSR_OUT_OF_MEMORY;
+    HIP_TRY(c, hipMemcpyAsync(d_chunk_ptr, chunk_ptr.data(), (d + 1) * 8, hipMemcpyHostToDevice, s));
+    if (nch) {
+        HIP_TRY(c, hipMemcpyAsync(d_cb, cb.data(), nch * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(d_ce, ce.data(), nch * 8, hipMemcpyHostToDevice, s));
+    }
+    if (S) {
+        HIP_TRY(c, hipMemcpyAsync(d_dA, desc.data(), S * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(d_dB, desc.data() + S, S * 4, hipMemcpyHostToDevice, s));
+    }
+    launch_basis_image(s, n, d, S1, S, Qrm, ent, nullptr, d_dA, d_dB, d_chunk_ptr, nch, nullptr, d_cb, d_ce,
+                       partial, out, atol);
+    return SDPSR_OK;
+}
+
+int BasisImage::run(bool& done_synced) {
+    Shortcut r;
+    int st = shortcut_commutative(r);
+    if (!st && r == FALL_THROUGH) st = shortcut_blocks(r);
+    done_synced = !st && r == DONE_SYNCED;
+    if (st || r != FALL_THROUGH) return st;  // (out is complete)
+    const Route kind = route();
+    if (kind == TWO_STAGE) return two_stage();
+    // _constraints(P): entries grouped by class (src/diagonalize.jl:42-50)
+    uint32_t* ent = nullptr;
+    std::vector<int64_t> class_ptr;  // size d+2: class_ptr[l]..class_ptr[l+1] = label l
+    st = sort_entries_by_label(c, len, d, L, &ent, class_ptr);
+    if (st) return st;
+    return kind == OUTER ? outer(ent, class_ptr) : chunk(ent, class_ptr);
 }
 }  // namespace sdpsr
 
@@ -112,10 +315,6 @@ int sdpsr_block_diagonalize(sdpsr_ctx* c, int64_t n, const uint32_t* P, int64_t 
                             int mem) {
     return block_diagonalize_impl(c, n, P, d, epsilon, nblocks, sum_sq, sum_s, phase_ms, mem, false, true, false, /*labels_are_u32=*/false);
 }
-
-}  // extern "C"
-
-extern "C" {
 
 int sdpsr_block_sizes(sdpsr_ctx* c, int32_t* blk_sizes) {
     if (!c || !blk_sizes) return SDPSR_BAD_ARGUMENT;
@@ -142,209 +341,23 @@ int sdpsr_block_images(sdpsr_ctx* c, double* blks, double* Q_hat, double* phase_
     if (!c->bd_valid) return ctx_fail(c, SDPSR_BAD_STATE, "sdpsr_block_diagonalize has not succeeded on this ctx");
     if (!blks) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "null pointer");
     hipStream_t s = c->stream;
-    const int64_t n = c->bd_n, d = c->bd_d, S1 = c->bd_sum_s, S = c->bd_sum_sq, len = n * n;
     TotalEvents ev_total(phase_ms != nullptr, s);
+    BasisImage bi(c);  // lives until the one host wait below: its host vectors are the sources of asynchronous uploads
+    const int64_t n = bi.n, d = bi.d, S1 = bi.S1, S = bi.S;
     int st = SDPSR_OK;
-    uint32_t* L = c->bd_labels_ext ? const_cast<uint32_t*>(c->bd_labels_ext) : (uint32_t*)ctx_buf(c, "bd_labels", len * 4);
     double* Qhat = (double*)ctx_buf(c, "bd_qhat", (size_t)n * S1 * 8);
-    double* Qrm = (double*)ctx_buf(c, "bd_qrm", (size_t)n * S1 * 8);
-    double* out = out_dev(c, "bd_blks", blks, (size_t)d * S, mem, &st);
-    if (st || !L || !Qhat || !Qrm) return st ? st : SDPSR_OUT_OF_MEMORY;
-    launch_transpose_to_rowmajor(s, n, S1, Qhat, Qrm);
-    const double atol = 1e-12 * (double)n;  // basis_image default atol (src/diagonalize.jl:67)
-    // opts.basis_image_kernel = 1 two_stage | 2 outer | 3 chunk forces one of the three kernels (tests: the
-    // automatic choice reaches `outer` / `chunk` only for shapes far beyond the test sizes)
-    const int force = c->opts.basis_image_kernel;
-    const bool f_two = force == 1, f_outer = force == 2, f_chunk = force == 3;
-    // commutative case (every block 1 x 1): the images are eigenvalues, lambda_ik = q_k'(1[P==i] x) for x = sum_k q_k
-    // -- one vector's class sums -- with a randomized self-check; the projection formula below runs if the check
-    // fails (kernels_blockdiag.hip, launch_basis_image_commutative) and always under SDPSR_FLAG_FULL_BASIS_IMAGE
-    bool done = false;
-    bool done_synced = false;  // the stream was synchronised by the commutative path's verdict and nothing was enqueued since
-    if (S == S1 && force == 0 && !(c->opts.flags & SDPSR_FLAG_FULL_BASIS_IMAGE) && d >= 1 && n >= 64) {
-        double* ws = (double*)ctx_buf(c, "bi_comm_ws", basis_image_commutative_workspace_doubles(n, d) * 8);
-        // per-column verdicts, stored by the check kernel straight into pinned host memory: its own words, beside
-        // (not inside) the refinement's counters at the start of the buffer
-        uint32_t* hv = (uint32_t*)ctx_pinned(c, 256 + (size_t)(S1 + 1) * 4);
-        if (!ws || !hv) return SDPSR_OUT_OF_MEMORY;
-        hv += 64;
-        if (launch_basis_image_commutative(s, n, d, S1, L, Qrm, next_key(c), atol, 2e-10, ws, out, hv)) {
-            HIP_TRY(c, ctx_sync_stream(c, s));
-            HIP_TRY(c, hipGetLastError());
-            const uint32_t nbad = hv[0];
-            done = nbad == 0;
-            done_synced = done;
-            if (!done && nbad <= 8) {
-                // a few columns failed (the eigenvectors of a pair of close eigenvalues): the projection formula for
-                // those columns only, two per extra class-sum pass
-                std::vector<int> badk;
-                for (int64_t k2 = 0; k2 < S1; ++k2)
-                    if (hv[1 + k2]) badk.push_back((int)k2);
-                done = true;
-                for (size_t q = 0; q < badk.size() && done; q += 2)
-                    done = launch_basis_image_fix_pair(s, n, d, S1, L, Qrm, badk[q], badk[q + 1 < badk.size() ? q + 1 : q], atol, ws, out);
-                if (dbg_on()) fprintf(stderr, "[sdpsr] basis_image: invariance check failed for %u column(s), projection formula for those\n", nbad);
-            } else if (!done && dbg_on()) {
-                fprintf(stderr, "[sdpsr] basis_image: invariance check failed for %u columns, projection formula instead\n", nbad);
-            }
-        }
-    }
-    // blocks up to 3 x 3 (non-commutative algebras with small blocks: ER(q) (x) K_k): the images from FOUR vectors' class
-    // sums with a per-block check (kernels_blockdiag.hip, launch_basis_image_blocks); blocks that fail get the projection
-    // formula, one block per extra pair of passes; many failures: the two-stage kernels below for everything
-    if (!done && S != S1 && force == 0 && !(c->opts.flags & SDPSR_FLAG_FULL_BASIS_IMAGE) && d >= 1 && n >= 64 && c->bd_sizes.size() <= 4096) {
-        int max_s = 0;
-        for (int32_t sz : c->bd_sizes) max_s = std::max(max_s, (int)sz);
-        if (max_s <= 3) {
-            const int nb = (int)c->bd_sizes.size();
-            std::vector<int32_t> hcs(2 * (size_t)nb);
-            std::vector<int64_t> hoff(nb);
-            int64_t colbase = 0, off = 0;
-            for (int k2 = 0; k2 < nb; ++k2) {
-                hcs[k2] = (int32_t)colbase;
-                hcs[nb + k2] = c->bd_sizes[k2];
-                hoff[k2] = off;
-                colbase += c->bd_sizes[k2];
-                off += (int64_t)c->bd_sizes[k2] * c->bd_sizes[k2];
-            }
-            int32_t* d_cs = (int32_t*)ctx_buf(c, "bi_colsz", (size_t)2 * nb * 4);
-            int64_t* d_off = (int64_t*)ctx_buf(c, "bi_off", (size_t)nb * 8);
-            double* ws = (double*)ctx_buf(c, "bi_comm_ws", basis_image_blocks_workspace_doubles(n, d) * 8);
-            uint32_t* hv = (uint32_t*)ctx_pinned(c, 256 + (size_t)(nb + 1) * 4);
-            if (!d_cs || !d_off || !ws || !hv) return SDPSR_OUT_OF_MEMORY;
-            hv += 64;
-            st = h2d_sync(c, d_cs, hcs.data(), (size_t)2 * nb * 4);
-            if (!st) st = h2d_sync(c, d_off, hoff.data(), (size_t)nb * 8);
-            if (st) return st;
-            if (launch_basis_image_blocks(s, n, d, S1, S, nb, d_cs, d_cs + nb, d_off, L, Qrm, next_key(c), -1, atol, 2e-10, ws, out, hv)) {
-                HIP_TRY(c, ctx_sync_stream(c, s));
-                HIP_TRY(c, hipGetLastError());
-                const uint32_t nbad = hv[0];
-                done = nbad == 0;
-                done_synced = done;
-                if (!done && nbad <= 4) {
-                    done = true;
-                    for (int k2 = 0; k2 < nb && done; ++k2)
-                        if (hv[1 + k2]) done = launch_basis_image_blocks(s, n, d, S1, S, nb, d_cs, d_cs + nb, d_off, L, Qrm, 0, k2, atol, 2e-10, ws, out, nullptr);
-                }
-                if (!done_synced && dbg_on()) fprintf(stderr, "[sdpsr] basis_image: invariance check failed for %u block(s)%s\n", nbad, done ? ", projection formula for those" : ", two-stage kernels instead");
-            }
-        }
-    }
-    if (done) {
-        // (out is complete)
-    } else if (basis_image_two_stage_fits(n, d, S1) && !f_outer && !f_chunk) {
-        // two-stage form (class sums per row, then the s_k x s_k dots): descriptor = the two
-        // columns of Q_hat every output multiplies, blocks side by side, column-major inside
-        std::vector<int32_t> hdesc(2 * (size_t)S);
-        {
-            int64_t o = 0, colbase = 0;
-            for (int32_t sz : c->bd_sizes) {
-                for (int b2 = 0; b2 < sz; ++b2)
-                    for (int a2 = 0; a2 < sz; ++a2) {
-                        hdesc[o] = (int32_t)(colbase + a2);
-                        hdesc[S + o] = (int32_t)(colbase + b2);
-                        ++o;
-                    }
-                colbase += sz;
-            }
-        }
-        int32_t* d_desc = (int32_t*)ctx_buf(c, "bi_desc", (size_t)2 * S * 4);
-        double* Tb = (double*)ctx_buf(c, "bi_T", (size_t)d * n * S1 * 8);
-        if (!d_desc || !Tb) return SDPSR_OUT_OF_MEMORY;
-        st = h2d_sync(c, d_desc, hdesc.data(), (size_t)2 * S * 4);
-        if (st) return st;
-        launch_basis_image_two_stage(s, n, d, S1, S, L, Qrm, Tb, d_desc, d_desc + S, atol, out);
-    } else {
-    // _constraints(P): entries grouped by class (src/diagonalize.jl:42-50)
-    uint32_t* ent = nullptr;
-    int64_t* class_ptr = nullptr;  // host, size d+2: class_ptr[l]..class_ptr[l+1] = label l
-    st = sort_entries_by_label(c, len, d, L, &ent, &class_ptr);
+    bi.Qrm = (double*)ctx_buf(c, "bd_qrm", (size_t)n * S1 * 8);
+    bi.out = out_dev(c, "bd_blks", blks, (size_t)d * S, mem, &st);
+    if (st || !bi.L || !Qhat || !bi.Qrm) return st ? st : SDPSR_OUT_OF_MEMORY;
+    launch_transpose_to_rowmajor(s, n, S1, Qhat, bi.Qrm);
+    bool done_synced = false;  // the stream was synchronised by a shortcut's verdict and nothing was enqueued since
+    st = bi.run(done_synced);
     if (st) return st;
-    int max_s = 0;
-    for (int32_t sz : c->bd_sizes) max_s = std::max(max_s, (int)sz);
-    // many small classes (average class below 4096 entries) and blocks up to 256: outer-product
-    // kernel, one workgroup per (class, block), every output written once, no partial sums
-    (void)f_two;
-    if (max_s <= 256 && d > 0 && (len / d < 4096 || f_outer) && !f_chunk && d <= 0x7FFFFFFF && c->bd_sizes.size() <= 65535) {
-        const int nb = (int)c->bd_sizes.size();
-        std::vector<int32_t> hcol(nb), hsz(nb);
-        std::vector<int64_t> hoff(nb);
-        int64_t colbase = 0, off = 0;
-        for (int k2 = 0; k2 < nb; ++k2) {
-            hcol[k2] = (int32_t)colbase;
-            hsz[k2] = c->bd_sizes[k2];
-            hoff[k2] = off;
-            colbase += hsz[k2];
-            off += (int64_t)hsz[k2] * hsz[k2];
-        }
-        int32_t* d_col = (int32_t*)ctx_buf(c, "bi_col", (size_t)nb * 4);
-        int32_t* d_sz = (int32_t*)ctx_buf(c, "bi_sz", (size_t)nb * 4);
-        int64_t* d_off = (int64_t*)ctx_buf(c, "bi_off", (size_t)nb * 8);
-        int64_t* d_cls = (int64_t*)ctx_buf(c, "bi_cls_ptr", (size_t)(d + 2) * 8);
-        if (!d_col || !d_sz || !d_off || !d_cls) {
-            free(class_ptr);
-            return SDPSR_OUT_OF_MEMORY;
-        }
-        st = h2d_sync(c, d_col, hcol.data(), (size_t)nb * 4);
-        if (!st) st = h2d_sync(c, d_sz, hsz.data(), (size_t)nb * 4);
-        if (!st) st = h2d_sync(c, d_off, hoff.data(), (size_t)nb * 8);
-        if (!st) st = h2d_sync(c, d_cls, class_ptr, (size_t)(d + 2) * 8);
-        free(class_ptr);
-        if (st) return st;
-        launch_basis_image_outer(s, n, d, S1, S, nb, max_s, Qrm, ent, d_cls, d_col, d_sz, d_off, atol, out);
-    } else {
-    // chunks + output descriptors
-    const int64_t CH = 4096;
-    std::vector<int64_t> chunk_ptr(d + 1, 0), cb, ce;
-    for (int64_t i = 1; i <= d; ++i) {
-        chunk_ptr[i - 1] = (int64_t)cb.size();
-        for (int64_t p = class_ptr[i]; p < class_ptr[i + 1]; p += CH) {
-            cb.push_back(p);
-            ce.push_back(std::min(p + CH, class_ptr[i + 1]));
-        }
-    }
-    chunk_ptr[d] = (int64_t)cb.size();
-    free(class_ptr);
-    std::vector<int32_t> dA(S), dB(S);
-    {
-        int64_t o = 0, colbase = 0;
-        for (int32_t sz : c->bd_sizes) {
-            for (int b = 0; b < sz; ++b)
-                for (int a = 0; a < sz; ++a) {
-                    dA[o] = (int32_t)(colbase + a);
-                    dB[o] = (int32_t)(colbase + b);
-                    ++o;
-                }
-            colbase += sz;
-        }
-    }
-    const int64_t nch = (int64_t)cb.size();
-    int64_t* d_chunk_ptr = (int64_t*)ctx_buf(c, "bi_chunk_ptr", (d + 1) * 8);
-    int64_t* d_cb = (int64_t*)ctx_buf(c, "bi_cb", std::max<int64_t>(nch, 1) * 8);
-    int64_t* d_ce = (int64_t*)ctx_buf(c, "bi_ce", std::max<int64_t>(nch, 1) * 8);
-    int32_t* d_dA = (int32_t*)ctx_buf(c, "bi_da", std::max<int64_t>(S, 1) * 4);
-    int32_t* d_dB = (int32_t*)ctx_buf(c, "bi_db", std::max<int64_t>(S, 1) * 4);
-    double* partial = (double*)ctx_buf(c, "bi_partial", (size_t)std::max<int64_t>(nch * S, 1) * 8);
-    if (!d_chunk_ptr || !d_cb || !d_ce || !d_dA || !d_dB || !partial) return SDPSR_OUT_OF_MEMORY;
-    HIP_TRY(c, hipMemcpyAsync(d_chunk_ptr, chunk_ptr.data(), (d + 1) * 8, hipMemcpyHostToDevice, s));
-    if (nch) {
-        HIP_TRY(c, hipMemcpyAsync(d_cb, cb.data(), nch * 8, hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemcpyAsync(d_ce, ce.data(), nch * 8, hipMemcpyHostToDevice, s));
-    }
-    if (S) {
-        HIP_TRY(c, hipMemcpyAsync(d_dA, dA.data(), S * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemcpyAsync(d_dB, dB.data(), S * 4, hipMemcpyHostToDevice, s));
-    }
-    launch_basis_image(s, n, d, S1, S, Qrm, ent, nullptr, d_dA, d_dB, d_chunk_ptr, nch, nullptr, d_cb, d_ce,
-                       partial, out, atol);
-    }
-    }
     HIP_TRY(c, hipGetLastError());
-    // ONE host wait for everything (the images, Q_hat, and the host vectors above, which must outlive their copies): the
+    // ONE host wait for everything (the images, Q_hat, and the host vectors of `bi`, which must outlive their copies): the
     // copies are enqueued first.  (Three waits before: the second and third found an idle stream, ~3 us each.)
     if (mem != SDPSR_MEM_DEVICE) {
-        HIP_TRY(c, hipMemcpyAsync(blks, out, (size_t)d * S * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(blks, bi.out, (size_t)d * S * 8, hipMemcpyDeviceToHost, s));
         c->d2h_bytes += (size_t)d * S * 8;
     }
     if (Q_hat) {

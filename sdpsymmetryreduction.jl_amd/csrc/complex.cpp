@@ -191,18 +191,9 @@ int sdpsr_block_diagonalize_complex(sdpsr_ctx* c, int64_t n, const uint32_t* P, 
         st = cx_heev_general(c, n, Hr, Hi, atol, Vr, Vi, ei.vals);
         if (st) return st;
     }
-    ei.ptrs.assign(1, 0);
-    for (int64_t i = 0; i < n; ++i) {
-        if (i == n - 1) {
-            ei.ptrs.push_back((int)n);
-            break;
-        }
-        if (!(std::fabs(ei.vals[i + 1] - ei.vals[i]) <= atol)) ei.ptrs.push_back((int)i + 1);
-    }
+    ei.ptrs = eigenspace_ptrs(ei.vals.data(), n, atol);
     const int neig = (int)ei.ptrs.size() - 1;
-    std::vector<int32_t> space_of(n);
-    for (int b = 0; b < neig; ++b)
-        for (int i = ei.ptrs[b]; i < ei.ptrs[b + 1]; ++i) space_of[i] = b;
+    const std::vector<int32_t> space_of = space_of_ptrs(ei.ptrs);
     // Step 3: second generic element, Q'AQ, block norms, isomorphism classes (:259-262, :201-217)
     int32_t* dspace = (int32_t*)ctx_buf(c, "bd_space", (size_t)n * 4);
     unsigned long long* dnorms = (unsigned long long*)ctx_buf(c, "bd_norms", (size_t)neig * neig * 8);
@@ -220,31 +211,25 @@ int sdpsr_block_diagonalize_complex(sdpsr_ctx* c, int64_t n, const uint32_t* P, 
     st = d2h_sync(c, norms.data(), dnorms, (size_t)neig * neig * 8);
     if (st) return st;
     auto dimof = [&](int b) { return ei.ptrs[b + 1] - ei.ptrs[b]; };
-    for (int i = 0; i < neig; ++i)
-        for (int j = i; j < neig; ++j) {
-            const double v = (dimof(i) != dimof(j)) ? 0.0 : norms[(size_t)i * neig + j];
-            norms[(size_t)i * neig + j] = norms[(size_t)j * neig + i] = v;
-        }
+    symmetrize_coupling(ei.ptrs, norms.data(), norms.data());
     st = isomorphism_classes(c, norms, neig, atol, ei.kpart);
     if (st) return st;
     // irreducible_decomposition (:295-348)
     std::vector<int> roots;
     std::vector<std::vector<int>> members;
     class_structure(ei.kpart, roots, members);
-    std::vector<int32_t> sizes(roots.size());
+    std::vector<int32_t> sizes;
     int64_t S1 = 0, S = 0;
+    block_sizes(members, sizes, S1, S);
     std::vector<int32_t> desc;
+    int32_t col = 0;
     for (size_t p = 0; p < roots.size(); ++p) {
-        sizes[p] = (int32_t)members[p].size();
         const int i = roots[p];
         for (size_t q = 0; q < members[p].size(); ++q) {
             const int j = members[p][q];
-            const int32_t dsc[6] = {q == 0 ? 0 : 1, (int32_t)ei.ptrs[i], (int32_t)dimof(i), (int32_t)ei.ptrs[j], (int32_t)dimof(j),
-                                    (int32_t)(S1 + (int64_t)q)};
+            const int32_t dsc[6] = {q == 0 ? 0 : 1, (int32_t)ei.ptrs[i], (int32_t)dimof(i), (int32_t)ei.ptrs[j], (int32_t)dimof(j), col++};
             desc.insert(desc.end(), dsc, dsc + 6);
         }
-        S1 += sizes[p];
-        S += (int64_t)sizes[p] * sizes[p];
     }
     double* Qhat = (double*)ctx_buf(c, "bdc_qhat", (size_t)2 * n * S1 * 8);
     int32_t* ddesc = (int32_t*)ctx_buf(c, "bdc_desc", desc.size() * 4);
@@ -297,19 +282,7 @@ int sdpsr_block_images_complex(sdpsr_ctx* c, double* blks, double* Q_hat, int me
     double* out = out_dev(c, "bdc_blks", blks, (size_t)2 * d * S, mem, &st);
     int32_t* ddesc = (int32_t*)ctx_buf(c, "bdc_desc2", (size_t)2 * S * 4);
     if (st || !L || !Qhat || !ddesc) return st ? st : SDPSR_OUT_OF_MEMORY;
-    std::vector<int32_t> hdesc(2 * (size_t)S);
-    {
-        int64_t o = 0, colbase = 0;
-        for (int32_t sz : c->bdc_sizes) {
-            for (int b2 = 0; b2 < sz; ++b2)
-                for (int a2 = 0; a2 < sz; ++a2) {
-                    hdesc[o] = (int32_t)(colbase + a2);
-                    hdesc[S + o] = (int32_t)(colbase + b2);
-                    ++o;
-                }
-            colbase += sz;
-        }
-    }
+    const std::vector<int32_t> hdesc = pair_descriptor(c->bdc_sizes, S);
     st = h2d_sync(c, ddesc, hdesc.data(), hdesc.size() * 4);
     if (st) return st;
     if (n <= 64) {
@@ -317,16 +290,12 @@ int sdpsr_block_images_complex(sdpsr_ctx* c, double* blks, double* Q_hat, int me
     } else {
         // entries grouped by class (_constraints(P), src/diagonalize.jl:42-50): a class workgroup walks its own entries only
         uint32_t* ent = nullptr;
-        int64_t* class_ptr = nullptr;
-        st = sort_entries_by_label(c, n * n, d, L, &ent, &class_ptr);
+        std::vector<int64_t> class_ptr;
+        st = sort_entries_by_label(c, n * n, d, L, &ent, class_ptr);
         if (st) return st;
         int64_t* d_cls = (int64_t*)ctx_buf(c, "bi_cls_ptr", (size_t)(d + 2) * 8);
-        if (!d_cls) {
-            free(class_ptr);
-            return SDPSR_OUT_OF_MEMORY;
-        }
-        st = h2d_sync(c, d_cls, class_ptr, (size_t)(d + 2) * 8);
-        free(class_ptr);
+        if (!d_cls) return SDPSR_OUT_OF_MEMORY;
+        st = h2d_sync(c, d_cls, class_ptr.data(), (size_t)(d + 2) * 8);
         if (st) return st;
         launch_cx_basis_image_sorted(s, n, d, S, ent, d_cls, Qhat, ddesc, ddesc + S, 1e-12 * (double)n, out);
     }

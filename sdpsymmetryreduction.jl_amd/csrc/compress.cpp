@@ -13,17 +13,6 @@ using namespace sdpsr;
 
 namespace {
 
-// closes the phase it opened on every exit path; collect: as the successful path does behind this phase
-struct PhaseScope {
-    PhaseTimer& tm;
-    bool collect;
-    PhaseScope(PhaseTimer& t, int slot, bool col) : tm(t), collect(col) { tm.begin(slot); }
-    ~PhaseScope() {
-        tm.end();
-        if (collect) tm.collect();
-    }
-};
-
 struct Rider { double *dBs, *gps; };  // device buffers of the speculative second element (Module::growth_round)
 
 // ===========================================================================

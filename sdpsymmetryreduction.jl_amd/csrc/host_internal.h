@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 
+#include "iso_classes.h"
 #include "sdpsr_internal.h"
 
 namespace sdpsr {
@@ -177,6 +178,17 @@ struct PhaseTimer {
     }
 };
 
+// closes the phase it opened on every exit path; collect: as the successful path does behind this phase
+struct PhaseScope {
+    PhaseTimer& tm;
+    bool collect;
+    PhaseScope(PhaseTimer& t, int slot, bool col) : tm(t), collect(col) { tm.begin(slot); }
+    ~PhaseScope() {
+        tm.end();
+        if (collect) tm.collect();
+    }
+};
+
 // start / stop events of a whole entry point (phase_ms[SDPSR_T_TOTAL]); freed on every exit path
 struct TotalEvents {
     hipEvent_t a = nullptr, b = nullptr;
@@ -214,6 +226,9 @@ constexpr PinnedWords PINNED_SPECULATIVE{144, 1};     // the same for the specul
 constexpr PinnedWords PINNED_BASIS_CONSTANT{192, 1};  // != 0: some U_k is not constant on the classes
 constexpr PinnedWords PINNED_SAMPLE{224, 4};          // sample of the signatures: non-zero, distinct, seen once, seen twice
 constexpr size_t PINNED_FIXED_BYTES = 1024;
+// basis_image's shortcuts (blockdiag.cpp): a count, then one verdict per column / block, from this word on.  Variable length: the tail runs
+// over the loop's words behind it; the shortcut waits for the stream and reads its words before it returns
+constexpr PinnedWords PINNED_BASIS_IMAGE_VERDICTS{64, 1};
 constexpr PinnedWords PINNED_SMALL_FLAG{0, 1};                   // c->pinned_small (256 B): the flag of the one-shot entries ("a label exceeds d", symmetry)
 constexpr PinnedWords PINNED_SMALL_DEFERRED_VERIFY{8, 1};        // sdpsr_jordan_reduce: the two verdicts the loop left unread (c->deferred_verdict)
 constexpr PinnedWords PINNED_SMALL_DEFERRED_SPECULATIVE{24, 1};
@@ -226,7 +241,7 @@ constexpr bool pinned_words_disjoint(std::initializer_list<PinnedWords> w, size_
     }
     return true;
 }
-static_assert(pinned_words_disjoint({PINNED_REFINE, PINNED_SYMMETRY, PINNED_VERIFY, PINNED_SPECULATIVE, PINNED_BASIS_CONSTANT, PINNED_SAMPLE}, PINNED_FIXED_BYTES) &&
+static_assert(pinned_words_disjoint({PINNED_REFINE, PINNED_SYMMETRY, PINNED_BASIS_IMAGE_VERDICTS, PINNED_VERIFY, PINNED_SPECULATIVE, PINNED_BASIS_CONSTANT, PINNED_SAMPLE}, PINNED_FIXED_BYTES) &&
               PINNED_FIXED_BYTES % sizeof(double) == 0, "two reports share a word of c->pinned, or one reaches into the symmetry probe's doubles");
 static_assert(pinned_words_disjoint({PINNED_SMALL_FLAG, PINNED_SMALL_DEFERRED_VERIFY, PINNED_SMALL_DEFERRED_SPECULATIVE, PINNED_SMALL_NARROW}, 256), "two reports share a word of c->pinned_small");
 inline uint32_t* pinned_report(sdpsr_ctx* c, PinnedWords w) {  // the pinned words of one report (nullptr: no pinned buffer)
@@ -285,9 +300,8 @@ struct ElemGen {
     std::function<int()> fork;
 };
 int make_element(sdpsr_ctx* c, const ElemGen* gen, int64_t n, int64_t ld, const uint32_t* L, double* dst);
-double otsu_threshold(const std::vector<double>& X, double atol);
+// iso_classes.h holds the host arithmetic (Otsu threshold, union-find, class structure, layouts); this adds the one error message
 int isomorphism_classes(sdpsr_ctx* c, const std::vector<double>& norms, int neig, double atol, std::vector<int>& kpart);
-void class_structure(const std::vector<int>& kpart, std::vector<int>& roots, std::vector<std::vector<int>>& members);
 int eigen_decomposition_device(sdpsr_ctx* c, int64_t n, const uint32_t* L, double atol, EigInfo& info, PhaseTimer& tm,
                                const ElemGen* gen = nullptr, int64_t expect_dim = -1);
 // status used internally when a driver of diagonalize hands over to the dense one

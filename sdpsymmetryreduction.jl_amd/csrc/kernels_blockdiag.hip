@@ -1616,7 +1616,7 @@ void launch_radix_sort_pairs(hipStream_t s, int64_t len, int bits, const uint32_
 }
 
 int sort_entries_by_label(sdpsr_ctx* c, int64_t len, int64_t d, const uint32_t* L,
-                          uint32_t** ent_out, int64_t** class_ptr_host) {
+                          uint32_t** ent_out, std::vector<int64_t>& class_ptr_host) {
     hipStream_t s = c->stream;
     if (len >= (int64_t(1) << 32)) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "sort_entries_by_label: len >= 2^32");
     uint32_t* kA = (uint32_t*)ctx_buf(c, "bi_key_a", len * sizeof(uint32_t));
@@ -1633,19 +1633,15 @@ int sort_entries_by_label(sdpsr_ctx* c, int64_t len, int64_t d, const uint32_t* 
     uint32_t* idx_sorted = vB;
     HIP_TRY(c, hipMemsetAsync(cstart, 0xFF, (d + 2) * sizeof(int64_t), s));  // -1 = class absent
     class_starts_kernel<<<grid_for(len, 256), 256, 0, s>>>(len, key_sorted, cstart);
-    int64_t* h = (int64_t*)malloc((d + 2) * sizeof(int64_t));  // handed to the caller, who frees it
-    if (!h) return SDPSR_OUT_OF_MEMORY;
-    const int st = d2h_sync(c, h, cstart, (size_t)(d + 1) * sizeof(int64_t));  // (a wait that yields inside a batch call)
-    if (st) {
-        free(h);
-        return st;
-    }
+    std::vector<int64_t>& h = class_ptr_host;
+    h.resize(d + 2);
+    const int st = d2h_sync(c, h.data(), cstart, (size_t)(d + 1) * sizeof(int64_t));  // (a wait that yields inside a batch call)
+    if (st) return st;
     // class_ptr[i] .. class_ptr[i+1] = entries of label i (i = 0..d); fill absent classes
     h[d + 1] = len;
     for (int64_t l = d; l >= 0; --l)
         if (h[l] < 0) h[l] = h[l + 1];
     *ent_out = idx_sorted;
-    *class_ptr_host = h;
     return SDPSR_OK;
 }
 

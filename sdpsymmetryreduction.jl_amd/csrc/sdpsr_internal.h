@@ -488,7 +488,7 @@ void launch_radix_sort_pairs(hipStream_t s, int64_t len, int bits, const uint32_
                              uint32_t* vB, uint32_t* hist);
 // stable sort of entries by label (label 0 dropped): ent sorted, hist[d+1]
 int sort_entries_by_label(sdpsr_ctx* c, int64_t len, int64_t d, const uint32_t* L,
-                          uint32_t** ent_out, int64_t** class_ptr_host);
+                          uint32_t** ent_out, std::vector<int64_t>& class_ptr_host);
 
 // ---------------------------------------------------------------------------
 // eigen.cpp (rocSOLVER)

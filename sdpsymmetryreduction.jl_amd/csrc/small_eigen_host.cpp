@@ -33,15 +33,9 @@ int murota_small_host(sdpsr_ctx* c, int w, const double* B1, const std::function
     std::vector<double> vals(w), Q((size_t)w * w);
     const int info = host_syev(w, B1, w, vals.data(), Q.data(), w);
     if (info != 0) return ctx_fail(c, SDPSR_SOLVER_ERROR, "host eigensolver did not converge, info=" + std::to_string(info));
-    // EigenDecomposition ctor (:19-40): a new eigenspace where |dv| > atol
-    std::vector<int> ptrs(1, 0);
-    for (int i = 0; i + 1 < w; ++i)
-        if (!(std::fabs(vals[i + 1] - vals[i]) <= atol)) ptrs.push_back(i + 1);
-    ptrs.push_back(w);
+    const std::vector<int> ptrs = eigenspace_ptrs(vals.data(), w, atol);  // EigenDecomposition ctor (:19-40)
     const int neig = (int)ptrs.size() - 1;
-    std::vector<int> space_of(w);
-    for (int b = 0; b < neig; ++b)
-        for (int i = ptrs[b]; i < ptrs[b + 1]; ++i) space_of[i] = b;
+    const std::vector<int32_t> space_of = space_of_ptrs(ptrs);
     auto dimof = [&](int b) { return ptrs[b + 1] - ptrs[b]; };
     // second generic element: T = A2 Q, M = Q' T, block maxima (:201-205)
     std::vector<double> A2((size_t)w * w), T((size_t)w * w), M((size_t)w * w), norms((size_t)neig * neig, 0.0);
@@ -62,24 +56,12 @@ int murota_small_host(sdpsr_ctx* c, int w, const double* B1, const std::function
     int st = couple(T);
     if (st) return st;
     std::vector<double> sym((size_t)neig * neig);
+    const bool single = (c->opts.flags & SDPSR_FLAG_SINGLE_COUPLING_ELEMENT) != 0;
     for (int extra = 0;; ++extra) {
-        // blocks between eigenspaces of different dimension count as zero (:185-186)
-        for (int i = 0; i < neig; ++i)
-            for (int j = i; j < neig; ++j) {
-                const double v = (dimof(i) != dimof(j)) ? 0.0 : norms[(size_t)i * neig + j];
-                sym[(size_t)i * neig + j] = sym[(size_t)j * neig + i] = v;
-            }
+        symmetrize_coupling(ptrs, norms.data(), sym.data());
         st = isomorphism_classes(c, sym, neig, atol, kpart);
         if (st != SDPSR_OK && st != SDPSR_NUMERICAL_INCONSISTENCY) return st;
-        bool done = extra >= 2 || expect_dim < 0 || (c->opts.flags & SDPSR_FLAG_SINGLE_COUPLING_ELEMENT);
-        if (!done && st == SDPSR_OK) {
-            std::vector<int> cnt(neig, 0);
-            for (int i = 0; i < neig; ++i) ++cnt[kpart[i]];
-            int64_t fd = 0;
-            for (int i = 0; i < neig; ++i) fd += (int64_t)cnt[i] * (cnt[i] + 1) / 2;
-            done = fd == expect_dim;
-        }
-        if (done) {
+        if (coupling_settled(extra, expect_dim, single, st == SDPSR_OK, kpart)) {
             if (st) return st;
             c->err.clear();
             break;
@@ -95,16 +77,8 @@ int murota_small_host(sdpsr_ctx* c, int w, const double* B1, const std::function
     std::vector<int> roots;
     std::vector<std::vector<int>> members;
     class_structure(kpart, roots, members);
-    sizes.assign(roots.size(), 0);
-    S1 = 0;
-    S = 0;
-    bool merged = false;
-    for (size_t p = 0; p < roots.size(); ++p) {
-        sizes[p] = (int32_t)members[p].size();
-        S1 += sizes[p];
-        S += (int64_t)sizes[p] * sizes[p];
-        merged = merged || members[p].size() > 1;
-    }
+    block_sizes(members, sizes, S1, S);
+    const bool merged = S != S1;  // some class has more than one member
     if (merged && (!t_valid || (c->opts.flags & SDPSR_FLAG_FRESH_IRREDUCIBLE_ELEMENT))) {
         st = next_element(A2.data());  // generic element #3 (:306)
         if (st) return st;
