@@ -19,7 +19,8 @@
  *     SDPSR_MEM_DEVICE: device pointers on ctx's device, used in place);
  *  - scalar outputs (int64_t* etc.) are always host pointers;
  *  - calls on one ctx are serialised on ctx's HIP stream; distinct ctxs (on the same or on
- *    different devices) may be used from distinct host threads; no global state; no callbacks;
+ *    different devices) may be used from distinct host threads; no global state (but the function table of RCCL, filled
+ *    once on the first sdpsr_comm_* call); no callbacks;
  *  - ordering of SDPSR_MEM_DEVICE arguments: inputs must be complete when the call is made, or
  *    be produced on a stream that ctx has been told about (sdpsr_set_stream, or
  *    sdpsr_wait_stream right before the call); on return from EVERY entry point the outputs
@@ -567,6 +568,90 @@ int sdpsr_eigen_decomposition_batched(sdpsr_ctx* ctx, int64_t n, const uint32_t*
    orthonormal vectors (column-major n x n, overwrites nothing of A). */
 int sdpsr_syev_f64(sdpsr_ctx* ctx, int64_t n, const double* A, double* values, double* vectors,
                    int mem);
+
+/* ---- agreement of independent restarts ---------------------------------------------------
+   The reference's answer to its randomized steps is "try again" (src/eigen_decomposition.jl:264-270, src/diagonalize.jl:4-9);
+   here the tries run side by side -- R restarts per ctx (sdpsr_jordan_reduce_batch, sdpsr_problem_reduce_batch), one process
+   per GPU -- and return partitions that are equal (Base.:(==), src/partitions.jl:16-17) with probability 1 - eps.  These entry
+   points reconcile them: when they differ every restart receives their MEET, the coarsest common refinement -- refine!
+   (src/partitions.jl:62-66) folded over the restarts, a restart whose draws missed a split is refined by the others.
+
+   A restart is a SLOT, numbered rank * R + i over all ranks.  The meet's keys are
+       keys[e] = sum over i < R with valid[i] of labels_i[e] * m(first_slot + i)   mod 2^64,
+       m(k) = ODD[k mod 8] * (2 floor(k / 8) + 1) mod 2^64,
+       ODD = 0x9E3779B97F4A7C15, 0xBF58476D1CE4E5B9, 0x94D049BB133111EB, 0xD6E8FEB86659FD93,
+             0xC2B2AE3D27D4EB4F, 0x165667B19E3779F9, 0x27D4EB2F165667C5, 0x85EBCA77C2B2AE63,
+   summed over the ranks mod 2^64; their canonical relabel (sdpsr_partition_from_u64: first occurrence, 0 stays 0) is the meet.
+   A key is 0 where every valid array is 0 -- and, like two entries of different label tuples receiving equal keys, elsewhere
+   only by a collision of the universal hash: probability ~ d^2 / 2^64 for a meet of d classes, on top of the ~ d^2 / 2^65 of
+   the relabel's own mixing hash (sdpsr_refine). */
+typedef struct sdpsr_comm sdpsr_comm; /* one rank's handle of a communicator, sdpsr_comm_create */
+
+/* The key pass alone, one streaming kernel ((R * B / 8 + 8) bytes per entry at label width B): for a caller with a transport
+   of its own (MPI.jl, a thread pool), who sums the ranks' keys itself and hands the sum to sdpsr_partition_from_u64.
+     labels   host array of R pointers (1 <= R <= 64) to label arrays of len entries at the ctx's label width, in `mem`;
+              device arrays are read where they lie, aligned to their element only (sub-arrays);
+     valid    host array of R ints, NULL = all: a restart with valid[i] == 0 is not read;
+     first_slot >= 0: the slot of labels[0] (rank * R);
+     keys     len words in `mem` (8-byte aligned); every word is written. */
+int sdpsr_meet_keys(sdpsr_ctx* ctx, int32_t R, const uint32_t* const* labels, const int32_t* valid, int64_t len,
+                    int64_t first_slot, uint64_t* keys, int mem);
+
+/* The agreement of the partitions of R restarts on every rank of comm (NULL: this process alone).  COLLECTIVE.
+     1. sdpsr_partition_checksum of every valid array; the ranks' records (len, R, label width, valid and checksum per
+        restart) are all-gathered and every rank takes the same decision from the same table:
+     2. some rank's len, R or label width differs: SDPSR_BAD_ARGUMENT on every rank; no valid restart anywhere:
+        SDPSR_BAD_STATE; every restart of every rank valid and all checksums equal: *met = 0, nothing is written, *dim_out is
+        untouched;
+     3. anything else: the key pass over the valid restarts, with a comm ONE sum all-reduce of the len keys, the canonical
+        relabel; the result is written into ALL R arrays, the invalid ones included, *met = 1, *dim_out = its class count.
+        After an OK return every array of every rank holds the same canonical partition, the meet of the valid restarts.
+   valid[i] (NULL = all): restart i's labels are a partition -- its status was SDPSR_OK, SDPSR_NUMERICAL_INCONSISTENCY or
+   SDPSR_DIMENSION_MISMATCH (the loop ended; blockDiagonalize's randomized failure does not touch P_out).  An invalid restart's
+   array is never read: whatever it holds cannot refine the others.
+   SDPSR_LABEL_OVERFLOW: the meet has more than 2^B - 1 classes at label width B; *dim_out is set, every array is untouched
+   (decided on the host from the count, which is the same on every rank).
+   R outside 1 .. 64, a NULL pointer, len out of range: SDPSR_BAD_ARGUMENT before any kernel or collective.  The ctx stays
+   usable after every error.
+   Host arrays (SDPSR_MEM_HOST): the valid arrays are uploaded once (len * B / 8 bytes each) for the checksums and the key
+   pass, and all R arrays are delivered back only after a meet; sdpsr_transfer_bytes counts both, and 16 bytes of checksum
+   read back per restart in either memory space. */
+int sdpsr_agree_partitions(sdpsr_ctx* ctx, sdpsr_comm* comm, int32_t R, uint32_t* const* labels, const int32_t* valid,
+                           int64_t len, int64_t* dim_out, int32_t* met, int mem);
+
+/* blockDiagonalize's side of the agreement: the tries have run side by side, the LOWEST rank whose status is SDPSR_OK wins
+   and every rank receives its blkSizes (the reference retries after NumericalInconsistency / DimensionMismatch,
+   src/eigen_decomposition.jl:264-270, src/diagonalize.jl:4-9).  COLLECTIVE: one all-gather of (status, nblocks), one broadcast
+   of the winner's sizes.  comm == NULL: the winner is this process or nobody.
+     status, nblocks, blk_sizes   this rank's result (blk_sizes is read only with status == SDPSR_OK);
+     *winner       the winning rank, -1 when every rank failed (SDPSR_OK is returned: the caller retries with fresh draws);
+     *nblocks_out  the winner's block count (0 without a winner); sizes_out[capacity]: its sizes.  capacity < *nblocks_out:
+                   sizes_out is untouched and SDPSR_BAD_ARGUMENT is returned -- after the collectives have completed, so the
+                   ranks stay in step.  Q_hat of the winner travels with sdpsr_comm_broadcast. */
+int sdpsr_agree_block_diagonalization(sdpsr_ctx* ctx, sdpsr_comm* comm, int32_t status, int32_t nblocks,
+                                      const int32_t* blk_sizes, int32_t* winner, int32_t* nblocks_out, int32_t* sizes_out,
+                                      int32_t capacity);
+
+/* ---- the communicator: RCCL behind the C ABI -------------------------------------------------------------
+   One process per GPU.  RCCL is opened lazily on the first sdpsr_comm_* call, with dlopen("librccl.so.1") -- by SONAME, not
+   by path: libsdpsr_hip.so does not link against it (a process that never calls these loads what it loaded before), and a
+   process that has imported torch shares the RCCL torch has already mapped.  A library that cannot be opened or lacks a
+   symbol: SDPSR_BAD_STATE (dlerror() in sdpsr_last_error); an RCCL call that fails: SDPSR_SOLVER_ERROR (ncclGetErrorString
+   in sdpsr_last_error).
+   EVERY RANK MUST MAKE THE SAME SEQUENCE OF COLLECTIVE CALLS (sdpsr_comm_create, sdpsr_comm_broadcast,
+   sdpsr_agree_partitions and sdpsr_agree_block_diagonalization with a comm), with arguments that pass the checks made before
+   the first collective of a call: a rank that returns early, or never arrives, leaves the others waiting.  THE LIBRARY ADDS
+   NO TIME-OUT OF ITS OWN.  All collectives run on the ctx's stream; the calls return with their outputs complete. */
+/* 128 bytes of host memory (ncclUniqueId): any one rank calls it, the caller distributes the bytes to the others */
+int sdpsr_comm_unique_id(void* id128);
+/* collective over the `world` ranks holding the same id; the communicator lives on ctx's device */
+int sdpsr_comm_create(sdpsr_ctx* ctx, int32_t world, int32_t rank, const void* id128, sdpsr_comm** out);
+int sdpsr_comm_rank(const sdpsr_comm* comm); /* -1 for a NULL comm, as sdpsr_comm_world */
+int sdpsr_comm_world(const sdpsr_comm* comm);
+/* `bytes` bytes of buf (in `mem`) of rank `root` to every rank's buf: the winner's Q_hat (sdpsr_q_hat) */
+int sdpsr_comm_broadcast(sdpsr_ctx* ctx, sdpsr_comm* comm, void* buf, int64_t bytes, int32_t root, int mem);
+/* before the ctx it was created on is destroyed */
+int sdpsr_comm_destroy(sdpsr_comm* comm);
 
 #ifdef __cplusplus
 }

@@ -14,3 +14,5 @@ from .api import (BlockDiagonalization, Context, DimensionMismatch, InvalidDecom
                   diagonalize, dim, eigen_decomposition, jordan_reduce_batch, Problem, eigen_decomposition_batched, fill, labels_convert, partition_checksum, randomize, reduce_constraints,
                   reduce_constraints_csr,
                   refine, relabel_keys)
+from . import agree  # noqa: F401
+from .agree import Comm, agree_block_diagonalization, agree_partitions, meet_keys  # noqa: F401

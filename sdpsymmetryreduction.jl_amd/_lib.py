@@ -164,6 +164,15 @@ def load_library():
         "sdpsr_set_label_width": (C.c_int, [vp, C.c_int]),
         "sdpsr_label_width": (C.c_int, [vp]),
         "sdpsr_labels_convert": (C.c_int, [vp, i64, vp, C.c_int, vp, C.c_int, C.c_int]),
+        "sdpsr_meet_keys": (C.c_int, [vp, i32, vp, vp, i64, i64, vp, C.c_int]),
+        "sdpsr_agree_partitions": (C.c_int, [vp, vp, i32, vp, vp, i64, pi64, pi32, C.c_int]),
+        "sdpsr_agree_block_diagonalization": (C.c_int, [vp, vp, i32, i32, vp, pi32, pi32, vp, i32]),
+        "sdpsr_comm_unique_id": (C.c_int, [vp]),
+        "sdpsr_comm_create": (C.c_int, [vp, i32, i32, vp, C.POINTER(vp)]),
+        "sdpsr_comm_rank": (C.c_int, [vp]),
+        "sdpsr_comm_world": (C.c_int, [vp]),
+        "sdpsr_comm_broadcast": (C.c_int, [vp, vp, vp, i64, i32, C.c_int]),
+        "sdpsr_comm_destroy": (C.c_int, [vp]),
     }
     missing = [s for s in declared_symbols() if not hasattr(lib, s)]
     if missing:

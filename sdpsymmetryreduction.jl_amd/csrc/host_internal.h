@@ -8,8 +8,16 @@
 #include <string>
 #include <vector>
 
+#include "agree_plan.h"
 #include "iso_classes.h"
 #include "sdpsr_internal.h"
+
+// sdpsr_comm_create (comm.cpp): one rank's handle of an RCCL communicator on the device of the ctx it was created on
+struct sdpsr_comm {
+    int device = 0;
+    int32_t world = 1, rank = 0;
+    void* nccl = nullptr;  // ncclComm_t
+};
 
 namespace sdpsr {
 
@@ -86,6 +94,15 @@ int label_width_fail(sdpsr_ctx* c, const char* where, uint64_t classes);
 // kernels_labels.hip
 void launch_labels_narrow(hipStream_t s, int64_t len, const uint32_t* in, void* out, int bits, uint32_t* flag, int num_cus);
 void launch_labels_widen(hipStream_t s, int64_t len, const void* in, int bits, uint32_t* out, int num_cus);
+// kernels_agree.hip: keys[e] = sum_i arrays[i][e] * mult[i] mod 2^64 (0 <= R <= 64 device arrays of `bits`-wide labels)
+void launch_meet_keys(hipStream_t s, int64_t len, int R, const void* const* arrays, const uint64_t* mult, int bits, uint64_t* keys, int num_cus);
+// comm.cpp: the collectives of the agreement (agree.cpp), on ctx's stream; comm != nullptr.  comm_usable: comm lives on ctx's device.
+// all_gather: `bytes` of host memory per rank into table (world * bytes, host, rank order) through device staging and ONE read-back;
+// all_reduce_sum_u64 / broadcast_dev: device memory in place, stream-ordered, no host wait
+int comm_usable(sdpsr_ctx* c, const sdpsr_comm* comm);
+int comm_all_gather(sdpsr_ctx* c, sdpsr_comm* comm, const void* mine, size_t bytes, void* table);
+int comm_all_reduce_sum_u64(sdpsr_ctx* c, sdpsr_comm* comm, uint64_t* dev, int64_t count);
+int comm_broadcast_dev(sdpsr_ctx* c, sdpsr_comm* comm, void* dev, size_t bytes, int32_t root);
 // loop.cpp: sdpsr_desymmetrize on uint32 device labels, in place
 int desymmetrize_device(sdpsr_ctx* c, int64_t n, uint32_t* L, int64_t* dim, int32_t* iters);
 

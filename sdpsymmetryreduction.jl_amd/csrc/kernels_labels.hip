@@ -9,38 +9,18 @@
 // the OUTPUT to a 16-byte boundary, so every store of the body is an aligned 16-byte store; the input behind the head is read
 // with 16-byte loads when it is aligned too, else with whatever the compiler makes of a 16-byte read at element alignment.
 // The tail finishes the last len % K elements one by one.  No LDS, nothing shared between workgroups; grid-stride, sized by
-// the CU count.
+// the CU count.  (load16, narrow_piece_get, head_elements and stream_grid live in label_stream.h: the key pass of
+// kernels_agree.hip streams label arrays the same way.)
 // Access shape: a lane's 2 / 4 uint32 pieces are ADJACENT, so a wave instruction on that side covers a 2 / 4 KiB span at 50 % /
 // 25 % density.  The form with every wave instruction dense (uint32 piece q * 64 + lane, the chunks of four labels changing
 // lanes inside groups of 2 / 4 by shuffles) was built and measured: the same 3.3 TB/s at 16 bits, 1.7 TB/s instead of 3.1 / 2.2
 // at 8 bits (profiles/r08_label_width.txt) -- the shuffles and selects cost more than the density gains.
 #include "host_internal.h"
+#include "label_stream.h"
 
 namespace sdpsr {
 
 namespace {
-
-template <int ALIGN>
-__device__ __forceinline__ uint4 load16(const void* p) {
-    uint4 v;
-    __builtin_memcpy(&v, __builtin_assume_aligned(p, ALIGN), 16);
-    return v;
-}
-
-// the K labels of one 16-byte piece of a narrow array, lowest address first (little endian)
-template <typename TN>
-__device__ __forceinline__ uint32_t narrow_piece_get(const uint4& v, int i) {
-    constexpr int PER = 4 / (int)sizeof(TN);  // labels per 32-bit word
-    constexpr int BITS = 8 * (int)sizeof(TN);
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-    return (w[i / PER] >> ((i % PER) * BITS)) & (uint32_t)(TN)~(TN)0;
-}
-
-// elements in front of the first 16-byte boundary of `out`
-__device__ __forceinline__ int64_t head_elements(const void* out, int elem_bytes, int64_t len) {
-    const int64_t head = (int64_t)(((16u - (uint32_t)((uintptr_t)out & 15u)) & 15u) / (uint32_t)elem_bytes);
-    return head < len ? head : len;
-}
 
 // uint32 -> TN.  `over` collects the OR of everything read: a value above typemax(TN) = 2^B - 1 sets a bit above B, and values
 // that fit never do
@@ -102,14 +82,6 @@ labels_widen_kernel(int64_t len, const TN* __restrict__ in, uint32_t* __restrict
                                               narrow_piece_get<TN>(v, 4 * q + 2), narrow_piece_get<TN>(v, 4 * q + 3));
     }
     for (int64_t e = head + nvec * K + t; e < len; e += stride) out[e] = (uint32_t)in[e];
-}
-
-// a grid-stride pass over `pieces` 16-byte pieces: at most 8 workgroups of 256 per CU
-inline int stream_grid(int64_t pieces, int num_cus) {
-    int64_t g = (pieces + 255) / 256;
-    const int64_t cap = (int64_t)(num_cus > 0 ? num_cus : 256) * 8;
-    if (g > cap) g = cap;
-    return (int)(g < 1 ? 1 : g);
 }
 
 template <typename TN>

@@ -367,4 +367,69 @@ function eigen_decomposition_batched(P::HIPPartition, count::Integer; atol=1e-12
     return (status=st, neig=ne, nclasses=nc)
 end
 
+# ---- the agreement of independent restarts (SURVEY 8e): sdpsr_comm_*, sdpsr_agree_partitions,
+# sdpsr_agree_block_diagonalization.  One process per GPU; `unique_id()` is made by one rank and distributed by the caller
+# (MPI.jl, Distributed, a file).  EVERY RANK MUST MAKE THE SAME SEQUENCE OF COLLECTIVE CALLS; the library adds no time-out. ----
+unique_id() = (id = zeros(UInt8, 128);
+               st = ccall((:sdpsr_comm_unique_id, libsdpsr), Cint, (Ptr{UInt8},), id);
+               st == 0 || throw(StatusError(st, "sdpsr_comm_unique_id (can librccl.so.1 be opened?)")); id)
+mutable struct Comm
+    handle::Ptr{Cvoid}
+    ctx::Context
+    function Comm(world::Integer, rank::Integer, id::Vector{UInt8}; cx::Context=ctx())   # collective
+        length(id) == 128 || throw(ArgumentError("the unique id has 128 bytes"))
+        h = Ref{Ptr{Cvoid}}(C_NULL)
+        check(cx, ccall((:sdpsr_comm_create, libsdpsr), Cint, (Ptr{Cvoid}, Int32, Int32, Ptr{UInt8}, Ref{Ptr{Cvoid}}),
+                        cx.handle, world, rank, id, h))
+        return new(h[], cx)   # (no finalizer: the comm goes before its ctx, and destroying it is the caller's collective-free call)
+    end
+end
+Base.close(c::Comm) = (c.handle != C_NULL && ccall((:sdpsr_comm_destroy, libsdpsr), Cint, (Ptr{Cvoid},), c.handle); c.handle = C_NULL; nothing)
+comm_rank(c::Comm) = Int(ccall((:sdpsr_comm_rank, libsdpsr), Cint, (Ptr{Cvoid},), c.handle))
+comm_world(c::Comm) = Int(ccall((:sdpsr_comm_world, libsdpsr), Cint, (Ptr{Cvoid},), c.handle))
+_handle(c::Comm) = c.handle
+_handle(::Nothing) = C_NULL
+_ctx(c::Comm) = c.ctx
+_ctx(::Nothing) = ctx()
+
+# The partitions of this rank's restarts (and, with a comm, of every other rank's) end as ONE partition: when they differ --
+# `==`, partitions.jl:16-17, by checksum -- every one of `ps` is overwritten with their meet, refine! (partitions.jl:62-66) folded
+# over the valid restarts.  valid[i] = false: restart i holds no partition (its status was not 0, 2 or 3); it is not read and
+# receives the result.  Returns true when a meet was needed.  More than typemax(T) classes: InexactError, nothing written.
+# Block images of a restart whose partition the meet changed belong to the OLD partition: blockDiagonalize it again.
+function agree!(ps::Vector{HIPPartition{T}}, comm::Union{Nothing,Comm}=nothing;
+                valid::Union{Nothing,AbstractVector{Bool}}=nothing) where {T<:LabelT}
+    R = length(ps); cx = width!(_ctx(comm), T)
+    pP = Ptr{Cvoid}[pointer(p.matrix) for p in ps]
+    v = valid === nothing ? C_NULL : Int32[x ? 1 : 0 for x in valid]
+    d = Ref{Int64}(0); met = Ref{Int32}(0)
+    st = GC.@preserve ps ccall((:sdpsr_agree_partitions, libsdpsr), Cint,
+                               (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Ptr{Cvoid}}, Ptr{Int32}, Int64, Ref{Int64}, Ref{Int32}, Cint),
+                               cx.handle, _handle(comm), R, pP, v, length(ps[1].matrix), d, met, MEM_HOST)
+    check(cx, st)
+    if met[] != 0
+        for p in ps
+            p.nparts = Int(d[])
+        end
+    end
+    return met[] != 0
+end
+
+# blockDiagonalize's side (eigen_decomposition.jl:264-270, diagonalize.jl:4-9: "try again" -- the tries ran side by side): the
+# lowest rank whose status is 0 wins; returns (winner, its blkSizes), (-1, nothing) when every rank failed.  `capacity`: the same
+# on every rank.  The winner's Q_hat travels with broadcast!.
+function agree_block_sizes(status::Integer, blk_sizes::AbstractVector{<:Integer}, comm::Union{Nothing,Comm}=nothing; capacity::Integer=65536)
+    cx = _ctx(comm); mine = Vector{Int32}(blk_sizes); out = zeros(Int32, capacity)
+    w = Ref{Int32}(-1); nb = Ref{Int32}(0)
+    check(cx, ccall((:sdpsr_agree_block_diagonalization, libsdpsr), Cint,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32, Ptr{Int32}, Ref{Int32}, Ref{Int32}, Ptr{Int32}, Int32),
+                    cx.handle, _handle(comm), status, length(mine), mine, w, nb, out, capacity))
+    return w[] < 0 ? (-1, nothing) : (Int(w[]), Int.(out[1:nb[]]))
+end
+function broadcast!(buf::Array, comm::Comm; root::Integer=0)
+    check(comm.ctx, ccall((:sdpsr_comm_broadcast, libsdpsr), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Cint),
+                          comm.ctx.handle, comm.handle, buf, sizeof(buf), root, MEM_HOST))
+    return buf
+end
+
 end # module
