@@ -448,6 +448,48 @@ int sdpsr_q_hat(sdpsr_ctx* ctx, double* Q_hat, int mem);
    blks: d * sum_sq doubles, class-major, then block, each block column-major s_k x s_k.
    Q_hat (optional, may be NULL): n x sum_s column-major, blocks side by side. */
 int sdpsr_block_images(sdpsr_ctx* ctx, double* blks, double* Q_hat, double* phase_ms, int mem);
+/* basis_image(Q, P; atol), src/diagonalize.jl:64-89 (_constraints :42-50), for a caller's Q_hat and the classes
+   class_first .. class_first + class_count - 1 (1-based): blks[i][k] = Q_k' 1[P==i] Q_k for the classes i of that window.
+   The Q_hat that sdpsr_comm_broadcast delivered to every rank becomes images here, each rank taking its own window; a large
+   output is taken window by window.
+     P            n x n labels at the ctx's label width (sdpsr_set_label_width), in `mem`; must be symmetric;
+     d            dim(P);
+     blk_sizes    host array of nblocks sizes s_k >= 1, sum s_k <= n;
+     Q_hat        n x sum s_k column-major, blocks side by side, in `mem`.  ARBITRARY: neither orthonormal columns nor
+                  invariant subspaces are assumed.  The shortcuts of sdpsr_block_images still run, because their checks
+                  are exact about cross terms: a Q they do not hold for fails the check and gets the projection formula;
+     blks         class_count * sum s_k^2 doubles in `mem`: class-major starting at class_first, then block, each block
+                  column-major (the layout of sdpsr_block_images).  Nothing outside those elements is written;
+     atol         entries below it in absolute value become 0; atol < 0: the reference's default 1e-12 * n; 0: no clamp;
+     route        (may be NULL) what produced the output: SDPSR_BI_ROUTE_COMMUTATIVE .. _CHUNK, or-ed with
+                  SDPSR_BI_ROUTE_REPAIRED when a shortcut recomputed some columns / blocks by the projection formula, with
+                  SDPSR_BI_ROUTE_SHORTCUT_REFUSED when a shortcut ran, failed its check and a kernel route produced everything;
+     phase_ms     (may be NULL) as sdpsr_block_images fills it.
+   opts.basis_image_kernel and SDPSR_FLAG_FULL_BASIS_IMAGE apply as they do to sdpsr_block_images.  On the three kernel routes a
+   window's output equals, bit for bit, the same slice of the full call (every class is summed on its own, in a fixed order);
+   the shortcuts draw a fresh key per call and agree to rounding (their checks accept 2e-10 absolute, as in sdpsr_block_images:
+   meant for columns of norm <= 1; SDPSR_FLAG_FULL_BASIS_IMAGE evaluates the projection formula for everything).
+   The ctx's block diagonalisation (sdpsr_block_sizes / sdpsr_q_hat / sdpsr_block_images) is neither needed nor disturbed.
+   SDPSR_BAD_ARGUMENT, before any kernel and with the ctx usable afterwards: a NULL pointer, n < 1, d < 0, nblocks < 1, some
+   s_k < 1, sum s_k > n, class_count < 0, class_first < 1 or a window that ends beyond d.  class_count == 0 is legal: SDPSR_OK,
+   nothing written, no kernel launched (a split over more ranks than classes).  Found on the device, in the pass that brings
+   the labels in: "partition is not symmetric" and "a label exceeds d" (SDPSR_BAD_ARGUMENT; host blks: nothing is delivered,
+   device blks: the window's contents are unspecified).  Labels outside the window -- of any value -- are read as the skipped
+   class 0 where they are loaded and index nothing.
+   sdpsr_transfer_bytes, host arrays: n^2 * B / 8 + n * sum s_k * 8 bytes up at label width B, class_count * sum s_k^2 * 8 down
+   (the routes' descriptor words are not counted by this entry); device arrays: nothing up, the 8 bytes of the two verdicts down. */
+enum {
+    SDPSR_BI_ROUTE_COMMUTATIVE = 1,
+    SDPSR_BI_ROUTE_BLOCKS = 2,
+    SDPSR_BI_ROUTE_TWO_STAGE = 3,
+    SDPSR_BI_ROUTE_OUTER = 4,
+    SDPSR_BI_ROUTE_CHUNK = 5,
+    SDPSR_BI_ROUTE_REPAIRED = 0x100,
+    SDPSR_BI_ROUTE_SHORTCUT_REFUSED = 0x200
+};
+int sdpsr_basis_image(sdpsr_ctx* ctx, int64_t n, const uint32_t* P, int64_t d, int32_t nblocks, const int32_t* blk_sizes,
+                      const double* Q_hat, int64_t class_first, int64_t class_count, double atol, double* blks, int32_t* route,
+                      double* phase_ms, int mem);
 /* ---- one reduction in one call ---------------------------------------------------------------------
    sdpsr_admissible_subspace followed by sdpsr_block_diagonalize on its result and -- when the images fit the
    caller's buffer -- sdpsr_block_images, with the partition staying on the device and no host synchronisation

@@ -10,7 +10,7 @@ from ._lib import (MEM_DEVICE, MEM_HOST, SQUARE_AUTO, SQUARE_F32, SQUARE_F64, SQ
                    load_library)
 from .api import (BlockDiagonalization, Context, DimensionMismatch, InvalidDecompositionField,  # noqa: F401
                   LabelOverflow, NotConverged, NumericalInconsistency, Partition, SdpsrError,
-                  admissible_setup, admissible_setup_csr, admissible_subspace, csr_arrays, blockDiagonalize, default_context, desymmetrize, unSymmetrize,
+                  admissible_setup, admissible_setup_csr, admissible_subspace, basis_image, class_window, csr_arrays, blockDiagonalize, default_context, desymmetrize, unSymmetrize,
                   diagonalize, dim, eigen_decomposition, jordan_reduce_batch, Problem, eigen_decomposition_batched, fill, labels_convert, partition_checksum, randomize, reduce_constraints,
                   reduce_constraints_csr,
                   refine, relabel_keys)

@@ -38,6 +38,9 @@ FLAG_COUPLING_ON_HOST = 1 << 13
 FLAG_SYTRD_ONE_LAUNCH = 1 << 14
 FLAG_WAIT_FOR_EVERY_VERDICT = 1 << 15
 BASIS_IMAGE_KERNELS = {"auto": 0, "two_stage": 1, "outer": 2, "chunk": 3}
+# sdpsr_basis_image: *route
+BI_ROUTE_COMMUTATIVE, BI_ROUTE_BLOCKS, BI_ROUTE_TWO_STAGE, BI_ROUTE_OUTER, BI_ROUTE_CHUNK = 1, 2, 3, 4, 5
+BI_ROUTE_REPAIRED, BI_ROUTE_SHORTCUT_REFUSED = 0x100, 0x200
 REFINE_PATHS = {"auto": 0, "hash": 1, "sort": 2, "bucket": 3, "no_mid": 4, "mid_no_first": 6}
 
 # sdpsr_set_label_width: the element type of a label array at each interface width (the reference's Partition{T})
@@ -154,6 +157,7 @@ def load_library():
         "sdpsr_block_sizes": (C.c_int, [vp, vp]),
         "sdpsr_q_hat": (C.c_int, [vp, vp, C.c_int]),
         "sdpsr_block_images": (C.c_int, [vp, vp, vp, vp, C.c_int]),
+        "sdpsr_basis_image": (C.c_int, [vp, i64, vp, i64, i32, vp, vp, i64, i64, dbl, vp, pi32, vp, C.c_int]),
         "sdpsr_eigen_decomposition": (C.c_int, [vp, i64, vp, i64, dbl, pi32, pi32, C.c_int]),
         "sdpsr_block_diagonalize_complex": (C.c_int, [vp, i64, vp, i64, dbl, vp, pi64, pi32, pi64, pi64, C.c_int]),
         "sdpsr_block_sizes_complex": (C.c_int, [vp, vp]),

@@ -910,6 +910,93 @@ def blockDiagonalize(P, verbose=False, epsilon=RTOL_DEFAULT, complex=False, ctx=
     return BlockDiagonalization([int(s) for s in sizes], out, Q, ms)
 
 
+def class_window(d, parts, index):
+    """``(first, count)``: window ``index`` (0-based) of ``parts`` contiguous windows that tile the classes ``1..d`` in
+    order, their sizes differing by at most one (the larger ones first); ``count == 0`` -- with ``first`` where the window
+    would start -- once ``parts > d`` leaves nothing for this index.  Pure arithmetic: every rank computes its own."""
+    d, parts, index = int(d), int(parts), int(index)
+    if d < 0 or parts < 1 or not 0 <= index < parts:
+        raise ValueError(f"class_window(d={d}, parts={parts}, index={index}): need d >= 0, parts >= 1, 0 <= index < parts")
+    q, r = divmod(d, parts)
+    return 1 + index * q + min(index, r), q + (1 if index < r else 0)
+
+
+def _q_hat_arg(Q_hat, n):
+    """(matrix, sizes) from a list of n x s_k arrays or a pair (matrix, blkSizes); NumPy or torch, checked against n."""
+    if isinstance(Q_hat, tuple) and len(Q_hat) == 2 and getattr(Q_hat[0], "ndim", 0) == 2 and getattr(Q_hat[1], "ndim", 1) == 1:
+        M, sizes = Q_hat[0], [int(s) for s in Q_hat[1]]  # (matrix, blkSizes): the second member is a flat list of sizes
+    else:
+        blocks = list(Q_hat)
+        if not blocks:
+            raise ValueError("basis_image: Q_hat has no blocks")
+        for q in blocks:
+            if getattr(q, "ndim", 0) != 2 or q.shape[0] != n:
+                raise ValueError(f"basis_image: every block of Q_hat is an n x s_k matrix with n = {n} rows, got shape "
+                                 f"{tuple(getattr(q, 'shape', ()))}")
+        sizes = [int(q.shape[1]) for q in blocks]
+        if _is_torch(blocks[0]):
+            import torch
+            M = torch.cat(list(blocks), dim=1)
+        else:
+            M = np.concatenate([np.asarray(q, dtype=np.float64) for q in blocks], axis=1)
+    if M.shape[0] != n:
+        raise ValueError(f"basis_image: Q_hat has {M.shape[0]} rows, the partition is {n} x {n}")
+    if not sizes or any(s < 1 for s in sizes):
+        raise ValueError(f"basis_image: block sizes must be >= 1, got {sizes}")
+    if sum(sizes) != M.shape[1]:
+        raise ValueError(f"basis_image: the block sizes {sizes} sum to {sum(sizes)}, Q_hat has {M.shape[1]} columns")
+    if sum(sizes) > n:
+        raise ValueError(f"basis_image: the block sizes sum to {sum(sizes)} > n = {n}")
+    return M, sizes
+
+
+def basis_image(Q_hat, P, classes=None, atol=None, ctx=None, return_route=False):
+    """``basis_image(Q, P; atol)`` (src/diagonalize.jl:64-89) for a caller's ``Q_hat`` and a window of classes
+    (``sdpsr_basis_image``): ``blks[i][k] = Q_k' 1[P == first + i] Q_k``.
+
+    ``Q_hat``: a list of n x s_k arrays, as ``blockDiagonalize`` / ``diagonalize`` return them, or a pair
+    ``(matrix, blkSizes)`` with the blocks side by side; any real matrices, not only those of this library.
+    ``classes = (first, count)`` (1-based, e.g. from ``class_window``); ``None``: every class.  ``atol=None``: the
+    reference's ``1e-12 * n``; ``0`` clamps nothing.  Returns the window's images nested as ``blks`` of
+    ``blockDiagonalize`` (``count`` rows); with ``return_route=True`` the pair ``(blks, route)``, ``route`` as
+    ``SDPSR_BI_ROUTE_*`` of include/sdpsr.h.  With a device-resident partition (torch) ``Q_hat`` is taken as, or moved
+    into, torch tensors of that device and the images are views of one device tensor.  The context's own block
+    diagonalisation is not touched."""
+    ctx = _ctx(ctx)
+    n = P.shape[0]
+    d = int(P.nparts)
+    M, sizes = _q_hat_arg(Q_hat, n)
+    first, count = (1, d) if classes is None else (int(classes[0]), int(classes[1]))
+    if count < 0 or (count > 0 and (first < 1 or first + count - 1 > d)):
+        raise ValueError(f"basis_image: classes = ({first}, {count}) is not a window of 1..{d}")
+    S = sum(s * s for s in sizes)
+    lab, mem = _labels_arg(P, ctx)
+    route = C.c_int32(0)
+    if mem == L.MEM_DEVICE:
+        import torch
+        Mt = M if _is_torch(M) else torch.from_numpy(np.asarray(M, dtype=np.float64))
+        q = Mt.to(device=lab.device, dtype=torch.float64).t().contiguous().view(-1)  # column-major
+        blks = torch.empty(max(count * S, 1), dtype=torch.float64, device=lab.device)
+        ctx.wait_for(lab, q, blks)
+    else:
+        Mh = np.asarray(M.cpu()) if _is_torch(M) else M
+        q = np.ascontiguousarray(np.asarray(Mh, dtype=np.float64).ravel(order="F"))
+        blks = np.empty(max(count * S, 1), dtype=np.float64)
+    sz = np.asarray(sizes, dtype=np.int32)
+    ctx.check(ctx._lib.sdpsr_basis_image(ctx._h, n, _ptr(lab), d, len(sizes), _ptr(sz), _ptr(q), first, count,
+                                         -1.0 if atol is None else float(atol), _ptr(blks), C.byref(route), None, mem))
+    blks = blks[:count * S].reshape(count, S)
+    out = []
+    for i in range(count):
+        row, off = [], 0
+        for s in sizes:
+            b = blks[i, off:off + s * s]
+            row.append(b.reshape(s, s).t() if _is_torch(b) else b.reshape(s, s, order="F"))
+            off += s * s
+        out.append(row)
+    return (out, route.value) if return_route else out
+
+
 def _block_diagonalize_complex(P, verbose, epsilon, ctx, retries):
     """``blockDiagonalize(ComplexF64, P)`` (src/compat.jl:46-68, src/diagonalize.jl:13-28): the
     block images are indexed by the classes of the DESYMMETRIZED partition (src/compat.jl:54-57),

@@ -1,5 +1,5 @@
 // blockDiagonalize (src/compat.jl:46-68): diagonalize + check_block_sizes (src/diagonalize.jl:1-40),
-// then basis_image (:42-89).  Entry points sdpsr_block_diagonalize / _block_sizes / _q_hat / _block_images.
+// then basis_image (:42-89).  Entry points sdpsr_block_diagonalize / _block_sizes / _q_hat / _block_images / sdpsr_basis_image.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -116,25 +116,33 @@ int block_diagonalize_impl(sdpsr_ctx* c, int64_t n, const uint32_t* P, int64_t d
 }
 
 // basis_image (src/diagonalize.jl:42-89) as routes over one state: two shortcuts that check themselves, then one of three
-// kernels for the projection formula
+// kernels for the projection formula.  The state is built from explicit arguments -- the labels, Q_hat row-major, the block
+// sizes, a window of classes, atol, the output -- so that sdpsr_block_images (the ctx's own Q_hat, the window (1, d)) and
+// sdpsr_basis_image (a caller's Q_hat, any window) are two callers of the same routes.  Nothing below assumes anything about
+// Q: the shortcuts' checks are exact about cross terms (kernels_blockdiag.hip), so a Q that is not invariant fails them.
 struct BasisImage {
     enum Shortcut { FALL_THROUGH, DONE, DONE_SYNCED };  // DONE_SYNCED: the verdict's host wait was the last thing on the stream
     enum Route { TWO_STAGE, OUTER, CHUNK };
     sdpsr_ctx* c;
     hipStream_t s;
-    int64_t n, d, S1, S, len;
-    uint32_t* L;
-    double *Qrm = nullptr, *out = nullptr;
-    double atol;  // basis_image default atol (src/diagonalize.jl:67)
+    int64_t n, d, S1, S, len;  // d: the number of classes of the window, i.e. of output slabs
+    uint32_t first;            // the window's first class (1-based): labels are read as window_label(l, first, d)
+    const uint32_t* L;
+    const double* Qrm;
+    double* out;  // the window's d * S doubles
+    double atol;
+    const std::vector<int32_t>& sizes;
     BlockLayout lay;
+    bool own_labels = false;  // the ctx's own labels and the window (1, d): the shortcuts' class sums use the labels as they are
+    int route_flags = 0;      // SDPSR_BI_ROUTE_*: what produced `out`
     // sources of asynchronous uploads (chunk)
     std::vector<int32_t> desc;
     std::vector<int64_t> chunk_ptr, cb, ce;
 
-    explicit BasisImage(sdpsr_ctx* ctx)
-        : c(ctx), s(ctx->stream), n(ctx->bd_n), d(ctx->bd_d), S1(ctx->bd_sum_s), S(ctx->bd_sum_sq), len(ctx->bd_n * ctx->bd_n),
-          L(ctx->bd_labels_ext ? const_cast<uint32_t*>(ctx->bd_labels_ext) : (uint32_t*)ctx_buf(ctx, "bd_labels", (size_t)ctx->bd_n * ctx->bd_n * 4)),
-          atol(1e-12 * (double)ctx->bd_n), lay(block_layout(ctx->bd_sizes)) {}
+    BasisImage(sdpsr_ctx* ctx, int64_t n_, const uint32_t* labels, const double* Q_rowmajor, const std::vector<int32_t>& blk_sizes, int64_t sum_s,
+               int64_t sum_sq, int64_t class_first, int64_t class_count, double atol_, double* out_)
+        : c(ctx), s(ctx->stream), n(n_), d(class_count), S1(sum_s), S(sum_sq), len(n_ * n_), first((uint32_t)class_first), L(labels),
+          Qrm(Q_rowmajor), out(out_), atol(atol_), sizes(blk_sizes), lay(block_layout(blk_sizes)) {}
 
     bool shortcuts_allowed() const { return c->opts.basis_image_kernel == 0 && !(c->opts.flags & SDPSR_FLAG_FULL_BASIS_IMAGE) && d >= 1 && n >= 64; }
     uint32_t* verdict_words(size_t count);
@@ -163,11 +171,12 @@ int BasisImage::shortcut_commutative(Shortcut& r) {
     double* ws = (double*)ctx_buf(c, "bi_comm_ws", basis_image_commutative_workspace_doubles(n, d) * 8);
     uint32_t* hv = verdict_words((size_t)S1);
     if (!ws || !hv) return SDPSR_OUT_OF_MEMORY;
-    if (!launch_basis_image_commutative(s, n, d, S1, L, Qrm, next_key(c), atol, 2e-10, ws, out, hv)) return SDPSR_OK;
+    if (!launch_basis_image_commutative(s, n, d, first, S1, L, Qrm, next_key(c), atol, 2e-10, ws, out, hv, own_labels)) return SDPSR_OK;
     HIP_TRY(c, ctx_sync_stream(c, s));
     HIP_TRY(c, hipGetLastError());
     const uint32_t nbad = hv[0];
     if (nbad == 0) r = DONE_SYNCED;
+    route_flags = nbad == 0 ? SDPSR_BI_ROUTE_COMMUTATIVE : SDPSR_BI_ROUTE_SHORTCUT_REFUSED;
     if (nbad == 0 || nbad > 8) {
         if (nbad && dbg_on()) fprintf(stderr, "[sdpsr] basis_image: invariance check failed for %u columns, projection formula instead\n", nbad);
         return SDPSR_OK;
@@ -179,9 +188,9 @@ int BasisImage::shortcut_commutative(Shortcut& r) {
         if (hv[1 + k2]) badk.push_back((int)k2);
     bool done = true;
     for (size_t q = 0; q < badk.size() && done; q += 2)
-        done = launch_basis_image_fix_pair(s, n, d, S1, L, Qrm, badk[q], badk[q + 1 < badk.size() ? q + 1 : q], atol, ws, out);
+        done = launch_basis_image_fix_pair(s, n, d, first, S1, L, Qrm, badk[q], badk[q + 1 < badk.size() ? q + 1 : q], atol, ws, out, own_labels);
     if (dbg_on()) fprintf(stderr, "[sdpsr] basis_image: invariance check failed for %u column(s), projection formula for those\n", nbad);
-    if (done) r = DONE;
+    if (done) r = DONE, route_flags = SDPSR_BI_ROUTE_COMMUTATIVE | SDPSR_BI_ROUTE_REPAIRED;
     return SDPSR_OK;
 }
 
@@ -200,19 +209,20 @@ int BasisImage::shortcut_blocks(Shortcut& r) {
     int st = h2d_sync(c, d_cs, lay.colsz.data(), (size_t)2 * nb * 4);
     if (!st) st = h2d_sync(c, d_off, lay.off.data(), (size_t)nb * 8);
     if (st) return st;
-    if (!launch_basis_image_blocks(s, n, d, S1, S, nb, d_cs, d_cs + nb, d_off, L, Qrm, next_key(c), -1, atol, 2e-10, ws, out, hv)) return SDPSR_OK;
+    if (!launch_basis_image_blocks(s, n, d, first, S1, S, nb, d_cs, d_cs + nb, d_off, L, Qrm, next_key(c), -1, atol, 2e-10, ws, out, hv, own_labels)) return SDPSR_OK;
     HIP_TRY(c, ctx_sync_stream(c, s));
     HIP_TRY(c, hipGetLastError());
     const uint32_t nbad = hv[0];
+    route_flags = nbad == 0 ? SDPSR_BI_ROUTE_BLOCKS : SDPSR_BI_ROUTE_SHORTCUT_REFUSED;
     if (nbad == 0) {
         r = DONE_SYNCED;
         return SDPSR_OK;
     }
     bool done = nbad <= 4;
     for (int k2 = 0; k2 < nb && done; ++k2)
-        if (hv[1 + k2]) done = launch_basis_image_blocks(s, n, d, S1, S, nb, d_cs, d_cs + nb, d_off, L, Qrm, 0, k2, atol, 2e-10, ws, out, nullptr);
+        if (hv[1 + k2]) done = launch_basis_image_blocks(s, n, d, first, S1, S, nb, d_cs, d_cs + nb, d_off, L, Qrm, 0, k2, atol, 2e-10, ws, out, nullptr, own_labels);
     if (dbg_on()) fprintf(stderr, "[sdpsr] basis_image: invariance check failed for %u block(s)%s\n", nbad, done ? ", projection formula for those" : ", two-stage kernels instead");
-    if (done) r = DONE;
+    if (done) r = DONE, route_flags = SDPSR_BI_ROUTE_BLOCKS | SDPSR_BI_ROUTE_REPAIRED;
     return SDPSR_OK;
 }
 
@@ -230,13 +240,13 @@ BasisImage::Route BasisImage::route() const {
 
 // two-stage form (class sums per row, then the s_k x s_k dots)
 int BasisImage::two_stage() {
-    desc = pair_descriptor(c->bd_sizes, S);
+    desc = pair_descriptor(sizes, S);
     int32_t* d_desc = (int32_t*)ctx_buf(c, "bi_desc", (size_t)2 * S * 4);
     double* Tb = (double*)ctx_buf(c, "bi_T", (size_t)d * n * S1 * 8);
     if (!d_desc || !Tb) return SDPSR_OUT_OF_MEMORY;
     const int st = h2d_sync(c, d_desc, desc.data(), (size_t)2 * S * 4);
     if (st) return st;
-    launch_basis_image_two_stage(s, n, d, S1, S, L, Qrm, Tb, d_desc, d_desc + S, atol, out);
+    launch_basis_image_two_stage(s, n, d, first, S1, S, L, Qrm, Tb, d_desc, d_desc + S, atol, out);
     return SDPSR_OK;
 }
 
@@ -268,7 +278,7 @@ int BasisImage::chunk(const uint32_t* ent, const std::vector<int64_t>& class_ptr
         }
     }
     chunk_ptr[d] = (int64_t)cb.size();
-    desc = pair_descriptor(c->bd_sizes, S);
+    desc = pair_descriptor(sizes, S);
     const int64_t nch = (int64_t)cb.size();
     int64_t* d_chunk_ptr = (int64_t*)ctx_buf(c, "bi_chunk_ptr", (d + 1) * 8);
     int64_t* d_cb = (int64_t*)ctx_buf(c, "bi_cb", std::max<int64_t>(nch, 1) * 8);
@@ -298,11 +308,12 @@ int BasisImage::run(bool& done_synced) {
     done_synced = !st && r == DONE_SYNCED;
     if (st || r != FALL_THROUGH) return st;  // (out is complete)
     const Route kind = route();
+    route_flags = (route_flags & SDPSR_BI_ROUTE_SHORTCUT_REFUSED) | (kind == TWO_STAGE ? SDPSR_BI_ROUTE_TWO_STAGE : kind == OUTER ? SDPSR_BI_ROUTE_OUTER : SDPSR_BI_ROUTE_CHUNK);
     if (kind == TWO_STAGE) return two_stage();
-    // _constraints(P): entries grouped by class (src/diagonalize.jl:42-50)
+    // _constraints(P): entries grouped by class (src/diagonalize.jl:42-50); the keys are window-relative
     uint32_t* ent = nullptr;
-    std::vector<int64_t> class_ptr;  // size d+2: class_ptr[l]..class_ptr[l+1] = label l
-    st = sort_entries_by_label(c, len, d, L, &ent, class_ptr);
+    std::vector<int64_t> class_ptr;  // size d+2: class_ptr[l]..class_ptr[l+1] = class first + l - 1 (l = 0: everything outside the window)
+    st = sort_entries_by_label(c, len, d, L, &ent, class_ptr, first);
     if (st) return st;
     return kind == OUTER ? outer(ent, class_ptr) : chunk(ent, class_ptr);
 }
@@ -342,14 +353,18 @@ int sdpsr_block_images(sdpsr_ctx* c, double* blks, double* Q_hat, double* phase_
     if (!blks) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "null pointer");
     hipStream_t s = c->stream;
     TotalEvents ev_total(phase_ms != nullptr, s);
-    BasisImage bi(c);  // lives until the one host wait below: its host vectors are the sources of asynchronous uploads
-    const int64_t n = bi.n, d = bi.d, S1 = bi.S1, S = bi.S;
+    const int64_t n = c->bd_n, d = c->bd_d, S1 = c->bd_sum_s, S = c->bd_sum_sq;
     int st = SDPSR_OK;
+    const uint32_t* L = c->bd_labels_ext ? c->bd_labels_ext : (const uint32_t*)ctx_buf(c, "bd_labels", (size_t)n * n * 4);
     double* Qhat = (double*)ctx_buf(c, "bd_qhat", (size_t)n * S1 * 8);
-    bi.Qrm = (double*)ctx_buf(c, "bd_qrm", (size_t)n * S1 * 8);
-    bi.out = out_dev(c, "bd_blks", blks, (size_t)d * S, mem, &st);
-    if (st || !bi.L || !Qhat || !bi.Qrm) return st ? st : SDPSR_OUT_OF_MEMORY;
-    launch_transpose_to_rowmajor(s, n, S1, Qhat, bi.Qrm);
+    double* Qrm = (double*)ctx_buf(c, "bd_qrm", (size_t)n * S1 * 8);
+    double* out = out_dev(c, "bd_blks", blks, (size_t)d * S, mem, &st);
+    if (st || !L || !Qhat || !Qrm) return st ? st : SDPSR_OUT_OF_MEMORY;
+    // the ctx's own state, every class, basis_image's default atol (src/diagonalize.jl:67); lives until the one host wait
+    // below: its host vectors are the sources of asynchronous uploads
+    BasisImage bi(c, n, L, Qrm, c->bd_sizes, S1, S, 1, d, 1e-12 * (double)n, out);
+    bi.own_labels = true;
+    launch_transpose_to_rowmajor(s, n, S1, Qhat, Qrm);
     bool done_synced = false;  // the stream was synchronised by a shortcut's verdict and nothing was enqueued since
     st = bi.run(done_synced);
     if (st) return st;
@@ -365,6 +380,80 @@ int sdpsr_block_images(sdpsr_ctx* c, double* blks, double* Q_hat, double* phase_
         if (mem != SDPSR_MEM_DEVICE) c->d2h_bytes += (size_t)n * S1 * 8;
     }
     if (!(done_synced && mem == SDPSR_MEM_DEVICE && !Q_hat)) HIP_TRY(c, ctx_sync_stream(c, s));
+    if (phase_ms) {
+        const float ms = ev_total.stop(s);
+        for (int i = 0; i < SDPSR_T_COUNT; ++i) phase_ms[i] = 0;
+        phase_ms[SDPSR_T_IMAGE] = ms;
+        phase_ms[SDPSR_T_TOTAL] = ms;
+    }
+    return SDPSR_OK;
+}
+
+// basis_image(Q, P; atol) (src/diagonalize.jl:64-89) of a caller's Q_hat for a window of classes.  Buffers of its own for the
+// labels ("bie_labels"), Q_hat and its row-major copy: the ctx's block diagonalisation is not touched.
+int sdpsr_basis_image(sdpsr_ctx* c, int64_t n, const uint32_t* P, int64_t d, int32_t nblocks, const int32_t* blk_sizes, const double* Q_hat,
+                      int64_t class_first, int64_t class_count, double atol, double* blks, int32_t* route, double* phase_ms, int mem) {
+    CHECK_CTX(c);
+    if (!P || !blk_sizes || !Q_hat || !blks) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "null pointer");
+    if (n < 1 || d < 0 || nblocks < 1) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "bad arguments: n < 1, d < 0 or nblocks < 1");
+    int64_t S1 = 0, S = 0;
+    for (int32_t k = 0; k < nblocks; ++k) {
+        if (blk_sizes[k] < 1) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "a block size is < 1");
+        S1 += blk_sizes[k];
+        S += (int64_t)blk_sizes[k] * blk_sizes[k];
+        if (S1 > n) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "the block sizes sum to more than n");
+    }
+    if (class_count < 0) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "class_count < 0");
+    if (class_count > 0 && (class_first < 1 || class_first > d || class_count > d - class_first + 1))
+        return ctx_fail(c, SDPSR_BAD_ARGUMENT, "the window of classes is not inside 1 .. d");
+    int st = check_len(c, n * n);
+    if (st) return st;
+    if (route) *route = 0;
+    if (class_count == 0) return SDPSR_OK;
+    if (!c->pinned_small) return SDPSR_OUT_OF_MEMORY;
+    hipStream_t s = c->stream;
+    const int64_t len = n * n;
+    const size_t out_count = (size_t)class_count * S;
+    const uint64_t h2d0 = c->h2d_bytes, d2h0 = c->d2h_bytes;
+    TotalEvents ev_total(phase_ms != nullptr, s);
+    uint32_t* L = (uint32_t*)ctx_buf(c, "bie_labels", (size_t)len * 4);
+    uint32_t* flag = (uint32_t*)ctx_buf(c, "bie_flag", 64);
+    double* Qrm = (double*)ctx_buf(c, "bie_qrm", (size_t)n * S1 * 8);
+    if (!L || !flag || !Qrm) return SDPSR_OUT_OF_MEMORY;
+    const double* Qcm = in_dev(c, "bie_qhat", Q_hat, (size_t)n * S1, mem, &st);
+    double* out = out_dev(c, "bie_blks", blks, out_count, mem, &st);
+    if (st || !Qcm || !out) return st ? st : SDPSR_OUT_OF_MEMORY;
+    // the labels come in and are judged in the same pass: symmetry (the routes read one triangle) and "a label exceeds d"
+    HIP_TRY(c, hipMemsetAsync(flag, 0, 8, s));
+    const uint32_t dmax = (uint32_t)std::min<int64_t>(d, 0xFFFFFFFFll);
+    if (mem == SDPSR_MEM_DEVICE && c->label_width == 32) {
+        launch_copy_check_labels(s, n, P, L, dmax, flag);
+    } else {  // host arrays and narrow labels arrive through labels_fetch; the check runs over them in place
+        st = labels_fetch(c, L, P, (size_t)len, mem);
+        if (st) return st;
+        launch_copy_check_labels(s, n, L, L, dmax, flag);
+    }
+    uint32_t* verdict = c->pinned_small + PINNED_SMALL_LABEL_CHECK.first;
+    HIP_TRY(c, hipMemcpyAsync(verdict, flag, 8, hipMemcpyDeviceToHost, s));
+    launch_transpose_to_rowmajor(s, n, S1, Qcm, Qrm);
+    const std::vector<int32_t> sizes(blk_sizes, blk_sizes + nblocks);
+    BasisImage bi(c, n, L, Qrm, sizes, S1, S, class_first, class_count, atol < 0 ? 1e-12 * (double)n : atol, out);  // lives until the last host wait
+    bool done_synced = false;
+    st = bi.run(done_synced);
+    if (st) return st;
+    HIP_TRY(c, hipGetLastError());
+    if (!done_synced) HIP_TRY(c, ctx_sync_stream(c, s));
+    // what this entry moved: the arrays and the verdicts (the routes' descriptor words are not part of its account)
+    c->h2d_bytes = h2d0 + (mem != SDPSR_MEM_DEVICE ? (uint64_t)len * (c->label_width / 8) + (uint64_t)n * S1 * 8 : 0);
+    c->d2h_bytes = d2h0 + (mem != SDPSR_MEM_DEVICE ? 0 : 8);
+    if (verdict[0]) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "basis_image: partition is not symmetric");
+    if (verdict[1]) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "basis_image: a label exceeds d = dim(P)");
+    if (mem != SDPSR_MEM_DEVICE) {
+        HIP_TRY(c, hipMemcpyAsync(blks, out, out_count * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, ctx_sync_stream(c, s));
+        c->d2h_bytes += out_count * 8;
+    }
+    if (route) *route = bi.route_flags;
     if (phase_ms) {
         const float ms = ev_total.stop(s);
         for (int i = 0; i < SDPSR_T_COUNT; ++i) phase_ms[i] = 0;

@@ -407,6 +407,14 @@ void launch_inv_norm(hipStream_t s, int64_t m, const double* v, double* out) {
 // the entries, keep BI_OT accumulators in registers and reduce them across the workgroup.
 // Chunk partials are summed in chunk order by a second kernel (bitwise reproducible).
 // ---------------------------------------------------------------------------
+// A window of classes first .. first + cnt - 1: label l counts as class l - first + 1 inside it and as the skipped class 0
+// outside (unsigned wrap-around: one comparison).  Applied where a label is loaded, so every table behind it has cnt + 1
+// entries and no label value can index past them.  (first, cnt) = (1, d) is the identity on the labels 0 .. d.
+__device__ __forceinline__ uint32_t window_label(uint32_t l, uint32_t first, uint32_t cnt) {
+    const uint32_t t = l - first;
+    return t < cnt ? t + 1u : 0u;
+}
+
 constexpr int BI_THREADS = 256;
 constexpr int BI_CHUNK = 4096;
 constexpr int BI_OT = 16;
@@ -693,8 +701,9 @@ void launch_basis_image_outer(hipStream_t s, int64_t n, int64_t d, int64_t S1, i
 // ---------------------------------------------------------------------------
 template <int VEC>
 __global__ void __launch_bounds__(64)
-basis_image_rows_kernel(int n, int d, int S1, const uint32_t* __restrict__ L, const double* __restrict__ Qrm,
+basis_image_rows_kernel(int n, int d, uint32_t first, int S1, const uint32_t* __restrict__ L, const double* __restrict__ Qrm,
                         double* __restrict__ T, int lower) {
+    // d: the number of classes of the window that starts at class `first` (window_label); T has d slabs
     // One wave per row r.  The n labels of column r of L (== row r, symmetric partition) are
     // first sorted by class with a STABLE counting sort in LDS (ranks inside a 64-entry chunk
     // come from ballots over the distinct labels of the chunk), then every class segment is
@@ -728,7 +737,7 @@ basis_image_rows_kernel(int n, int d, int S1, const uint32_t* __restrict__ L, co
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const bool valid = (c0 + q * 64 + lane) < n;
-            const uint32_t l = lq[q];
+            const uint32_t l = window_label(lq[q], first, (uint32_t)d);  // (0 stays 0)
             unsigned long long m = __ballot(valid);
             for (int b = 0; b < nbits; ++b) {
                 const bool bit = (l >> b) & 1u;
@@ -762,7 +771,7 @@ basis_image_rows_kernel(int n, int d, int S1, const uint32_t* __restrict__ L, co
         for (int q = 0; q < 4; ++q) {
             const int c = c0 + q * 64 + lane;
             const bool valid = c < n;
-            const uint32_t l = lq[q];
+            const uint32_t l = window_label(lq[q], first, (uint32_t)d);
             unsigned long long m = __ballot(valid);
             for (int b = 0; b < nbits; ++b) {
                 const bool bit = (l >> b) & 1u;
@@ -789,7 +798,7 @@ basis_image_rows_kernel(int n, int d, int S1, const uint32_t* __restrict__ L, co
     const int groups = 64 / sub;
     const int jl = lane % sub, g = lane / sub;  // g == groups: idle lanes behind the last whole group
     const vec_t* __restrict__ Qv = reinterpret_cast<const vec_t*>(Qrm);
-    const uint32_t diag = lower ? col[r] : 0u;
+    const uint32_t diag = lower ? window_label(col[r], first, (uint32_t)d) : 0u;
     for (int j0 = 0; j0 < cols; j0 += sub) {
         const int j = j0 + jl;
         const bool act = j < cols && g < groups;
@@ -885,7 +894,7 @@ bool basis_image_two_stage_fits(int64_t n, int64_t d, int64_t S1) {
 // then lane i adds the 64 tables of class i in lane order: fixed order, reproducible.
 // Workgroup = 4 waves = 4 rows at a time, sharing x.
 __global__ void __launch_bounds__(256)
-class_sums_small_d_kernel(int n, int d, int tstride, const uint32_t* __restrict__ L, const double* __restrict__ x,
+class_sums_small_d_kernel(int n, int d, uint32_t first, int tstride, const uint32_t* __restrict__ L, const double* __restrict__ x,
                           double* __restrict__ out, int64_t ldo) {
     extern __shared__ __attribute__((aligned(16))) double cs_smem[];
     double* sx = cs_smem;                                  // [n]
@@ -928,7 +937,7 @@ class_sums_small_d_kernel(int n, int d, int tstride, const uint32_t* __restrict_
             vv[u] = c < n ? sx[c] : 0.0;
         }
 #pragma unroll
-        for (int u = 0; u < 8; ++u) atomicAdd(&mine[lab[u]], vv[u]);
+        for (int u = 0; u < 8; ++u) atomicAdd(&mine[window_label(lab[u], first, (uint32_t)d)], vv[u]);  // (the window where the label is used: the fetch stays a pure load)
         if (bb == bpr - 1) {
             const int r = blockIdx.x * 4 + rr * rows_per_round + wave;
             __syncthreads();
@@ -1030,9 +1039,12 @@ bi_contract_pair_kernel(int n, int S1, const double* __restrict__ Qrm, const dou
 // tables hold double2 (one 16-byte read-modify-write per entry); X comes from global memory (64 KiB at
 // N = 4096, L2-resident, coalesced along c) and is prefetched with the labels.  W waves per workgroup:
 // W * 64 * tstride * 16 bytes of LDS.
-template <int W>
+// WIN = false: the labels are used as they are -- the window is (1, d) and every label is known to be <= d (the ctx's own
+// labels in sdpsr_block_images: its kernel is what it was, measured 2 % faster at ER(7) (x) K_72 than with the mapping's
+// three VALU operations per label).  WIN = true: a caller's labels, any window.
+template <int W, bool WIN>
 __global__ void __launch_bounds__(64 * W)
-class_sums2_kernel(int n, int d, int tstride, const uint32_t* __restrict__ L, const double2* __restrict__ X,
+class_sums2_kernel(int n, int d, uint32_t first, int tstride, const uint32_t* __restrict__ L, const double2* __restrict__ X,
                    double2* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) double2 cs2_smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1064,10 +1076,11 @@ class_sums2_kernel(int n, int d, int tstride, const uint32_t* __restrict__ L, co
         for (int u = 0; u < 8; ++u) {
             const int c = bb * 512 + u * 64 + lane;
             if (c < n) {
-                double2 t = mine[lab[u]];
+                const uint32_t l = WIN ? window_label(lab[u], first, (uint32_t)d) : lab[u];  // (where the label is used: the fetch stays a pure load)
+                double2 t = mine[l];
                 t.x += xv[u].x;
                 t.y += xv[u].y;
-                mine[lab[u]] = t;
+                mine[l] = t;
             }
         }
         if (bb == bpr - 1) {
@@ -1146,13 +1159,27 @@ bi_contract_check_kernel(int n, int S1, const double* __restrict__ Qrm, const do
     }
 }
 
+static void launch_class_sums2(hipStream_t s, int W, int g, size_t lds, int64_t n, int64_t d, uint32_t first, bool plain, int tstride, const uint32_t* L,
+                               const double2* X, double2* Y) {
+    if (plain && first == 1u) {
+        if (W == 4) class_sums2_kernel<4, false><<<g, 256, lds, s>>>((int)n, (int)d, first, tstride, L, X, Y);
+        else if (W == 2) class_sums2_kernel<2, false><<<g, 128, lds, s>>>((int)n, (int)d, first, tstride, L, X, Y);
+        else class_sums2_kernel<1, false><<<g, 64, lds, s>>>((int)n, (int)d, first, tstride, L, X, Y);
+    } else {
+        if (W == 4) class_sums2_kernel<4, true><<<g, 256, lds, s>>>((int)n, (int)d, first, tstride, L, X, Y);
+        else if (W == 2) class_sums2_kernel<2, true><<<g, 128, lds, s>>>((int)n, (int)d, first, tstride, L, X, Y);
+        else class_sums2_kernel<1, true><<<g, 64, lds, s>>>((int)n, (int)d, first, tstride, L, X, Y);
+    }
+}
+
 size_t basis_image_commutative_workspace_doubles(int64_t n, int64_t d) { return (size_t)2 * n * (d + 1); }
 // All blocks 1 x 1 (S = S1).  ws: 2 n (d + 1) doubles.  Returns false when the shape has no instance (d > 148);
 // after the launches flag[0] = number of columns whose check failed, flag[1 + k] = 1 for those columns (flag: 1 + S1
 // words the device can write, e.g. pinned host memory): their entries of `out` must be recomputed by the projection
 // formula (launch_basis_image_fix_pair, or everything by the caller).
-bool launch_basis_image_commutative(hipStream_t s, int64_t n, int64_t d, int64_t S1, const uint32_t* L, const double* Qrm, uint64_t key,
-                                    double atol, double tol, double* ws, double* out, uint32_t* flag) {
+// d: the classes of the window that starts at class `first`; out: d * S1 doubles, the window's
+bool launch_basis_image_commutative(hipStream_t s, int64_t n, int64_t d, uint32_t first, int64_t S1, const uint32_t* L, const double* Qrm, uint64_t key,
+                                    double atol, double tol, double* ws, double* out, uint32_t* flag, bool plain) {
     const int tstride = (int)((d + 1) | 1);
     const size_t per_wave = (size_t)64 * tstride * sizeof(double2);
     int W = 4;
@@ -1164,9 +1191,7 @@ bool launch_basis_image_commutative(hipStream_t s, int64_t n, int64_t d, int64_t
     int g = (int)((n + W - 1) / W);
     if (g > 256) g = 256;  // one resident workgroup per CU, rows in rounds
     const size_t lds = per_wave * W;
-    if (W == 4) class_sums2_kernel<4><<<g, 256, lds, s>>>((int)n, (int)d, tstride, L, X, Y);
-    else if (W == 2) class_sums2_kernel<2><<<g, 128, lds, s>>>((int)n, (int)d, tstride, L, X, Y);
-    else class_sums2_kernel<1><<<g, 64, lds, s>>>((int)n, (int)d, tstride, L, X, Y);
+    launch_class_sums2(s, W, g, lds, n, d, first, plain, tstride, L, X, Y);
     dim3 gc((unsigned)d, (unsigned)((S1 + 3) / 4));
     bi_contract_check_kernel<<<gc, 256, 0, s>>>((int)n, (int)S1, Qrm, Y, key, atol, tol, out, flag);
     return true;
@@ -1174,8 +1199,8 @@ bool launch_basis_image_commutative(hipStream_t s, int64_t n, int64_t d, int64_t
 
 // The projection formula for two columns k1, k2 of a commutative Q_hat (k2 = k1 allowed): one more class-sum pass of
 // the pair (q_k1, q_k2) and its contraction, overwriting out[i * S1 + k1], out[i * S1 + k2] for every class i.
-bool launch_basis_image_fix_pair(hipStream_t s, int64_t n, int64_t d, int64_t S1, const uint32_t* L, const double* Qrm, int k1, int k2,
-                                 double atol, double* ws, double* out) {
+bool launch_basis_image_fix_pair(hipStream_t s, int64_t n, int64_t d, uint32_t first, int64_t S1, const uint32_t* L, const double* Qrm, int k1, int k2,
+                                 double atol, double* ws, double* out, bool plain) {
     const int tstride = (int)((d + 1) | 1);
     const size_t per_wave = (size_t)64 * tstride * sizeof(double2);
     int W = 4;
@@ -1187,9 +1212,7 @@ bool launch_basis_image_fix_pair(hipStream_t s, int64_t n, int64_t d, int64_t S1
     int g = (int)((n + W - 1) / W);
     if (g > 256) g = 256;
     const size_t lds = per_wave * W;
-    if (W == 4) class_sums2_kernel<4><<<g, 256, lds, s>>>((int)n, (int)d, tstride, L, X, Y);
-    else if (W == 2) class_sums2_kernel<2><<<g, 128, lds, s>>>((int)n, (int)d, tstride, L, X, Y);
-    else class_sums2_kernel<1><<<g, 64, lds, s>>>((int)n, (int)d, tstride, L, X, Y);
+    launch_class_sums2(s, W, g, lds, n, d, first, plain, tstride, L, X, Y);
     bi_contract_pair_kernel<<<(unsigned)d, 256, 0, s>>>((int)n, (int)S1, Qrm, Y, k1, k2, atol, out);
     return true;
 }
@@ -1359,10 +1382,10 @@ bib_contract_kernel(int n, int S1, int64_t S, const int32_t* __restrict__ blk_co
 size_t basis_image_blocks_workspace_doubles(int64_t n, int64_t d) { return (size_t)4 * n * (d + 1) + 9 * 65536; }
 // Blocks up to 3 x 3.  ws: 4 n (d + 1) doubles.  only < 0: every block from four generic vectors, flag[0] = blocks whose
 // check failed, flag[1 + k] = 1 for those; only = k: block k alone by the projection formula (no check, flag untouched).
-// Returns false when the shape has no instance.
-bool launch_basis_image_blocks(hipStream_t s, int64_t n, int64_t d, int64_t S1, int64_t S, int nblocks, const int32_t* blk_col, const int32_t* blk_size,
+// Returns false when the shape has no instance.  d: the classes of the window that starts at class `first`.
+bool launch_basis_image_blocks(hipStream_t s, int64_t n, int64_t d, uint32_t first, int64_t S1, int64_t S, int nblocks, const int32_t* blk_col, const int32_t* blk_size,
                                const int64_t* blk_off, const uint32_t* L, const double* Qrm, uint64_t key, int only, double atol, double tol, double* ws,
-                               double* out, uint32_t* flag) {
+                               double* out, uint32_t* flag, bool plain) {
     const int tstride = (int)((d + 1) | 1);
     const size_t per_wave = (size_t)64 * tstride * sizeof(double2);
     int W = 4;
@@ -1381,9 +1404,7 @@ bool launch_basis_image_blocks(hipStream_t s, int64_t n, int64_t d, int64_t S1, 
     for (int pass = 0; pass < 2; ++pass) {
         const double2* X = pass ? X1 : X0;
         double2* Y = pass ? Y1 : Y0;
-        if (W == 4) class_sums2_kernel<4><<<g, 256, lds, s>>>((int)n, (int)d, tstride, L, X, Y);
-        else if (W == 2) class_sums2_kernel<2><<<g, 128, lds, s>>>((int)n, (int)d, tstride, L, X, Y);
-        else class_sums2_kernel<1><<<g, 64, lds, s>>>((int)n, (int)d, tstride, L, X, Y);
+        launch_class_sums2(s, W, g, lds, n, d, first, plain, tstride, L, X, Y);
     }
     dim3 gc((unsigned)d, only >= 0 ? 1u : (unsigned)nblocks);
     bib_contract_kernel<<<gc, 256, 0, s>>>((int)n, (int)S1, S, blk_col, blk_size, blk_off, Qrm, Y0, Y1, ginv, key, only, atol, tol, out, flag);
@@ -1393,9 +1414,12 @@ bool launch_basis_image_blocks(hipStream_t s, int64_t n, int64_t d, int64_t S1, 
 // per-device kernel attributes, set by sdpsr_create() (see gemm_set_device_attributes)
 bool blockdiag_set_device_attributes() {
     bool ok = true;
-    ok &= hipSuccess == hipFuncSetAttribute(reinterpret_cast<const void*>(&class_sums2_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    ok &= hipSuccess == hipFuncSetAttribute(reinterpret_cast<const void*>(&class_sums2_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    ok &= hipSuccess == hipFuncSetAttribute(reinterpret_cast<const void*>(&class_sums2_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+    ok &= hipSuccess == hipFuncSetAttribute(reinterpret_cast<const void*>(&class_sums2_kernel<4, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+    ok &= hipSuccess == hipFuncSetAttribute(reinterpret_cast<const void*>(&class_sums2_kernel<4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+    ok &= hipSuccess == hipFuncSetAttribute(reinterpret_cast<const void*>(&class_sums2_kernel<2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+    ok &= hipSuccess == hipFuncSetAttribute(reinterpret_cast<const void*>(&class_sums2_kernel<2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+    ok &= hipSuccess == hipFuncSetAttribute(reinterpret_cast<const void*>(&class_sums2_kernel<1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+    ok &= hipSuccess == hipFuncSetAttribute(reinterpret_cast<const void*>(&class_sums2_kernel<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
     ok &= hipSuccess == hipFuncSetAttribute(reinterpret_cast<const void*>(&class_sums_small_d_kernel),
                         hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
     ok &= hipSuccess == hipFuncSetAttribute(reinterpret_cast<const void*>(&small_qtaq_block_norms_kernel),
@@ -1416,27 +1440,27 @@ bool class_sums_supports(int64_t n, int64_t d, int64_t ldo) {
     const int tstride = (int)((d + 1) | 1);
     return ldo == n || ((size_t)n + (size_t)4 * 64 * tstride) * sizeof(double) <= 150 * 1024;
 }
-void launch_class_sums(hipStream_t s, int64_t n, int64_t d, const uint32_t* L, const double* x, double* out, int64_t ldo) {
+void launch_class_sums(hipStream_t s, int64_t n, int64_t d, const uint32_t* L, const double* x, double* out, int64_t ldo, uint32_t first) {
     const int tstride = (int)((d + 1) | 1);
     const size_t lds_small = ((size_t)n + (size_t)4 * 64 * tstride) * sizeof(double);
     if (lds_small <= 150 * 1024) {
         int g = (int)((n + 3) / 4);
         if (g > 256) g = 256;  // one resident workgroup per CU, rows in rounds
-        class_sums_small_d_kernel<<<g, 256, lds_small, s>>>((int)n, (int)d, tstride, L, x, out, ldo);
+        class_sums_small_d_kernel<<<g, 256, lds_small, s>>>((int)n, (int)d, first, tstride, L, x, out, ldo);
         return;
     }
     const size_t lds = (size_t)2 * (d + 2) * 4 + (size_t)n * 2 + 16;
-    basis_image_rows_kernel<1><<<(unsigned)n, 64, lds, s>>>((int)n, (int)d, 1, L, x, out, 0);
+    basis_image_rows_kernel<1><<<(unsigned)n, 64, lds, s>>>((int)n, (int)d, first, 1, L, x, out, 0);
 }
 
-void launch_basis_image_two_stage(hipStream_t s, int64_t n, int64_t d, int64_t S1, int64_t S,
+void launch_basis_image_two_stage(hipStream_t s, int64_t n, int64_t d, uint32_t first, int64_t S1, int64_t S,
                                   const uint32_t* L, const double* Qrm, double* T, const int32_t* colA,
                                   const int32_t* colB, double atol, double* out) {
     const size_t lds = (size_t)2 * (d + 2) * 4 + (size_t)n * 2 + 16;
     if (S1 % 2 == 0)  // rows of Qrm are 16-byte aligned
-        basis_image_rows_kernel<2><<<(unsigned)n, 64, lds, s>>>((int)n, (int)d, (int)S1, L, Qrm, T, 1);
+        basis_image_rows_kernel<2><<<(unsigned)n, 64, lds, s>>>((int)n, (int)d, first, (int)S1, L, Qrm, T, 1);
     else
-        basis_image_rows_kernel<1><<<(unsigned)n, 64, lds, s>>>((int)n, (int)d, (int)S1, L, Qrm, T, 1);
+        basis_image_rows_kernel<1><<<(unsigned)n, 64, lds, s>>>((int)n, (int)d, first, (int)S1, L, Qrm, T, 1);
     dim3 g((unsigned)d, (unsigned)((S + 3) / 4));
     basis_image_blocks_kernel<<<g, 256, 0, s>>>((int)n, (int)S1, S, Qrm, T, colA, colB, atol, out);
 }
@@ -1475,17 +1499,18 @@ __global__ void class_starts_kernel(int64_t len, const uint32_t* __restrict__ so
 // linear exclusive scan gives every workgroup its write offset per digit: no atomics anywhere, a deterministic order), then
 // the scatter with ranks from a block-wide scan of the threads' packed digit counts.
 constexpr int RX_T = 256, RX_E = 8, RX_CH = RX_T * RX_E;
-__device__ __forceinline__ void rx_load(int64_t len, int64_t e0, const uint32_t* __restrict__ k, const uint32_t* __restrict__ v, uint32_t (&kk)[RX_E],
-                                        uint32_t (&vv)[RX_E]) {
+// (first, cnt): the window the keys are read through (window_label); (1, 0xFFFFFFFF) leaves every key as it is
+__device__ __forceinline__ void rx_load(int64_t len, int64_t e0, const uint32_t* __restrict__ k, const uint32_t* __restrict__ v, uint32_t first, uint32_t cnt,
+                                        uint32_t (&kk)[RX_E], uint32_t (&vv)[RX_E]) {
 #pragma unroll
     for (int q = 0; q < RX_E; ++q) {
         const int64_t e = e0 + q;
-        kk[q] = e < len ? k[e] : 0xFFFFFFFFu;
+        kk[q] = e < len ? window_label(k[e], first, cnt) : 0xFFFFFFFFu;
         vv[q] = e < len ? (v ? v[e] : (uint32_t)e) : 0u;
     }
 }
 __global__ void __launch_bounds__(RX_T)
-rx_hist_kernel(int64_t len, const uint32_t* __restrict__ keys, int shift, uint32_t G, uint32_t* __restrict__ hist) {
+rx_hist_kernel(int64_t len, const uint32_t* __restrict__ keys, uint32_t first, uint32_t cnt, int shift, uint32_t G, uint32_t* __restrict__ hist) {
     __shared__ uint32_t h[16];
     if (threadIdx.x < 16) h[threadIdx.x] = 0u;
     __syncthreads();
@@ -1494,7 +1519,7 @@ rx_hist_kernel(int64_t len, const uint32_t* __restrict__ keys, int shift, uint32
 #pragma unroll
     for (int q = 0; q < RX_E; ++q)
         if (e0 + q < len) {
-            const uint32_t dg = (keys[e0 + q] >> shift) & 15u;
+            const uint32_t dg = (window_label(keys[e0 + q], first, cnt) >> shift) & 15u;
 #pragma unroll
             for (int b = 0; b < 16; ++b) c[b] += dg == (uint32_t)b;
         }
@@ -1541,13 +1566,13 @@ rx_scan_kernel(int64_t m, uint32_t* __restrict__ v) {
     }
 }
 __global__ void __launch_bounds__(RX_T)
-rx_scatter_kernel(int64_t len, const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals, int shift, uint32_t G,
+rx_scatter_kernel(int64_t len, const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals, uint32_t first, uint32_t cnt, int shift, uint32_t G,
                   const uint32_t* __restrict__ offs, uint32_t* __restrict__ keys_out, uint32_t* __restrict__ vals_out) {
     __shared__ uint32_t wtot[RX_T / 64][8];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int64_t e0 = (int64_t)blockIdx.x * RX_CH + (int64_t)threadIdx.x * RX_E;
     uint32_t kk[RX_E], vv[RX_E];
-    rx_load(len, e0, keys, vals, kk, vv);
+    rx_load(len, e0, keys, vals, first, cnt, kk, vv);
     // the thread's counts per digit, two 16-bit counters per word (<= 2048 per workgroup)
     uint32_t pk[8] = {};
 #pragma unroll
@@ -1595,8 +1620,10 @@ rx_scatter_kernel(int64_t len, const uint32_t* __restrict__ keys, const uint32_t
 
 size_t radix_sort_hist_words(int64_t len) { return (size_t)16 * (size_t)((len + RX_CH - 1) / RX_CH); }
 
+// (first, cnt): the keys are read through that window (window_label) by the first pass -- the sorted keys are 0 .. cnt, and
+// `bits` covers cnt; the default leaves them as they are
 void launch_radix_sort_pairs(hipStream_t s, int64_t len, int bits, const uint32_t* keys, uint32_t* kA, uint32_t* kB, uint32_t* vA,
-                             uint32_t* vB, uint32_t* hist) {
+                             uint32_t* vB, uint32_t* hist, uint32_t first, uint32_t cnt) {
     const uint32_t G = (uint32_t)((len + RX_CH - 1) / RX_CH);
     const int passes = (bits + 3) / 4;
     // pass p reads (kin, vin) and writes (kout, vout); the first pass reads the keys themselves with the index as the value
@@ -1605,9 +1632,10 @@ void launch_radix_sort_pairs(hipStream_t s, int64_t len, int bits, const uint32_
     uint32_t* kout = (passes & 1) ? kB : kA;  // so that the last pass ends in (kB, vB)
     uint32_t* vout = (passes & 1) ? vB : vA;
     for (int p = 0; p < passes; ++p) {
-        rx_hist_kernel<<<G, RX_T, 0, s>>>(len, kin, 4 * p, G, hist);
+        const uint32_t f = p == 0 ? first : 1u, w = p == 0 ? cnt : 0xFFFFFFFFu;  // later passes read keys already mapped
+        rx_hist_kernel<<<G, RX_T, 0, s>>>(len, kin, f, w, 4 * p, G, hist);
         rx_scan_kernel<<<1, 1024, 0, s>>>((int64_t)16 * G, hist);
-        rx_scatter_kernel<<<G, RX_T, 0, s>>>(len, kin, vin, 4 * p, G, hist, kout, vout);
+        rx_scatter_kernel<<<G, RX_T, 0, s>>>(len, kin, vin, f, w, 4 * p, G, hist, kout, vout);
         kin = kout;
         vin = vout;
         kout = (kout == kA) ? kB : kA;
@@ -1615,8 +1643,9 @@ void launch_radix_sort_pairs(hipStream_t s, int64_t len, int bits, const uint32_
     }
 }
 
+// d: the classes of the window that starts at class `first`; class_ptr_host[i] .. [i + 1] = entries of class first + i - 1
 int sort_entries_by_label(sdpsr_ctx* c, int64_t len, int64_t d, const uint32_t* L,
-                          uint32_t** ent_out, std::vector<int64_t>& class_ptr_host) {
+                          uint32_t** ent_out, std::vector<int64_t>& class_ptr_host, uint32_t first) {
     hipStream_t s = c->stream;
     if (len >= (int64_t(1) << 32)) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "sort_entries_by_label: len >= 2^32");
     uint32_t* kA = (uint32_t*)ctx_buf(c, "bi_key_a", len * sizeof(uint32_t));
@@ -1628,7 +1657,7 @@ int sort_entries_by_label(sdpsr_ctx* c, int64_t len, int64_t d, const uint32_t* 
     if (!kA || !kB || !vA || !vB || !hist || !cstart) return SDPSR_OUT_OF_MEMORY;
     int bits = 1;
     while (((int64_t)1 << bits) <= d) ++bits;
-    launch_radix_sort_pairs(s, len, bits, L, kA, kB, vA, vB, hist);
+    launch_radix_sort_pairs(s, len, bits, L, kA, kB, vA, vB, hist, first, (uint32_t)std::min<int64_t>(d, 0xFFFFFFFFll));
     const uint32_t* key_sorted = kB;
     uint32_t* idx_sorted = vB;
     HIP_TRY(c, hipMemsetAsync(cstart, 0xFF, (d + 2) * sizeof(int64_t), s));  // -1 = class absent

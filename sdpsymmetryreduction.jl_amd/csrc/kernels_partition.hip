@@ -2498,6 +2498,32 @@ void launch_copy_check_symmetric(hipStream_t s, int64_t n, const uint32_t* src, 
     if (v4) copy_check_symmetric_kernel<true><<<dim3(t, t), 256, 0, s>>>(n, src, dst, flag, epoch);
     else copy_check_symmetric_kernel<false><<<dim3(t, t), 256, 0, s>>>(n, src, dst, flag, epoch);
 }
+// The same pass for a caller's labels of unknown quality (sdpsr_basis_image): symmetry, and "a label exceeds dmax" from the
+// words that pass through the registers anyway.  src == dst (labels already in place) is allowed: the values written are the
+// values read.  Plain stores of 1 into words the caller cleared.
+struct MapNoteExceeds {
+    uint32_t dmax;
+    bool* over;
+    __device__ __forceinline__ uint32_t operator()(uint32_t v) const {
+        if (v > dmax) *over = true;
+        return v;
+    }
+};
+template <bool VEC4>
+__global__ void __launch_bounds__(256)
+copy_check_labels_kernel(int64_t n, const uint32_t* src, uint32_t* dst, uint32_t dmax, uint32_t* flag) {
+    __shared__ uint32_t tile[64][65];
+    if (blockIdx.x < blockIdx.y) return;
+    bool over = false;
+    if (sym_tile_pass<VEC4>(n, src, dst, MapNoteExceeds{dmax, &over}, tile)) flag[0] = 1u;
+    if (over) flag[1] = 1u;
+}
+void launch_copy_check_labels(hipStream_t s, int64_t n, const uint32_t* src, uint32_t* dst, uint32_t dmax, uint32_t* flag) {
+    const unsigned t = (unsigned)((n + 63) / 64);
+    const bool v4 = n % 4 == 0 && (reinterpret_cast<uintptr_t>(src) % 16) == 0 && (reinterpret_cast<uintptr_t>(dst) % 16) == 0;
+    if (v4) copy_check_labels_kernel<true><<<dim3(t, t), 256, 0, s>>>(n, src, dst, dmax, flag);
+    else copy_check_labels_kernel<false><<<dim3(t, t), 256, 0, s>>>(n, src, dst, dmax, flag);
+}
 void launch_check_symmetric(hipStream_t s, int64_t n, const uint32_t* L, uint32_t* flag) {
     hipMemsetAsync(flag, 0, sizeof(uint32_t), s);
     const unsigned t = (unsigned)((n + 63) / 64);

@@ -463,32 +463,40 @@ void launch_basis_image_outer(hipStream_t s, int64_t n, int64_t d, int64_t S1, i
                               const double* Qrm, const uint32_t* ent, const int64_t* cls_ptr,
                               const int32_t* blk_col, const int32_t* blk_size, const int64_t* blk_off, double atol,
                               double* out);
-// out[r + i*n] = sum over c with L[c + r*n] == i+1 of x[c]   (class sums of a vector, i < d)
+// A window of classes (first, d): in the launchers below that take `first`, d counts the classes first .. first + d - 1; labels
+// are read through the window where they are loaded (class l - first + 1 inside, the skipped class 0 outside), tables,
+// workspaces and outputs have d slabs.  (1, d) is the whole partition.  plain (the shortcuts' launchers): the window is (1, d) and
+// every label is known to be <= d -- the ctx's own labels -- so the pair class-sum kernel uses them as they are.
+// out[r + i*n] = sum over c with L[c + r*n] == first+i of x[c]   (class sums of a vector, i < d)
 bool class_sums_supports(int64_t n, int64_t d, int64_t ldo);
-void launch_class_sums(hipStream_t s, int64_t n, int64_t d, const uint32_t* L, const double* x, double* out, int64_t ldo);
-void launch_basis_image_two_stage(hipStream_t s, int64_t n, int64_t d, int64_t S1, int64_t S,
+void launch_class_sums(hipStream_t s, int64_t n, int64_t d, const uint32_t* L, const double* x, double* out, int64_t ldo, uint32_t first = 1);
+void launch_basis_image_two_stage(hipStream_t s, int64_t n, int64_t d, uint32_t first, int64_t S1, int64_t S,
                                   const uint32_t* L, const double* Qrm, double* T, const int32_t* colA,
                                   const int32_t* colB, double atol, double* out);
 size_t basis_image_commutative_workspace_doubles(int64_t n, int64_t d);
 size_t basis_image_blocks_workspace_doubles(int64_t n, int64_t d);
-bool launch_basis_image_blocks(hipStream_t s, int64_t n, int64_t d, int64_t S1, int64_t S, int nblocks, const int32_t* blk_col, const int32_t* blk_size,
+bool launch_basis_image_blocks(hipStream_t s, int64_t n, int64_t d, uint32_t first, int64_t S1, int64_t S, int nblocks, const int32_t* blk_col, const int32_t* blk_size,
                                const int64_t* blk_off, const uint32_t* L, const double* Qrm, uint64_t key, int only, double atol, double tol, double* ws,
-                               double* out, uint32_t* flag);
-bool launch_basis_image_fix_pair(hipStream_t s, int64_t n, int64_t d, int64_t S1, const uint32_t* L, const double* Qrm, int k1, int k2,
-                                 double atol, double* ws, double* out);
-bool launch_basis_image_commutative(hipStream_t s, int64_t n, int64_t d, int64_t S1, const uint32_t* L, const double* Qrm, uint64_t key,
-                                    double atol, double tol, double* ws, double* out, uint32_t* flag);
+                               double* out, uint32_t* flag, bool plain = false);
+bool launch_basis_image_fix_pair(hipStream_t s, int64_t n, int64_t d, uint32_t first, int64_t S1, const uint32_t* L, const double* Qrm, int k1, int k2,
+                                 double atol, double* ws, double* out, bool plain = false);
+bool launch_basis_image_commutative(hipStream_t s, int64_t n, int64_t d, uint32_t first, int64_t S1, const uint32_t* L, const double* Qrm, uint64_t key,
+                                    double atol, double tol, double* ws, double* out, uint32_t* flag, bool plain = false);
 void launch_transpose_to_rowmajor(hipStream_t s, int64_t n, int64_t S1, const double* Qcm,
                                   double* Qrm);
 // Stable LSD radix sort of the pairs (keys[e], e), e < len < 2^32, by the low `bits` bits of the key (4 bits per pass; the
 // keys must not exceed them).  kA / kB / vA / vB: len words each, hist: radix_sort_hist_words(len).  The sorted keys and
-// indices end in (kB, vB).  No atomics on the way: the order is a function of the keys alone.
+// indices end in (kB, vB).  No atomics on the way: the order is a function of the keys alone.  (first, cnt): the first pass
+// reads the keys through that window of classes; the default leaves every key as it is.
 size_t radix_sort_hist_words(int64_t len);
 void launch_radix_sort_pairs(hipStream_t s, int64_t len, int bits, const uint32_t* keys, uint32_t* kA, uint32_t* kB, uint32_t* vA,
-                             uint32_t* vB, uint32_t* hist);
-// stable sort of entries by label (label 0 dropped): ent sorted, hist[d+1]
+                             uint32_t* vB, uint32_t* hist, uint32_t first = 1, uint32_t cnt = 0xFFFFFFFFu);
+// stable sort of entries by label (label 0 dropped): ent sorted, hist[d+1]; the d classes from `first` on
 int sort_entries_by_label(sdpsr_ctx* c, int64_t len, int64_t d, const uint32_t* L,
-                          uint32_t** ent_out, std::vector<int64_t>& class_ptr_host);
+                          uint32_t** ent_out, std::vector<int64_t>& class_ptr_host, uint32_t first = 1);
+// kernels_partition.hip: dst = src (n x n labels; dst == src allowed) with two verdicts from the same tiles:
+// flag[0] = 1 if src is not symmetric, flag[1] = 1 if a label exceeds dmax.  The caller clears flag[0..1] first.
+void launch_copy_check_labels(hipStream_t s, int64_t n, const uint32_t* src, uint32_t* dst, uint32_t dmax, uint32_t* flag);
 
 // ---------------------------------------------------------------------------
 // eigen.cpp (rocSOLVER)

@@ -266,6 +266,38 @@ function SR.diagonalize(::Type{Float64}, P::HIPPartition; verbose=false, atol=1e
     return [Q[:, offs[k]+1:offs[k+1]] for k in eachindex(sizes)]
 end
 
+# ---- basis_image(Q, P; atol) (diagonalize.jl:64-89) of a caller's Q_hat, for a window of classes ----
+# Q_hat: the vector of n x s_k matrices diagonalize returns (any real matrices: nothing is assumed about them);
+# classes = (first, count), 1-based, e.g. class_window(dim(P), world, rank) after broadcast!(Q_hat, comm; root=winner).
+# Returns blks[i][k] for the classes first .. first + count - 1, and with route=true the pair (blks, route).
+class_window(d::Integer, parts::Integer, index::Integer) =   # index 0-based; contiguous, sizes within one, empty when parts > d
+    (1 + index * div(d, parts) + min(index, rem(d, parts)), div(d, parts) + (index < rem(d, parts) ? 1 : 0))
+
+function basis_image(Q_hat::AbstractVector{<:AbstractMatrix{Float64}}, P::HIPPartition;
+                     classes::Tuple{<:Integer,<:Integer}=(1, P.nparts), atol::Real=-1.0, route::Bool=false)
+    n = size(P, 1); cx = width!(ctx(), labeltype(P))
+    all(q -> size(q, 1) == n, Q_hat) || throw(DimensionMismatch("every block of Q_hat has size(P, 1) rows"))
+    sizes = Int32[size(q, 2) for q in Q_hat]
+    Q = Matrix{Float64}(reduce(hcat, Q_hat))
+    first, count = Int64(classes[1]), Int64(classes[2])
+    S = sum(Int64(s)^2 for s in sizes)
+    flat = Vector{Float64}(undef, max(count, 0) * S)
+    rt = Ref{Int32}(0)
+    check(cx, ccall((:sdpsr_basis_image, libsdpsr), Cint,
+                    (Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Int32, Ptr{Int32}, Ptr{Float64}, Int64, Int64, Float64,
+                     Ptr{Float64}, Ref{Int32}, Ptr{Float64}, Cint),
+                    cx.handle, n, P.matrix, P.nparts, length(sizes), sizes, Q, first, count, Float64(atol),
+                    flat, rt, C_NULL, MEM_HOST))
+    blks = Vector{Vector{Matrix{Float64}}}(undef, count)
+    for i in 1:count
+        off = (i - 1) * S; blks[i] = Matrix{Float64}[]
+        for s in sizes
+            push!(blks[i], reshape(flat[off+1:off+s*s], Int(s), Int(s))); off += s * s
+        end
+    end
+    return route ? (blks, Int(rt[])) : blks
+end
+
 # ---- blockDiagonalize(ComplexF64, P) (compat.jl:26-32,54-57; n <= 3072 in this library version) ---
 function SR.blockDiagonalize(::Type{ComplexF64}, P::HIPPartition, verbose=true;
                              epsilon=Base.rtoldefault(Float64))
