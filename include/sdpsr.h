@@ -586,6 +586,45 @@ int sdpsr_block_sizes_complex(sdpsr_ctx* ctx, int32_t* blk_sizes);
 /* blks: d_desym * sum_sq complex numbers as (re, im) pairs, class-major, then block, each block
    column-major s_k x s_k.  Q_hat (optional): n x sum_s complex, (re, im) pairs, column-major. */
 int sdpsr_block_images_complex(sdpsr_ctx* ctx, double* blks, double* Q_hat, int mem);
+/* basis_image(Q, P; atol) over ComplexF64, src/diagonalize.jl:64-89 (_constraints :42-50) as blockDiagonalize(P; complex = true)
+   calls it with the desymmetrized partition (src/compat.jl:54-57), for a caller's Q_hat and the classes class_first ..
+   class_first + class_count - 1 (1-based): blks[i][k] = Q_k^H 1[P==i] Q_k, i.e.
+   blks[i][k][a,b] = sum over the entries (r,c) with P[r,c] == i of conj(Q_k[r,a]) * Q_k[c,b].
+   The complex counterpart of sdpsr_basis_image: the complex Q_hat that sdpsr_comm_broadcast delivered to every rank becomes
+   images here, each rank taking its own window; a large output is taken window by window.
+     P            n x n labels at the ctx's label width (sdpsr_set_label_width), column-major, in `mem`.  NOT required to be
+                  symmetric (desymmetrized partitions are not); label 0 is skipped;
+     d            dim(P);
+     blk_sizes    host array of nblocks sizes s_k >= 1, sum s_k <= n;
+     Q_hat        n x sum s_k complex numbers as (re, im) pairs, column-major, blocks side by side, in `mem` (the layout
+                  sdpsr_block_images_complex writes).  ARBITRARY: neither orthonormal columns nor invariant subspaces are assumed;
+     blks         class_count * sum s_k^2 complex numbers as (re, im) pairs in `mem`: class-major starting at class_first, then
+                  block, each block column-major (the layout of sdpsr_block_images_complex).  Nothing outside those elements
+                  is written;
+     atol         entries with |z| < atol (the complex magnitude, strict <, as clamptol does with abs, src/utils.jl:14-16) become
+                  0 + 0i; atol < 0: the reference's default 1e-12 * n; 0: no clamp;
+     route        (may be NULL) SDPSR_BI_ROUTE_OUTER or SDPSR_BI_ROUTE_CHUNK: the kernels that produced the output;
+     phase_ms     (may be NULL) as sdpsr_block_images fills it.
+   Routes.  There are no shortcuts over C, so SDPSR_FLAG_FULL_BASIS_IMAGE has no effect here.  opts.basis_image_kernel = outer or
+   chunk forces that route (outer covers blocks up to 128 x 128; with a larger block a forced `outer` runs `chunk` and *route
+   says so); two_stage is treated as auto (the real two-stage kernels rely on a symmetric partition).  The automatic choice is
+   a function of (n, d, the block sizes) alone, never of the window: an average class below 4096 entries and every block within
+   what the outer kernel supports gives outer, else chunk.
+   A window's output equals, bit for bit, the same slice of the full call, on both routes and under auto; equal inputs give
+   equal bits on any ctx and any seed (no random numbers, no floating-point atomics, every class summed on its own in a fixed
+   order).  The ctx's block diagonalisations and what sdpsr_basis_image keeps are neither needed nor disturbed:
+   sdpsr_block_images_complex, sdpsr_block_images and sdpsr_basis_image behave after this call exactly as before it.
+   SDPSR_BAD_ARGUMENT, before any kernel, with nothing written and the ctx usable afterwards: a NULL pointer, n < 1, d < 0,
+   nblocks < 1, some s_k < 1, sum s_k > n, class_count < 0, class_first < 1 or a window that ends beyond d.  class_count == 0 is
+   legal: SDPSR_OK, nothing written, no kernel launched.  Found on the device, in the pass that brings the labels in: "a label
+   exceeds d" (SDPSR_BAD_ARGUMENT; host blks: nothing is delivered, device blks: the window's contents are unspecified).
+   Labels outside the window -- of any value -- are read as the skipped class 0 where they are loaded and index nothing.
+   sdpsr_transfer_bytes, host arrays: n^2 * B / 8 + n * sum s_k * 16 bytes up at label width B, class_count * sum s_k^2 * 16 down
+   (the routes' descriptor words are not counted by this entry); device arrays: nothing up, the 8 bytes of the two label
+   verdicts down. */
+int sdpsr_basis_image_complex(sdpsr_ctx* ctx, int64_t n, const uint32_t* P, int64_t d, int32_t nblocks, const int32_t* blk_sizes,
+                              const double* Q_hat, int64_t class_first, int64_t class_count, double atol, double* blks,
+                              int32_t* route, double* phase_ms, int mem);
 
 /* eigen_decomposition(P, A; atol), src/eigen_decomposition.jl:236-273: status only
    (test/numerical_issues.jl:91-94), *neig = number of eigenspaces, *nclasses = number of

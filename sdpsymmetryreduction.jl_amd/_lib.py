@@ -162,6 +162,7 @@ def load_library():
         "sdpsr_block_diagonalize_complex": (C.c_int, [vp, i64, vp, i64, dbl, vp, pi64, pi32, pi64, pi64, C.c_int]),
         "sdpsr_block_sizes_complex": (C.c_int, [vp, vp]),
         "sdpsr_block_images_complex": (C.c_int, [vp, vp, vp, C.c_int]),
+        "sdpsr_basis_image_complex": (C.c_int, [vp, i64, vp, i64, i32, vp, vp, i64, i64, dbl, vp, pi32, vp, C.c_int]),
         "sdpsr_eigen_decomposition_batched": (C.c_int, [vp, i64, vp, i64, dbl, i64, vp, vp, vp, vp, C.c_int]),
         "sdpsr_syev_f64": (C.c_int, [vp, i64, vp, vp, vp, C.c_int]),
         "sdpsr_hint_symmetric_basis": (C.c_int, [vp, C.c_int]),

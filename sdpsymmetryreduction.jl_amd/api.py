@@ -921,8 +921,16 @@ def class_window(d, parts, index):
     return 1 + index * q + min(index, r), q + (1 if index < r else 0)
 
 
+def _is_complex(x):
+    """A NumPy or torch array of complex64 / complex128 elements."""
+    if _is_torch(x):
+        return x.is_complex()
+    return np.iscomplexobj(x)
+
+
 def _q_hat_arg(Q_hat, n):
-    """(matrix, sizes) from a list of n x s_k arrays or a pair (matrix, blkSizes); NumPy or torch, checked against n."""
+    """(matrix, sizes) from a list of n x s_k arrays or a pair (matrix, blkSizes); NumPy or torch, checked against n.
+    The element type is kept: a complex Q_hat comes back complex, a real one as it was (NumPy lists: float64)."""
     if isinstance(Q_hat, tuple) and len(Q_hat) == 2 and getattr(Q_hat[0], "ndim", 0) == 2 and getattr(Q_hat[1], "ndim", 1) == 1:
         M, sizes = Q_hat[0], [int(s) for s in Q_hat[1]]  # (matrix, blkSizes): the second member is a flat list of sizes
     else:
@@ -937,8 +945,9 @@ def _q_hat_arg(Q_hat, n):
         if _is_torch(blocks[0]):
             import torch
             M = torch.cat(list(blocks), dim=1)
-        else:
-            M = np.concatenate([np.asarray(q, dtype=np.float64) for q in blocks], axis=1)
+        else:  # a complex Q_hat stays complex (complex128); everything else is taken as float64
+            dt = np.complex128 if any(_is_complex(q) for q in blocks) else np.float64
+            M = np.concatenate([np.asarray(q, dtype=dt) for q in blocks], axis=1)
     if M.shape[0] != n:
         raise ValueError(f"basis_image: Q_hat has {M.shape[0]} rows, the partition is {n} x {n}")
     if not sizes or any(s < 1 for s in sizes):
@@ -955,7 +964,10 @@ def basis_image(Q_hat, P, classes=None, atol=None, ctx=None, return_route=False)
     (``sdpsr_basis_image``): ``blks[i][k] = Q_k' 1[P == first + i] Q_k``.
 
     ``Q_hat``: a list of n x s_k arrays, as ``blockDiagonalize`` / ``diagonalize`` return them, or a pair
-    ``(matrix, blkSizes)`` with the blocks side by side; any real matrices, not only those of this library.
+    ``(matrix, blkSizes)`` with the blocks side by side; any matrices, not only those of this library.  A complex
+    ``Q_hat`` (NumPy or torch, complex64 / complex128) goes to ``sdpsr_basis_image_complex``: ``blks[i][k] =
+    Q_k^H 1[P == first + i] Q_k`` as complex128, for a partition that need not be symmetric (the ``.partition`` of
+    ``blockDiagonalize(..., complex=True)``); a real ``Q_hat`` needs a symmetric partition.
     ``classes = (first, count)`` (1-based, e.g. from ``class_window``); ``None``: every class.  ``atol=None``: the
     reference's ``1e-12 * n``; ``0`` clamps nothing.  Returns the window's images nested as ``blks`` of
     ``blockDiagonalize`` (``count`` rows); with ``return_route=True`` the pair ``(blks, route)``, ``route`` as
@@ -970,6 +982,8 @@ def basis_image(Q_hat, P, classes=None, atol=None, ctx=None, return_route=False)
     if count < 0 or (count > 0 and (first < 1 or first + count - 1 > d)):
         raise ValueError(f"basis_image: classes = ({first}, {count}) is not a window of 1..{d}")
     S = sum(s * s for s in sizes)
+    if _is_complex(M):
+        return _basis_image_complex(M, sizes, P, first, count, atol, ctx, return_route)
     lab, mem = _labels_arg(P, ctx)
     route = C.c_int32(0)
     if mem == L.MEM_DEVICE:
@@ -985,6 +999,39 @@ def basis_image(Q_hat, P, classes=None, atol=None, ctx=None, return_route=False)
     sz = np.asarray(sizes, dtype=np.int32)
     ctx.check(ctx._lib.sdpsr_basis_image(ctx._h, n, _ptr(lab), d, len(sizes), _ptr(sz), _ptr(q), first, count,
                                          -1.0 if atol is None else float(atol), _ptr(blks), C.byref(route), None, mem))
+    blks = blks[:count * S].reshape(count, S)
+    out = []
+    for i in range(count):
+        row, off = [], 0
+        for s in sizes:
+            b = blks[i, off:off + s * s]
+            row.append(b.reshape(s, s).t() if _is_torch(b) else b.reshape(s, s, order="F"))
+            off += s * s
+        out.append(row)
+    return (out, route.value) if return_route else out
+
+
+def _basis_image_complex(M, sizes, P, first, count, atol, ctx, return_route):
+    """``basis_image`` for a complex ``Q_hat`` (``sdpsr_basis_image_complex``): ``blks[i][k] = Q_k^H 1[P == first + i] Q_k``
+    as complex128, nested like ``blockDiagonalize(..., complex=True).blks``; ``P`` need not be symmetric (the
+    desymmetrized partition of the complex path is not).  On torch the blocks are views of one device tensor."""
+    n, d = P.shape[0], int(P.nparts)
+    S = sum(s * s for s in sizes)
+    lab, mem = _labels_arg(P, ctx)
+    route = C.c_int32(0)
+    if mem == L.MEM_DEVICE:
+        import torch
+        Mt = M if _is_torch(M) else torch.from_numpy(np.asarray(M, dtype=np.complex128))
+        q = Mt.to(device=lab.device, dtype=torch.complex128).t().contiguous().view(-1)  # column-major, (re, im) pairs
+        blks = torch.empty(max(count * S, 1), dtype=torch.complex128, device=lab.device)
+        ctx.wait_for(lab, q, blks)
+    else:
+        Mh = np.asarray(M.cpu()) if _is_torch(M) else M
+        q = np.ascontiguousarray(np.asarray(Mh, dtype=np.complex128).ravel(order="F"))
+        blks = np.empty(max(count * S, 1), dtype=np.complex128)
+    sz = np.asarray(sizes, dtype=np.int32)
+    ctx.check(ctx._lib.sdpsr_basis_image_complex(ctx._h, n, _ptr(lab), d, len(sizes), _ptr(sz), _ptr(q), first, count,
+                                                 -1.0 if atol is None else float(atol), _ptr(blks), C.byref(route), None, mem))
     blks = blks[:count * S].reshape(count, S)
     out = []
     for i in range(count):

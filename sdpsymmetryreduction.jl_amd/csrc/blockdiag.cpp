@@ -268,16 +268,7 @@ int BasisImage::outer(const uint32_t* ent, const std::vector<int64_t>& class_ptr
 
 // chunks of 4096 entries of a class + output descriptors; the uploads are asynchronous, from vectors of the state
 int BasisImage::chunk(const uint32_t* ent, const std::vector<int64_t>& class_ptr) {
-    const int64_t CH = 4096;
-    chunk_ptr.assign(d + 1, 0);
-    for (int64_t i = 1; i <= d; ++i) {
-        chunk_ptr[i - 1] = (int64_t)cb.size();
-        for (int64_t p = class_ptr[i]; p < class_ptr[i + 1]; p += CH) {
-            cb.push_back(p);
-            ce.push_back(std::min(p + CH, class_ptr[i + 1]));
-        }
-    }
-    chunk_ptr[d] = (int64_t)cb.size();
+    cut_chunks(class_ptr, d, 4096, chunk_ptr, cb, ce);
     desc = pair_descriptor(sizes, S);
     const int64_t nch = (int64_t)cb.size();
     int64_t* d_chunk_ptr = (int64_t*)ctx_buf(c, "bi_chunk_ptr", (d + 1) * 8);

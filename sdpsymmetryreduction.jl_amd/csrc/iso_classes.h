@@ -282,5 +282,20 @@ inline std::vector<int32_t> pair_descriptor(const std::vector<int32_t>& sizes, i
     }
     return desc;
 }
+// every class of class_ptr (size d + 2, class i = class_ptr[i] .. class_ptr[i + 1], i = 1 .. d) cut into chunks of at most
+// `chunk` entries, each starting at the class's own first entry: chunk_ptr[i - 1] .. chunk_ptr[i] = the chunks of class i,
+// chunk q = entries cb[q] .. ce[q].  A class's chunks depend on nothing but the class.
+inline void cut_chunks(const std::vector<int64_t>& class_ptr, int64_t d, int64_t chunk, std::vector<int64_t>& chunk_ptr,
+                       std::vector<int64_t>& cb, std::vector<int64_t>& ce) {
+    chunk_ptr.assign(d + 1, 0);
+    for (int64_t i = 1; i <= d; ++i) {
+        chunk_ptr[i - 1] = (int64_t)cb.size();
+        for (int64_t p = class_ptr[i]; p < class_ptr[i + 1]; p += chunk) {
+            cb.push_back(p);
+            ce.push_back(std::min(p + chunk, class_ptr[i + 1]));
+        }
+    }
+    chunk_ptr[d] = (int64_t)cb.size();
+}
 
 }  // namespace sdpsr

@@ -356,6 +356,16 @@ void launch_cx_irreducible(hipStream_t s, int64_t n, const double* Hr, const dou
                            const int32_t* desc, int ncols, double atol, double* Qhat);
 void launch_cx_basis_image(hipStream_t s, int64_t n, int64_t d, int64_t S, const uint32_t* L, const double* Qhat,
                            const int32_t* descA, const int32_t* descB, double atol, double* out);
+// kernels_complex_image.hip: basis_image over C for a caller's Q_hat (sdpsr_basis_image_complex).  Qrm: n x S1 complex,
+// row-major, (re, im) interleaved; out: the window's d * S complex numbers; ent / cls_ptr / chunks as on the real path
+void launch_cx_rowmajor(hipStream_t s, int64_t n, int64_t S1, const double* Qcm, double* Qrm);
+void launch_cx_image_chunk(hipStream_t s, int64_t n, int64_t d, int64_t S1, int64_t S, const double* Qrm, const uint32_t* ent,
+                           const int32_t* descA, const int32_t* descB, const int64_t* chunk_ptr, int64_t nchunks,
+                           const int64_t* chunk_begin, const int64_t* chunk_end, double* partial, double* out, double atol);
+bool cx_image_outer_supports(int max_s, int nblocks, int64_t d);
+void launch_cx_image_outer(hipStream_t s, int64_t n, int64_t d, int64_t S1, int64_t S, int nblocks, int max_s, const double* Qrm,
+                           const uint32_t* ent, const int64_t* cls_ptr, const int32_t* blk_col, const int32_t* blk_size,
+                           const int64_t* blk_off, double atol, double* out);
 // kernels_batched.hip: `count` runs of eigen_decomposition on one partition of order n <= 64
 void launch_eigdec_batched64(hipStream_t s, int64_t n, int64_t d, int64_t count, const uint32_t* L, const double* values,
                              uint64_t seed, uint64_t stream_base, double atol, int32_t* status, int32_t* neig,

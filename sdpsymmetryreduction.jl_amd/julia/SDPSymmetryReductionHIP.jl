@@ -298,6 +298,34 @@ function basis_image(Q_hat::AbstractVector{<:AbstractMatrix{Float64}}, P::HIPPar
     return route ? (blks, Int(rt[])) : blks
 end
 
+# The same over ComplexF64 (sdpsr_basis_image_complex): blks[i][k] = Q_k' * (P .== i) * Q_k with the adjoint, for a P that need
+# not be symmetric -- the desymmetrized partition blockDiagonalize(ComplexF64, P) hands to basis_image (compat.jl:54-57).
+# route is SDPSR_BI_ROUTE_OUTER (4) or _CHUNK (5).
+function basis_image(Q_hat::AbstractVector{<:AbstractMatrix{ComplexF64}}, P::HIPPartition;
+                     classes::Tuple{<:Integer,<:Integer}=(1, P.nparts), atol::Real=-1.0, route::Bool=false)
+    n = size(P, 1); cx = width!(ctx(), labeltype(P))
+    all(q -> size(q, 1) == n, Q_hat) || throw(DimensionMismatch("every block of Q_hat has size(P, 1) rows"))
+    sizes = Int32[size(q, 2) for q in Q_hat]
+    Q = Matrix{ComplexF64}(reduce(hcat, Q_hat))         # (re, im) pairs = ComplexF64 layout
+    first, count = Int64(classes[1]), Int64(classes[2])
+    S = sum(Int64(s)^2 for s in sizes)
+    flat = Vector{ComplexF64}(undef, max(count, 0) * S)
+    rt = Ref{Int32}(0)
+    check(cx, ccall((:sdpsr_basis_image_complex, libsdpsr), Cint,
+                    (Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Int32, Ptr{Int32}, Ptr{ComplexF64}, Int64, Int64, Float64,
+                     Ptr{ComplexF64}, Ref{Int32}, Ptr{Float64}, Cint),
+                    cx.handle, n, P.matrix, P.nparts, length(sizes), sizes, Q, first, count, Float64(atol),
+                    flat, rt, C_NULL, MEM_HOST))
+    blks = Vector{Vector{Matrix{ComplexF64}}}(undef, count)
+    for i in 1:count
+        off = (i - 1) * S; blks[i] = Matrix{ComplexF64}[]
+        for s in sizes
+            push!(blks[i], reshape(flat[off+1:off+s*s], Int(s), Int(s))); off += s * s
+        end
+    end
+    return route ? (blks, Int(rt[])) : blks
+end
+
 # ---- blockDiagonalize(ComplexF64, P) (compat.jl:26-32,54-57; n <= 3072 in this library version) ---
 function SR.blockDiagonalize(::Type{ComplexF64}, P::HIPPartition, verbose=true;
                              epsilon=Base.rtoldefault(Float64))
