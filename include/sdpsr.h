@@ -626,6 +626,43 @@ int sdpsr_basis_image_complex(sdpsr_ctx* ctx, int64_t n, const uint32_t* P, int6
                               const double* Q_hat, int64_t class_first, int64_t class_count, double atol, double* blks,
                               int32_t* route, double* phase_ms, int mem);
 
+/* ---- block images as solver triplets, README.md:72-79, test/sd_problems.jl:46-52,
+        docs/src/examples/ReduceAndSolveJuMP.jl:56-84 ---------------------------------------------------------
+   Every consumer of the reduced SDP takes its PSD part as sparse per-variable, per-block entries (variable i, block k, row, col,
+   value) -- JuMP's PSDCone expressions sum_i x_i blks[i][k], SDPA-sparse files, a first-order method's operator.  This entry
+   compacts a window of dense block images into those entries on the device, in order, so that a large d * sum s_k^2 output
+   leaves the device as what it holds and not as its zeros: take sdpsr_basis_image window by window and compact each slab.
+     blk_sizes    host array of nblocks sizes s_k >= 1;
+     blks         class_count * sum s_k^2 elements in `mem`, in exactly the layout sdpsr_basis_image{,_complex} and
+                  sdpsr_block_images{,_complex} write: class-major, then block, each block column-major s_k x s_k; doubles, or
+                  complex numbers as (re, im) pairs when is_complex != 0.  The pointer needs 8-byte alignment only: a window that
+                  starts at an odd element of a larger buffer is a supported input;
+     the VIRTUAL block k of a class is the block itself (real input, order s'_k = s_k) or its real embedding [Re -Im; Im Re] of
+                  order s'_k = 2 s_k (complex input; ReduceAndSolveJuMP.jl:59-76).  Negation is the only arithmetic on values;
+     kept         an element v of a virtual block is kept iff !(|v| <= tol): zeros of either sign never, a NaN always;
+     triangle     SDPSR_TRI_UPPER keeps row <= col only, SDPSR_TRI_FULL every position;
+     order        the scan order of the virtual blocks: class, then block, then column-major inside the block;
+     classptr     class_count + 1 offsets (0-based, `mem`): the entries of window class i are [classptr[i], classptr[i+1]);
+     blk row col  int32 in `mem`, 0-based plus index_base (0 or 1); val: the kept values;
+     nnz          (host) = classptr[class_count].  classptr and *nnz are ALWAYS written.  If *nnz > capacity the four entry
+                  arrays are not touched and the status is still SDPSR_OK (the capacity rule of sdpsr_jordan_reduce);
+                  capacity = 0 with NULL entry arrays is the sizing call;
+     max_asym     (host, may be NULL: the pass is skipped) the maximum over all virtual blocks and row < col of
+                  |M[row,col] - M[col,row]| -- what SDPSR_TRI_UPPER gives up.  0.0 for an empty window, unspecified when a NaN
+                  is involved.
+   The output is a function of the inputs alone: positions come from an exclusive scan over fixed chunks of the element range,
+   no atomics decide one and nothing is sorted, so two calls -- on any ctx -- give equal bytes.
+   SDPSR_BAD_ARGUMENT, before any kernel, with the ctx usable afterwards: a NULL blk_sizes, classptr or nnz; NULL blks with
+   class_count > 0; a NULL entry array with capacity > 0; capacity < 0; nblocks < 1, some s_k < 1, class_count < 0; tol < 0 or NaN;
+   index_base or triangle outside their values; an element count that does not fit int64.  class_count == 0: SDPSR_OK,
+   classptr[0] = 0, *nnz = 0, no kernel.  Workspace that does not fit: SDPSR_OUT_OF_MEMORY.
+   sdpsr_transfer_bytes, host arrays: the window up; 16 bytes of result words, (class_count + 1) * 8 bytes of classptr and -- when
+   delivered -- *nnz * 20 bytes of entries down (never `capacity` of them).  Device arrays: nothing up, the 16 bytes down. */
+enum { SDPSR_TRI_UPPER = 0, SDPSR_TRI_FULL = 1 };
+int sdpsr_block_images_sparse(sdpsr_ctx* ctx, int32_t nblocks, const int32_t* blk_sizes, int64_t class_count, const void* blks,
+                              int is_complex, int triangle, double tol, int index_base, int64_t capacity, int64_t* classptr,
+                              int32_t* blk, int32_t* row, int32_t* col, double* val, int64_t* nnz, double* max_asym, int mem);
+
 /* eigen_decomposition(P, A; atol), src/eigen_decomposition.jl:236-273: status only
    (test/numerical_issues.jl:91-94), *neig = number of eigenspaces, *nclasses = number of
    isomorphism classes. */

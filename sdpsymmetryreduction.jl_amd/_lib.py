@@ -41,6 +41,7 @@ BASIS_IMAGE_KERNELS = {"auto": 0, "two_stage": 1, "outer": 2, "chunk": 3}
 # sdpsr_basis_image: *route
 BI_ROUTE_COMMUTATIVE, BI_ROUTE_BLOCKS, BI_ROUTE_TWO_STAGE, BI_ROUTE_OUTER, BI_ROUTE_CHUNK = 1, 2, 3, 4, 5
 BI_ROUTE_REPAIRED, BI_ROUTE_SHORTCUT_REFUSED = 0x100, 0x200
+TRI_UPPER, TRI_FULL = 0, 1  # sdpsr_block_images_sparse: triangle
 REFINE_PATHS = {"auto": 0, "hash": 1, "sort": 2, "bucket": 3, "no_mid": 4, "mid_no_first": 6}
 
 # sdpsr_set_label_width: the element type of a label array at each interface width (the reference's Partition{T})
@@ -163,6 +164,8 @@ def load_library():
         "sdpsr_block_sizes_complex": (C.c_int, [vp, vp]),
         "sdpsr_block_images_complex": (C.c_int, [vp, vp, vp, C.c_int]),
         "sdpsr_basis_image_complex": (C.c_int, [vp, i64, vp, i64, i32, vp, vp, i64, i64, dbl, vp, pi32, vp, C.c_int]),
+        "sdpsr_block_images_sparse": (C.c_int, [vp, i32, vp, i64, vp, C.c_int, C.c_int, dbl, C.c_int, i64, vp, vp, vp, vp, vp, pi64,
+                                                C.POINTER(C.c_double), C.c_int]),
         "sdpsr_eigen_decomposition_batched": (C.c_int, [vp, i64, vp, i64, dbl, i64, vp, vp, vp, vp, C.c_int]),
         "sdpsr_syev_f64": (C.c_int, [vp, i64, vp, vp, vp, C.c_int]),
         "sdpsr_hint_symmetric_basis": (C.c_int, [vp, C.c_int]),

@@ -959,7 +959,7 @@ def _q_hat_arg(Q_hat, n):
     return M, sizes
 
 
-def basis_image(Q_hat, P, classes=None, atol=None, ctx=None, return_route=False):
+def basis_image(Q_hat, P, classes=None, atol=None, ctx=None, return_route=False, _flat=False):
     """``basis_image(Q, P; atol)`` (src/diagonalize.jl:64-89) for a caller's ``Q_hat`` and a window of classes
     (``sdpsr_basis_image``): ``blks[i][k] = Q_k' 1[P == first + i] Q_k``.
 
@@ -983,7 +983,7 @@ def basis_image(Q_hat, P, classes=None, atol=None, ctx=None, return_route=False)
         raise ValueError(f"basis_image: classes = ({first}, {count}) is not a window of 1..{d}")
     S = sum(s * s for s in sizes)
     if _is_complex(M):
-        return _basis_image_complex(M, sizes, P, first, count, atol, ctx, return_route)
+        return _basis_image_complex(M, sizes, P, first, count, atol, ctx, return_route, _flat)
     lab, mem = _labels_arg(P, ctx)
     route = C.c_int32(0)
     if mem == L.MEM_DEVICE:
@@ -999,6 +999,8 @@ def basis_image(Q_hat, P, classes=None, atol=None, ctx=None, return_route=False)
     sz = np.asarray(sizes, dtype=np.int32)
     ctx.check(ctx._lib.sdpsr_basis_image(ctx._h, n, _ptr(lab), d, len(sizes), _ptr(sz), _ptr(q), first, count,
                                          -1.0 if atol is None else float(atol), _ptr(blks), C.byref(route), None, mem))
+    if _flat:  # basis_image_sparse: the window as the library wrote it, one flat array
+        return (blks[:count * S], route.value) if return_route else blks[:count * S]
     blks = blks[:count * S].reshape(count, S)
     out = []
     for i in range(count):
@@ -1011,7 +1013,7 @@ def basis_image(Q_hat, P, classes=None, atol=None, ctx=None, return_route=False)
     return (out, route.value) if return_route else out
 
 
-def _basis_image_complex(M, sizes, P, first, count, atol, ctx, return_route):
+def _basis_image_complex(M, sizes, P, first, count, atol, ctx, return_route, _flat=False):
     """``basis_image`` for a complex ``Q_hat`` (``sdpsr_basis_image_complex``): ``blks[i][k] = Q_k^H 1[P == first + i] Q_k``
     as complex128, nested like ``blockDiagonalize(..., complex=True).blks``; ``P`` need not be symmetric (the
     desymmetrized partition of the complex path is not).  On torch the blocks are views of one device tensor."""
@@ -1032,6 +1034,8 @@ def _basis_image_complex(M, sizes, P, first, count, atol, ctx, return_route):
     sz = np.asarray(sizes, dtype=np.int32)
     ctx.check(ctx._lib.sdpsr_basis_image_complex(ctx._h, n, _ptr(lab), d, len(sizes), _ptr(sz), _ptr(q), first, count,
                                                  -1.0 if atol is None else float(atol), _ptr(blks), C.byref(route), None, mem))
+    if _flat:  # basis_image_sparse: the window as the library wrote it, one flat array
+        return (blks[:count * S], route.value) if return_route else blks[:count * S]
     blks = blks[:count * S].reshape(count, S)
     out = []
     for i in range(count):
@@ -1042,6 +1046,175 @@ def _basis_image_complex(M, sizes, P, first, count, atol, ctx, return_route):
             off += s * s
         out.append(row)
     return (out, route.value) if return_route else out
+
+
+class SparseBlocks:
+    """Block images as solver triplets (``sdpsr_block_images_sparse``): the entries of window class ``i`` are
+    ``[classptr[i], classptr[i + 1])`` of ``blk`` / ``row`` / ``col`` (int32, shifted by ``index_base``) and ``val``, in the
+    scan order class, block, column-major inside the block.  ``sizes`` are the orders of the VIRTUAL blocks the indices
+    refer to: ``s_k`` for real images, ``2 s_k`` -- the real embedding ``[Re -Im; Im Re]`` -- for complex ones.  The arrays
+    are torch tensors when the input was one."""
+
+    def __init__(self, classptr, blk, row, col, val, sizes, nnz, upper=True, index_base=0):
+        self.classptr, self.blk, self.row, self.col, self.val = classptr, blk, row, col, val
+        self.sizes = [int(s) for s in sizes]
+        self.nnz = int(nnz)
+        self.upper = bool(upper)
+        self.index_base = int(index_base)
+
+    @property
+    def nclasses(self):
+        return int(self.classptr.shape[0]) - 1
+
+    @property
+    def cls(self):
+        """The window class of every entry (0-based plus ``index_base``), expanded from ``classptr``."""
+        if _is_torch(self.classptr):
+            import torch
+            ids = torch.arange(self.nclasses, dtype=torch.int64, device=self.classptr.device) + self.index_base
+            return torch.repeat_interleave(ids, self.classptr[1:] - self.classptr[:-1])
+        return np.repeat(np.arange(self.nclasses, dtype=np.int64) + self.index_base, np.diff(self.classptr))
+
+    def to_dense(self, mirror=False):
+        """``dense[i][k]``: the virtual block as a NumPy matrix with the entries put back where they came from (for tests);
+        ``mirror=True`` also writes every entry at its transposed position (the symmetric matrix an upper triangle stands for)."""
+        h = [np.asarray(a.cpu()) if _is_torch(a) else np.asarray(a) for a in (self.cls, self.blk, self.row, self.col, self.val)]
+        ci, bk, r, c = (a.astype(np.int64) - self.index_base for a in h[:4])
+        out = [[np.zeros((s, s)) for s in self.sizes] for _ in range(self.nclasses)]
+        for e in range(self.nnz):
+            out[ci[e]][bk[e]][r[e], c[e]] = h[4][e]
+            if mirror:
+                out[ci[e]][bk[e]][c[e], r[e]] = h[4][e]
+        return out
+
+
+def _flat_images(blks, sizes):
+    """One flat array (NumPy or torch, float64 / complex128) in the layout of ``sdpsr_block_images`` from a flat array or
+    from the nested ``blks[i][k]`` that ``basis_image`` / ``blockDiagonalize`` return."""
+    if _is_torch(blks):
+        import torch
+        return blks.reshape(-1).contiguous().to(torch.complex128 if blks.is_complex() else torch.float64)
+    if isinstance(blks, np.ndarray):
+        return np.ascontiguousarray(blks.reshape(-1), dtype=np.complex128 if np.iscomplexobj(blks) else np.float64)
+    rows = [list(r) for r in blks]
+    if any(len(r) != len(sizes) or any(tuple(b.shape) != (s, s) for b, s in zip(r, sizes)) for r in rows):
+        raise ValueError(f"block_images_sparse: every class has one s_k x s_k image per block, blkSizes = {list(sizes)}")
+    if rows and _is_torch(rows[0][0]):
+        import torch
+        cx = any(b.is_complex() for r in rows for b in r)
+        return torch.cat([b.t().reshape(-1) for r in rows for b in r]).to(torch.complex128 if cx else torch.float64).contiguous()
+    cx = any(np.iscomplexobj(b) for r in rows for b in r)
+    dt = np.complex128 if cx else np.float64
+    if not rows:
+        return np.empty(0, dtype=dt)
+    return np.concatenate([np.asarray(b, dtype=dt).ravel(order="F") for r in rows for b in r])
+
+
+def block_images_sparse(blks, blkSizes, upper=True, tol=0.0, index_base=0, ctx=None, return_asym=False):
+    """The PSD blocks as solver triplets (``sdpsr_block_images_sparse``): compacts dense block images, on the device and in
+    order, into the entries ``(class, block, row, col, value)`` with ``!(|value| <= tol)``.
+
+    ``blks``: a flat NumPy array or torch device tensor in the layout of ``sdpsr_block_images`` (class-major, then block,
+    each block column-major), or the nested ``blks[i][k]`` of ``basis_image`` / ``blockDiagonalize``; ``blkSizes``: the
+    ``s_k``.  Complex images (by dtype) are taken as their real embedding ``[Re -Im; Im Re]`` of order ``2 s_k``
+    (docs/src/examples/ReduceAndSolveJuMP.jl:59-76 of the reference).  ``upper=True`` keeps ``row <= col`` only.  Returns
+    a ``SparseBlocks``; with ``return_asym=True`` the pair ``(SparseBlocks, max |M[r,c] - M[c,r]|)`` -- what the upper
+    triangle gives up."""
+    ctx = _ctx(ctx)
+    sizes = [int(s) for s in blkSizes]
+    if not sizes or any(s < 1 for s in sizes):
+        raise ValueError(f"block_images_sparse: block sizes must be >= 1, got {sizes}")
+    S = sum(s * s for s in sizes)
+    flat = _flat_images(blks, sizes)
+    dev = _is_torch(flat)
+    cx = bool(_is_complex(flat))
+    total = int(flat.numel() if dev else flat.size)
+    if total % S:
+        raise ValueError(f"block_images_sparse: {total} elements are no multiple of sum s_k^2 = {S}")
+    count = total // S
+    sz = np.asarray(sizes, dtype=np.int32)
+    mem = L.MEM_DEVICE if dev else L.MEM_HOST
+    tri = L.TRI_UPPER if upper else L.TRI_FULL
+    if dev:
+        import torch
+        if not flat.is_cuda:
+            raise TypeError("block_images_sparse takes a torch tensor on the device (or a NumPy array)")
+        classptr = torch.empty(count + 1, dtype=torch.int64, device=flat.device)
+        ctx.wait_for(flat, classptr)
+    else:
+        classptr = np.empty(count + 1, dtype=np.int64)
+    nnz, asym = C.c_int64(0), C.c_double(0.0)
+    fn = ctx._lib.sdpsr_block_images_sparse
+    src = _ptr(flat) if count else None
+    ctx.check(fn(ctx._h, len(sizes), _ptr(sz), count, src, int(cx), tri, float(tol), int(index_base), 0, _ptr(classptr),
+                 None, None, None, None, C.byref(nnz), C.byref(asym) if return_asym else None, mem))
+    m = nnz.value
+    if dev:
+        blk, row, col = (torch.empty(m, dtype=torch.int32, device=flat.device) for _ in range(3))
+        val = torch.empty(m, dtype=torch.float64, device=flat.device)
+        ctx.wait_for(blk, row, col, val)
+    else:
+        blk, row, col = (np.empty(m, dtype=np.int32) for _ in range(3))
+        val = np.empty(m, dtype=np.float64)
+    if m:
+        ctx.check(fn(ctx._h, len(sizes), _ptr(sz), count, src, int(cx), tri, float(tol), int(index_base), m, _ptr(classptr),
+                     _ptr(blk), _ptr(row), _ptr(col), _ptr(val), C.byref(nnz), None, mem))
+    out = SparseBlocks(classptr, blk, row, col, val, [2 * s if cx else s for s in sizes], m, upper, index_base)
+    return (out, asym.value) if return_asym else out
+
+
+def _device_partition(P, ctx):
+    """``P`` with its labels on the context's device (a torch tensor at the context's label width); ``P`` itself when it
+    is there already."""
+    if _is_torch(P.matrix):
+        return P
+    import torch
+    n = P.shape[0]
+    flat = _lab(P.matrix, ctx)  # column-major
+    signed = {8: np.uint8, 16: np.uint16 if hasattr(torch, "uint16") else np.int16, 32: np.int32}[ctx.label_width]
+    t = torch.from_numpy(flat.view(signed)).to(torch.device("cuda", ctx.device))
+    return Partition(P.nparts, t.view(n, n).t())  # _labels_arg reads the transposed view back as this flat buffer
+
+
+def basis_image_sparse(Q_hat, P, parts=1, classes=None, atol=None, upper=True, tol=0.0, ctx=None, index_base=0):
+    """``basis_image`` delivered as solver triplets: the classes (``classes = (first, count)``, default all) are cut into
+    ``parts`` windows (``class_window``), each window's dense slab is made by ``basis_image`` and stays on the device, is
+    compacted there (``block_images_sparse``) and only its entries are kept: peak dense memory is one slab, however large
+    ``d * sum s_k^2`` is.  ``classptr`` of the result runs over all ``count`` classes.  Arguments as ``basis_image`` and
+    ``block_images_sparse``; the arrays of the result are torch tensors when ``P`` is device-resident, else NumPy."""
+    ctx = _ctx(ctx)
+    d = int(P.nparts)
+    first, count = (1, d) if classes is None else (int(classes[0]), int(classes[1]))
+    if count < 0 or (count > 0 and (first < 1 or first + count - 1 > d)):
+        raise ValueError(f"basis_image_sparse: classes = ({first}, {count}) is not a window of 1..{d}")
+    M, sizes = _q_hat_arg(Q_hat, P.shape[0])
+    cx = bool(_is_complex(M))
+    to_host = not _is_torch(P.matrix)
+    Pd = _device_partition(P, ctx)
+    import torch
+    dev = Pd.matrix.device
+    if not _is_torch(M):
+        M = torch.from_numpy(np.asarray(M, dtype=np.complex128 if cx else np.float64)).to(dev)
+    ptr = [torch.zeros(1, dtype=torch.int64, device=dev)]
+    pieces = {k: [] for k in ("blk", "row", "col", "val")}
+    nnz = 0
+    for j in range(int(parts)):
+        f, cnt = class_window(count, parts, j)
+        if cnt == 0:
+            continue
+        slab = basis_image((M, sizes), Pd, classes=(first + f - 1, cnt), atol=atol, ctx=ctx, _flat=True)
+        sp = block_images_sparse(slab, sizes, upper=upper, tol=tol, index_base=index_base, ctx=ctx)
+        del slab
+        ptr.append(sp.classptr[1:] + nnz)
+        nnz += sp.nnz
+        for k in pieces:
+            pieces[k].append(getattr(sp, k))
+    cat = {k: torch.cat(v) if v else torch.empty(0, dtype=torch.float64 if k == "val" else torch.int32, device=dev) for k, v in pieces.items()}
+    cp = torch.cat(ptr)
+    if to_host:
+        cp = cp.cpu().numpy()
+        cat = {k: v.cpu().numpy() for k, v in cat.items()}
+    return SparseBlocks(cp, cat["blk"], cat["row"], cat["col"], cat["val"], [2 * s if cx else s for s in sizes], nnz, upper, index_base)
 
 
 def _block_diagonalize_complex(P, verbose, epsilon, ctx, retries):

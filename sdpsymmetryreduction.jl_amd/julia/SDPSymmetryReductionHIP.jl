@@ -326,6 +326,35 @@ function basis_image(Q_hat::AbstractVector{<:AbstractMatrix{ComplexF64}}, P::HIP
     return route ? (blks, Int(rt[])) : blks
 end
 
+# ---- block images as solver triplets (sdpsr_block_images_sparse; README.md:72-79, ReduceAndSolveJuMP.jl:56-84) ----
+# blks: the nested blks[i][k] of basis_image / blockDiagonalize (real, or ComplexF64: taken as the real embedding [re -im; im re]
+# of order 2 s_k, ReduceAndSolveJuMP.jl:59-76).  Returns the named tuple (classptr, blk, row, col, val, sizes): the entries of
+# class i (1-based) are classptr[i]+1 : classptr[i+1]; blk / row / col are 1-based; sizes are the orders the indices refer to.
+# upper=true keeps row <= col only; entries with !(|v| <= tol) are kept, in the order class, block, column-major.
+function block_images_sparse(blks::AbstractVector{<:AbstractVector{<:AbstractMatrix{T}}}; upper::Bool=true,
+                             tol::Real=0.0) where {T<:Union{Float64,ComplexF64}}
+    cx = ctx()
+    count = Int64(length(blks))
+    sizes = count == 0 ? Int32[1] : Int32[size(b, 1) for b in blks[1]]
+    flat = T[]
+    for row in blks, b in row
+        append!(flat, vec(Matrix{T}(b)))
+    end
+    isc = T === ComplexF64 ? Cint(1) : Cint(0)
+    classptr = Vector{Int64}(undef, count + 1)
+    nnz = Ref{Int64}(0)
+    sig = (Ptr{Cvoid}, Int32, Ptr{Int32}, Int64, Ptr{Cvoid}, Cint, Cint, Float64, Cint, Int64, Ptr{Int64}, Ptr{Int32}, Ptr{Int32},
+           Ptr{Int32}, Ptr{Float64}, Ref{Int64}, Ptr{Float64}, Cint)
+    tri = upper ? Cint(0) : Cint(1)   # SDPSR_TRI_UPPER / SDPSR_TRI_FULL
+    check(cx, ccall((:sdpsr_block_images_sparse, libsdpsr), Cint, sig, cx.handle, length(sizes), sizes, count, flat, isc, tri,
+                    Float64(tol), Cint(1), 0, classptr, C_NULL, C_NULL, C_NULL, C_NULL, nnz, C_NULL, MEM_HOST))   # sizing call
+    m = nnz[]
+    blk = Vector{Int32}(undef, m); row = Vector{Int32}(undef, m); col = Vector{Int32}(undef, m); val = Vector{Float64}(undef, m)
+    m > 0 && check(cx, ccall((:sdpsr_block_images_sparse, libsdpsr), Cint, sig, cx.handle, length(sizes), sizes, count, flat, isc,
+                             tri, Float64(tol), Cint(1), m, classptr, blk, row, col, val, nnz, C_NULL, MEM_HOST))
+    return (classptr=classptr, blk=blk, row=row, col=col, val=val, sizes=(T === ComplexF64 ? 2 .* sizes : sizes))
+end
+
 # ---- blockDiagonalize(ComplexF64, P) (compat.jl:26-32,54-57; n <= 3072 in this library version) ---
 function SR.blockDiagonalize(::Type{ComplexF64}, P::HIPPartition, verbose=true;
                              epsilon=Base.rtoldefault(Float64))
