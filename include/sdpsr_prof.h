@@ -71,6 +71,48 @@ int sdpsr_profile_gather_packed(sdpsr_ctx* ctx, int64_t n, int T, int64_t d, uin
 int sdpsr_profile_verify(sdpsr_ctx* ctx, int64_t n, int T, int64_t d, int mode, const uint32_t* Lp_host, const uint32_t* first_idx_host,
                          const int32_t* C_host, const double* U_host, double coef, uint64_t key, double atol, uint32_t* out);
 
+/* ---- The kernels of the module-compression driver on caller-made inputs (tests/test_gpu_module_kernels.py). ----
+   All matrices are column-major host arrays of doubles; labels are n x n uint32, column-major.  Every *_inout array is uploaded as the caller
+   filled it, handed to the product's own launcher the way the driver calls it, and downloaded WHOLE -- padding and the `guard` elements behind
+   it included -- so that what no kernel wrote comes back as it went in.  Nothing is measured.  SDPSR_BAD_ARGUMENT, before anything is uploaded
+   or launched, for: a null pointer, a dimension < 1 or above its cap (n, k <= 8192; leading dimensions <= 16384; guard <= 2^20), a leading
+   dimension smaller than the rows it strides, a label > d. */
+
+/* C = A' B.  A_host: lda x mp (k rows and ma columns used), B_host: ldb x np (k rows, nb columns), C_inout: mp * np + guard, leading
+   dimension mp; ma <= mp <= 256, nb <= np <= 256.  mode 0: gram_tn as Module::ortho_step / make_element call it, result padded to mp x np;
+   when the shape takes the split-K route, mp, np, k, lda and ldb must be multiples of 128 and the route multiplies ALL mp, np columns.
+   mode 1: launch_gram_small itself with ldc = mp (the exact-shape result ldc = mp = ma, np = nb of the small host tail); refused for a
+   shape the exact-shape kernel does not take.  pinned_inout (optional, like C_inout): goes through the ctx's pinned host memory, which the
+   exact-shape kernel stores the result into as well.  report[0] = 1: the exact-shape (skinny) kernel ran, 0: split-K; report[1] = 1 when the
+   pinned copy was filled. */
+int sdpsr_profile_gram(sdpsr_ctx* ctx, int mode, int64_t k, int64_t ma, int64_t nb, int64_t lda, int64_t ldb, int64_t mp, int64_t np,
+                       const double* A_host, const double* B_host, double* C_inout, double* pinned_inout, int64_t guard, int32_t* report);
+/* out[:, c] = beta out[:, c] + alpha In S[:, c] through launch_tall_times_small.  In_host: ldi x kk (n rows used), S_host: lds x ncols
+   (kk rows used), out_inout: ldo * ncols + guard; kk, ncols <= 512, lds <= 1024. */
+int sdpsr_profile_tall_times_small(sdpsr_ctx* ctx, int64_t n, int64_t ldi, int64_t kk, int64_t lds, int64_t ncols, double alpha, double beta,
+                                   int64_t ldo, const double* In_host, const double* S_host, double* out_inout, int64_t guard);
+/* The label product Y[:, g w + j] = A(keys[g]) W[:, j] through launch_label_spmm_multi (launch_label_spmm when G == 1).  L_host: labels
+   <= d; W_host: ldw x 64 (w columns used); Y_inout: ldy * G * w + guard.  SDPSR_BAD_ARGUMENT where the launcher refuses the shape (G = 3, G w > 64, d > 4000,
+   a class table too large for LDS).  report = the form that ran, from the function the launcher itself asks: [0] = 1 matrix cores
+   (label_spmm_mfma_kernel<JT, G>) or 0 VALU (label_spmm_sload_kernel<WMAX, G>), [1] = JT resp. WMAX, [2] = the column split z,
+   [3] = columns per workgroup. */
+int sdpsr_profile_label_product(sdpsr_ctx* ctx, int64_t n, int64_t d, int G, int64_t w, int64_t ldw, int64_t ldy, const uint64_t* keys,
+                                const uint32_t* L_host, const double* W_host, double* Y_inout, int64_t guard, int32_t* report);
+/* Class sums of one vector, out[(i - 1) ldo + r] = sum over c with L[c + r n] == i of x[c], through launch_class_sums with first = 1;
+   d <= 4000, out_inout: ldo * d + guard.  report[0] = class_sums_supports(n, d, ldo) -- when 0, nothing ran (as in the driver) --,
+   report[1] = 1: the kernel with per-lane tables in LDS, 0: the row-sort fallback (ldo == n only). */
+int sdpsr_profile_class_sums(sdpsr_ctx* ctx, int64_t n, int64_t d, int64_t ldo, const uint32_t* L_host, const double* x_host,
+                             double* out_inout, int64_t guard, int32_t* report);
+/* The glue kernels.  symmetrize: B <- (B + B') / 2 on the leading m x m of B_inout (ld * m + guard; m <= 1024, ld <= 2048).
+   extract_symmetric: dst_inout (mp * mp + guard, dense mp x mp, mp <= 1024) <- the symmetric part of the leading m x m of src_host
+   (lds x m), zero elsewhere.  normalize_columns: H[r hstride + i] = X[i + r ldx] / |X[:, r]|, norm[r] = |X[:, r]| for nruns <= 64 runs
+   (H_inout: hstride (nruns - 1) + n + guard, norm_inout: nruns + guard).  random_vector: x[i] = 2 u(key, i + 1) - 1 (x_inout: n + guard). */
+int sdpsr_profile_symmetrize(sdpsr_ctx* ctx, int64_t m, int64_t ld, double* B_inout, int64_t guard);
+int sdpsr_profile_extract_symmetric(sdpsr_ctx* ctx, int64_t m, int64_t mp, int64_t lds, const double* src_host, double* dst_inout, int64_t guard);
+int sdpsr_profile_normalize_columns(sdpsr_ctx* ctx, int64_t n, int64_t ldx, int64_t hstride, int64_t nruns, const double* X_host,
+                                    double* H_inout, double* norm_inout, int64_t guard);
+int sdpsr_profile_random_vector(sdpsr_ctx* ctx, int64_t n, uint64_t key, double* x_inout, int64_t guard);
+
 #ifdef __cplusplus
 }
 #endif

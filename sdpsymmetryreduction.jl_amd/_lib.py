@@ -226,5 +226,23 @@ def load_prof_library():
     lib.sdpsr_profile_verify.restype = C.c_int
     lib.sdpsr_profile_verify.argtypes = [vp, i64, C.c_int, i64, C.c_int, vp, vp, vp, vp, C.c_double, C.c_uint64, C.c_double,
                                          C.POINTER(C.c_uint32)]
+    # the module-compression kernels on caller-made inputs (tests)
+    f64, rep = C.c_double, C.POINTER(C.c_int32)
+    lib.sdpsr_profile_gram.restype = C.c_int
+    lib.sdpsr_profile_gram.argtypes = [vp, C.c_int, i64, i64, i64, i64, i64, i64, i64, vp, vp, vp, vp, i64, rep]
+    lib.sdpsr_profile_tall_times_small.restype = C.c_int
+    lib.sdpsr_profile_tall_times_small.argtypes = [vp, i64, i64, i64, i64, i64, f64, f64, i64, vp, vp, vp, i64]
+    lib.sdpsr_profile_label_product.restype = C.c_int
+    lib.sdpsr_profile_label_product.argtypes = [vp, i64, i64, C.c_int, i64, i64, i64, vp, vp, vp, vp, i64, rep]
+    lib.sdpsr_profile_class_sums.restype = C.c_int
+    lib.sdpsr_profile_class_sums.argtypes = [vp, i64, i64, i64, vp, vp, vp, i64, rep]
+    lib.sdpsr_profile_symmetrize.restype = C.c_int
+    lib.sdpsr_profile_symmetrize.argtypes = [vp, i64, i64, vp, i64]
+    lib.sdpsr_profile_extract_symmetric.restype = C.c_int
+    lib.sdpsr_profile_extract_symmetric.argtypes = [vp, i64, i64, i64, vp, vp, i64]
+    lib.sdpsr_profile_normalize_columns.restype = C.c_int
+    lib.sdpsr_profile_normalize_columns.argtypes = [vp, i64, i64, i64, i64, vp, vp, vp, i64]
+    lib.sdpsr_profile_random_vector.restype = C.c_int
+    lib.sdpsr_profile_random_vector.argtypes = [vp, i64, C.c_uint64, vp, i64]
     _prof = lib
     return lib

@@ -32,14 +32,24 @@ int gemm_tn_splitk(sdpsr_ctx* c, int64_t m, int64_t n, int64_t k, const double* 
     return SDPSR_OK;
 }
 
-// C = A' B of the exact shape ma x nb (A: k x ma, B: k x nb) into the mp x np padded result (zero
-// outside ma x nb): the skinny Gram kernel when both operands fit its LDS stage, the padded split-K
-// MFMA product otherwise.
+// The route of gram_tn: true when both operands fit the LDS stage of the skinny Gram kernel (32 rows of each, pitch = the
+// columns rounded up to 16, + 1; (128, 112) is the last shape that fits 64 KiB), false for the padded split-K MFMA product.
+bool gram_tn_is_skinny(int64_t ma, int64_t nb) {
+    const int64_t pa = (ma + 15) / 16 * 16 + 1, pb = (nb + 15) / 16 * 16 + 1;
+    return ma >= 1 && nb >= 1 && ma <= 128 && nb <= 128 && 32 * (pa + pb) * 8 <= 64 * 1024;
+}
+
+// C = A' B of the exact shape ma x nb (A: k x ma, B: k x nb) into the mp x np padded result, zero
+// outside ma x nb: the skinny Gram kernel when both operands fit its LDS stage (gram_tn_is_skinny), the padded
+// split-K MFMA product otherwise.  The two routes keep "zero outside ma x nb" differently.  The skinny kernel
+// reads the columns < ma of A and < nb of B only and WRITES the zeros.  The split-K product multiplies all
+// mp columns of A by all np columns of B (mp, np multiples of 128, k a multiple of 128): its padding is the
+// product of the operands' padding columns, so there the caller must hold A zero in columns ma..mp and B zero in
+// columns nb..np (compress.cpp clears W and T before it fills them).
 int gram_tn(sdpsr_ctx* c, int64_t ma, int64_t nb, int64_t k, const double* A, int64_t lda, const double* B, int64_t ldb,
             double* C, int64_t mp, int64_t np, double* host_C, bool* host_filled) {
     if (host_filled) *host_filled = false;
-    const int64_t pa = (ma + 15) / 16 * 16 + 1, pb = (nb + 15) / 16 * 16 + 1;
-    if (ma >= 1 && nb >= 1 && ma <= 128 && nb <= 128 && 32 * (pa + pb) * 8 <= 64 * 1024) {
+    if (gram_tn_is_skinny(ma, nb)) {
         double* P = (double*)ctx_buf(c, "gram_partials", gram_small_partial_doubles(k, (int)ma, (int)nb) * 8);
         if (!P) return SDPSR_OUT_OF_MEMORY;
         launch_gram_small(c->stream, k, (int)ma, (int)nb, A, lda, B, ldb, P, C, mp, (int)mp, (int)np, host_C);

@@ -331,6 +331,7 @@ int gemm_tn_splitk(sdpsr_ctx* c, int64_t m, int64_t n, int64_t k, const double* 
                    double* C, int64_t ldc, const char* partials = "splitk_partials");
 // host_C (optional, pinned host memory, mp x np like C): filled by the product itself when the exact-shape kernel
 // runs; *host_filled says whether it did (the padded split-K path does not)
+bool gram_tn_is_skinny(int64_t ma, int64_t nb);  // the route gram_tn takes: the exact-shape kernel (true) or split-K
 int gram_tn(sdpsr_ctx* c, int64_t ma, int64_t nb, int64_t k, const double* A, int64_t lda, const double* B, int64_t ldb, double* C,
             int64_t mp, int64_t np, double* host_C = nullptr, bool* host_filled = nullptr);
 int compressed_diagonalize(sdpsr_ctx* c, int64_t n, const uint32_t* L, int64_t d, double atol, EigInfo& info,

@@ -568,11 +568,11 @@ size_t label_spmm_partial_doubles(int64_t n, int w) {
     return (size_t)zg * n * 64 + (size_t)(n + 8 + 4 * 128) * 80;
 }
 
-// returns false when the shape is not supported (w > 64 or the class table does not fit in LDS).
-// G keys: Y gets G blocks of w columns (G w <= 64).
-bool launch_label_spmm_multi(hipStream_t s, int64_t n, const uint32_t* L, const uint64_t* keys, int G, int64_t d, const double* W,
-                             int64_t ldw, int w, double* partials, double* Y, int64_t ldy) {
-    if (w < 1 || G < 1 || G > 4 || G == 3 || G * w > 64 || d > 4000 || (size_t)G * (d + 2) * 8 > 64 * 1024) return false;
+// The form of the label product for a shape, chosen in ONE place: the launcher below launches what this returns, and the
+// test entry point (prof/prof.cpp) reports it.  Pure host arithmetic.  false: the shape is not supported (w > 64, G not
+// 1, 2 or 4, G w > 64, or the class table does not fit in LDS).
+bool label_spmm_select(int64_t n, int64_t d, int G, int w, LabelSpmmForm* f) {
+    if (n < 1 || d < 0 || w < 1 || G < 1 || G > 4 || G == 3 || G * w > 64 || d > 4000 || (size_t)G * (d + 2) * 8 > 64 * 1024) return false;
     const int rb = (int)((n + 63) / 64);
     int zg = 2048 / rb;
     if (zg < 1) zg = 1;
@@ -608,65 +608,81 @@ bool launch_label_spmm_multi(hipStream_t s, int64_t n, const uint32_t* L, const 
             }
         }
         if (best_zg && lds <= (JT == 4 ? 150 : 64) * 1024) {
-            double* Wt = partials + (size_t)zg_cap * n * 64;
-            const int64_t rows = (int64_t)best_zg * best_cpb + SPMM_SLAB;
-            transpose_w_rowmajor_kernel<<<dim3((unsigned)((rows + 31) / 32), (unsigned)((stride + 31) / 32)), dim3(32, 8), 0, s>>>(
-                (int)n, rows, w, stride, W, ldw, Wt);
-            SpmmKeys kk;
-            for (int i = 0; i < 4; ++i) kk.k[i] = keys[i < G ? i : 0];
-            dim3 g((unsigned)rb, (unsigned)best_zg);
-            auto go = [&](auto kern) { kern<<<g, 256, lds, s>>>((int)n, L, kk, (int)d, Wt, w, best_cpb, partials); };
-            if (G == 1) {
-                if (JT == 1) go(label_spmm_mfma_kernel<1, 1>);
-                else if (JT == 2) go(label_spmm_mfma_kernel<2, 1>);
-                else if (JT == 3) go(label_spmm_mfma_kernel<3, 1>);
-                else go(label_spmm_mfma_kernel<4, 1>);
-            } else if (G == 2) {
-                if (JT == 1) go(label_spmm_mfma_kernel<1, 2>);
-                else go(label_spmm_mfma_kernel<2, 2>);
-            } else {
-                go(label_spmm_mfma_kernel<1, 4>);
-            }
-            const int wt = G * w;
-            int64_t gr = ((int64_t)n * wt + 255) / 256;
-            if (gr > 2048) gr = 2048;
-            label_spmm_reduce_kernel<<<(unsigned)gr, 256, 0, s>>>((int)n, wt, best_zg, partials, Y, ldy);
+            f->mfma = 1, f->tile = JT, f->z = best_zg, f->cols_per_block = best_cpb;
             return true;
         }
     }
     int cpb = (int)((n + zg - 1) / zg);
     cpb = (cpb + 7) / 8 * 8;  // the kernel walks its columns in steps of 8 (rounding to 128 halved the grid at n = 4104)
     zg = (int)((n + cpb - 1) / cpb);
-    dim3 g((unsigned)rb, (unsigned)zg);
+    f->mfma = 0, f->z = zg, f->cols_per_block = cpb;
+    if (G == 1) f->tile = w <= 8 ? 8 : w <= 16 ? 16 : w <= 32 ? 32 : w <= 48 ? 48 : 64;
+    else if (G == 2) f->tile = w <= 8 ? 8 : w <= 16 ? 16 : 32;
+    else f->tile = w <= 8 ? 8 : 16;
+    return true;
+}
+
+// returns false when the shape is not supported (label_spmm_select).  G keys: Y gets G blocks of w columns (G w <= 64).
+bool launch_label_spmm_multi(hipStream_t s, int64_t n, const uint32_t* L, const uint64_t* keys, int G, int64_t d, const double* W,
+                             int64_t ldw, int w, double* partials, double* Y, int64_t ldy) {
+    LabelSpmmForm f;
+    if (!label_spmm_select(n, d, G, w, &f)) return false;
+    const int rb = (int)((n + 63) / 64);
+    int zg_cap = 2048 / rb;
+    if (zg_cap < 1) zg_cap = 1;
+    if (zg_cap > 32) zg_cap = 32;
     // transposed zero-padded copy of W behind the partial sums (label_spmm_partial_doubles leaves room)
     double* Wt = partials + (size_t)zg_cap * n * 64;
-    const int npad = (int)n + 8;
     SpmmKeys kk;
     for (int i = 0; i < 4; ++i) kk.k[i] = keys[i < G ? i : 0];
-    auto go = [&](auto kern, int wmax) {
-        transpose_pad_w_kernel<<<(unsigned)std::min<int64_t>(((int64_t)npad * wmax + 255) / 256, 2048), 256, 0, s>>>(
-            (int)n, npad, w, wmax / 4, W, ldw, Wt);
-        const size_t lds = (size_t)G * ((size_t)d + 2) * sizeof(double);
-        kern<<<g, 256, lds, s>>>((int)n, npad, L, kk, (int)d, Wt, w, cpb, partials);
-    };
-    if (G == 1) {
-        if (w <= 8) go(label_spmm_sload_kernel<8, 1>, 8);
-        else if (w <= 16) go(label_spmm_sload_kernel<16, 1>, 16);
-        else if (w <= 32) go(label_spmm_sload_kernel<32, 1>, 32);
-        else if (w <= 48) go(label_spmm_sload_kernel<48, 1>, 48);
-        else go(label_spmm_sload_kernel<64, 1>, 64);
-    } else if (G == 2) {
-        if (w <= 8) go(label_spmm_sload_kernel<8, 2>, 8);
-        else if (w <= 16) go(label_spmm_sload_kernel<16, 2>, 16);
-        else go(label_spmm_sload_kernel<32, 2>, 32);
+    dim3 g((unsigned)rb, (unsigned)f.z);
+    if (f.mfma) {
+        const int JT = f.tile;
+        const int stride = spmm_stride(JT);
+        const size_t lds = (size_t)G * ((d + 2) & ~(int64_t)1) * 8 + (size_t)2 * SPMM_SLAB * stride * 8;
+        const int64_t rows = (int64_t)f.z * f.cols_per_block + SPMM_SLAB;
+        transpose_w_rowmajor_kernel<<<dim3((unsigned)((rows + 31) / 32), (unsigned)((stride + 31) / 32)), dim3(32, 8), 0, s>>>(
+            (int)n, rows, w, stride, W, ldw, Wt);
+        auto go = [&](auto kern) { kern<<<g, 256, lds, s>>>((int)n, L, kk, (int)d, Wt, w, f.cols_per_block, partials); };
+        if (G == 1) {
+            if (JT == 1) go(label_spmm_mfma_kernel<1, 1>);
+            else if (JT == 2) go(label_spmm_mfma_kernel<2, 1>);
+            else if (JT == 3) go(label_spmm_mfma_kernel<3, 1>);
+            else go(label_spmm_mfma_kernel<4, 1>);
+        } else if (G == 2) {
+            if (JT == 1) go(label_spmm_mfma_kernel<1, 2>);
+            else go(label_spmm_mfma_kernel<2, 2>);
+        } else {
+            go(label_spmm_mfma_kernel<1, 4>);
+        }
     } else {
-        if (w <= 8) go(label_spmm_sload_kernel<8, 4>, 8);
-        else go(label_spmm_sload_kernel<16, 4>, 16);
+        const int npad = (int)n + 8;
+        auto go = [&](auto kern, int wmax) {
+            transpose_pad_w_kernel<<<(unsigned)std::min<int64_t>(((int64_t)npad * wmax + 255) / 256, 2048), 256, 0, s>>>(
+                (int)n, npad, w, wmax / 4, W, ldw, Wt);
+            const size_t lds = (size_t)G * ((size_t)d + 2) * sizeof(double);
+            kern<<<g, 256, lds, s>>>((int)n, npad, L, kk, (int)d, Wt, w, f.cols_per_block, partials);
+        };
+        const int wm = f.tile;
+        if (G == 1) {
+            if (wm == 8) go(label_spmm_sload_kernel<8, 1>, 8);
+            else if (wm == 16) go(label_spmm_sload_kernel<16, 1>, 16);
+            else if (wm == 32) go(label_spmm_sload_kernel<32, 1>, 32);
+            else if (wm == 48) go(label_spmm_sload_kernel<48, 1>, 48);
+            else go(label_spmm_sload_kernel<64, 1>, 64);
+        } else if (G == 2) {
+            if (wm == 8) go(label_spmm_sload_kernel<8, 2>, 8);
+            else if (wm == 16) go(label_spmm_sload_kernel<16, 2>, 16);
+            else go(label_spmm_sload_kernel<32, 2>, 32);
+        } else {
+            if (wm == 8) go(label_spmm_sload_kernel<8, 4>, 8);
+            else go(label_spmm_sload_kernel<16, 4>, 16);
+        }
     }
     const int wt = G * w;
     int64_t gr = ((int64_t)n * wt + 255) / 256;
     if (gr > 2048) gr = 2048;
-    label_spmm_reduce_kernel<<<(unsigned)gr, 256, 0, s>>>((int)n, wt, zg, partials, Y, ldy);
+    label_spmm_reduce_kernel<<<(unsigned)gr, 256, 0, s>>>((int)n, wt, f.z, partials, Y, ldy);
     return true;
 }
 bool launch_label_spmm(hipStream_t s, int64_t n, const uint32_t* L, uint64_t key, int64_t d, const double* W,

@@ -254,6 +254,213 @@ extern "C" int sdpsr_profile_verify(sdpsr_ctx* c, int64_t n, int T, int64_t d, i
     return SDPSR_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// The kernels of the module-compression driver on caller-made inputs (tests/test_gpu_module_kernels.py): host arrays in, the
+// product's own launcher called the way compress.cpp calls it, everything back.  Every output array is in/out: uploaded as the
+// caller filled it and downloaded whole (padding and `guard` elements behind it included), so what no kernel wrote is visible.
+// Every argument that could index outside a buffer is refused before anything is uploaded or launched.
+// ---------------------------------------------------------------------------------------------------------------------------
+namespace {
+constexpr int64_t MK_MAX_N = 8192, MK_MAX_LD = 16384, MK_MAX_GUARD = 1 << 20;
+bool mk_labels_ok(const uint32_t* L, size_t len, int64_t d) {
+    for (size_t e = 0; e < len; ++e)
+        if ((int64_t)L[e] > d) return false;
+    return true;
+}
+}  // namespace
+
+extern "C" int sdpsr_profile_gram(sdpsr_ctx* c, int mode, int64_t k, int64_t ma, int64_t nb, int64_t lda, int64_t ldb, int64_t mp, int64_t np,
+                                  const double* A_host, const double* B_host, double* C_inout, double* pinned_inout, int64_t guard, int32_t* report) {
+    CHECK_CTX(c);
+    if (!A_host || !B_host || !C_inout || !report || (mode != 0 && mode != 1) || k < 1 || k > MK_MAX_N || ma < 1 || nb < 1 || mp < ma || np < nb ||
+        mp > 256 || np > 256 || lda < k || ldb < k || lda > MK_MAX_LD || ldb > MK_MAX_LD || guard < 0 || guard > MK_MAX_GUARD)
+        return ctx_fail(c, SDPSR_BAD_ARGUMENT, "gram: bad arguments");
+    const bool skinny = gram_tn_is_skinny(ma, nb);
+    if (mode == 1 && !skinny) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "gram: the exact-shape kernel does not take this shape");
+    // the split-K route is the tiled MFMA product over all mp x np columns: whole tiles, K in tiles, aligned columns
+    if (mode == 0 && !skinny && (mp % 128 || np % 128 || k % 128 || lda % 128 || ldb % 128))
+        return ctx_fail(c, SDPSR_BAD_ARGUMENT, "gram: the split-K route needs mp, np, k, lda, ldb in multiples of 128");
+    hipStream_t s = c->stream;
+    const size_t cn = (size_t)(mp * np + guard);
+    double* A = (double*)ctx_buf(c, "prof_mk_a", (size_t)lda * mp * 8);
+    double* B = (double*)ctx_buf(c, "prof_mk_b", (size_t)ldb * np * 8);
+    double* Cd = (double*)ctx_buf(c, "prof_mk_c", cn * 8);
+    double* gp = mode == 1 ? (double*)ctx_buf(c, "gram_partials", gram_small_partial_doubles(k, (int)ma, (int)nb) * 8) : nullptr;
+    double* pin = pinned_inout ? (double*)ctx_pinned(c, cn * 8) : nullptr;
+    if (!A || !B || !Cd || (mode == 1 && !gp) || (pinned_inout && !pin)) return SDPSR_OUT_OF_MEMORY;
+    if (pin) memcpy(pin, pinned_inout, cn * 8);
+    HIP_TRY(c, hipMemcpyAsync(A, A_host, (size_t)lda * mp * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(B, B_host, (size_t)ldb * np * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(Cd, C_inout, cn * 8, hipMemcpyHostToDevice, s));
+    bool host_filled = false;
+    if (mode == 0) {
+        const int st = gram_tn(c, ma, nb, k, A, lda, B, ldb, Cd, mp, np, pin, &host_filled);
+        if (st) return st;
+    } else {
+        launch_gram_small(s, k, (int)ma, (int)nb, A, lda, B, ldb, gp, Cd, mp, (int)mp, (int)np, pin);
+        host_filled = pin != nullptr;
+    }
+    HIP_TRY(c, hipMemcpyAsync(C_inout, Cd, cn * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, hipGetLastError());
+    if (pin) memcpy(pinned_inout, pin, cn * 8);
+    report[0] = skinny ? 1 : 0;
+    report[1] = host_filled ? 1 : 0;
+    return SDPSR_OK;
+}
+
+extern "C" int sdpsr_profile_tall_times_small(sdpsr_ctx* c, int64_t n, int64_t ldi, int64_t kk, int64_t lds, int64_t ncols, double alpha, double beta,
+                                              int64_t ldo, const double* In_host, const double* S_host, double* out_inout, int64_t guard) {
+    CHECK_CTX(c);
+    if (!In_host || !S_host || !out_inout || n < 1 || n > MK_MAX_N || ldi < n || ldo < n || ldi > MK_MAX_LD || ldo > MK_MAX_LD || kk < 1 || kk > 512 ||
+        lds < kk || lds > 1024 || ncols < 1 || ncols > 512 || guard < 0 || guard > MK_MAX_GUARD)
+        return ctx_fail(c, SDPSR_BAD_ARGUMENT, "tall_times_small: bad arguments");
+    hipStream_t s = c->stream;
+    const size_t on = (size_t)(ldo * ncols + guard);
+    double* In = (double*)ctx_buf(c, "prof_mk_a", (size_t)ldi * kk * 8);
+    double* S = (double*)ctx_buf(c, "prof_mk_b", (size_t)lds * ncols * 8);
+    double* out = (double*)ctx_buf(c, "prof_mk_c", on * 8);
+    if (!In || !S || !out) return SDPSR_OUT_OF_MEMORY;
+    HIP_TRY(c, hipMemcpyAsync(In, In_host, (size_t)ldi * kk * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(S, S_host, (size_t)lds * ncols * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(out, out_inout, on * 8, hipMemcpyHostToDevice, s));
+    launch_tall_times_small(s, n, ldi, In, (int)kk, S, (int)lds, (int)ncols, alpha, beta, out, ldo);
+    HIP_TRY(c, hipMemcpyAsync(out_inout, out, on * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, hipGetLastError());
+    return SDPSR_OK;
+}
+
+extern "C" int sdpsr_profile_label_product(sdpsr_ctx* c, int64_t n, int64_t d, int G, int64_t w, int64_t ldw, int64_t ldy, const uint64_t* keys,
+                                           const uint32_t* L_host, const double* W_host, double* Y_inout, int64_t guard, int32_t* report) {
+    CHECK_CTX(c);
+    if (!keys || !L_host || !W_host || !Y_inout || !report || n < 1 || n > MK_MAX_N || d < 0 || ldw < n || ldy < n || ldw > MK_MAX_LD ||
+        ldy > MK_MAX_LD || w < 1 || w > 64 || G < 1 || G > 4 || guard < 0 || guard > MK_MAX_GUARD)
+        return ctx_fail(c, SDPSR_BAD_ARGUMENT, "label_product: bad arguments");
+    LabelSpmmForm f;
+    if (!label_spmm_select(n, d, G, (int)w, &f)) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "label_product: shape not supported by the label product");
+    if (!mk_labels_ok(L_host, (size_t)n * n, d)) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "label_product: a label exceeds d");
+    hipStream_t s = c->stream;
+    const size_t yn = (size_t)(ldy * G * w + guard);
+    uint32_t* Lb = (uint32_t*)ctx_buf(c, "prof_l", (size_t)n * n * 4);
+    const size_t wn = (size_t)ldw * 64;  // all 64 columns the launcher could take: those >= w are the caller's poison
+    double* W = (double*)ctx_buf(c, "prof_mk_a", wn * 8);
+    double* Y = (double*)ctx_buf(c, "prof_mk_c", yn * 8);
+    double* part = (double*)ctx_buf(c, "cm_part", label_spmm_partial_doubles(n, 64) * 8);
+    if (!Lb || !W || !Y || !part) return SDPSR_OUT_OF_MEMORY;
+    HIP_TRY(c, hipMemcpyAsync(Lb, L_host, (size_t)n * n * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(W, W_host, wn * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(Y, Y_inout, yn * 8, hipMemcpyHostToDevice, s));
+    const bool ran = G == 1 ? launch_label_spmm(s, n, Lb, keys[0], d, W, ldw, (int)w, part, Y, ldy)
+                            : launch_label_spmm_multi(s, n, Lb, keys, G, d, W, ldw, (int)w, part, Y, ldy);
+    HIP_TRY(c, hipMemcpyAsync(Y_inout, Y, yn * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, hipGetLastError());
+    if (!ran) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "label_product: shape not supported by the label product");
+    report[0] = f.mfma, report[1] = f.tile, report[2] = f.z, report[3] = f.cols_per_block;
+    return SDPSR_OK;
+}
+
+extern "C" int sdpsr_profile_class_sums(sdpsr_ctx* c, int64_t n, int64_t d, int64_t ldo, const uint32_t* L_host, const double* x_host,
+                                        double* out_inout, int64_t guard, int32_t* report) {
+    CHECK_CTX(c);
+    if (!L_host || !x_host || !out_inout || !report || n < 1 || n > MK_MAX_N || d < 1 || d > 4000 || ldo < n || ldo > MK_MAX_LD || guard < 0 ||
+        guard > MK_MAX_GUARD)
+        return ctx_fail(c, SDPSR_BAD_ARGUMENT, "class_sums: bad arguments");
+    if (!mk_labels_ok(L_host, (size_t)n * n, d)) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "class_sums: a label exceeds d");
+    // the per-lane tables in LDS take any ldo (class_sums_supports says so for an ldo != n); the fallback writes with ldo == n only
+    const bool table = class_sums_supports(n, d, n + 1);
+    report[0] = class_sums_supports(n, d, ldo) ? 1 : 0;
+    report[1] = table ? 1 : 0;
+    if (!report[0]) return SDPSR_OK;  // nothing ran: the caller (compress.cpp) does not call launch_class_sums either
+    if (!table && !basis_image_two_stage_fits(n, d, 1)) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "class_sums: the fallback does not take this shape");
+    hipStream_t s = c->stream;
+    const size_t on = (size_t)(ldo * d + guard);
+    uint32_t* Lb = (uint32_t*)ctx_buf(c, "prof_l", (size_t)n * n * 4);
+    double* x = (double*)ctx_buf(c, "prof_mk_a", (size_t)n * 8);
+    double* out = (double*)ctx_buf(c, "prof_mk_c", on * 8);
+    if (!Lb || !x || !out) return SDPSR_OUT_OF_MEMORY;
+    HIP_TRY(c, hipMemcpyAsync(Lb, L_host, (size_t)n * n * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(x, x_host, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(out, out_inout, on * 8, hipMemcpyHostToDevice, s));
+    launch_class_sums(s, n, d, Lb, x, out, ldo, 1);
+    HIP_TRY(c, hipMemcpyAsync(out_inout, out, on * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, hipGetLastError());
+    return SDPSR_OK;
+}
+
+extern "C" int sdpsr_profile_symmetrize(sdpsr_ctx* c, int64_t m, int64_t ld, double* B_inout, int64_t guard) {
+    CHECK_CTX(c);
+    if (!B_inout || m < 1 || m > 1024 || ld < m || ld > 2048 || guard < 0 || guard > MK_MAX_GUARD) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "symmetrize: bad arguments");
+    hipStream_t s = c->stream;
+    const size_t bn = (size_t)(ld * m + guard);
+    double* B = (double*)ctx_buf(c, "prof_mk_c", bn * 8);
+    if (!B) return SDPSR_OUT_OF_MEMORY;
+    HIP_TRY(c, hipMemcpyAsync(B, B_inout, bn * 8, hipMemcpyHostToDevice, s));
+    launch_symmetrize(s, m, ld, B);
+    HIP_TRY(c, hipMemcpyAsync(B_inout, B, bn * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, hipGetLastError());
+    return SDPSR_OK;
+}
+
+extern "C" int sdpsr_profile_extract_symmetric(sdpsr_ctx* c, int64_t m, int64_t mp, int64_t lds, const double* src_host, double* dst_inout, int64_t guard) {
+    CHECK_CTX(c);
+    if (!src_host || !dst_inout || m < 1 || mp < m || mp > 1024 || lds < m || lds > 2048 || guard < 0 || guard > MK_MAX_GUARD)
+        return ctx_fail(c, SDPSR_BAD_ARGUMENT, "extract_symmetric: bad arguments");
+    hipStream_t s = c->stream;
+    const size_t dn = (size_t)(mp * mp + guard);
+    double* src = (double*)ctx_buf(c, "prof_mk_a", (size_t)lds * m * 8);
+    double* dst = (double*)ctx_buf(c, "prof_mk_c", dn * 8);
+    if (!src || !dst) return SDPSR_OUT_OF_MEMORY;
+    HIP_TRY(c, hipMemcpyAsync(src, src_host, (size_t)lds * m * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(dst, dst_inout, dn * 8, hipMemcpyHostToDevice, s));
+    launch_extract_symmetric(s, m, mp, src, lds, dst);
+    HIP_TRY(c, hipMemcpyAsync(dst_inout, dst, dn * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, hipGetLastError());
+    return SDPSR_OK;
+}
+
+extern "C" int sdpsr_profile_normalize_columns(sdpsr_ctx* c, int64_t n, int64_t ldx, int64_t hstride, int64_t nruns, const double* X_host,
+                                               double* H_inout, double* norm_inout, int64_t guard) {
+    CHECK_CTX(c);
+    if (!X_host || !H_inout || !norm_inout || n < 1 || n > MK_MAX_N || ldx < n || ldx > MK_MAX_LD || nruns < 1 || nruns > 64 ||
+        (nruns > 1 && hstride < n) || hstride < 0 || hstride > 4 * MK_MAX_LD || guard < 0 || guard > MK_MAX_GUARD)
+        return ctx_fail(c, SDPSR_BAD_ARGUMENT, "normalize_columns: bad arguments");
+    hipStream_t s = c->stream;
+    const size_t hn = (size_t)(hstride * (nruns - 1) + n + guard), nn = (size_t)(nruns + guard);
+    double* X = (double*)ctx_buf(c, "prof_mk_a", (size_t)ldx * nruns * 8);
+    double* H = (double*)ctx_buf(c, "prof_mk_c", hn * 8);
+    double* nrm = (double*)ctx_buf(c, "prof_mk_b", nn * 8);
+    if (!X || !H || !nrm) return SDPSR_OUT_OF_MEMORY;
+    HIP_TRY(c, hipMemcpyAsync(X, X_host, (size_t)ldx * nruns * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(H, H_inout, hn * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(nrm, norm_inout, nn * 8, hipMemcpyHostToDevice, s));
+    launch_normalize_columns(s, n, ldx, H, hstride, X, ldx, (int)nruns, nrm);
+    HIP_TRY(c, hipMemcpyAsync(H_inout, H, hn * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(norm_inout, nrm, nn * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, hipGetLastError());
+    return SDPSR_OK;
+}
+
+extern "C" int sdpsr_profile_random_vector(sdpsr_ctx* c, int64_t n, uint64_t key, double* x_inout, int64_t guard) {
+    CHECK_CTX(c);
+    if (!x_inout || n < 1 || n > MK_MAX_N || guard < 0 || guard > MK_MAX_GUARD) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "random_vector: bad arguments");
+    hipStream_t s = c->stream;
+    const size_t xn = (size_t)(n + guard);
+    double* x = (double*)ctx_buf(c, "prof_mk_c", xn * 8);
+    if (!x) return SDPSR_OUT_OF_MEMORY;
+    HIP_TRY(c, hipMemcpyAsync(x, x_inout, xn * 8, hipMemcpyHostToDevice, s));
+    launch_random_vector(s, n, key, x);
+    HIP_TRY(c, hipMemcpyAsync(x_inout, x, xn * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, hipGetLastError());
+    return SDPSR_OK;
+}
+
 extern "C" int sdpsr_profile_kernel(sdpsr_ctx* c, int kind, int64_t n, int64_t aux, int reps,
                                     double* ms_per_launch) {
     CHECK_CTX(c);

@@ -321,6 +321,13 @@ void launch_col_norms2(hipStream_t s, int64_t len, int64_t k, const double* V, d
 void launch_scale_copy(hipStream_t s, int64_t len, const double* v, double alpha, double* out);
 void launch_rank1_update(hipStream_t s, int64_t len, int64_t m, double* R, const double* u, const double* dots);
 void launch_sub_round(hipStream_t s, int64_t len, const double* a, const double* b, double atol, double scale, double* out);
+// The form launch_label_spmm_multi gives a shape (kernels_module.hip): matrix cores (label_spmm_mfma_kernel<tile, G>, tile = JT
+// tiles of 16 columns of W) or VALU (label_spmm_sload_kernel<tile, G>, tile = WMAX), the column range split over z workgroups
+// of cols_per_block columns each.  false: shape not supported.
+struct LabelSpmmForm {
+    int mfma, tile, z, cols_per_block;
+};
+bool label_spmm_select(int64_t n, int64_t d, int G, int w, LabelSpmmForm* f);
 
 // Kernels with more than 64 KiB of dynamic LDS carry a per-DEVICE attribute: sdpsr_create() sets
 // them all with the ctx's device current (no process-global "already set" flags) and fails when one
