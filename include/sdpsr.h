@@ -426,6 +426,55 @@ int sdpsr_reduce_constraints_csr(sdpsr_ctx* ctx, int64_t len, const uint32_t* la
                                  const int64_t* rowptr, const int64_t* colind, const double* val, int index_base,
                                  double* out, int mem);
 
+/* ---- a device-resident sparse A: canonicalise once, on the device; use it for the setup stage and for A * PMat ------
+   The constraint matrix enters a work flow twice -- the setup stage (src/partitions.jl:117-142, projL of
+   src/utils.jl:58-66) and newA = A * PMat (README.md:57-60, docs/src/examples/ReduceAndSolveJuMP.jl:42-51) -- and each
+   _csr entry above validates and canonicalises it on one host thread and uploads it again.  A sdpsr_sparse handle holds
+   the canonical CSR form in device memory (upload once, use many times: the idiom of sdpsr_problem), made by a canonical
+   pass that runs ON THE DEVICE from host or device arrays.
+   sdpsr_sparse_create (src/partitions.jl:117-142, README.md:57-60): rowptr[m + 1], colind[nnz], val[nnz] live in `mem`;
+     device arrays are read where they lie and never modified, the handle aliases none of them.  Exactly the conventions
+     of sdpsr_admissible_setup_csr (colind = column-major linear index, index_base 0 or 1, unsorted columns, duplicates
+     and explicit zeros accepted, m = 0 and nnz = 0 legal).  nnz is passed explicitly (the host cannot read a device
+     rowptr[m]); rowptr[m] - index_base != nnz is SDPSR_BAD_ARGUMENT.
+     The canonical form is the host pass's, bit for bit on every input: rows sorted by column, duplicates summed in input
+     order (s = v0; s += v1; ...), every v == 0.0 of either sign dropped, uint32 columns.  The verdicts and messages are
+     the host pass's too, all SDPSR_BAD_ARGUMENT: "rowptr[0] != index_base", "rowptr is not monotone at row i" (the lowest
+     i), "column index out of [0, n^2) at entry p" / "non-finite value at entry p" (the lowest offending p of either kind,
+     the column message at equal p), "duplicate entries sum to a non-finite value", index_base outside {0, 1}, a NULL
+     array with nnz > 0, nnz >= 2^32, m >= 2^31, a len outside [1, 2^32 - 16).  *out stays NULL then, nothing is leaked,
+     the ctx stays usable.  The handle owns (m + 1) * 8 + nnz_canonical * 12 bytes of device memory (SDPSR_OUT_OF_MEMORY
+     when they do not fit); the workspace (7 bytes per raw entry, 51 when some row needs the sort, 16 more for the raw copies of
+     host arrays) belongs to the ctx.  Three host
+     waits.  sdpsr_transfer_bytes, host arrays: (m + 1) * 8 + nnz * 16 bytes up and 216 bytes of verdict words down; device
+     arrays: nothing up.  Like sdpsr_problem the handle is read-only after creation, any ctx of that device may use it,
+     and the caller destroys it after the last call that names it.
+   sdpsr_sparse_info: len, m, the canonical entry count, and rows_symmetric = 1 when len is a perfect square n^2 and
+     every canonical row is a symmetric n x n matrix bit for bit (the predicate behind hint_out = 3 of the setup entries).
+   sdpsr_sparse_export: the canonical arrays as int64 / int64 / double with index_base, rowptr[m + 1], colind / val
+     [nnz_canonical] in `mem` -- they go into the _csr entries, or into sdpsr_sparse_create again, as they are.
+   sdpsr_admissible_setup_sparse / sdpsr_admissible_subspace_sparse (src/partitions.jl:117-142, src/utils.jl:58-66): the
+     stage of sdpsr_admissible_setup_csr / _subspace_csr on the handle's arrays; n * n must equal the handle's len, its m
+     is the row count; b and C are host memory.  Every kernel of the stage sees the same inputs with the same launch
+     geometry as behind the host pass: the outputs equal those of the _csr entry on the same raw arrays bit for bit.
+   sdpsr_reduce_constraints_sparse (README.md:57-60, docs/src/examples/ReduceAndSolveJuMP.jl:42-51): the assembly of
+     sdpsr_reduce_constraints_csr on the handle's arrays, labels[len] and out (m x d) in `mem`; equal bits likewise. */
+typedef struct sdpsr_sparse sdpsr_sparse; /* canonical CSR of an m x len matrix, resident on ctx's device */
+int sdpsr_sparse_create(sdpsr_ctx* ctx, int64_t len, int64_t m, int64_t nnz, const int64_t* rowptr, const int64_t* colind,
+                        const double* val, int index_base, int mem, sdpsr_sparse** out);
+int sdpsr_sparse_destroy(sdpsr_sparse* A);
+int sdpsr_sparse_info(const sdpsr_sparse* A, int64_t* len, int64_t* m, int64_t* nnz_canonical, int* rows_symmetric);
+int sdpsr_sparse_export(sdpsr_ctx* ctx, const sdpsr_sparse* A, int index_base, int64_t* rowptr, int64_t* colind, double* val,
+                        int mem);
+int sdpsr_admissible_setup_sparse(sdpsr_ctx* ctx, int64_t n, const sdpsr_sparse* A, const double* b, const double* C,
+                                  double atol, double* CL, double* X0L, double* U, int64_t* r_out, int* hint_out,
+                                  int32_t* info_out, int mem_out);
+int sdpsr_admissible_subspace_sparse(sdpsr_ctx* ctx, int64_t n, const sdpsr_sparse* A, const double* b, const double* C,
+                                     double atol, uint32_t* P_out, int64_t* dim_out, int32_t* iters_out, double* phase_ms,
+                                     int mem_out);
+int sdpsr_reduce_constraints_sparse(sdpsr_ctx* ctx, const sdpsr_sparse* A, const uint32_t* labels, int64_t d, double* out,
+                                    int mem);
+
 /* ---- blockDiagonalize, src/compat.jl:46-68 ---------------------------------- */
 /* Phase 1 = diagonalize(Float64, P; atol=epsilon) (src/diagonalize.jl:25-40) +
    check_block_sizes (:1-11).  Keeps Q_hat on the device inside ctx.

@@ -153,6 +153,13 @@ def load_library():
         "sdpsr_transfer_bytes": (C.c_int, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "sdpsr_reduce_constraints": (C.c_int, [vp, i64, vp, i64, i64, vp, vp, C.c_int]),
         "sdpsr_reduce_constraints_csr": (C.c_int, [vp, i64, vp, i64, i64, vp, vp, vp, C.c_int, vp, C.c_int]),
+        "sdpsr_sparse_create": (C.c_int, [vp, i64, i64, i64, vp, vp, vp, C.c_int, C.c_int, C.POINTER(vp)]),
+        "sdpsr_sparse_destroy": (C.c_int, [vp]),
+        "sdpsr_sparse_info": (C.c_int, [vp, pi64, pi64, pi64, C.POINTER(C.c_int)]),
+        "sdpsr_sparse_export": (C.c_int, [vp, vp, C.c_int, vp, vp, vp, C.c_int]),
+        "sdpsr_admissible_setup_sparse": (C.c_int, [vp, i64, vp, vp, vp, dbl, vp, vp, vp, pi64, C.POINTER(C.c_int), pi32, C.c_int]),
+        "sdpsr_admissible_subspace_sparse": (C.c_int, [vp, i64, vp, vp, vp, dbl, vp, pi64, pi32, vp, C.c_int]),
+        "sdpsr_reduce_constraints_sparse": (C.c_int, [vp, vp, vp, i64, vp, C.c_int]),
         "sdpsr_desymmetrize": (C.c_int, [vp, i64, vp, pi64, pi32, C.c_int]),
         "sdpsr_block_diagonalize": (C.c_int, [vp, i64, vp, i64, dbl, pi32, pi64, pi64, vp, C.c_int]),
         "sdpsr_block_sizes": (C.c_int, [vp, vp]),

@@ -508,7 +508,17 @@ def csr_arrays(A, len_, index_base=0):
         first = np.ones(cols.size, dtype=bool)
         first[1:] = (rows[1:] != rows[:-1]) | (cols[1:] != cols[:-1])
         starts = np.flatnonzero(first)
-        val = np.add.reduceat(val, starts)  # left to right within a run
+        # left to right within a run, s = v0; s += v1; ... as the library's own pass adds them (np.add.reduceat adds the
+        # tail of a run first, v0 + (v1 + v2): other bits): step k adds the k-th follower of every run that has one
+        ends = np.append(starts[1:], cols.size)
+        sums = val[starts].copy()
+        k, live = 1, np.flatnonzero(ends - starts > 1)
+        with np.errstate(over="ignore", invalid="ignore"):  # (a non-finite sum is reported below)
+            while live.size:
+                sums[live] += val[starts[live] + k]
+                k += 1
+                live = live[ends[live] - starts[live] > k]
+        val = sums
         rows, cols = rows[starts], cols[starts]
         if not np.all(np.isfinite(val)):
             raise ValueError("duplicate entries sum to a non-finite value")
@@ -535,13 +545,195 @@ def _csr_inputs(C_, A, b, index_base):
     return n, c, m, rowptr, colind, val, bb
 
 
+def _is_torch_sparse_csr(A):
+    if not (hasattr(A, "layout") and hasattr(A, "crow_indices")):
+        return False
+    import torch
+    return A.layout == torch.sparse_csr
+
+
+def _raw_csr(A, len_, index_base):
+    """The CSR arrays of ``A`` as they are -- no sorting, no summing, no dropping: that is the device's work
+    (``SparseConstraints``).  Returns (rowptr, colind, val, index_base, on_device); ValueError for malformed shapes, dtypes
+    and lengths."""
+    len_ = int(len_)
+    if index_base not in (0, 1):
+        raise ValueError("index_base must be 0 or 1")
+    if _is_torch_sparse_csr(A):
+        if A.dim() != 2 or A.shape[1] != len_:
+            raise ValueError(f"A has shape {tuple(A.shape)}, expected (m, {len_})")
+        if not A.is_cuda:
+            raise ValueError("a torch sparse_csr A must be a CUDA tensor (pass a SciPy matrix or NumPy arrays for host data)")
+        A, index_base = (A.crow_indices(), A.col_indices(), A.values()), 0
+    if isinstance(A, tuple):
+        if len(A) != 3:
+            raise ValueError("CSR input is a tuple (rowptr, colind, val)")
+        if all(_is_torch(x) for x in A):
+            import torch
+            rowptr, colind, val = A
+            if not all(x.is_cuda for x in A):
+                raise ValueError("the three CSR tensors must be CUDA tensors")
+            if rowptr.dim() != 1 or rowptr.numel() < 1 or rowptr.dtype.is_floating_point or rowptr.dtype == torch.bool:
+                raise ValueError("rowptr must be a non-empty integer vector")
+            if colind.dim() != 1 or colind.dtype.is_floating_point or colind.dtype == torch.bool:
+                raise ValueError("colind must be an integer vector")
+            if val.dim() != 1 or val.numel() != colind.numel():
+                raise ValueError(f"colind has {colind.numel()} entries, val {val.numel()}")
+            return (rowptr.to(torch.int64).contiguous(), colind.to(torch.int64).contiguous(), val.to(torch.float64).contiguous(),
+                    index_base, True)
+        if any(_is_torch(x) for x in A):
+            raise ValueError("CSR input mixes torch tensors and host arrays")
+        rowptr = np.asarray(A[0])
+        colind = np.asarray(A[1])
+        val = np.asarray(A[2], dtype=np.float64).ravel()
+        if rowptr.ndim != 1 or rowptr.size < 1 or not np.issubdtype(rowptr.dtype, np.integer):
+            raise ValueError("rowptr must be a non-empty integer vector")
+        if colind.ndim != 1 or (colind.size and not np.issubdtype(colind.dtype, np.integer)):
+            raise ValueError("colind must be an integer vector")
+        if colind.size != val.size:
+            raise ValueError(f"colind has {colind.size} entries, val {val.size}")
+    elif hasattr(A, "tocsr"):
+        if A.ndim != 2 or A.shape[1] != len_:
+            raise ValueError(f"A has shape {A.shape}, expected (m, {len_})")
+        Ac = A.tocsr()
+        rowptr, colind, val, index_base = Ac.indptr, Ac.indices, Ac.data, 0
+    else:
+        Ad = np.asarray(A, dtype=np.float64)
+        if Ad.ndim != 2 or Ad.shape[1] != len_:
+            raise ValueError(f"A has shape {Ad.shape}, expected (m, {len_})")
+        rows, cols = np.nonzero(Ad)
+        val = Ad[rows, cols]
+        rowptr = np.zeros(Ad.shape[0] + 1, dtype=np.int64)
+        np.cumsum(np.bincount(rows, minlength=Ad.shape[0]), out=rowptr[1:])
+        colind, index_base = cols, 0
+    return (np.ascontiguousarray(rowptr, dtype=np.int64), np.ascontiguousarray(colind, dtype=np.int64),
+            np.ascontiguousarray(val, dtype=np.float64), index_base, False)
+
+
+class SparseConstraints:
+    """The m x ``len_`` constraint matrix ``A`` in canonical CSR form, device-resident (``sdpsr_sparse_create``): validated,
+    sorted, duplicates summed in input order and zeros dropped by a pass that runs on the device, ONCE; ``admissible_setup_csr``,
+    ``admissible_subspace`` and ``reduce_constraints_csr`` take it in place of ``A`` and read it where it lies (setup stage of
+    src/partitions.jl:117-142, ``A * PMat`` of README.md:57-60).
+
+    ``A``: a SciPy sparse matrix (its ``tocsr()`` arrays travel raw), a tuple ``(rowptr, colind, val)`` of NumPy arrays with
+    ``index_base`` 0 or 1, a torch ``sparse_csr`` CUDA tensor, a tuple of three CUDA tensors (read in place; integer dtypes
+    other than int64 are converted), or a dense 2-D array.  Malformed input raises ValueError -- shapes, dtypes and lengths
+    before any library call, the content with the library's message."""
+
+    def __init__(self, A, len_, ctx=None, index_base=0):
+        self._h = None
+        rowptr, colind, val, base, on_dev = _raw_csr(A, len_, index_base)
+        m = int(rowptr.shape[0]) - 1
+        nnz = int(colind.shape[0])
+        self.ctx = _ctx(ctx)
+        if on_dev:
+            self.ctx.wait_for(rowptr, colind, val)
+        h = C.c_void_p()
+        st = self.ctx._lib.sdpsr_sparse_create(self.ctx._h, int(len_), m, nnz, _ptr(rowptr), _ptr(colind) if nnz else None,
+                                               _ptr(val) if nnz else None, int(base), L.MEM_DEVICE if on_dev else L.MEM_HOST, C.byref(h))
+        if st == 5:  # SDPSR_BAD_ARGUMENT: what csr_arrays raises for the same input
+            raise ValueError(self.ctx._lib.sdpsr_last_error(self.ctx._h).decode())
+        self.ctx.check(st)
+        self._h = h
+        ln, mm, nz, sym = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int(0)
+        self.ctx.check(self.ctx._lib.sdpsr_sparse_info(self._h, C.byref(ln), C.byref(mm), C.byref(nz), C.byref(sym)))
+        self.len, self.m, self.nnz, self.rows_symmetric = int(ln.value), int(mm.value), int(nz.value), bool(sym.value)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.ctx._lib.sdpsr_sparse_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def arrays(self, index_base=0, device=False):
+        """The canonical arrays (rowptr, colind, val) as int64 / int64 / float64 with ``index_base`` (``sdpsr_sparse_export``):
+        NumPy arrays, or torch CUDA tensors with ``device=True``.  They go into ``csr_arrays`` consumers as they are."""
+        ctx = self.ctx
+        if device:
+            import torch
+            dev = torch.device("cuda", ctx.device)
+            rowptr = torch.empty(self.m + 1, dtype=torch.int64, device=dev)
+            colind = torch.empty(self.nnz, dtype=torch.int64, device=dev)
+            val = torch.empty(self.nnz, dtype=torch.float64, device=dev)
+            ctx.wait_for(rowptr)
+        else:
+            rowptr = np.empty(self.m + 1, dtype=np.int64)
+            colind = np.empty(self.nnz, dtype=np.int64)
+            val = np.empty(self.nnz, dtype=np.float64)
+        ctx.check(ctx._lib.sdpsr_sparse_export(ctx._h, self._h, int(index_base), _ptr(rowptr), _ptr(colind) if self.nnz else None,
+                                               _ptr(val) if self.nnz else None, L.MEM_DEVICE if device else L.MEM_HOST))
+        return rowptr, colind, val
+
+
+def _sparse_inputs(C_, A, b, ctx):
+    c = np.asarray(C_.todense()).reshape(-1) if hasattr(C_, "todense") else np.asarray(C_, dtype=np.float64).reshape(-1)
+    c = np.ascontiguousarray(c, dtype=np.float64)
+    n = math.isqrt(len(c))
+    if n * n != len(c):  # @assert n^2 == length(C), :118
+        raise ValueError("length(C) is not a perfect square")
+    if n * n != A.len:
+        raise ValueError(f"A has {A.len} columns, expected {n * n}")
+    bb = np.ascontiguousarray(np.asarray(b, dtype=np.float64).reshape(-1))
+    if bb.size != A.m:
+        raise ValueError(f"length(b) = {bb.size} != {A.m} rows of A")
+    if not np.all(np.isfinite(bb)):
+        raise ValueError("non-finite value in b")
+    return n, c, bb, (A.ctx if ctx is None else ctx)
+
+
+def _admissible_setup_sparse(C_, A, b, atol, ctx):
+    import torch
+    n, c, bb, ctx = _sparse_inputs(C_, A, b, ctx)
+    m = A.m
+    dev = torch.device("cuda", ctx.device)
+    CL = torch.empty(n * n, dtype=torch.float64, device=dev)
+    X0L = torch.empty(n * n, dtype=torch.float64, device=dev)
+    Ubuf = torch.empty((m, n * n), dtype=torch.float64, device=dev)  # U = Ubuf.t(): column-major n^2 x m
+    r = C.c_int64(0)
+    hint = C.c_int(0)
+    info = C.c_int32(0)
+    ctx.wait_for(CL)
+    ctx.check(ctx._lib.sdpsr_admissible_setup_sparse(ctx._h, n, A._h, _ptr(bb), _ptr(c), float(atol), _ptr(CL), _ptr(X0L),
+                                                     _ptr(Ubuf) if m > 0 else None, C.byref(r), C.byref(hint), C.byref(info), L.MEM_DEVICE))
+    U = Ubuf.t()[:, :r.value]
+    return Setup((n, CL, X0L, U), bool(hint.value & 1), bool(hint.value & 2), info=int(info.value))
+
+
+def _admissible_subspace_sparse(C_, A, b, atol, ctx, verbose):
+    n, c, bb, ctx = _sparse_inputs(C_, A, b, ctx)
+    P = np.empty(n * n, dtype=ctx.label_dtype)
+    d = C.c_int64(0)
+    it = C.c_int32(0)
+    ms = (C.c_double * L.T_COUNT)()
+    ctx.check(ctx._lib.sdpsr_admissible_subspace_sparse(ctx._h, n, A._h, _ptr(bb), _ptr(c), float(atol), _ptr(P), C.byref(d), C.byref(it),
+                                                        C.cast(ms, C.c_void_p), L.MEM_HOST))
+    if verbose:
+        print(f"[sdpsr] admissible subspace (sparse handle): dim {d.value} after {it.value} iterations, loop {ms[L.T_TOTAL]:.3f} ms")
+    out = Partition(d.value, P.reshape(n, n, order="F"))
+    out.iterations = it.value
+    out.phase_ms = list(ms)
+    out.dims = ctx.dimension_trajectory()
+    return out
+
+
 def admissible_setup_csr(C_, A, b, atol=RTOL_DEFAULT, ctx=None, index_base=0):
     """Setup stage of ``admissible_subspace`` (src/partitions.jl:117-142) on the DEVICE from a sparse ``A``
     (``sdpsr_admissible_setup_csr``): A travels as CSR, C_L, X0_L and the orthonormal basis U stay in device memory.
     ``A``: anything ``csr_arrays`` takes.  Returns a ``Setup`` of torch CUDA tensors ``(n, CL, X0L, U)`` (U: n^2 x r,
     column-major) with ``.hint`` (the symmetry bits the library proved) and ``.info`` (``_lib.SETUP_*``: which
     orthogonalisation ran); it goes to ``admissible_subspace(setup=...)``, ``Problem(setup=...)`` and
-    ``jordan_reduce_batch(setup=...)`` as it is."""
+    ``jordan_reduce_batch(setup=...)`` as it is.  A ``SparseConstraints`` for ``A`` is read where it lies
+    (``sdpsr_admissible_setup_sparse``): no host pass, no upload of A."""
+    if isinstance(A, SparseConstraints):
+        return _admissible_setup_sparse(C_, A, b, atol, ctx)
     import torch
     n, c, m, rowptr, colind, val, bb = _csr_inputs(C_, A, b, index_base)  # (ValueError before any library call)
     ctx = _ctx(ctx)
@@ -587,7 +779,10 @@ def admissible_subspace(C_, A, b, atol=RTOL_DEFAULT, ctx=None, verbose=False, se
     By default the setup stage runs on the device too (dense copy of ``A``, at most 4 GiB);
     ``host_setup=True`` (or a precomputed ``setup``) uses the NumPy/SciPy setup, which is also the
     path for very large sparse ``A``.  ``csr_setup=True`` (opt-in) sends ``A`` as CSR and runs the setup
-    stage on the device from it (``sdpsr_admissible_subspace_csr``): no dense copy of ``A`` anywhere."""
+    stage on the device from it (``sdpsr_admissible_subspace_csr``): no dense copy of ``A`` anywhere.  A
+    ``SparseConstraints`` for ``A`` always takes its own entry (``sdpsr_admissible_subspace_sparse``)."""
+    if setup is None and isinstance(A, SparseConstraints):
+        return _admissible_subspace_sparse(C_, A, b, atol, ctx, verbose)
     if setup is None and csr_setup and not host_setup:
         return _admissible_subspace_csr(C_, A, b, atol, ctx, verbose)
     ctx = _ctx(ctx)
@@ -758,14 +953,36 @@ def reduce_constraints(P, A, ctx=None):
     return out[0] if vec else out
 
 
+def _reduce_constraints_sparse(P, A, ln, ctx):
+    if ln != A.len:
+        raise ValueError(f"A has {A.len} columns, P has {ln} entries")
+    m, d = A.m, int(P.nparts)
+    if not 1 <= d <= ln:
+        raise ValueError(f"dim(P) = {d} outside [1, {ln}]")
+    ctx = A.ctx if ctx is None else ctx
+    lab, mem = _labels_arg(P, ctx)
+    if mem == L.MEM_DEVICE:
+        import torch
+        t_out = torch.empty(m * d, dtype=torch.float64, device=lab.device)
+        ctx.wait_for(lab, t_out)
+        ctx.check(ctx._lib.sdpsr_reduce_constraints_sparse(ctx._h, A._h, _ptr(lab), d, _ptr(t_out), mem))
+        return t_out.cpu().numpy().reshape(m, d, order="F")
+    out = np.zeros((m, d), order="F")
+    ctx.check(ctx._lib.sdpsr_reduce_constraints_sparse(ctx._h, A._h, _ptr(lab), d, _ptr(out), mem))
+    return out
+
+
 def reduce_constraints_csr(P, A, ctx=None, index_base=0):
     """``A * PMat`` (README.md:57-60, test/sd_problems.jl:32-37,113-118) from a sparse ``A``, for any dim(P)
     (``sdpsr_reduce_constraints_csr``): A travels as CSR and is never densified.  ``A``: anything ``csr_arrays`` takes
     -- SciPy sparse, dense 2-D, or ``(rowptr, colind, val)`` with ``index_base`` -- with n^2 columns; returns an
     m x dim(P) NumPy array.  A 1-D array or a SciPy-sparse vector (n^2 x 1, or 1-D) means ``C' * PMat``: a vector of
-    length dim(P) comes back.  Malformed input raises ValueError before any library call.  Equal inputs give equal bits."""
+    length dim(P) comes back.  Malformed input raises ValueError before any library call.  Equal inputs give equal bits.
+    A ``SparseConstraints`` for ``A`` is read where it lies (``sdpsr_reduce_constraints_sparse``)."""
     ln = int(P.shape[0]) * int(P.shape[1])
     vec = False
+    if isinstance(A, SparseConstraints):
+        return _reduce_constraints_sparse(P, A, ln, ctx)
     if not isinstance(A, tuple):
         if hasattr(A, "tocsr"):
             if A.ndim == 1:

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "agree_plan.h"
+#include "csr_canon.h"
 #include "iso_classes.h"
 #include "sdpsr_internal.h"
 
@@ -250,6 +251,7 @@ constexpr PinnedWords PINNED_SMALL_FLAG{0, 1};                   // c->pinned_sm
 constexpr PinnedWords PINNED_SMALL_LABEL_CHECK{2, 2};             // sdpsr_basis_image: [0] != 0 the caller's P is not symmetric, [1] != 0 a label exceeds d
 constexpr PinnedWords PINNED_SMALL_DEFERRED_VERIFY{8, 1};        // sdpsr_jordan_reduce: the two verdicts the loop left unread (c->deferred_verdict)
 constexpr PinnedWords PINNED_SMALL_DEFERRED_SPECULATIVE{24, 1};
+constexpr PinnedWords PINNED_SMALL_CANON{44, 18};                // sdpsr_sparse_create: the nine 64-bit words of CanonVerdict (csr_canon.h)
 constexpr PinnedWords PINNED_SMALL_NARROW{40, 1};                // != 0: a label did not fit the narrow type (kernels_labels.hip); cleared by the host before each pass
 constexpr bool pinned_words_disjoint(std::initializer_list<PinnedWords> w, size_t bytes) {
     for (const PinnedWords* a = w.begin(); a != w.end(); ++a) {
@@ -261,7 +263,8 @@ constexpr bool pinned_words_disjoint(std::initializer_list<PinnedWords> w, size_
 }
 static_assert(pinned_words_disjoint({PINNED_REFINE, PINNED_SYMMETRY, PINNED_BASIS_IMAGE_VERDICTS, PINNED_VERIFY, PINNED_SPECULATIVE, PINNED_BASIS_CONSTANT, PINNED_SAMPLE}, PINNED_FIXED_BYTES) &&
               PINNED_FIXED_BYTES % sizeof(double) == 0, "two reports share a word of c->pinned, or one reaches into the symmetry probe's doubles");
-static_assert(pinned_words_disjoint({PINNED_SMALL_FLAG, PINNED_SMALL_LABEL_CHECK, PINNED_SMALL_DEFERRED_VERIFY, PINNED_SMALL_DEFERRED_SPECULATIVE, PINNED_SMALL_NARROW}, 256), "two reports share a word of c->pinned_small");
+static_assert(pinned_words_disjoint({PINNED_SMALL_FLAG, PINNED_SMALL_LABEL_CHECK, PINNED_SMALL_DEFERRED_VERIFY, PINNED_SMALL_DEFERRED_SPECULATIVE, PINNED_SMALL_NARROW, PINNED_SMALL_CANON}, 256) &&
+              (PINNED_SMALL_CANON.first * 4) % 8 == 0 && PINNED_SMALL_CANON.count * 4 == sizeof(CanonVerdict), "two reports share a word of c->pinned_small");
 inline uint32_t* pinned_report(sdpsr_ctx* c, PinnedWords w) {  // the pinned words of one report (nullptr: no pinned buffer)
     uint32_t* p = (uint32_t*)ctx_pinned(c, PINNED_FIXED_BYTES);
     return p ? p + w.first : nullptr;
@@ -387,6 +390,33 @@ struct CanonCsr {
 };
 int canonicalize_csr(sdpsr_ctx* c, int64_t len, int64_t m, const int64_t* rowptr, const int64_t* colind, const double* val, int base,
                      CanonCsr& out);
+// setup_csr.cpp / reduce_csr.cpp: the parts behind "canonical CSR is on the device" (rowptr int64 0-based, columns uint32 sorted per
+// row, no duplicates, no zeros) -- shared by the _csr entries (host pass + upload) and the _sparse entries (a handle's arrays)
+struct CsrSetupOut {
+    double *CL = nullptr, *X0 = nullptr;
+    const double* U = nullptr;  // len x r on the device
+    int64_t r = 0;
+    int hint = 0;
+    int32_t info = SDPSR_SETUP_NO_CONSTRAINTS;
+};
+int setup_from_device_csr(sdpsr_ctx* c, int64_t n, int64_t m, const int64_t* drp, const uint32_t* dcol, const double* dval, int64_t nnz,
+                          bool symmetric, const double* b, const double* C, double atol, CsrSetupOut& o);
+int reduce_from_device_csr(sdpsr_ctx* c, int64_t len, const uint32_t* labels, int64_t d, int64_t m, const int64_t* drp, const uint32_t* dcol,
+                           const double* dval, int64_t nnz, double* out, int mem);
+// kernels_csr_canon.hip: the canonical pass on the device (sparse_handle.cpp); every launcher is stream-ordered, no host wait
+void launch_canon_check(hipStream_t s, int64_t len, int64_t m, int64_t nnz, const int64_t* rowptr, const int64_t* colind, const double* val,
+                        int base, uint32_t* col32, unsigned char* keep, CanonVerdict* verdict);
+void launch_canon_row_ids(hipStream_t s, int64_t nnz, int64_t m, const int64_t* rowptr, int base, uint32_t* row);
+void launch_canon_gather_u32(hipStream_t s, int64_t nnz, const uint32_t* idx, const uint32_t* src, uint32_t* dst);
+void launch_canon_runs(hipStream_t s, int64_t nnz, const uint32_t* pos2, const uint32_t* col1, const uint32_t* idx1, const uint32_t* row_sorted,
+                       const double* val, uint32_t* col_sorted, uint32_t* idx_sorted, double* sum, unsigned char* keep, CanonVerdict* verdict);
+void launch_canon_count_scan(hipStream_t s, int64_t n, const unsigned char* keep, int64_t* cnt, CanonVerdict* verdict);  // cnt: canon_chunks(n) + 1
+void launch_canon_fill(hipStream_t s, int64_t n, int64_t m, const unsigned char* keep, const uint32_t* col, const double* x, const int64_t* cnt,
+                       const int64_t* rowptr, int base, unsigned short* rel, int64_t* rowptr_out, uint32_t* col_out, double* val_out);
+void launch_canon_symmetry(hipStream_t s, int64_t nnz, int64_t m, int64_t n, const int64_t* rowptr, const uint32_t* col, const double* val,
+                           CanonVerdict* verdict);
+void launch_canon_export(hipStream_t s, int64_t m, int64_t nnz, const int64_t* rowptr, const uint32_t* col, int base, int64_t* rowptr_out,
+                         int64_t* col_out);
 // kernels_reduce_csr.hip: A * PMat from canonical CSR (reduce_csr.cpp)
 void launch_labels_exceed(hipStream_t s, int64_t len, const uint32_t* L, int64_t d, uint32_t* flag);
 void launch_csr_entry_labels(hipStream_t s, int64_t nnz, const uint32_t* col, const uint32_t* L, int64_t d, uint32_t* key);

@@ -49,6 +49,44 @@ int sdpsr_reduce_constraints_csr(sdpsr_ctx* c, int64_t len, const uint32_t* labe
     if (nnz >= (int64_t(1) << 32))
         return ctx_fail(c, SDPSR_BAD_ARGUMENT, "nnz >= 2^32: the entries of A are indexed with 32 bits");
     if (m == 0) return SDPSR_OK;  // an empty result
+    int64_t* drp = nullptr;
+    uint32_t* dcol = nullptr;
+    double* dval = nullptr;
+    if (nnz > 0) {
+        hipStream_t s = c->stream;
+        drp = (int64_t*)ctx_buf(c, "csr_rowptr", (size_t)(m + 1) * 8);  // (the CSR buffers of the setup entries)
+        dcol = (uint32_t*)ctx_buf(c, "csr_col", (size_t)nnz * 4);
+        dval = (double*)ctx_buf(c, "csr_val", (size_t)nnz * 8);
+        if (!drp || !dcol || !dval) return SDPSR_OUT_OF_MEMORY;
+        // (pageable sources: A lives until the return, and the stream is waited for before it)
+        HIP_TRY(c, hipMemcpyAsync(drp, A.rowptr.data(), (size_t)(m + 1) * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(dcol, A.col.data(), (size_t)nnz * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(dval, A.val.data(), (size_t)nnz * 8, hipMemcpyHostToDevice, s));
+        c->h2d_bytes += (size_t)(m + 1) * 8 + (size_t)nnz * 12;
+    }
+    st = reduce_from_device_csr(c, len, labels, d, m, drp, dcol, dval, nnz, out, mem);
+    if (st && nnz > 0) (void)ctx_sync_stream(c, c->stream);  // (a failure before the assembly's own wait: the copies still read A)
+    return st;
+}
+
+// the same assembly on a handle's arrays (sdpsr_sparse_create): no host pass, no upload of A
+int sdpsr_reduce_constraints_sparse(sdpsr_ctx* c, const sdpsr_sparse* A, const uint32_t* labels, int64_t d, double* out, int mem) {
+    CHECK_CTX(c);
+    if (!A) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "no sparse handle");
+    if (A->device != c->device) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "the sparse handle lives on another device");
+    if (!labels || d < 1 || (A->m > 0 && !out)) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "bad arguments");
+    if (d > A->len) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "d > len: more classes than entries");
+    if (A->m == 0) return SDPSR_OK;  // an empty result
+    return reduce_from_device_csr(c, A->len, labels, d, A->m, A->rowptr, A->col, A->val, A->nnz, out, mem);
+}
+
+}  // extern "C"
+
+// The assembly from canonical CSR arrays that are on the device already (m >= 1): every kernel sees the same inputs with the
+// same launch geometry whether the arrays came from the host pass or from a handle
+int sdpsr::reduce_from_device_csr(sdpsr_ctx* c, int64_t len, const uint32_t* labels, int64_t d, int64_t m, const int64_t* drp,
+                                  const uint32_t* dcol, const double* dval, int64_t nnz, double* out, int mem) {
+    int st = SDPSR_OK;
     hipStream_t s = c->stream;
     const uint32_t* dL = labels_in_dev(c, "prim_in_a", labels, len, mem, &st);
     double* dO = out_dev(c, "red_out", out, (size_t)m * d, mem, &st);
@@ -59,9 +97,6 @@ int sdpsr_reduce_constraints_csr(sdpsr_ctx* c, int64_t len, const uint32_t* labe
     // every element of out is written: exact zeros first, then one store per (row, class) pair that has entries
     HIP_TRY(c, hipMemsetAsync(dO, 0, (size_t)m * d * 8, s));
     if (nnz > 0) {
-        int64_t* drp = (int64_t*)ctx_buf(c, "csr_rowptr", (size_t)(m + 1) * 8);  // (the CSR buffers of the setup entries)
-        uint32_t* dcol = (uint32_t*)ctx_buf(c, "csr_col", (size_t)nnz * 4);
-        double* dval = (double*)ctx_buf(c, "csr_val", (size_t)nnz * 8);
         uint32_t* key = (uint32_t*)ctx_buf(c, "redc_key", (size_t)nnz * 4);
         uint32_t* kA = (uint32_t*)ctx_buf(c, "redc_key_a", (size_t)nnz * 4);
         uint32_t* kB = (uint32_t*)ctx_buf(c, "redc_key_b", (size_t)nnz * 4);
@@ -69,12 +104,7 @@ int sdpsr_reduce_constraints_csr(sdpsr_ctx* c, int64_t len, const uint32_t* labe
         uint32_t* vB = (uint32_t*)ctx_buf(c, "redc_idx_b", (size_t)nnz * 4);
         uint32_t* hist = (uint32_t*)ctx_buf(c, "redc_hist", radix_sort_hist_words(nnz) * 4);
         void* carry = ctx_buf(c, "redc_carry", csr_class_sums_carry_bytes(nnz));
-        if (!drp || !dcol || !dval || !key || !kA || !kB || !vA || !vB || !hist || !carry) return SDPSR_OUT_OF_MEMORY;
-        // (pageable sources: A lives until the return, and the stream is waited for before it)
-        HIP_TRY(c, hipMemcpyAsync(drp, A.rowptr.data(), (size_t)(m + 1) * 8, hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemcpyAsync(dcol, A.col.data(), (size_t)nnz * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemcpyAsync(dval, A.val.data(), (size_t)nnz * 8, hipMemcpyHostToDevice, s));
-        c->h2d_bytes += (size_t)(m + 1) * 8 + (size_t)nnz * 12;
+        if (!key || !kA || !kB || !vA || !vB || !hist || !carry) return SDPSR_OUT_OF_MEMORY;
         launch_csr_entry_labels(s, nnz, dcol, dL, d, key);
         int bits = 1;
         while (((int64_t)1 << bits) <= d) ++bits;
@@ -88,5 +118,3 @@ int sdpsr_reduce_constraints_csr(sdpsr_ctx* c, int64_t len, const uint32_t* labe
     if (c->pinned_small[0]) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "reduce_constraints_csr: a label exceeds d = dim(P)");
     return SDPSR_OK;
 }
-
-}  // extern "C"

@@ -103,6 +103,16 @@ struct sdpsr_problem {
     int hint = 0;  // sdpsr_hint_symmetric_basis bits that hold for these inputs
 };
 
+// sdpsr_sparse_create: a sparse constraint matrix in canonical CSR form, device-resident, shared (read-only) by every entry that names it
+struct sdpsr_sparse {
+    int device = 0;
+    int64_t len = 0, m = 0, nnz = 0;  // nnz: canonical entries
+    int64_t* rowptr = nullptr;        // m + 1, 0-based; hipMalloc'ed, owned (like col and val)
+    uint32_t* col = nullptr;          // sorted per row, no duplicates
+    double* val = nullptr;            // no zeros
+    int rows_symmetric = 0;           // len = n^2 and every row is a symmetric n x n matrix bit for bit
+};
+
 // Host wait for a stream of ctx c (every wait of the library goes through here).  Inside a batch call the wait polls and
 // hands the thread to the other restarts' fibers.  hipStreamQuery records its "not ready" as the thread's last error, and
 // all fibers share that slot: exactly that value is dropped on every way out (a fiber whose first query succeeds must not

@@ -139,23 +139,23 @@ std::vector<double> upper_inverse(const std::vector<double>& R, int64_t m) {
     return X;
 }
 
-struct CsrSetupOut {
-    double *CL = nullptr, *X0 = nullptr;
-    const double* U = nullptr;  // len x r on the device
-    int64_t r = 0;
-    int hint = 0;
-    int32_t info = SDPSR_SETUP_NO_CONSTRAINTS;
-};
-
 constexpr size_t PINNED_OFF = 8192;  // the refinement's reports live at the start of the pinned area
 
-int setup_csr_impl(sdpsr_ctx* c, int64_t n, int64_t m, const int64_t* rowptr, const int64_t* colind, const double* val, int base,
-                   const double* b, const double* C, double atol, CsrSetupOut& o) {
+// the checks every setup entry makes before it looks at A
+int setup_check_arguments(sdpsr_ctx* c, int64_t n, int64_t m, const double* b, const double* C, double atol) {
     if (!C || n < 1 || m < 0 || (m > 0 && !b) || !(atol > 0)) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "bad arguments");
-    const int64_t len = n * n;
-    int st = check_len(c, len);
+    int st = check_len(c, n * n);
     if (st) return st;
     if (m > 0x7FFFFFFF) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "m too large");
+    return SDPSR_OK;
+}
+
+// the _csr entries: the host pass, the upload of the canonical arrays into the ctx's CSR buffers, then the stage itself
+int setup_csr_impl(sdpsr_ctx* c, int64_t n, int64_t m, const int64_t* rowptr, const int64_t* colind, const double* val, int base,
+                   const double* b, const double* C, double atol, CsrSetupOut& o) {
+    int st = setup_check_arguments(c, n, m, b, C, atol);
+    if (st) return st;
+    const int64_t len = n * n;
     CanonCsr A;
     st = canonicalize_csr(c, len, m, rowptr, colind, val, base, A);
     if (st) return st;
@@ -163,14 +163,41 @@ int setup_csr_impl(sdpsr_ctx* c, int64_t n, int64_t m, const int64_t* rowptr, co
     for (int64_t i = 0; i < m; ++i)
         if (!std::isfinite(b[i])) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "non-finite b");
     hipStream_t s = c->stream;
-    const int64_t mm = std::max<int64_t>(m, 1);
     const int64_t nnz = (int64_t)A.col.size();
-    const int nblk = 2048;
-    double* W = m > 0 ? (double*)ctx_buf(c, "csr_w", (size_t)len * m * 8) : nullptr;  // A's rows as columns, then U
+    double* W = m > 0 ? (double*)ctx_buf(c, "csr_w", (size_t)len * m * 8) : nullptr;  // (the largest buffer first: its failure costs nothing else)
     if (m > 0 && !W) return SDPSR_OUT_OF_MEMORY;
     int64_t* drp = (int64_t*)ctx_buf(c, "csr_rowptr", (size_t)(m + 1) * 8);
     uint32_t* dcol = (uint32_t*)ctx_buf(c, "csr_col", (size_t)std::max<int64_t>(nnz, 1) * 4);
     double* dval = (double*)ctx_buf(c, "csr_val", (size_t)std::max<int64_t>(nnz, 1) * 8);
+    if (!drp || !dcol || !dval) return SDPSR_OUT_OF_MEMORY;
+    // (pageable sources: the copies have read them by the stage's first host wait; A lives until the return)
+    if (m > 0) {
+        HIP_TRY(c, hipMemcpyAsync(drp, A.rowptr.data(), (size_t)(m + 1) * 8, hipMemcpyHostToDevice, s));
+        if (nnz > 0) {
+            HIP_TRY(c, hipMemcpyAsync(dcol, A.col.data(), (size_t)nnz * 4, hipMemcpyHostToDevice, s));
+            HIP_TRY(c, hipMemcpyAsync(dval, A.val.data(), (size_t)nnz * 8, hipMemcpyHostToDevice, s));
+        }
+        c->h2d_bytes += (size_t)(m + 1) * 8 + (size_t)nnz * 12;
+    }
+    st = setup_from_device_csr(c, n, m, drp, dcol, dval, nnz, symmetric, b, C, atol, o);
+    if (st && m > 0) (void)ctx_sync_stream(c, s);  // (a failure before the stage's first wait: the copies still read A)
+    return st;
+}
+
+}  // namespace
+
+// The setup stage from canonical CSR arrays that are on the device already: every kernel sees the same inputs with the same
+// launch geometry whether the arrays came from the host pass above or from a handle (sdpsr_admissible_setup_sparse)
+int sdpsr::setup_from_device_csr(sdpsr_ctx* c, int64_t n, int64_t m, const int64_t* drp, const uint32_t* dcol, const double* dval, int64_t nnz,
+                                 bool symmetric, const double* b, const double* C, double atol, CsrSetupOut& o) {
+    (void)nnz;
+    const int64_t len = n * n;
+    int st = SDPSR_OK;
+    hipStream_t s = c->stream;
+    const int64_t mm = std::max<int64_t>(m, 1);
+    const int nblk = 2048;
+    double* W = m > 0 ? (double*)ctx_buf(c, "csr_w", (size_t)len * m * 8) : nullptr;  // A's rows as columns, then U
+    if (m > 0 && !W) return SDPSR_OUT_OF_MEMORY;
     double* v1 = (double*)ctx_buf(c, "set_v1", (size_t)len * 8);
     double* v2 = (double*)ctx_buf(c, "set_v2", (size_t)len * 8);
     o.CL = (double*)ctx_buf(c, "adm_cl", (size_t)len * 8);
@@ -180,25 +207,16 @@ int setup_csr_impl(sdpsr_ctx* c, int64_t n, int64_t m, const int64_t* rowptr, co
     double* gpart = m > 0 ? (double*)ctx_buf(c, "csr_gram_part", gram_tall_partial_doubles(len, m) * 8) : nullptr;
     double* dX = m > 0 ? (double*)ctx_buf(c, "csr_x", (size_t)m * m * 8) : nullptr;
     int32_t* dpiv = m > 0 ? (int32_t*)ctx_buf(c, "csr_piv", (size_t)m * 4) : nullptr;
-    if (!drp || !dcol || !dval || !v1 || !v2 || !o.CL || !o.X0 || !partial || !coef || (m > 0 && (!gpart || !dX || !dpiv)))
-        return SDPSR_OUT_OF_MEMORY;
+    if (!v1 || !v2 || !o.CL || !o.X0 || !partial || !coef || (m > 0 && (!gpart || !dX || !dpiv))) return SDPSR_OUT_OF_MEMORY;
     // pinned staging of the small m x m traffic: G (written by the Gram kernel), X and piv (uploaded in stream order)
     char* pin = m > 0 ? (char*)ctx_pinned(c, PINNED_OFF + (size_t)m * m * 16 + (size_t)m * 4) : nullptr;
     if (m > 0 && !pin) return ctx_fail(c, SDPSR_OUT_OF_MEMORY, "pinned staging");
     double* hG = m > 0 ? (double*)(pin + PINNED_OFF) : nullptr;
     double* hX = m > 0 ? hG + (size_t)m * m : nullptr;
     int32_t* hpiv = m > 0 ? (int32_t*)(hX + (size_t)m * m) : nullptr;
-    // (pageable sources: the copies have read them by the first host wait below; A lives until the return)
+    // (a pageable source: the copy has read it by the first host wait below)
     HIP_TRY(c, hipMemcpyAsync(v1, C, (size_t)len * 8, hipMemcpyHostToDevice, s));  // v1 = c
     c->h2d_bytes += (size_t)len * 8;
-    if (m > 0) {
-        HIP_TRY(c, hipMemcpyAsync(drp, A.rowptr.data(), (size_t)(m + 1) * 8, hipMemcpyHostToDevice, s));
-        if (nnz > 0) {
-            HIP_TRY(c, hipMemcpyAsync(dcol, A.col.data(), (size_t)nnz * 4, hipMemcpyHostToDevice, s));
-            HIP_TRY(c, hipMemcpyAsync(dval, A.val.data(), (size_t)nnz * 8, hipMemcpyHostToDevice, s));
-        }
-        c->h2d_bytes += (size_t)(m + 1) * 8 + (size_t)nnz * 12;
-    }
     o.hint = symmetric ? 3 : 0;
     std::vector<std::vector<double>> coeffs;  // coeffs[i][j]: coefficient of U's column j in row i (as setup_mgs has them)
     std::vector<int64_t> piv;
@@ -278,19 +296,11 @@ int setup_csr_impl(sdpsr_ctx* c, int64_t n, int64_t m, const int64_t* rowptr, co
     return SDPSR_OK;
 }
 
-}  // namespace
+namespace {
 
-extern "C" {
-
-int sdpsr_admissible_setup_csr(sdpsr_ctx* c, int64_t n, int64_t m, const int64_t* rowptr, const int64_t* colind, const double* val,
-                               int index_base, const double* b, const double* C, double atol, double* CL, double* X0L, double* U,
-                               int64_t* r_out, int* hint_out, int32_t* info_out, int mem_out) {
-    CHECK_CTX(c);
-    c->hint_symmetric_basis = 0;
-    if (!CL || !X0L || !r_out || (m > 0 && !U)) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "bad arguments");
-    CsrSetupOut o;
-    int st = setup_csr_impl(c, n, m, rowptr, colind, val, index_base, b, C, atol, o);
-    if (st) return st;
+// what the two setup entries of either kind do with the stage's result
+int setup_deliver(sdpsr_ctx* c, int64_t n, const CsrSetupOut& o, double* CL, double* X0L, double* U, int64_t* r_out, int* hint_out,
+                  int32_t* info_out, int mem_out) {
     const int64_t len = n * n;
     const hipMemcpyKind kind = mem_out == SDPSR_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     hipStream_t s = c->stream;
@@ -305,6 +315,72 @@ int sdpsr_admissible_setup_csr(sdpsr_ctx* c, int64_t n, int64_t m, const int64_t
     return SDPSR_OK;
 }
 
+int subspace_after_setup(sdpsr_ctx* c, int64_t n, const CsrSetupOut& o, double atol, uint32_t* P_out, int64_t* dim_out, int32_t* iters_out,
+                         double* phase_ms, int mem_out) {
+    const int64_t len = n * n;
+    int st_buf = SDPSR_OK;
+    uint32_t* dP = labels_out_dev(c, "adm_labels", P_out, (size_t)len, mem_out, &st_buf);
+    if (!dP) return SDPSR_OUT_OF_MEMORY;
+    c->hint_symmetric_basis = o.hint;  // proved by the setup: symmetric rows, position-independent arithmetic
+    int st = admissible_subspace_impl(c, n, o.CL, o.X0, o.U, o.r, atol, dP, dim_out, iters_out, phase_ms, SDPSR_MEM_DEVICE, SDPSR_MEM_DEVICE, true, nullptr);  // (dP: uint32 labels)
+    if (st && st != SDPSR_NOT_CONVERGED) return st;
+    const int st_loop = st;
+    if (label_width_overflows(c, (uint64_t)*dim_out)) return label_width_fail(c, "admissible_subspace", (uint64_t)*dim_out);  // (P_out untouched)
+    st = labels_out_finish(c, P_out, dP, len, mem_out);
+    return st ? st : st_loop;
+}
+
+// the _sparse entries: the handle's arrays are the stage's inputs as they lie
+int setup_sparse_impl(sdpsr_ctx* c, int64_t n, const sdpsr_sparse* A, const double* b, const double* C, double atol, CsrSetupOut& o) {
+    if (!A) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "no sparse handle");
+    if (A->device != c->device) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "the sparse handle lives on another device");
+    int st = setup_check_arguments(c, n, A->m, b, C, atol);
+    if (st) return st;
+    if (n * n != A->len) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "n^2 != len of the sparse handle");
+    for (int64_t i = 0; i < A->m; ++i)
+        if (!std::isfinite(b[i])) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "non-finite b");
+    return setup_from_device_csr(c, n, A->m, A->rowptr, A->col, A->val, A->nnz, A->rows_symmetric != 0, b, C, atol, o);
+}
+
+}  // namespace
+
+extern "C" {
+
+int sdpsr_admissible_setup_csr(sdpsr_ctx* c, int64_t n, int64_t m, const int64_t* rowptr, const int64_t* colind, const double* val,
+                               int index_base, const double* b, const double* C, double atol, double* CL, double* X0L, double* U,
+                               int64_t* r_out, int* hint_out, int32_t* info_out, int mem_out) {
+    CHECK_CTX(c);
+    c->hint_symmetric_basis = 0;
+    if (!CL || !X0L || !r_out || (m > 0 && !U)) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "bad arguments");
+    CsrSetupOut o;
+    int st = setup_csr_impl(c, n, m, rowptr, colind, val, index_base, b, C, atol, o);
+    if (st) return st;
+    return setup_deliver(c, n, o, CL, X0L, U, r_out, hint_out, info_out, mem_out);
+}
+
+// the same stage on a handle's arrays (sdpsr_sparse_create): no host pass, no upload of A
+int sdpsr_admissible_setup_sparse(sdpsr_ctx* c, int64_t n, const sdpsr_sparse* A, const double* b, const double* C, double atol, double* CL,
+                                  double* X0L, double* U, int64_t* r_out, int* hint_out, int32_t* info_out, int mem_out) {
+    CHECK_CTX(c);
+    c->hint_symmetric_basis = 0;
+    if (!A || !CL || !X0L || !r_out || (A->m > 0 && !U)) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "bad arguments");
+    CsrSetupOut o;
+    int st = setup_sparse_impl(c, n, A, b, C, atol, o);
+    if (st) return st;
+    return setup_deliver(c, n, o, CL, X0L, U, r_out, hint_out, info_out, mem_out);
+}
+
+int sdpsr_admissible_subspace_sparse(sdpsr_ctx* c, int64_t n, const sdpsr_sparse* A, const double* b, const double* C, double atol,
+                                     uint32_t* P_out, int64_t* dim_out, int32_t* iters_out, double* phase_ms, int mem_out) {
+    CHECK_CTX(c);
+    c->hint_symmetric_basis = 0;
+    if (!A || !P_out || !dim_out) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "bad arguments");
+    CsrSetupOut o;
+    int st = setup_sparse_impl(c, n, A, b, C, atol, o);
+    if (st) return st;
+    return subspace_after_setup(c, n, o, atol, P_out, dim_out, iters_out, phase_ms, mem_out);
+}
+
 int sdpsr_admissible_subspace_csr(sdpsr_ctx* c, int64_t n, int64_t m, const int64_t* rowptr, const int64_t* colind, const double* val,
                                   int index_base, const double* b, const double* C, double atol, uint32_t* P_out, int64_t* dim_out,
                                   int32_t* iters_out, double* phase_ms, int mem_out) {
@@ -314,17 +390,7 @@ int sdpsr_admissible_subspace_csr(sdpsr_ctx* c, int64_t n, int64_t m, const int6
     CsrSetupOut o;
     int st = setup_csr_impl(c, n, m, rowptr, colind, val, index_base, b, C, atol, o);
     if (st) return st;
-    const int64_t len = n * n;
-    int st_buf = SDPSR_OK;
-    uint32_t* dP = labels_out_dev(c, "adm_labels", P_out, (size_t)len, mem_out, &st_buf);
-    if (!dP) return SDPSR_OUT_OF_MEMORY;
-    c->hint_symmetric_basis = o.hint;  // proved above: symmetric rows, position-independent arithmetic
-    st = admissible_subspace_impl(c, n, o.CL, o.X0, o.U, o.r, atol, dP, dim_out, iters_out, phase_ms, SDPSR_MEM_DEVICE, SDPSR_MEM_DEVICE, true, nullptr);  // (dP: uint32 labels)
-    if (st && st != SDPSR_NOT_CONVERGED) return st;
-    const int st_loop = st;
-    if (label_width_overflows(c, (uint64_t)*dim_out)) return label_width_fail(c, "admissible_subspace", (uint64_t)*dim_out);  // (P_out untouched)
-    st = labels_out_finish(c, P_out, dP, len, mem_out);
-    return st ? st : st_loop;
+    return subspace_after_setup(c, n, o, atol, P_out, dim_out, iters_out, phase_ms, mem_out);
 }
 
 }  // extern "C"

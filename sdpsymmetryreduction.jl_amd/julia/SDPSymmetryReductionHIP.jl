@@ -206,6 +206,72 @@ function reduce_constraints(P::HIPPartition, A::SparseMatrixCSC)
     return out
 end
 
+# ---- a device-resident sparse A (sdpsr_sparse_create): A is validated and canonicalised ONCE, on the device, and both
+# consumers -- the setup stage (partitions.jl:117-142, utils.jl:58-66) and A * PMat (README.md:57-60,
+# docs/src/examples/ReduceAndSolveJuMP.jl:42-51) -- read the handle where it lies.  sparse(A')'s colptr / rowval / nzval
+# are the CSR arrays of A and go in unchanged with index_base = 1; a caller whose arrays are AMDGPU.jl arrays passes
+# their device pointers with mem = MEM_DEVICE (SparseConstraints(len, m, rowptr, colind, val; mem=MEM_DEVICE)).
+# WRITTEN BLIND like the rest of this file: never run.
+mutable struct SparseConstraints
+    handle::Ptr{Cvoid}
+    len::Int64
+    m::Int64
+    nnz::Int64            # canonical entries
+    rows_symmetric::Bool
+    function SparseConstraints(len::Integer, m::Integer, rowptr, colind, val; index_base::Integer=1, mem::Cint=MEM_HOST,
+                               nnz::Integer=length(colind))
+        cx = ctx(); h = Ref{Ptr{Cvoid}}(C_NULL)
+        check(cx, ccall((:sdpsr_sparse_create, libsdpsr), Cint,
+                        (Ptr{Cvoid}, Int64, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Cint, Cint, Ref{Ptr{Cvoid}}),
+                        cx.handle, len, m, nnz, rowptr, colind, val, Cint(index_base), mem, h))
+        ln = Ref{Int64}(0); mm = Ref{Int64}(0); nz = Ref{Int64}(0); sym = Ref{Cint}(0)
+        ccall((:sdpsr_sparse_info, libsdpsr), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Cint}), h[], ln, mm, nz, sym)
+        s = new(h[], ln[], mm[], nz[], sym[] != 0)
+        finalizer(q -> (q.handle != C_NULL && ccall((:sdpsr_sparse_destroy, libsdpsr), Cint, (Ptr{Cvoid},), q.handle); q.handle = C_NULL), s)
+        return s
+    end
+end
+function SparseConstraints(A::SparseMatrixCSC)
+    At = sparse(SparseMatrixCSC{Float64}(A)')
+    return SparseConstraints(size(A, 2), size(A, 1), Vector{Int64}(At.colptr), Vector{Int64}(At.rowval), At.nzval)
+end
+# the canonical arrays (sdpsr_sparse_export), 1-based by default: sparse(A')'s colptr / rowval / nzval again
+function arrays(S::SparseConstraints; index_base::Integer=1)
+    rowptr = Vector{Int64}(undef, S.m + 1); colind = Vector{Int64}(undef, S.nnz); val = Vector{Float64}(undef, S.nnz); cx = ctx()
+    check(cx, ccall((:sdpsr_sparse_export, libsdpsr), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Cint),
+                    cx.handle, S.handle, Cint(index_base), rowptr, colind, val, MEM_HOST))
+    return rowptr, colind, val
+end
+# the setup stage from a handle (sdpsr_admissible_setup_sparse): what _setup returns for a sparse A
+function _setup(C::AbstractVector{Float64}, S::SparseConstraints, b::AbstractVector{Float64}, atol)
+    n = isqrt(length(C)); @assert n^2 == length(C) == S.len && length(b) == S.m
+    c = Vector{Float64}(undef, n^2); x0 = Vector{Float64}(undef, n^2); U = Matrix{Float64}(undef, n^2, max(S.m, 1))
+    r = Ref{Int64}(0); hint = Ref{Cint}(0); info = Ref{Int32}(0); cx = ctx()
+    check(cx, ccall((:sdpsr_admissible_setup_sparse, libsdpsr), Cint,
+                    (Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Float64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                     Ref{Int64}, Ref{Cint}, Ref{Int32}, Cint),
+                    cx.handle, n, S.handle, Vector{Float64}(b), Vector{Float64}(C), atol, c, x0, U, r, hint, info, MEM_HOST))
+    return n, c, x0, U[:, 1:r[]], Int(hint[])
+end
+# setup and loop in one call (sdpsr_admissible_subspace_sparse)
+function SR.admissible_subspace(::Type{PT}, C::AbstractVector{T}, S::SparseConstraints, b::AbstractVector{T};
+                                atol=Base.rtoldefault(real(T))) where {T<:AbstractFloat,PT<:HIPPartition}
+    LT = labeltype(PT); n = isqrt(length(C)); @assert n^2 == length(C) == S.len && length(b) == S.m
+    P = Matrix{LT}(undef, n, n); d = Ref{Int64}(0); it = Ref{Int32}(0); cx = width!(ctx(), LT)
+    check(cx, ccall((:sdpsr_admissible_subspace_sparse, libsdpsr), Cint,
+                    (Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Float64, Ptr{Cvoid}, Ref{Int64}, Ref{Int32}, Ptr{Float64}, Cint),
+                    cx.handle, n, S.handle, Vector{Float64}(b), Vector{Float64}(C), atol, P, d, it, C_NULL, MEM_HOST))
+    return HIPPartition(d[], P)
+end
+# newA = reduce_constraints(P, S) (sdpsr_reduce_constraints_sparse)
+function reduce_constraints(P::HIPPartition, S::SparseConstraints)
+    d = Int64(P.nparts); @assert length(P.matrix) == S.len
+    out = Matrix{Float64}(undef, S.m, d); cx = width!(ctx(), labeltype(P))
+    check(cx, ccall((:sdpsr_reduce_constraints_sparse, libsdpsr), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Float64}, Cint),
+                    cx.handle, S.handle, P.matrix, d, out, MEM_HOST))
+    return out
+end
+
 # ---- the whole reduction in ONE call (sdpsr_jordan_reduce): admissible_subspace + blockDiagonalize with the
 # partition staying on the device; the images are fetched with sdpsr_block_images once their size is known ----
 function jordan_reduce(C::AbstractVector{Float64}, A::AbstractMatrix{Float64}, b::AbstractVector{Float64};
