@@ -87,6 +87,7 @@ int block_diagonalize_impl(sdpsr_ctx* c, int64_t n, const uint32_t* P, int64_t d
         return ctx_fail(c, SDPSR_SOLVER_ERROR, "requested driver not applicable to this partition (" + c->err + ")");
     if (st != SDPSR_OK && st != DRIVER_FALLBACK) return st;
     if (st == DRIVER_FALLBACK) {
+        flush_deferred_tail(c);  // sdpsr_jordan_reduce: a pending deferred tail goes first, every host wait of the dense driver is for the stream
         st = dense_diagonalize(c, n, L, nullptr, atol, info, sizes, S1, S, tm, d);  // d: extra coupling elements on demand
         if (st) return st;
     }

@@ -144,6 +144,19 @@ int Module::ortho_step(int mc, double tol, bool take_ref, const Rider* rider, Se
     // the exact-shape Gram kernel stores the product into pinned host memory as well: no copy launch before the read-back
     double* hpin = (double*)ctx_pinned(c, (size_t)ap * mp * 8);
     bool host_filled = false;
+    // sdpsr_jordan_reduce, the loop's deferred tail pending (sdpsr_internal.h): the first step of a round whose product comes back in
+    // pinned memory takes ONE segment along -- a stamp behind the product (and the rider), the segment behind the stamp, and the host
+    // waits for the stamp: the segment's square and verify pass run while the host selects the directions (class sums) or solves the
+    // compressed problem (invariance round); what the host enqueues next follows them in stream order.  The segments' buffers belong to
+    // the loop (flush_deferred_tail names them); the growth works on "cm_*", "gram_partials", the labels and the pinned buffers only and
+    // runs no refinement, so "ref_first" stays what the verify passes expect.  Any other step waits for the stream, or may request
+    // buffers: everything pending is enqueued before its product.
+    const bool ride = take_ref && hpin && deferred_tail_pending(c) && small_on_host() && gram_tn_is_skinny(w + mc, mc);
+    // (Trade-off, off the benchmark's path: a step that does not ride -- the second orthogonalisation step of a non-commutative round --
+    // puts the pending segment in front of its product, so its stream wait is ~100 us longer than the product alone; and an upload behind
+    // a ride that finds the upload ring wrapped (h2d_sync) waits for the stream behind the segment.  Both cost what the segment would have
+    // cost in the loop, never more, and keep the rule that a segment is always enqueued before anything that could disturb it.)
+    if (!ride) flush_deferred_tail(c);
     int st = hpin ? gram_tn(c, w + mc, mc, ld, W, ld, W + (size_t)w * ld, ld, Cc, ap, mp, hpin, &host_filled) : SDPSR_OUT_OF_MEMORY;
     if (st) return st;
     if (rider && apply_generic(w, T) == SDPSR_OK) {  // T[:, 0:w) = A2 W
@@ -151,14 +164,22 @@ int Module::ortho_step(int mc, double tol, bool take_ref, const Rider* rider, Se
         spec_b2 = true;
     }
     hG.resize((size_t)ap * mp);
-    if (host_filled) {
+    if (host_filled && ride) {
+        uint32_t* stamp = c->pinned_small + PINNED_SMALL_GRAM_STAMP.first;
+        const uint32_t seq = ++c->report_seq ? c->report_seq : ++c->report_seq;
+        *(volatile uint32_t*)stamp = 0;
+        launch_report_stamp(c->stream, stamp, seq);  // (a kernel of its own: a ticket inside gram_reduce_kernel, last workgroup stamps, measured 3 % slower, profiles/r15)
+        flush_deferred_tail(c, 1);
+        if (ctx_wait_word(c, c->stream, stamp, seq) != hipSuccess) return ctx_fail(c, SDPSR_HIP_ERROR, "report wait (module growth)");
+        memcpy(hG.data(), hpin, (size_t)ap * mc * 8);
+    } else if (host_filled) {
         if (ctx_sync_stream(c, c->stream) != hipSuccess) return ctx_fail(c, SDPSR_HIP_ERROR, "hipStreamSynchronize (module growth)");
         memcpy(hG.data(), hpin, (size_t)ap * mc * 8);
     } else {
         st = d2h_sync(c, hG.data(), Cc, (size_t)ap * mc * 8);  // the mc columns the host looks at
         if (st) return st;
     }
-    if (!sym_checked) {  // the stream has been synchronised: the verdict of the symmetric check is in
+    if (!sym_checked) {  // the product is in (stream or stamp), and the verdict of the symmetric check was copied before it in the stream
         sym_checked = true;
         if (sym_pre ? c->pinned_small[0] == c->bd_sym_epoch : c->pinned_small[0] != 0)
             return ctx_fail(c, SDPSR_INVALID_DECOMPOSITION_FIELD,
@@ -217,7 +238,10 @@ int Module::absorb(int m, const Rider* rider, int& got) {
 // row-sum kernel of basis_image with a single column).  For a commutative algebra this
 // already is the whole module.
 int Module::class_sum_round() {
-    if (!(class_sums_supports(n, d, ld) && basis_image_two_stage_fits(n, d, 1) && d <= ycap && d + 1 < wmax)) return SDPSR_OK;
+    if (!(class_sums_supports(n, d, ld) && basis_image_two_stage_fits(n, d, 1) && d <= ycap && d + 1 < wmax)) {
+        flush_deferred_tail(c);  // no class-sum round: not the route with a host wait per segment (ortho_step)
+        return SDPSR_OK;
+    }
     launch_class_sums(c->stream, n, d, L, W, W + (size_t)w * ld, ld);  // W[:, w + i] = P_{i+1} x
     int got;
     return absorb((int)d, nullptr, got);
@@ -283,7 +307,11 @@ int Module::grow(PhaseTimer& tm) {
     PhaseScope phase{tm, SDPSR_T_EIGEN, true};
     int st = seed_basis(), got = 1;
     if (!st) st = class_sum_round();
-    for (int round = 0; round < 40 && !st && got != 0; ++round) st = growth_round(got);
+    for (int round = 0; round < 40 && !st && got != 0; ++round) {
+        if (round >= 1) flush_deferred_tail(c);  // (more than two rounds: one segment per round was the class sums' and the first growth round's)
+        st = growth_round(got);
+    }
+    flush_deferred_tail(c);  // the steps behind the growth wait for the stream
     if (st) return st;
     if (got != 0) return driver_fallback(c, "module growth did not close within 40 rounds");  // never diagonalise a module that no round has confirmed invariant
     // device tail: columns >= w must be zero for its padded products

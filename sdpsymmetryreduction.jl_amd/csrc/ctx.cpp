@@ -244,7 +244,8 @@ int sdpsr_create(int device_id, uint64_t seed, const sdpsr_opts* opts, sdpsr_ctx
         return SDPSR_HIP_ERROR;
     }
     c->pinned_bytes = 1 << 16;
-    if (hipHostMalloc((void**)&c->pinned_small, 256, hipHostMallocDefault) != hipSuccess) c->pinned_small = nullptr;
+    // (coherent: the module growth's stamp is read there while the stream runs, PINNED_SMALL_GRAM_STAMP)
+    if (hipHostMalloc((void**)&c->pinned_small, 256, hipHostMallocCoherent) != hipSuccess) c->pinned_small = nullptr;
     if (hipHostMalloc(&c->pinned, c->pinned_bytes, hipHostMallocCoherent) != hipSuccess) {
         hipStreamDestroy(c->stream);
         delete c;

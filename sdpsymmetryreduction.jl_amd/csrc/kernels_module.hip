@@ -281,6 +281,15 @@ void launch_gram_small(hipStream_t s, int64_t k, int ma, int nb, const double* A
     gram_reduce_kernel<<<(mp * np + 15) / 16, 256, 0, s>>>(ma, nb, mp, np, Z, partials, C, ldc, host_C);
 }
 
+// The stamp behind such products: the host waits for this word instead of for the stream (ctx_wait_word) and reads the pinned
+// copies host_C while the kernels enqueued behind the stamp run.  The products are complete when this kernel starts (stream
+// order); the fence is the one of the refinement's report (refine_label_kernel).
+__global__ void report_stamp_kernel(uint32_t* host_word, uint32_t seq) {
+    __threadfence_system();
+    *(volatile uint32_t*)host_word = seq;
+}
+void launch_report_stamp(hipStream_t s, uint32_t* host_word, uint32_t seq) { report_stamp_kernel<<<1, 1, 0, s>>>(host_word, seq); }
+
 // ---------------------------------------------------------------------------
 // Fused randomize! + product:  Y = A W  with  A[r,c] = value(L[r,c])  never materialised
 // (src/abstract_part.jl:107-110 fused into the products of the module-compression driver).

@@ -2221,8 +2221,12 @@ bool launch_basis_constant_on_classes(hipStream_t s, int64_t n, int64_t r, const
 }
 // q: SIG_JOINT_I32 or SIG_CHAN_I32 on the packed lower triangle with packed labels (q.L = Lp); flag[0] = verdict.
 // Returns false when there is no instance for the shape (the caller runs the refinement).
-bool launch_verify_no_split(hipStream_t s, const SigSource& q, int64_t d, const uint32_t* first_idx, void* ref, uint32_t* flag) {
+bool verify_no_split_supports(const SigSource& q, int64_t d) {
     if (!q.packed || !q.lab_packed || d < 1 || d > (int64_t)REFINE_FIRST_CAP || (q.T != 2 && q.T != 4)) return false;
+    return q.kind == SIG_CHAN_I32 || (q.kind == SIG_JOINT_I32 && q.r >= 0 && q.r <= 4);
+}
+bool launch_verify_no_split(hipStream_t s, const SigSource& q, int64_t d, const uint32_t* first_idx, void* ref, uint32_t* flag) {
+    if (!verify_no_split_supports(q, d)) return false;
     if (q.kind == SIG_CHAN_I32) {
         if (q.T == 2) launch_verify_rt<0, 2, false>(s, q, d, first_idx, ref, flag);
         else launch_verify_rt<0, 4, false>(s, q, d, first_idx, ref, flag);

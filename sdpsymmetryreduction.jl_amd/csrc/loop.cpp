@@ -120,9 +120,11 @@ struct Loop {
     // The symmetric int8 square of a fresh random element of S: X from the packed or the full labels, X'X = X X on the lower-triangle tiles only (X
     // is symmetric, the product exact).
     // write_full (packed labels only): the gather forms the full label matrix as well, unless it is current (LoopLabels).
-    void launch_square(bool from_packed, uint64_t key, void* X, void* C, int64_t dim, bool write_full = false) {
+    // gather_only: the product itself is a segment of the ctx's deferred tail (verify_round), enqueued and counted by flush_deferred_tail.
+    void launch_square(bool from_packed, uint64_t key, void* X, void* C, int64_t dim, bool write_full = false, bool gather_only = false) {
         if (from_packed) launch_gather_i8_sym_packed(s, n, ld, T, lab.Lp, key, (int8_t*)X, dim, write_full ? lab.full_from_gather() : nullptr);
         else launch_gather_i8(s, n, ld, T, lab.L, key, (int8_t*)X, dim);
+        if (gather_only) return;
         launch_gemm_tn_i8_sym(s, ld, ld, (const int8_t*)X, ld, (int32_t*)C, ld, T, ld * ld, ld * ld, zero_flag, c->num_cus, c->opts.square_kernel);
         ++c->squares_launched;
     }
@@ -151,7 +153,27 @@ struct Loop {
         return (it == 1 || confirming) && from_packed && c->first_idx_labels == lab.Lp && current >= 1 && current <= (int64_t)refine_first_cap() &&
                !(c->opts.flags & SDPSR_FLAG_NO_VERIFY_SHORTCUT);
     }
-    int verify_round(const SigSource& qj, bool confirming, bool from_packed, Verdict* v) {
+    bool guess_applies(bool confirming) const { return it == 1 && !confirming && confirm_left > 0 && c->predict_closed && c->predict_n == n && early_ok; }
+    // The guess inside sdpsr_jordan_reduce, both verdicts deferred: the round launches its two gathers only, and the two squares and
+    // verify passes wait on the ctx as its deferred tail (sdpsr_internal.h) for the host waits of blockDiagonalize.  Decided before the
+    // round's first launch, from everything verify_round would find out on its way: its buffers (asked for here, with its names and
+    // sizes) and the verify pass's instances.  With phase timers the tail would be booked under blockDiagonalize's phases (event
+    // pairs around a segment enqueued there would need a collect of their own behind another wait): a timed call launches everything here.
+    // confirm_left == 1: the speculative square is the LAST confirm round, so the round that registers the tail is the loop's last launch
+    // (another_confirm_round returns false on "confirmed").  With more confirm rounds the loop goes on: its next round gathers into
+    // "adm_xi8" again, and a refinement behind a violated verdict rewrites "adm_lpacked" / "ref_first" and outgrows "adm_vref" -- all of
+    // them the segments' operands (flush_deferred_tail).  Such a call launches everything here, in stream order, as before.
+    bool tail_applies(const SigSource& qj, bool confirming, bool from_packed) {
+        if (!verify_applies(confirming, from_packed) || !guess_applies(confirming) || confirm_left != 1 || !c->allow_deferred_verdict || !c->pinned_small || tm.enabled) return false;
+        SigSource q2 = qj;
+        q2.kind = SIG_CHAN_I32;
+        if (!verify_no_split_supports(qj, current) || !verify_no_split_supports(q2, current)) return false;
+        return ctx_buf(c, "adm_vref", verify_ref_bytes(current)) && ctx_buf(c, "ref_first", (size_t)refine_first_cap() * 4) &&
+               pinned_report(c, PINNED_VERIFY) && ctx_buf(c, "adm_xi8_spec", (size_t)T * ld * ld) &&
+               ctx_buf(c, "adm_ci32_spec", (size_t)T * ld * ld * 4) && ctx_buf(c, "adm_vref2", verify_ref_bytes(current));
+    }
+    // tail (tail_applies): the round's square has not been launched
+    int verify_round(const SigSource& qj, bool confirming, bool from_packed, bool tail, Verdict* v) {
         if (!verify_applies(confirming, from_packed)) return SDPSR_OK;
         SigSource qv = qj;
         if (confirming) qv.kind = SIG_CHAN_I32;
@@ -163,9 +185,31 @@ struct Loop {
         if (!vref || !first || !hv) return SDPSR_OUT_OF_MEMORY;
         // (inside sdpsr_jordan_reduce, on a guess that the input is closed: both verdicts go to words nobody else writes and are read by the
         // reduction behind its next host waits, not here) (no guess under SDPSR_FLAG_WAIT_FOR_EVERY_VERDICT: the control flow of rounds 1-4)
-        const bool guess = it == 1 && !confirming && confirm_left > 0 && c->predict_closed && c->predict_n == n && early_ok;
+        const bool guess = guess_applies(confirming);
         const bool defer = guess && c->allow_deferred_verdict && c->pinned_small != nullptr;
         if (defer) hv = c->pinned_small + PINNED_SMALL_DEFERRED_VERIFY.first, hv2 = c->pinned_small + PINNED_SMALL_DEFERRED_SPECULATIVE.first;
+        if (tail) {
+            // The speculative gather -- the key the confirm round would draw, the full labels for blockDiagonalize -- and then nothing:
+            // first square -> joint verify and speculative square -> channel verify are registered with the arguments they would be
+            // launched with here.  Until a segment is enqueued its verdict word reads as "violated".
+            int8_t* Xs = (int8_t*)ctx_buf(c, "adm_xi8_spec", (size_t)T * ld * ld);
+            int32_t* Cs = (int32_t*)ctx_buf(c, "adm_ci32_spec", (size_t)T * ld * ld * 4);
+            void* vref2 = ctx_buf(c, "adm_vref2", verify_ref_bytes(current));
+            if (!Xs || !Cs || !vref2) return SDPSR_OUT_OF_MEMORY;
+            launch_square(true, next_key(c), Xs, Cs, current, /*write_full=*/true, /*gather_only=*/true);
+            DeferredTail& t = c->deferred_tail;
+            t.ld = ld, t.d = current, t.T = T, t.zero_flag = zero_flag, t.first = first;
+            t.seg[0].X = (const int8_t*)Xp, t.seg[0].C = (int32_t*)Cp, t.seg[0].q = qv, t.seg[0].vref = vref, t.seg[0].flag = hv, t.seg[0].speculative = false;
+            t.seg[1].X = Xs, t.seg[1].C = Cs, t.seg[1].q = qj, t.seg[1].vref = vref2, t.seg[1].flag = hv2, t.seg[1].speculative = true;
+            t.seg[1].q.kind = SIG_CHAN_I32, t.seg[1].q.C = Cs;
+            *(volatile uint32_t*)hv = DEFERRED_NEVER_RAN;
+            *(volatile uint32_t*)hv2 = DEFERRED_NEVER_RAN;
+            t.next = 0, t.count = DEFERRED_SEGMENTS;
+            c->deferred_verdict = true;  // both words are read in reduce.cpp
+            HIP_TRY(c, hipGetLastError());
+            v->unchanged = v->spec_confirmed = true;
+            return SDPSR_OK;
+        }
         if (!launch_verify_no_split(s, qv, current, first, vref, hv)) return SDPSR_OK;  // the verdict is stored straight into pinned host memory
         // An input that was closed the last time (the restarts of ONE problem, the use this library is built for) will be closed again: the confirm
         // round -- a fresh square into its own buffers and its verify pass -- is enqueued behind the first verdict's kernels and both verdicts come
@@ -221,16 +265,18 @@ struct Loop {
         int64_t dj = current;
         bool confirming = false;  // this round repeats the square after a round that did not refine
         for (;;) {
+            flush_deferred_tail(c);  // (never pending here: the round that registers the tail is the loop's last, tail_applies)
             tm.begin(SDPSR_T_SQUARE);
             const uint64_t key2 = next_key(c);
             const bool jl2 = lab.packed();
             // a confirm round that the verify pass will judge is expected to leave the labels as they are: its gather writes the full matrix
-            launch_square(jl2, key2, Xp, Cp, current, /*write_full=*/confirming && verify_applies(confirming, jl2));
+            const SigSource qj = joint_source(jl2);
+            const bool tail = tail_applies(qj, confirming, jl2);  // this square and the speculative one go to the ctx's deferred tail
+            launch_square(jl2, key2, Xp, Cp, current, /*write_full=*/confirming && verify_applies(confirming, jl2), /*gather_only=*/tail);
             tm.end();
             tm.begin(SDPSR_T_REFINE);
-            const SigSource qj = joint_source(jl2);
             Verdict v;
-            st = verify_round(qj, confirming, jl2, &v);
+            st = verify_round(qj, confirming, jl2, tail, &v);
             if (st) return st;
             if (v.unchanged) dj = current;  // labels (packed, and full where a gather has written them), class representatives and table hints stay as they are
             else st = lab.refine_packed(qj, &dj);
@@ -376,6 +422,22 @@ struct Loop {
 }  // namespace
 
 namespace sdpsr {
+// The deferred tail's segments, in order, on the ctx's stream; squares are counted here, where they are enqueued.  A segment reads
+// "adm_xi8" / "adm_xi8_spec" (its gathered element), "adm_lpacked" and "ref_first" (labels and class representatives), "proj_coef" and
+// the caller's U (joint verify), "adm_symflag" (the constant zero); it writes "adm_ci32" / "adm_ci32_spec", "adm_vref" / "adm_vref2"
+// and its verdict word.  Whoever enqueues work of its own while segments are pending must touch none of these -- in particular run no
+// refinement (refine_signatures rewrites "ref_first") and request none of these buffers with another size (ctx_buf would free them).
+void flush_deferred_tail(sdpsr_ctx* c, int max_segments) {
+    DeferredTail& t = c->deferred_tail;
+    for (; max_segments > 0 && t.next < t.count; --max_segments, ++t.next) {
+        const DeferredSegment& g = t.seg[t.next];
+        launch_gemm_tn_i8_sym(c->stream, t.ld, t.ld, g.X, t.ld, g.C, t.ld, t.T, t.ld * t.ld, t.ld * t.ld, t.zero_flag, c->num_cus, c->opts.square_kernel);
+        ++c->squares_launched;
+        if (g.speculative) ++c->squares_speculative;
+        launch_verify_no_split(c->stream, g.q, t.d, t.first, g.vref, g.flag);  // (clears the word from the host where it is one launch)
+    }
+}
+
 // mem_in: where CL / X0L / U live; mem_out: where P_out lives.  final_sync = false (sdpsr_jordan_reduce): return with the last launches (the
 // gather or the unpack that forms the full labels) still in flight on ctx's stream -- the caller keeps enqueueing; *labels_sym_out = 1 if the labels written are symmetric by
 // construction.

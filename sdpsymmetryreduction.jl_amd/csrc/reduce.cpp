@@ -41,6 +41,12 @@ int jordan_reduce_impl(sdpsr_ctx* c, int64_t n, const double* CL, const double* 
     double pm_a[SDPSR_T_COUNT] = {}, pm_b[SDPSR_T_COUNT] = {}, pm_i[SDPSR_T_COUNT] = {};
     int labels_sym = 0;
     c->deferred_verdict = false;
+    // the loop's deferred tail lives inside this call: on the successful path it has been enqueued (below) well before the last host wait; an
+    // error return drops what is left of it, so that no later call on the ctx enqueues segments that point into this call's arguments
+    struct DropTail {
+        sdpsr_ctx* c;
+        ~DropTail() { c->deferred_tail.count = c->deferred_tail.next = 0; }
+    } drop_tail{c};
     c->allow_deferred_verdict = !(c->opts.flags & SDPSR_FLAG_WAIT_FOR_EVERY_VERDICT);  // (the loop's last verdicts may ride on this reduction's later host waits, see sdpsr_internal.h)
     st = admissible_subspace_impl(c, n, CL, X0L, U, r, atol, L, dim_out, iters_out, phase_ms ? pm_a : nullptr, mem_in, SDPSR_MEM_DEVICE,
                                   /*final_sync=*/false, &labels_sym);
@@ -60,6 +66,9 @@ int jordan_reduce_impl(sdpsr_ctx* c, int64_t n, const double* CL, const double* 
     st = overflow ? SDPSR_OK
                   : block_diagonalize_impl(c, n, L, d, epsilon, &nb, &S, &S1, phase_ms ? pm_b : nullptr, SDPSR_MEM_DEVICE, labels_sym != 0,
                                            /*final_sync=*/false, in_place);
+    // whatever blockDiagonalize did (a failure included): the rest of the deferred tail goes in front of the images' kernels and of the
+    // wait behind which the verdicts are read
+    flush_deferred_tail(c);
     if (nblocks) *nblocks = nb;
     if (sum_sq) *sum_sq = S;
     if (sum_s) *sum_s = S1;
@@ -91,6 +100,7 @@ int jordan_reduce_impl(sdpsr_ctx* c, int64_t n, const double* CL, const double* 
         forget.ok = true;
     }
     if (!images_done) {  // (sdpsr_block_images ends synchronised, and nothing has been enqueued since)
+        flush_deferred_tail(c);  // (nothing is pending here; a verdict must never be read with its segment not enqueued)
         const hipError_t e = ctx_sync_stream(c, s);
         if (e != hipSuccess && st == SDPSR_OK) st = ctx_fail(c, SDPSR_HIP_ERROR, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
     }

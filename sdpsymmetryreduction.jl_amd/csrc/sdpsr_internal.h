@@ -24,6 +24,54 @@ struct DevBuf {
     size_t bytes = 0;
 };
 
+namespace sdpsr {
+// Where the insert pass takes its signatures from: an array (SIG_ARRAY), or computed on the fly
+// (the signatures never travel through HBM).  Each kind is defined by one functor of
+// kernels_partition.hip (SrcPair, SrcProj<r>, SrcChan<CT, T>, SrcJoint<r, T>).
+// `sig` is the array (SIG_ARRAY) or len entries of scratch for the paths that need one
+// (launch_sig_materialize: sort / bucket, an overflowed table, a shape without a functor instance).
+enum { SIG_ARRAY = 0, SIG_PAIR = 1, SIG_PROJ = 2, SIG_CHAN_I32 = 3, SIG_CHAN_F32 = 4, SIG_JOINT_I32 = 5 };  // JOINT: SIG_PROJ and SIG_CHAN_I32 fields together (packed)
+struct SigSource {
+    int kind = SIG_ARRAY;
+    uint64_t* sig = nullptr;
+    const double *a = nullptr, *b = nullptr;                      // SIG_PAIR: bit patterns of (a[e], b[e])
+    const double *U = nullptr, *coef = nullptr;                   // SIG_PROJ: rounded x - U coef, x drawn from L and key; U: r matrices of n x n
+    const uint32_t* L = nullptr;                                  // old labels (SIG_PROJ, SIG_CHAN_*)
+    int r = 0;
+    uint64_t key = 0;
+    double atol = 0, scale = 1;
+    int64_t n = 0, ld = 0;                                        // matrix order (SIG_PROJ, SIG_CHAN_*, SIG_JOINT_I32; SIG_PAIR when packed); ld: SIG_CHAN_* / JOINT: T channels of ld x ld in C
+    int T = 0;
+    const void* C = nullptr;
+    int packed = 0;                                               // lower triangle only, densely packed (symmetric labels; SIG_PROJ: and symmetric basis, needs n)
+    int lab_packed = 0;                                           // (with packed) L is the packed lower triangle itself: label of packed entry e = L[e]
+};
+
+// The tail of the loop's guessed-closed path that sdpsr_jordan_reduce defers (loop.cpp, verify_round): two segments, each the
+// int8 square of a gathered element and the verify pass over its product, registered on the ctx instead of launched.  Nothing in
+// blockDiagonalize reads what they write, so they are enqueued -- same stream, same kernels, same arguments -- where the host
+// would otherwise leave the stream idle: behind the products of the module growth whose read-backs the host waits for
+// (compress.cpp, Module::ortho_step).  Every other route enqueues them before it enqueues anything of its own.
+struct DeferredSegment {
+    const int8_t* X = nullptr;  // the gathered channels (the gather itself ran in the loop)
+    int32_t* C = nullptr;       // their squares
+    SigSource q;                // the verify pass's source (q.C == C)
+    void* vref = nullptr;
+    uint32_t* flag = nullptr;   // the verdict's word of c->pinned_small
+    bool speculative = false;   // counts as a speculative square
+};
+constexpr int DEFERRED_SEGMENTS = 2;
+struct DeferredTail {
+    DeferredSegment seg[DEFERRED_SEGMENTS];
+    int count = 0, next = 0;  // registered, enqueued
+    int64_t ld = 0, d = 0;
+    int T = 0;
+    const uint32_t* zero_flag = nullptr;
+    const uint32_t* first = nullptr;  // "ref_first" of the packed labels
+};
+constexpr uint32_t DEFERRED_NEVER_RAN = 0xDEFE44EDu;  // what a verdict word holds until its segment is enqueued: reads as "violated"
+}  // namespace sdpsr
+
 struct sdpsr_ctx {
     int device = 0;
     int num_cus = 256;
@@ -93,6 +141,7 @@ struct sdpsr_ctx {
     // discard everything and the reduction is repeated without the guess.
     bool allow_deferred_verdict = false;
     bool deferred_verdict = false;  // both wait in c->pinned_small (host_internal.h: PINNED_SMALL_DEFERRED_*) and must be 0
+    sdpsr::DeferredTail deferred_tail;  // ... and the squares and verify passes that produce them, while they are not enqueued yet
 };
 
 // sdpsr_problem_create: the loop's inputs, device-resident, shared (read-only) by every reduction / restart that names them
@@ -261,27 +310,6 @@ struct RefineWs {
 size_t refine_block_entries();
 size_t refine_counters_bytes();
 uint32_t refine_small_k();
-// Where the insert pass takes its signatures from: an array (SIG_ARRAY), or computed on the fly
-// (the signatures never travel through HBM).  Each kind is defined by one functor of
-// kernels_partition.hip (SrcPair, SrcProj<r>, SrcChan<CT, T>, SrcJoint<r, T>).
-// `sig` is the array (SIG_ARRAY) or len entries of scratch for the paths that need one
-// (launch_sig_materialize: sort / bucket, an overflowed table, a shape without a functor instance).
-enum { SIG_ARRAY = 0, SIG_PAIR = 1, SIG_PROJ = 2, SIG_CHAN_I32 = 3, SIG_CHAN_F32 = 4, SIG_JOINT_I32 = 5 };  // JOINT: SIG_PROJ and SIG_CHAN_I32 fields together (packed)
-struct SigSource {
-    int kind = SIG_ARRAY;
-    uint64_t* sig = nullptr;
-    const double *a = nullptr, *b = nullptr;                      // SIG_PAIR: bit patterns of (a[e], b[e])
-    const double *U = nullptr, *coef = nullptr;                   // SIG_PROJ: rounded x - U coef, x drawn from L and key; U: r matrices of n x n
-    const uint32_t* L = nullptr;                                  // old labels (SIG_PROJ, SIG_CHAN_*)
-    int r = 0;
-    uint64_t key = 0;
-    double atol = 0, scale = 1;
-    int64_t n = 0, ld = 0;                                        // matrix order (SIG_PROJ, SIG_CHAN_*, SIG_JOINT_I32; SIG_PAIR when packed); ld: SIG_CHAN_* / JOINT: T channels of ld x ld in C
-    int T = 0;
-    const void* C = nullptr;
-    int packed = 0;                                               // lower triangle only, densely packed (symmetric labels; SIG_PROJ: and symmetric basis, needs n)
-    int lab_packed = 0;                                           // (with packed) L is the packed lower triangle itself: label of packed entry e = L[e]
-};
 bool sig_source_fusable(const SigSource& q);
 uint32_t refine_first_cap();
 size_t verify_ref_bytes(int64_t d);
@@ -293,6 +321,13 @@ int verify_lds_cap();
 bool launch_basis_constant_on_classes(hipStream_t s, int64_t n, int64_t r, const double* U, const uint32_t* Lp, int64_t d,
                                       const uint32_t* first_idx, double atol, double scale, void* ref, uint32_t* flag);
 bool launch_verify_no_split(hipStream_t s, const SigSource& q, int64_t d, const uint32_t* first_idx, void* ref, uint32_t* flag);
+bool verify_no_split_supports(const SigSource& q, int64_t d);  // launch_verify_no_split has an instance for this shape
+// loop.cpp: enqueue the next max_segments segments of the ctx's deferred tail on c->stream (none pending: nothing happens)
+void flush_deferred_tail(sdpsr_ctx* c, int max_segments = DEFERRED_SEGMENTS);
+inline bool deferred_tail_pending(const sdpsr_ctx* c) { return c->deferred_tail.next < c->deferred_tail.count; }
+// kernels_module.hip: one thread stores `seq` into a word of coherent pinned host memory, behind a system-scope fence: what the
+// kernels before it in the stream stored into pinned memory is complete when the host sees the stamp (ctx_wait_word)
+void launch_report_stamp(hipStream_t s, uint32_t* host_word, uint32_t seq);
 bool launch_sig_materialize(hipStream_t s, int64_t len, const SigSource& q, uint64_t* sig);  // false: nothing writes this source out
 // slot: len entries of scratch; labels_out may alias q.L (it is written only by a pass that succeeded)
 // sym_n > 0 (and len == sym_n^2): the label pass also checks the new labels for symmetry, counters[3] = 1 if NOT symmetric
