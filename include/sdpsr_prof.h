@@ -98,6 +98,21 @@ int sdpsr_profile_tall_times_small(sdpsr_ctx* ctx, int64_t n, int64_t ldi, int64
    [3] = columns per workgroup. */
 int sdpsr_profile_label_product(sdpsr_ctx* ctx, int64_t n, int64_t d, int G, int64_t w, int64_t ldw, int64_t ldy, const uint64_t* keys,
                                 const uint32_t* L_host, const double* W_host, double* Y_inout, int64_t guard, int32_t* report);
+/* Two label products on one W in ONE pass over the labels, through launch_label_spmm_pair (the invariance round of the module growth and
+   its rider): Y0 = A(keys[0]) W, Y1 = A(keys[1]) W, each Y_inout: ldy * w + guard.  The form is the one-element matrix-core form of
+   (n, d, w), run with two class tables: each block is bit for bit what sdpsr_profile_label_product gives with G = 1 and that key.
+   SDPSR_BAD_ARGUMENT where the pair launch refuses: w > 64, n < 64 (no matrix-core form), class tables that do not fit in LDS.
+   report as above: [0] = 1, [1] = JT, [2] = the column split z, [3] = columns per workgroup. */
+int sdpsr_profile_label_product_pair(sdpsr_ctx* ctx, int64_t n, int64_t d, int64_t w, int64_t ldw, int64_t ldy, const uint64_t* keys,
+                                     const uint32_t* L_host, const double* W_host, double* Y0_inout, double* Y1_inout, int64_t guard,
+                                     int32_t* report);
+/* Class sums of a PAIR of vectors over the window of d classes that starts at class `first`, through the class-sum pass of the
+   basis_image shortcuts (class_sums2_kernel): Y[((i - 1) n + r)] = sum over c with L[c + r n] == first + i - 1 of X[c], X_host: n
+   pairs (x, y interleaved), Y_inout: 2 n d + guard doubles.  plain = 1 (first = 1, every label <= d): the labels index the tables as
+   they are; plain = 0: any labels, mapped through the window.  report[0] = waves per workgroup (4, 2 or 1, by d).  Summation order:
+   lane q of a wave adds the columns c = q, q + 64, ... of its class ascending, from +0.0; the 64 lane sums are added in lane order. */
+int sdpsr_profile_class_sums2(sdpsr_ctx* ctx, int64_t n, int64_t d, uint32_t first, int plain, const uint32_t* L_host, const double* X_host,
+                              double* Y_inout, int64_t guard, int32_t* report);
 /* Class sums of one vector, out[(i - 1) ldo + r] = sum over c with L[c + r n] == i of x[c], through launch_class_sums with first = 1;
    d <= 4000, out_inout: ldo * d + guard.  report[0] = class_sums_supports(n, d, ldo) -- when 0, nothing ran (as in the driver) --,
    report[1] = 1: the kernel with per-lane tables in LDS, 0: the row-sort fallback (ldo == n only). */

@@ -241,6 +241,10 @@ def load_prof_library():
     lib.sdpsr_profile_tall_times_small.argtypes = [vp, i64, i64, i64, i64, i64, f64, f64, i64, vp, vp, vp, i64]
     lib.sdpsr_profile_label_product.restype = C.c_int
     lib.sdpsr_profile_label_product.argtypes = [vp, i64, i64, C.c_int, i64, i64, i64, vp, vp, vp, vp, i64, rep]
+    lib.sdpsr_profile_label_product_pair.restype = C.c_int
+    lib.sdpsr_profile_label_product_pair.argtypes = [vp, i64, i64, i64, i64, i64, vp, vp, vp, vp, vp, i64, rep]
+    lib.sdpsr_profile_class_sums2.restype = C.c_int
+    lib.sdpsr_profile_class_sums2.argtypes = [vp, i64, i64, C.c_uint32, C.c_int, vp, vp, vp, i64, rep]
     lib.sdpsr_profile_class_sums.restype = C.c_int
     lib.sdpsr_profile_class_sums.argtypes = [vp, i64, i64, i64, vp, vp, vp, i64, rep]
     lib.sdpsr_profile_symmetrize.restype = C.c_int

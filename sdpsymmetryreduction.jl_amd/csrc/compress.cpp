@@ -13,7 +13,8 @@ using namespace sdpsr;
 
 namespace {
 
-struct Rider { double *dBs, *gps; };  // device buffers of the speculative second element (Module::growth_round)
+// device buffers of the speculative second element (Module::growth_round); have_t: T = A2 W was formed with the round's own product
+struct Rider { double *dBs, *gps; bool have_t; };
 
 // ===========================================================================
 // Module-compression driver of diagonalize (DESIGN.md "module compression").
@@ -121,7 +122,7 @@ int Module::seed_basis() {
 int Module::apply_generic(int wcols, double* dst) {
     const uint64_t key = next_key(c);
     if (fused_product(wcols)) {
-        double* part = (double*)ctx_buf(c, "cm_part", label_spmm_partial_doubles(n, 64) * 8);
+        double* part = (double*)ctx_buf(c, "cm_part", label_spmm_pair_partial_doubles(n) * 8);
         if (!part) return SDPSR_OUT_OF_MEMORY;
         if (launch_label_spmm(c->stream, n, L, key, d, W, ld, wcols, part, dst, ld)) return SDPSR_OK;
     }
@@ -159,7 +160,7 @@ int Module::ortho_step(int mc, double tol, bool take_ref, const Rider* rider, Se
     if (!ride) flush_deferred_tail(c);
     int st = hpin ? gram_tn(c, w + mc, mc, ld, W, ld, W + (size_t)w * ld, ld, Cc, ap, mp, hpin, &host_filled) : SDPSR_OUT_OF_MEMORY;
     if (st) return st;
-    if (rider && apply_generic(w, T) == SDPSR_OK) {  // T[:, 0:w) = A2 W
+    if (rider && (rider->have_t || apply_generic(w, T) == SDPSR_OK)) {  // T[:, 0:w) = A2 W
         launch_gram_small(c->stream, n, w, w, W, ld, T, ld, rider->gps, rider->dBs, w, w, w, spec_b2_pinned());
         spec_b2 = true;
     }
@@ -262,7 +263,7 @@ int Module::growth_round(int& got) {
     bool batched = false;
     if (fused && G > 1 && G != 3 && G * w <= 64 && !(c->opts.flags & SDPSR_FLAG_SPMM_ONE_BY_ONE)) {
         // the G generic elements of the round in one pass over the labels
-        double* part = (double*)ctx_buf(c, "cm_part", label_spmm_partial_doubles(n, 64) * 8);
+        double* part = (double*)ctx_buf(c, "cm_part", label_spmm_pair_partial_doubles(n) * 8);
         if (!part) return SDPSR_OUT_OF_MEMORY;
         uint64_t keys[4];
         const uint64_t save = c->stream_counter;
@@ -270,14 +271,14 @@ int Module::growth_round(int& got) {
         batched = launch_label_spmm_multi(c->stream, n, L, keys, G, d, W, ld, w, part, Y, ld);
         if (!batched) c->stream_counter = save;
     }
-    for (int gidx = 0; gidx < G && !batched; ++gidx) {
-        int e2 = apply_generic(w, Y + (size_t)gidx * w * ld);
-        if (e2) return e2;
-    }
     // A round with ONE element is the invariance check of a module that is (almost surely) complete, and the host path of
     // the small problem will then want the second compressed element B2 = W'A2 W right away: it is formed behind this
     // round's product and comes back with the same host wait (its pinned words sit behind the round's Gram matrix).
     // If the round does add a direction, the element is dropped.
+    // A2 W has the same W, the same labels and another key: where the fused product takes the shape, both products are ONE pass
+    // over the labels (launch_label_spmm_pair: Y = A1 W behind the basis, T = A2 W, each bit for bit what a launch of its own
+    // gives), and the rider's part of ortho_step is the Gram product on T alone.  The keys are drawn in the order of the two
+    // launches (nothing draws between them).  SDPSR_FLAG_SPMM_ONE_BY_ONE keeps the two launches.
     spec_b2 = false;
     Rider rider{};
     bool armed = false;
@@ -288,6 +289,20 @@ int Module::growth_round(int& got) {
         rider.dBs = (double*)ctx_buf(c, "cm_bsmall", (size_t)64 * 64 * 8);
         rider.gps = (double*)ctx_buf(c, "gram_partials", gram_small_partial_doubles(n, 128, 128) * 8);
         armed = pinb && rider.dBs && rider.gps;
+    }
+    if (armed && fused && !(c->opts.flags & SDPSR_FLAG_SPMM_ONE_BY_ONE)) {
+        double* part = (double*)ctx_buf(c, "cm_part", label_spmm_pair_partial_doubles(n) * 8);
+        if (!part) return SDPSR_OUT_OF_MEMORY;
+        uint64_t keys[2];
+        const uint64_t save = c->stream_counter;
+        keys[0] = next_key(c);
+        keys[1] = next_key(c);
+        rider.have_t = launch_label_spmm_pair(c->stream, n, L, keys, d, W, ld, w, part, Y, ld, T, ld);
+        if (!rider.have_t) c->stream_counter = save;
+    }
+    for (int gidx = 0; gidx < G && !batched && !rider.have_t; ++gidx) {
+        int e2 = apply_generic(w, Y + (size_t)gidx * w * ld);
+        if (e2) return e2;
     }
     int st = absorb(m, armed ? &rider : nullptr, got);
     if (st) return st;

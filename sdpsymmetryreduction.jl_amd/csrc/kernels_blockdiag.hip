@@ -1172,6 +1172,20 @@ static void launch_class_sums2(hipStream_t s, int W, int g, size_t lds, int64_t 
     }
 }
 
+// The class-sum pass of the launchers below on its own (tests): X, Y as interleaved pairs (n resp. d * n of them), the waves per
+// workgroup and the grid chosen as they choose them.  Returns the waves per workgroup, 0 when the shape has no instance.
+int launch_class_sums_pair(hipStream_t s, int64_t n, int64_t d, uint32_t first, bool plain, const uint32_t* L, const double* X, double* Y) {
+    const int tstride = (int)((d + 1) | 1);
+    const size_t per_wave = (size_t)64 * tstride * sizeof(double2);
+    int W = 4;
+    while (W > 1 && per_wave * W > 150 * 1024) W >>= 1;
+    if (per_wave * W > 150 * 1024 || n < 1 || n > 0x7FFFFFFF / 2) return 0;
+    int g = (int)((n + W - 1) / W);
+    if (g > 256) g = 256;
+    launch_class_sums2(s, W, g, per_wave * W, n, d, first, plain, tstride, L, reinterpret_cast<const double2*>(X), reinterpret_cast<double2*>(Y));
+    return W;
+}
+
 size_t basis_image_commutative_workspace_doubles(int64_t n, int64_t d) { return (size_t)2 * n * (d + 1); }
 // All blocks 1 x 1 (S = S1).  ws: 2 n (d + 1) doubles.  Returns false when the shape has no instance (d > 148);
 // after the launches flag[0] = number of columns whose check failed, flag[1 + k] = 1 for those columns (flag: 1 + S1

@@ -393,6 +393,21 @@ __global__ void label_spmm_reduce_kernel(int n, int w, int Z, const double* __re
     }
 }
 
+// The reduction of a PAIR launch (launch_label_spmm_pair): block 0 (columns 0..w of the partial sums) goes to Y0,
+// block 1 (columns w..2w) to Y1.  Every output is the same sum over z, in the same order, as in the kernel above.
+__global__ void label_spmm_reduce_pair_kernel(int n, int w, int Z, const double* __restrict__ P, double* __restrict__ Y0,
+                                              int64_t ldy0, double* __restrict__ Y1, int64_t ldy1) {
+    const int64_t total = (int64_t)n * (2 * w);
+    const int64_t step = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += step) {
+        const int64_t j = e / n, r = e - j * n;
+        double acc = 0;
+        for (int z = 0; z < Z; ++z) acc += P[(int64_t)z * total + e];
+        if (j < w) Y0[r + j * ldy0] = acc;
+        else Y1[r + (j - w) * ldy1] = acc;
+    }
+}
+
 // ---------------------------------------------------------------------------
 // The same product on the fp64 matrix cores.  Y = A W is a GEMM whose left operand is formed on the
 // fly: v_mfma_f64_16x16x4_f64 wants A as one double per lane (row m = lane & 15, k = lane >> 4), which
@@ -565,6 +580,11 @@ bool module_set_device_attributes() {
     bool ok = true;
     ok &= hipSuccess == hipFuncSetAttribute(reinterpret_cast<const void*>(&label_spmm_mfma_kernel<4, 1>), hipFuncAttributeMaxDynamicSharedMemorySize,
                         150 * 1024);
+    // the pair launch (launch_label_spmm_pair): two class tables of up to 32 KiB each beside the slabs
+    ok &= hipSuccess == hipFuncSetAttribute(reinterpret_cast<const void*>(&label_spmm_mfma_kernel<3, 2>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                        150 * 1024);
+    ok &= hipSuccess == hipFuncSetAttribute(reinterpret_cast<const void*>(&label_spmm_mfma_kernel<4, 2>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                        150 * 1024);
     return ok;
 }
 
@@ -698,6 +718,54 @@ bool launch_label_spmm(hipStream_t s, int64_t n, const uint32_t* L, uint64_t key
                        int64_t ldw, int w, double* partials, double* Y, int64_t ldy) {
     if (w > 64) return false;
     return launch_label_spmm_multi(s, n, L, &key, 1, d, W, ldw, w, partials, Y, ldy);
+}
+
+// TWO elements applied to the same W (w <= 64 columns) in one pass over the labels, each result to a destination of its own:
+// Y0 = A(keys[0]) W, Y1 = A(keys[1]) W -- the invariance round of the module growth and its rider (compress.cpp).  The form is
+// the one label_spmm_select gives (n, d, w) with ONE element, launched as label_spmm_mfma_kernel<JT, 2> with that column split:
+// every output has the partial sums, in the order, of launch_label_spmm with its key, so both results are bit for bit those of
+// two such launches -- with one pass over the labels, one transposed copy of W and one reduction.  The partial sums take 2 w
+// columns: the buffer is sized by label_spmm_pair_partial_doubles.  false (nothing launched): the one-element form is not the
+// matrix-core one (n < 64, w > 64, d beyond its class table) or two class tables do not fit beside the slabs.
+size_t label_spmm_pair_partial_doubles(int64_t n) {
+    int zg = (int)(2048 / ((n + 63) / 64));
+    if (zg < 1) zg = 1;
+    if (zg > 32) zg = 32;
+    return (size_t)2 * zg * n * 64 + (size_t)(n + 8 + 4 * 128) * 80;
+}
+bool label_spmm_pair_select(int64_t n, int64_t d, int w, LabelSpmmForm* f) {
+    if (w > 64 || !label_spmm_select(n, d, 1, w, f) || !f->mfma) return false;
+    const size_t lds = (size_t)2 * ((d + 2) & ~(int64_t)1) * 8 + (size_t)2 * SPMM_SLAB * spmm_stride(f->tile) * 8;
+    return lds <= (size_t)(f->tile >= 3 ? 150 : 64) * 1024;
+}
+bool launch_label_spmm_pair(hipStream_t s, int64_t n, const uint32_t* L, const uint64_t* keys, int64_t d, const double* W, int64_t ldw,
+                            int w, double* partials, double* Y0, int64_t ldy0, double* Y1, int64_t ldy1) {
+    LabelSpmmForm f;
+    if (!label_spmm_pair_select(n, d, w, &f)) return false;
+    const int rb = (int)((n + 63) / 64);
+    int zg_cap = 2048 / rb;
+    if (zg_cap < 1) zg_cap = 1;
+    if (zg_cap > 32) zg_cap = 32;
+    if ((int64_t)f.z * w > (int64_t)zg_cap * 64) return false;  // (label_spmm_select keeps z w within the one-element buffer; twice that is this one)
+    double* Wt = partials + (size_t)2 * zg_cap * n * 64;
+    SpmmKeys kk;
+    for (int i = 0; i < 4; ++i) kk.k[i] = keys[i & 1];
+    const int JT = f.tile;
+    const int stride = spmm_stride(JT);
+    const size_t lds = (size_t)2 * ((d + 2) & ~(int64_t)1) * 8 + (size_t)2 * SPMM_SLAB * stride * 8;
+    const int64_t rows = (int64_t)f.z * f.cols_per_block + SPMM_SLAB;
+    transpose_w_rowmajor_kernel<<<dim3((unsigned)((rows + 31) / 32), (unsigned)((stride + 31) / 32)), dim3(32, 8), 0, s>>>(
+        (int)n, rows, w, stride, W, ldw, Wt);
+    dim3 g((unsigned)rb, (unsigned)f.z);
+    auto go = [&](auto kern) { kern<<<g, 256, lds, s>>>((int)n, L, kk, (int)d, Wt, w, f.cols_per_block, partials); };
+    if (JT == 1) go(label_spmm_mfma_kernel<1, 2>);
+    else if (JT == 2) go(label_spmm_mfma_kernel<2, 2>);
+    else if (JT == 3) go(label_spmm_mfma_kernel<3, 2>);
+    else go(label_spmm_mfma_kernel<4, 2>);
+    int64_t gr = ((int64_t)n * 2 * w + 255) / 256;
+    if (gr > 2048) gr = 2048;
+    label_spmm_reduce_pair_kernel<<<(unsigned)gr, 256, 0, s>>>((int)n, w, f.z, partials, Y0, ldy0, Y1, ldy1);
+    return true;
 }
 
 }  // namespace sdpsr

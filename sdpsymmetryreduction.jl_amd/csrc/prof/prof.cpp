@@ -361,6 +361,67 @@ extern "C" int sdpsr_profile_label_product(sdpsr_ctx* c, int64_t n, int64_t d, i
     return SDPSR_OK;
 }
 
+extern "C" int sdpsr_profile_label_product_pair(sdpsr_ctx* c, int64_t n, int64_t d, int64_t w, int64_t ldw, int64_t ldy, const uint64_t* keys,
+                                                const uint32_t* L_host, const double* W_host, double* Y0_inout, double* Y1_inout, int64_t guard,
+                                                int32_t* report) {
+    CHECK_CTX(c);
+    if (!keys || !L_host || !W_host || !Y0_inout || !Y1_inout || !report || n < 1 || n > MK_MAX_N || d < 0 || ldw < n || ldy < n || ldw > MK_MAX_LD ||
+        ldy > MK_MAX_LD || w < 1 || w > 64 || guard < 0 || guard > MK_MAX_GUARD)
+        return ctx_fail(c, SDPSR_BAD_ARGUMENT, "label_product_pair: bad arguments");
+    LabelSpmmForm f;
+    if (!label_spmm_pair_select(n, d, (int)w, &f)) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "label_product_pair: shape not supported by the pair launch");
+    if (!mk_labels_ok(L_host, (size_t)n * n, d)) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "label_product_pair: a label exceeds d");
+    hipStream_t s = c->stream;
+    const size_t yn = (size_t)(ldy * w + guard);
+    uint32_t* Lb = (uint32_t*)ctx_buf(c, "prof_l", (size_t)n * n * 4);
+    const size_t wn = (size_t)ldw * 64;  // all 64 columns the launcher could take: those >= w are the caller's poison
+    double* W = (double*)ctx_buf(c, "prof_mk_a", wn * 8);
+    double* Y0 = (double*)ctx_buf(c, "prof_mk_c", yn * 8);
+    double* Y1 = (double*)ctx_buf(c, "prof_mk_b", yn * 8);
+    double* part = (double*)ctx_buf(c, "cm_part", label_spmm_pair_partial_doubles(n) * 8);
+    if (!Lb || !W || !Y0 || !Y1 || !part) return SDPSR_OUT_OF_MEMORY;
+    HIP_TRY(c, hipMemcpyAsync(Lb, L_host, (size_t)n * n * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(W, W_host, wn * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(Y0, Y0_inout, yn * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(Y1, Y1_inout, yn * 8, hipMemcpyHostToDevice, s));
+    const bool ran = launch_label_spmm_pair(s, n, Lb, keys, d, W, ldw, (int)w, part, Y0, ldy, Y1, ldy);
+    HIP_TRY(c, hipMemcpyAsync(Y0_inout, Y0, yn * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(Y1_inout, Y1, yn * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, hipGetLastError());
+    if (!ran) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "label_product_pair: shape not supported by the pair launch");
+    report[0] = f.mfma, report[1] = f.tile, report[2] = f.z, report[3] = f.cols_per_block;
+    return SDPSR_OK;
+}
+
+extern "C" int sdpsr_profile_class_sums2(sdpsr_ctx* c, int64_t n, int64_t d, uint32_t first, int plain, const uint32_t* L_host, const double* X_host,
+                                         double* Y_inout, int64_t guard, int32_t* report) {
+    CHECK_CTX(c);
+    if (!L_host || !X_host || !Y_inout || !report || n < 1 || n > MK_MAX_N || d < 1 || d > 4000 || first < 1 || (plain != 0 && plain != 1) ||
+        (plain && first != 1) || guard < 0 || guard > MK_MAX_GUARD)
+        return ctx_fail(c, SDPSR_BAD_ARGUMENT, "class_sums2: bad arguments");
+    // (the launcher's own rule, asked before anything is uploaded: one wave's tables, 64 lanes x (d + 1, made odd) pairs, within 150 KiB)
+    if ((size_t)64 * ((d + 1) | 1) * 16 > 150 * 1024) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "class_sums2: no instance for this many classes");
+    // plain: the kernel indexes its tables with the labels as they are
+    if (plain && !mk_labels_ok(L_host, (size_t)n * n, d)) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "class_sums2: a label exceeds d");
+    hipStream_t s = c->stream;
+    const size_t yn = (size_t)(2 * n * d + guard);
+    uint32_t* Lb = (uint32_t*)ctx_buf(c, "prof_l", (size_t)n * n * 4);
+    double* X = (double*)ctx_buf(c, "prof_mk_a", (size_t)2 * n * 8);
+    double* Y = (double*)ctx_buf(c, "prof_mk_c", yn * 8);
+    if (!Lb || !X || !Y) return SDPSR_OUT_OF_MEMORY;
+    HIP_TRY(c, hipMemcpyAsync(Lb, L_host, (size_t)n * n * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(X, X_host, (size_t)2 * n * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(Y, Y_inout, yn * 8, hipMemcpyHostToDevice, s));
+    const int W = launch_class_sums_pair(s, n, d, first, plain != 0, Lb, X, Y);
+    HIP_TRY(c, hipMemcpyAsync(Y_inout, Y, yn * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, hipGetLastError());
+    if (!W) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "class_sums2: no instance for this many classes");
+    report[0] = W;
+    return SDPSR_OK;
+}
+
 extern "C" int sdpsr_profile_class_sums(sdpsr_ctx* c, int64_t n, int64_t d, int64_t ldo, const uint32_t* L_host, const double* x_host,
                                         double* out_inout, int64_t guard, int32_t* report) {
     CHECK_CTX(c);

@@ -373,6 +373,14 @@ struct LabelSpmmForm {
     int mfma, tile, z, cols_per_block;
 };
 bool label_spmm_select(int64_t n, int64_t d, int G, int w, LabelSpmmForm* f);
+// Two elements on one W in one pass over the labels, each result to its own destination: Y0 = A(keys[0]) W, Y1 = A(keys[1]) W
+// (w <= 64).  The form is label_spmm_select(n, d, 1, w)'s matrix-core form, run as label_spmm_mfma_kernel<tile, 2>: both results
+// are bit for bit those of two one-element launches.  label_spmm_pair_select says whether the pair can run (false: n < 64,
+// w > 64, or the class tables do not fit) and with which form; partials: label_spmm_pair_partial_doubles(n) doubles.
+bool label_spmm_pair_select(int64_t n, int64_t d, int w, LabelSpmmForm* f);
+size_t label_spmm_pair_partial_doubles(int64_t n);
+bool launch_label_spmm_pair(hipStream_t s, int64_t n, const uint32_t* L, const uint64_t* keys, int64_t d, const double* W, int64_t ldw,
+                            int w, double* partials, double* Y0, int64_t ldy0, double* Y1, int64_t ldy1);
 
 // Kernels with more than 64 KiB of dynamic LDS carry a per-DEVICE attribute: sdpsr_create() sets
 // them all with the ctx's device current (no process-global "already set" flags) and fails when one
@@ -532,6 +540,9 @@ void launch_basis_image_outer(hipStream_t s, int64_t n, int64_t d, int64_t S1, i
 // out[r + i*n] = sum over c with L[c + r*n] == first+i of x[c]   (class sums of a vector, i < d)
 bool class_sums_supports(int64_t n, int64_t d, int64_t ldo);
 void launch_class_sums(hipStream_t s, int64_t n, int64_t d, const uint32_t* L, const double* x, double* out, int64_t ldo, uint32_t first = 1);
+// the pair class-sum pass of the basis_image shortcuts alone (tests): X n pairs, Y d * n pairs (interleaved); returns the waves
+// per workgroup it ran with, 0 (nothing launched) when d is beyond its tables
+int launch_class_sums_pair(hipStream_t s, int64_t n, int64_t d, uint32_t first, bool plain, const uint32_t* L, const double* X, double* Y);
 void launch_basis_image_two_stage(hipStream_t s, int64_t n, int64_t d, uint32_t first, int64_t S1, int64_t S,
                                   const uint32_t* L, const double* Qrm, double* T, const int32_t* colA,
                                   const int32_t* colB, double atol, double* out);
