@@ -128,6 +128,40 @@ int sdpsr_profile_normalize_columns(sdpsr_ctx* ctx, int64_t n, int64_t ldx, int6
                                     double* H_inout, double* norm_inout, int64_t guard);
 int sdpsr_profile_random_vector(sdpsr_ctx* ctx, int64_t n, uint64_t key, double* x_inout, int64_t guard);
 
+/* ---- The steps of blockDiagonalize(P; complex = true) on caller-made inputs (tests/test_gpu_complex_steps.py). ----
+   Conventions of the module-kernel entries above.  A complex matrix is two column-major planes of doubles (real, imaginary) with leading
+   dimension n.  `route` 0 = the one-workgroup kernels the driver takes for n <= 64 (refused above 64), 1 = the route through the real symmetric
+   embedding that it takes for n > 64 (here for any n >= 1: cx_embed, the real eigensolver, cx_zero_pad, cx_rot, cx_stack, cx_combine and the
+   host's pivoted Cholesky all run inside a route-1 call).  SDPSR_BAD_ARGUMENT, before anything is uploaded, for: a null pointer, n < 1 or
+   n > 4096, guard outside [0, 2^20], a route other than 0 / 1, a space_of or a descriptor that points outside its arrays. */
+
+/* H = A + A^H, A[r, c] = the complex class value of L[r + c n] under `key` (real part from sdpsr_class_uniform(key, l), imaginary part from
+   sdpsr_class_uniform(key ^ 0xA5A5A5A55A5A5A5A, l), label 0 -> 0), through launch_cx_gather_herm.  L_host: n * n labels, any values;
+   Hr_inout, Hi_inout: n * n + guard. */
+int sdpsr_profile_cx_gather_herm(sdpsr_ctx* ctx, int64_t n, const uint32_t* L_host, uint64_t key, double* Hr_inout, double* Hi_inout, int64_t guard);
+/* Eigenpairs of the Hermitian H: w ascending (w_inout: n + guard), orthonormal eigenvectors in the columns of V (Vr_inout, Vi_inout:
+   n * n + guard).  Route 0: launch_cx_heev; info_out[0] = 1 when the Jacobi iteration did not converge, info_out[1] = sweeps; `atol` unused.
+   Route 1: cx_heev_general with the cluster tolerance `atol` (eigenvalues of the embedding within atol of their neighbour share one
+   eigenspace, and the eigenvectors of one cluster span it without being matched to its single eigenvalues); the eigenvalues come back
+   through the host, so the guard of w_inout is left as the caller filled it; info_out = {0, 0}; the route's own status (e.g.
+   SDPSR_NUMERICAL_INCONSISTENCY for a cluster of odd size) is returned as it is. */
+int sdpsr_profile_cx_heev(sdpsr_ctx* ctx, int route, int64_t n, const double* Hr_host, const double* Hi_host, double atol, double* w_inout,
+                          double* Vr_inout, double* Vi_inout, int64_t guard, int32_t* info_out);
+/* norms[sa * neig + sb] = max |(V^H H V)[a, b]| over space_of[a] == sa, space_of[b] == sb, as doubles, from a zero fill of the neig * neig
+   results as in the driver (a pair with an empty space stays 0).  V: n x n, any columns; space_of: n entries in [0, neig), 1 <= neig <= n;
+   norms_inout: neig * neig + guard.  Route 0: launch_cx_block_norms; route 1: cx_block_norms_general. */
+int sdpsr_profile_cx_block_norms(sdpsr_ctx* ctx, int route, int64_t n, const double* Hr_host, const double* Hi_host, const double* Vr_host,
+                                 const double* Vi_host, const int32_t* space_of, int32_t neig, double* norms_inout, int64_t guard);
+/* The columns of Q-hat (irreducible_decomposition).  V: n x vcols (vcols <= 4096, leading dimension n); desc: ncols x {kind, i0, mi, j0, mj,
+   col}.  kind 0: column col = V[:, i0], entries of magnitude < atol set to +0; kind 1: column col = Q_j (Q_j^H H q_i1) / |Q_i^H H q_j1|
+   with Q_i = V[:, i0 .. i0 + mi), Q_j = V[:, j0 .. j0 + mj), q_x1 their first columns, then the same clamp; i0 + mi, j0 + mj <= vcols,
+   1 <= mi, mj <= n, 0 <= col < ncols.  Only the columns of V that desc names are read.  Qhat_inout: 2 n ncols + guard, column col at
+   2 n col, (re, im) interleaved.  Route 0: launch_cx_irreducible; route 1: launch_cx_irreducible_general, which takes every n <= 4096
+   (4 n doubles of dynamic LDS). */
+int sdpsr_profile_cx_irreducible(sdpsr_ctx* ctx, int route, int64_t n, int64_t vcols, const double* Hr_host, const double* Hi_host,
+                                 const double* Vr_host, const double* Vi_host, const int32_t* desc, int32_t ncols, double atol,
+                                 double* Qhat_inout, int64_t guard);
+
 #ifdef __cplusplus
 }
 #endif

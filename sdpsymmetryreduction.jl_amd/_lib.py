@@ -255,5 +255,14 @@ def load_prof_library():
     lib.sdpsr_profile_normalize_columns.argtypes = [vp, i64, i64, i64, i64, vp, vp, vp, i64]
     lib.sdpsr_profile_random_vector.restype = C.c_int
     lib.sdpsr_profile_random_vector.argtypes = [vp, i64, C.c_uint64, vp, i64]
+    # the steps of the complex path on caller-made inputs (tests)
+    lib.sdpsr_profile_cx_gather_herm.restype = C.c_int
+    lib.sdpsr_profile_cx_gather_herm.argtypes = [vp, i64, vp, C.c_uint64, vp, vp, i64]
+    lib.sdpsr_profile_cx_heev.restype = C.c_int
+    lib.sdpsr_profile_cx_heev.argtypes = [vp, C.c_int, i64, vp, vp, f64, vp, vp, vp, i64, rep]
+    lib.sdpsr_profile_cx_block_norms.restype = C.c_int
+    lib.sdpsr_profile_cx_block_norms.argtypes = [vp, C.c_int, i64, vp, vp, vp, vp, vp, C.c_int32, vp, i64]
+    lib.sdpsr_profile_cx_irreducible.restype = C.c_int
+    lib.sdpsr_profile_cx_irreducible.argtypes = [vp, C.c_int, i64, i64, vp, vp, vp, vp, vp, C.c_int32, f64, vp, i64]
     _prof = lib
     return lib

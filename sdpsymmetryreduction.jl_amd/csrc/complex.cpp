@@ -14,13 +14,15 @@
 
 using namespace sdpsr;
 
+namespace sdpsr {
+
 // ---- complex path, orders n > 64: Hermitian eigendecomposition through the real embedding ----------
 // M(H) (2n x 2n, symmetric) goes through the real dense eigensolver; every eigenvalue of H shows
 // up twice and a cluster of 2m real eigenvectors (x; y) spans, read as z = x + iy, the m-dimensional
 // complex eigenspace.  The m orthonormal complex vectors are picked by a pivoted Cholesky
 // factorisation of the cluster's Gram matrix  G = Z^H Z = I + i (X'Y - Y'X)  (eigenvalues 0 and 2:
 // rank m, perfectly conditioned) on the host; the combinations run on the device.
-static int cx_heev_general(sdpsr_ctx* c, int64_t n, const double* Hr, const double* Hi, double atol, double* Vr, double* Vi,
+int cx_heev_general(sdpsr_ctx* c, int64_t n, const double* Hr, const double* Hi, double atol, double* Vr, double* Vi,
                            std::vector<double>& vals) {
     hipStream_t s = c->stream;
     const int64_t n2 = 2 * n, ld2 = round_up(n2, 128);
@@ -59,8 +61,10 @@ static int cx_heev_general(sdpsr_ctx* c, int64_t n, const double* Hr, const doub
             for (int a = 0; a < sz; ++a) G[(size_t)a + (size_t)b * sz] = cd(a == b ? 1.0 : 0.0, hK[(size_t)(o + a) + (size_t)(o + b) * ld2]);
         std::vector<int> perm(sz);
         for (int i = 0; i < sz; ++i) perm[i] = i;
+        // the cluster's 2m real eigenvectors span, as complex vectors, m dimensions: m pivots.  What is left of G after them is the
+        // square of how far the computed vectors are from a J-invariant subspace (rounding error over the gap to the next cluster).
         int r = 0;
-        for (int k = 0; k < sz; ++k) {
+        for (int k = 0; k < m; ++k) {
             int p = k;
             double best = G[(size_t)k + (size_t)k * sz].real();
             for (int j = k + 1; j < sz; ++j)
@@ -80,9 +84,11 @@ static int cx_heev_general(sdpsr_ctx* c, int64_t n, const double* Hr, const doub
                     G[(size_t)i + (size_t)j * sz] -= std::conj(Rf[(size_t)k + (size_t)i * sz]) * Rf[(size_t)k + (size_t)j * sz];
             ++r;
         }
-        if (r != m)
+        double left = 0;
+        for (int j = m; j < sz && r == m; ++j) left = std::max(left, G[(size_t)j + (size_t)j * sz].real());
+        if (r != m || left > 1e-4)
             return ctx_fail(c, SDPSR_NUMERICAL_INCONSISTENCY,
-                            "complex path: eigenspace extraction found rank " + std::to_string(r) + " in a cluster of " +
+                            "complex path: eigenspace extraction found rank " + std::to_string(r != m ? r : m + 1) + " in a cluster of " +
                                 std::to_string(sz) + " embedded eigenvectors (decrease `atol`, or try again)");
         // X = R11^{-1} (upper triangular m x m); column a of the coefficients = P[:, :m] X[:, a]
         std::vector<cd> X((size_t)m * m, cd(0, 0));
@@ -114,12 +120,25 @@ static int cx_heev_general(sdpsr_ctx* c, int64_t n, const double* Hr, const doub
     if (!st) st = h2d_sync(c, dcoef, coef.data(), coef.size() * 8);
     if (st) return st;
     launch_cx_combine(s, n, ld2, M, ddesc, dcoef, Vr, Vi);
+    // The vectors of one cluster are orthonormal by construction; between clusters they are orthogonal only as far as the real
+    // solver's subspaces are J-invariant, i.e. to rounding error / gap (1e-5 and more for eigenvalues 1e-11 |H| apart).  Three
+    // Newton-Schulz steps  V <- V (3 I - V^H V) / 2  on the embedding bring V^H V to I (the error is squared by each); a
+    // correction that couples two vectors is inversely proportional to their eigenvalue gap, so the residual H V - V diag(w) keeps
+    // its size.  M(V)' M(V) = M(V^H V), and M(V) M(F) = M(V^H)' M(F) in terms of the TN product.
+    for (int it = 0; it < 3; ++it) {
+        launch_cx_embed(s, n, Vr, Vi, ld2, M);
+        launch_gemm_tn_f64(s, ld2, ld2, ld2, M, ld2, M, ld2, K, ld2, 1, 0, 0, 0);  // K = M(V^H V)
+        launch_cx_newton_schulz_factor(s, n2, ld2, K);                             // K = (3 I - K) / 2 on the leading 2n x 2n
+        launch_cx_embed_adjoint(s, n, Vr, Vi, ld2, M);                             // M = M(V^H) = M(V)'
+        launch_gemm_tn_f64(s, ld2, ld2, ld2, M, ld2, K, ld2, R, ld2, 1, 0, 0, 0);  // R = M(V) K = M(V F)
+        launch_cx_unstack(s, n, n, R, ld2, Vr, Vi, n);
+    }
     HIP_TRY(c, hipGetLastError());
     return SDPSR_OK;
 }
 
 // max |(V^H H V)[a, b]| over the pairs of eigenspaces, n > 64: three real MFMA GEMMs on the embedding
-static int cx_block_norms_general(sdpsr_ctx* c, int64_t n, const double* Hr, const double* Hi, const double* Vr, const double* Vi,
+int cx_block_norms_general(sdpsr_ctx* c, int64_t n, const double* Hr, const double* Hi, const double* Vr, const double* Vi,
                                   const int32_t* dspace, int neig, unsigned long long* dnorms) {
     hipStream_t s = c->stream;
     const int64_t ld2 = round_up(2 * n, 128), ldn = round_up(n, 128);
@@ -143,6 +162,8 @@ static int cx_block_norms_general(sdpsr_ctx* c, int64_t n, const double* Hr, con
     return SDPSR_OK;
 }
 
+}  // namespace sdpsr
+
 // ---- blockDiagonalize over C (src/compat.jl:26-32,46-68 with T = ComplexF64) ----------------
 extern "C" {
 
@@ -151,7 +172,7 @@ int sdpsr_block_diagonalize_complex(sdpsr_ctx* c, int64_t n, const uint32_t* P, 
                                     int64_t* sum_s, int mem) {
     CHECK_CTX(c);
     if (!P || n < 1 || d < 0 || !(epsilon > 0)) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "bad arguments");
-    if (n > 4096) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "complex path: this version covers n <= 4096 (see sdpsr.h)");
+    if (n > SDPSR_CX_MAX_N) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "complex path: this version covers n <= 4096 (see sdpsr.h)");
     const bool small = n <= 64;  // one-workgroup kernels; larger orders go through the real embedding
     const int64_t len = n * n;
     hipStream_t s = c->stream;
@@ -238,7 +259,9 @@ int sdpsr_block_diagonalize_complex(sdpsr_ctx* c, int64_t n, const uint32_t* P, 
     if (st) return st;
     launch_cx_gather_herm(s, n, L, next_key(c), Hr, Hi);  // generic element #3 (:306)
     if (small) launch_cx_irreducible(s, n, Hr, Hi, Vr, Vi, ddesc, (int)S1, atol, Qhat);
-    else launch_cx_irreducible_general(s, n, Hr, Hi, Vr, Vi, ddesc, (int)S1, atol, Qhat);
+    else if (!launch_cx_irreducible_general(s, n, Hr, Hi, Vr, Vi, ddesc, (int)S1, atol, Qhat))
+        return ctx_fail(c, SDPSR_BAD_ARGUMENT, "complex path: the irreducible decomposition's vectors of order " + std::to_string(n) +
+                                                   " do not fit a workgroup's LDS");
     HIP_TRY(c, hipGetLastError());
     if (P_desym && (st = labels_deliver(c, P_desym, L, (size_t)len, mem)) != SDPSR_OK) return st;
     HIP_TRY(c, ctx_sync_stream(c, s));

@@ -424,6 +424,14 @@ void launch_csr_entry_labels(hipStream_t s, int64_t nnz, const uint32_t* col, co
 size_t csr_class_sums_carry_bytes(int64_t nnz);
 void launch_csr_class_sums(hipStream_t s, int64_t nnz, int64_t m, const int64_t* rowptr, const uint32_t* key_sorted,
                            const uint32_t* idx_sorted, const double* val, void* carry, double* out);
+// complex.cpp, the complex path through the real embedding (the driver takes it for n > 64; any n >= 1 works).  cx_heev_general:
+// eigenpairs of the Hermitian H (device planes, ld = n) into Vr, Vi (device) and vals (ascending, host); eigenvalues of the
+// embedding within atol of each other are one cluster.  cx_block_norms_general: dnorms[sa * neig + sb] (device, zeroed by the
+// caller) = max |(V^H H V)[a, b]| over space_of[a] == sa, space_of[b] == sb, as the bits of a double.
+int cx_heev_general(sdpsr_ctx* c, int64_t n, const double* Hr, const double* Hi, double atol, double* Vr, double* Vi,
+                    std::vector<double>& vals);
+int cx_block_norms_general(sdpsr_ctx* c, int64_t n, const double* Hr, const double* Hi, const double* Vr, const double* Vi,
+                           const int32_t* dspace, int neig, unsigned long long* dnorms);
 
 }  // namespace sdpsr
 

@@ -127,10 +127,18 @@ cx_heev_jacobi64_kernel(int n, const double* __restrict__ Hr, const double* __re
                     const double app = sAr[p + p * ldl], aqq = sAr[q + q * ldl];
                     const double pr = sAr[p + q * ldl], pi = sAi[p + q * ldl];
                     const double b2 = fma(pr, pr, pi * pi);
-                    if (b2 > 0.0) {
+                    if (b2 > 1e-280 && b2 < 1e280) {
                         const double b = sqrt(b2);
                         e = {pr / b, pi / b};
                         jacobi_angle(app, aqq, b, c, s);
+                    } else if (pr != 0.0 || pi != 0.0) {
+                        // the squares leave the normal range (|a_pq| below ~1e-140 or above ~1e140): a subnormal b2 has a few
+                        // bits left, and a phase pr / b, pi / b from it is not of modulus 1 -- U would not be unitary.  Scale first.
+                        const double big = fmax(fabs(pr), fabs(pi));
+                        const double xr = pr / big, xi = pi / big;
+                        const double r = sqrt(fma(xr, xr, xi * xi));  // in [1, sqrt 2]
+                        e = {xr / r, xi / r};
+                        jacobi_angle(app, aqq, big * r, c, s);
                     } else {
                         e = {1.0, 0.0};
                         c = 1.0;
@@ -417,6 +425,37 @@ __global__ void cx_stack_kernel(int n, int64_t cols, const double* __restrict__ 
         E[(r + n) + j * ld2] = Vi[r + j * ldv];
     }
 }
+// M (ld2 x ld2, zeroed by the caller beyond 2n) = M(Z^H) = M(Z)' for any complex n x n Z
+__global__ void cx_embed_adjoint_kernel(int n, const double* __restrict__ Zr, const double* __restrict__ Zi, int64_t ld2,
+                                        double* __restrict__ M) {
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < (int64_t)n * n; e += (int64_t)gridDim.x * blockDim.x) {
+        const int c = (int)(e / n), r = (int)(e - (int64_t)c * n);  // Z^H[c, r] = conj(Z[r, c])
+        const double re = Zr[e], im = Zi[e];
+        M[c + (int64_t)r * ld2] = re;
+        M[(c + n) + (int64_t)(r + n) * ld2] = re;
+        M[(c + n) + (int64_t)r * ld2] = -im;
+        M[c + (int64_t)(r + n) * ld2] = im;
+    }
+}
+// K <- (3 I - K) / 2 on the leading m x m of an ld-strided buffer (the factor of a Newton-Schulz orthonormalisation step)
+__global__ void cx_newton_schulz_factor_kernel(int64_t m, int64_t ld, double* __restrict__ K) {
+    const int64_t total = m * m;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t j = e / m, i = e - j * m;
+        K[i + j * ld] = ((i == j ? 3.0 : 0.0) - K[i + j * ld]) * 0.5;
+    }
+}
+// [Vr; Vi] (planes, leading dimension ldv) = the first `cols` columns of E (ld2 x ., a complex n x cols matrix stacked): cx_stack undone
+__global__ void cx_unstack_kernel(int n, int64_t cols, const double* __restrict__ E, int64_t ld2, double* __restrict__ Vr,
+                                  double* __restrict__ Vi, int64_t ldv) {
+    const int64_t total = (int64_t)n * cols;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t j = e / n;
+        const int r = (int)(e - j * n);
+        Vr[r + j * ldv] = E[r + j * ld2];
+        Vi[r + j * ldv] = E[(r + n) + j * ld2];
+    }
+}
 // norms[sa * neig + sb] = max |Gr + i Gi| over the block (Gr, Gi: n x n in ldn x ldn buffers)
 __global__ void cx_block_norms_general_kernel(int n, int64_t ldn, const double* __restrict__ Gr, const double* __restrict__ Gi,
                                               const int32_t* __restrict__ space_of, int neig, unsigned long long* __restrict__ norms) {
@@ -429,15 +468,23 @@ __global__ void cx_block_norms_general_kernel(int n, int64_t ldn, const double* 
     }
 }
 
-// cx_irreducible_kernel for any n: the vectors t = H3 q_i1, u = H3 q_j1 and the coefficients live
-// in dynamic LDS (6 n doubles), every loop strides over the workgroup.
+// cx_irreducible_kernel for any n, every loop strided over the workgroup.  Dynamic LDS: 4 n doubles, one complex n-vector
+// (t = H3 q_i1 first, u = H3 q_j1 once the coefficients c = Q_j^H t are taken from t) and the coefficients (mj <= n).  With the
+// static 2 KB of the norm's partial sums that is 32 n + 2048 bytes of the 160 KB a workgroup has: every n <= 4096 the complex
+// path documents fits (the arithmetic limit is n = 5056); cx_irreducible_general_lds_bytes is the one place that says so.
+constexpr size_t CX_IRR_STATIC_LDS = 256 * sizeof(double), CX_LDS_PER_WORKGROUP = 160 * 1024;
+size_t cx_irreducible_general_lds_bytes(int64_t n) {
+    if (n < 1) return 0;
+    const size_t dyn = (size_t)4 * (size_t)n * sizeof(double);
+    return dyn + CX_IRR_STATIC_LDS <= CX_LDS_PER_WORKGROUP ? dyn : 0;
+}
 __global__ void __launch_bounds__(256)
 cx_irreducible_general_kernel(int n, const double* __restrict__ Hr, const double* __restrict__ Hi, const double* __restrict__ Vr,
                               const double* __restrict__ Vi, const int32_t* __restrict__ desc, double atol,
                               double* __restrict__ Qhat) {
     extern __shared__ __attribute__((aligned(16))) double sg[];
     __shared__ double s_part[256];
-    double *tr = sg, *ti = tr + n, *ur = ti + n, *ui = ur + n, *cr = ui + n, *ci = cr + n;
+    double *xr = sg, *xi = xr + n, *cr = xi + n, *ci = cr + n;  // x: t, then u
     const int32_t* dsc = desc + 6 * blockIdx.x;
     const int kind = dsc[0], i0 = dsc[1], mi = dsc[2], j0 = dsc[3], mj = dsc[4], col = dsc[5];
     const int tid = threadIdx.x, nthr = blockDim.x;
@@ -451,38 +498,39 @@ cx_irreducible_general_kernel(int n, const double* __restrict__ Hr, const double
         }
         return;
     }
-    for (int r = tid; r < n; r += nthr) {  // t = H3 q_i1, u = H3 q_j1
-        cxd t = {0, 0}, u = {0, 0};
-        for (int k = 0; k < n; ++k) {
-            const cxd h = {Hr[r + (int64_t)k * n], Hi[r + (int64_t)k * n]};
-            const cxd p = cx_mul(h, {Vr[k + (int64_t)i0 * n], Vi[k + (int64_t)i0 * n]});
-            const cxd q = cx_mul(h, {Vr[k + (int64_t)j0 * n], Vi[k + (int64_t)j0 * n]});
-            t.re += p.re;
-            t.im += p.im;
-            u.re += q.re;
-            u.im += q.im;
+    auto h3_times = [&](int c0) {  // x = H3 V[:, c0]
+        for (int r = tid; r < n; r += nthr) {
+            cxd x = {0, 0};
+            for (int k = 0; k < n; ++k) {
+                const cxd h = {Hr[r + (int64_t)k * n], Hi[r + (int64_t)k * n]};
+                const cxd p = cx_mul(h, {Vr[k + (int64_t)c0 * n], Vi[k + (int64_t)c0 * n]});
+                x.re += p.re;
+                x.im += p.im;
+            }
+            xr[r] = x.re;
+            xi[r] = x.im;
         }
-        tr[r] = t.re;
-        ti[r] = t.im;
-        ur[r] = u.re;
-        ui[r] = u.im;
-    }
+    };
+    h3_times(i0);  // t = H3 q_i1
     __syncthreads();
     for (int a = tid; a < mj; a += nthr) {  // c = Q_j^H t
         cxd acc = {0, 0};
         for (int k = 0; k < n; ++k) {
-            const cxd p = cx_cmul({Vr[k + (int64_t)(j0 + a) * n], Vi[k + (int64_t)(j0 + a) * n]}, {tr[k], ti[k]});
+            const cxd p = cx_cmul({Vr[k + (int64_t)(j0 + a) * n], Vi[k + (int64_t)(j0 + a) * n]}, {xr[k], xi[k]});
             acc.re += p.re;
             acc.im += p.im;
         }
         cr[a] = acc.re;
         ci[a] = acc.im;
     }
+    __syncthreads();  // t is read out: its storage takes u
+    h3_times(j0);     // u = H3 q_j1
+    __syncthreads();
     double s2 = 0;  // || Q_i^H u ||^2, members of the root eigenspace strided over the threads
     for (int a = tid; a < mi; a += nthr) {
         cxd acc = {0, 0};
         for (int k = 0; k < n; ++k) {
-            const cxd p = cx_cmul({Vr[k + (int64_t)(i0 + a) * n], Vi[k + (int64_t)(i0 + a) * n]}, {ur[k], ui[k]});
+            const cxd p = cx_cmul({Vr[k + (int64_t)(i0 + a) * n], Vi[k + (int64_t)(i0 + a) * n]}, {xr[k], xi[k]});
             acc.re += p.re;
             acc.im += p.im;
         }
@@ -519,6 +567,16 @@ void launch_cx_embed(hipStream_t s, int64_t n, const double* Hr, const double* H
     hipMemsetAsync(M, 0, (size_t)ld2 * ld2 * 8, s);
     cx_embed_kernel<<<cx_grid(n * n), 256, 0, s>>>((int)n, Hr, Hi, ld2, M);
 }
+void launch_cx_embed_adjoint(hipStream_t s, int64_t n, const double* Zr, const double* Zi, int64_t ld2, double* M) {
+    hipMemsetAsync(M, 0, (size_t)ld2 * ld2 * 8, s);
+    cx_embed_adjoint_kernel<<<cx_grid(n * n), 256, 0, s>>>((int)n, Zr, Zi, ld2, M);
+}
+void launch_cx_newton_schulz_factor(hipStream_t s, int64_t m, int64_t ld, double* K) {
+    cx_newton_schulz_factor_kernel<<<cx_grid(m * m), 256, 0, s>>>(m, ld, K);
+}
+void launch_cx_unstack(hipStream_t s, int64_t n, int64_t cols, const double* E, int64_t ld2, double* Vr, double* Vi, int64_t ldv) {
+    cx_unstack_kernel<<<cx_grid(n * cols), 256, 0, s>>>((int)n, cols, E, ld2, Vr, Vi, ldv);
+}
 void launch_cx_rot(hipStream_t s, int64_t n, int64_t cols, int64_t ld2, const double* E, double* R) {
     cx_rot_kernel<<<cx_grid(n * cols), 256, 0, s>>>((int)n, cols, ld2, E, R);
 }
@@ -537,9 +595,12 @@ void launch_cx_block_norms_general(hipStream_t s, int64_t n, int64_t ldn, const 
                                    int neig, unsigned long long* norms) {
     cx_block_norms_general_kernel<<<cx_grid(n * n), 256, 0, s>>>((int)n, ldn, Gr, Gi, space_of, neig, norms);
 }
-void launch_cx_irreducible_general(hipStream_t s, int64_t n, const double* Hr, const double* Hi, const double* Vr, const double* Vi,
+bool launch_cx_irreducible_general(hipStream_t s, int64_t n, const double* Hr, const double* Hi, const double* Vr, const double* Vi,
                                    const int32_t* desc, int ncols, double atol, double* Qhat) {
-    cx_irreducible_general_kernel<<<ncols, 256, (size_t)6 * n * sizeof(double), s>>>((int)n, Hr, Hi, Vr, Vi, desc, atol, Qhat);
+    const size_t lds = cx_irreducible_general_lds_bytes(n);
+    if (!lds) return false;  // the order does not fit a workgroup's LDS: nothing is launched
+    cx_irreducible_general_kernel<<<ncols, 256, lds, s>>>((int)n, Hr, Hi, Vr, Vi, desc, atol, Qhat);
+    return true;
 }
 
 // cx_basis_image_kernel over the entries of the class only (ent: linear indices grouped by label,
@@ -583,7 +644,7 @@ bool complex_set_device_attributes() {
     ok &= hipSuccess == hipFuncSetAttribute(reinterpret_cast<const void*>(&cx_block_norms_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                         64 * 1024);
     ok &= hipSuccess == hipFuncSetAttribute(reinterpret_cast<const void*>(&cx_irreducible_general_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                        144 * 1024);
+                        (int)cx_irreducible_general_lds_bytes(SDPSR_CX_MAX_N));
     return ok;
 }
 

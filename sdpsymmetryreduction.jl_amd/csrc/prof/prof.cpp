@@ -522,6 +522,154 @@ extern "C" int sdpsr_profile_random_vector(sdpsr_ctx* c, int64_t n, uint64_t key
     return SDPSR_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// The steps of blockDiagonalize(P; complex = true) on caller-made inputs (tests/test_gpu_complex_steps.py), by the conventions
+// of the module-kernel entries above: host arrays in (column-major, real / imaginary planes with ld = n), every *_inout array
+// uploaded as the caller filled it and downloaded whole, the product's own launcher or host function called the way
+// complex.cpp calls it, nothing measured, every argument that could index outside a buffer refused before any upload.
+// route 0: the one-workgroup kernels of n <= 64; route 1: the route through the real embedding (the driver's for n > 64).
+// ---------------------------------------------------------------------------------------------------------------------------
+namespace {
+bool cx_common_ok(int route, int64_t n, int64_t guard) {
+    return (route == 0 || route == 1) && n >= 1 && n <= SDPSR_CX_MAX_N && (route == 1 || n <= 64) && guard >= 0 && guard <= MK_MAX_GUARD;
+}
+// the planes of H (n x n) and of V (n x vcols) on the device
+int cx_upload_planes(sdpsr_ctx* c, int64_t n, int64_t vcols, const double* Hr_host, const double* Hi_host, const double* Vr_host,
+                     const double* Vi_host, double** Hr, double** Hi, double** Vr, double** Vi) {
+    hipStream_t s = c->stream;
+    const size_t hb = (size_t)n * n * 8, vb = (size_t)n * vcols * 8;
+    *Hr = (double*)ctx_buf(c, "prof_cx_hr", hb);
+    *Hi = (double*)ctx_buf(c, "prof_cx_hi", hb);
+    *Vr = (double*)ctx_buf(c, "prof_cx_vr", vb);
+    *Vi = (double*)ctx_buf(c, "prof_cx_vi", vb);
+    if (!*Hr || !*Hi || !*Vr || !*Vi) return SDPSR_OUT_OF_MEMORY;
+    HIP_TRY(c, hipMemcpyAsync(*Hr, Hr_host, hb, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(*Hi, Hi_host, hb, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(*Vr, Vr_host, vb, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(*Vi, Vi_host, vb, hipMemcpyHostToDevice, s));
+    return SDPSR_OK;
+}
+}  // namespace
+
+extern "C" int sdpsr_profile_cx_gather_herm(sdpsr_ctx* c, int64_t n, const uint32_t* L_host, uint64_t key, double* Hr_inout, double* Hi_inout,
+                                            int64_t guard) {
+    CHECK_CTX(c);
+    if (!L_host || !Hr_inout || !Hi_inout || !cx_common_ok(1, n, guard)) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "cx_gather_herm: bad arguments");
+    hipStream_t s = c->stream;
+    const size_t hn = (size_t)(n * n + guard);
+    uint32_t* L = (uint32_t*)ctx_buf(c, "prof_l", (size_t)n * n * 4);
+    double* Hr = (double*)ctx_buf(c, "prof_cx_hr", hn * 8);
+    double* Hi = (double*)ctx_buf(c, "prof_cx_hi", hn * 8);
+    if (!L || !Hr || !Hi) return SDPSR_OUT_OF_MEMORY;
+    HIP_TRY(c, hipMemcpyAsync(L, L_host, (size_t)n * n * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(Hr, Hr_inout, hn * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(Hi, Hi_inout, hn * 8, hipMemcpyHostToDevice, s));
+    launch_cx_gather_herm(s, n, L, key, Hr, Hi);
+    HIP_TRY(c, hipMemcpyAsync(Hr_inout, Hr, hn * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(Hi_inout, Hi, hn * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, hipGetLastError());
+    return SDPSR_OK;
+}
+
+extern "C" int sdpsr_profile_cx_heev(sdpsr_ctx* c, int route, int64_t n, const double* Hr_host, const double* Hi_host, double atol, double* w_inout,
+                                     double* Vr_inout, double* Vi_inout, int64_t guard, int32_t* info_out) {
+    CHECK_CTX(c);
+    if (!Hr_host || !Hi_host || !w_inout || !Vr_inout || !Vi_inout || !info_out || !cx_common_ok(route, n, guard) || !(atol >= 0))
+        return ctx_fail(c, SDPSR_BAD_ARGUMENT, route == 0 && n > 64 ? "cx_heev: route 0 takes n <= 64" : "cx_heev: bad arguments");
+    hipStream_t s = c->stream;
+    const size_t hb = (size_t)n * n * 8, wn = (size_t)(n + guard), vn = (size_t)(n * n + guard);
+    double* Hr = (double*)ctx_buf(c, "prof_cx_hr", hb);
+    double* Hi = (double*)ctx_buf(c, "prof_cx_hi", hb);
+    double* Vr = (double*)ctx_buf(c, "prof_cx_vr", vn * 8);
+    double* Vi = (double*)ctx_buf(c, "prof_cx_vi", vn * 8);
+    double* w = (double*)ctx_buf(c, "prof_cx_w", wn * 8);
+    int* info = (int*)ctx_buf(c, "prof_cx_info", 64);
+    if (!Hr || !Hi || !Vr || !Vi || !w || !info) return SDPSR_OUT_OF_MEMORY;
+    HIP_TRY(c, hipMemcpyAsync(Hr, Hr_host, hb, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(Hi, Hi_host, hb, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(Vr, Vr_inout, vn * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(Vi, Vi_inout, vn * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(w, w_inout, wn * 8, hipMemcpyHostToDevice, s));
+    info_out[0] = info_out[1] = 0;
+    if (route == 0) {
+        launch_cx_heev(s, n, Hr, Hi, w, Vr, Vi, info);
+        HIP_TRY(c, hipMemcpyAsync(w_inout, w, wn * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(info_out, info, 8, hipMemcpyDeviceToHost, s));
+    } else {
+        std::vector<double> vals;  // the general route hands its eigenvalues back on the host: the guard of w stays the caller's
+        const int st = cx_heev_general(c, n, Hr, Hi, atol, Vr, Vi, vals);
+        if (st) return st;
+        memcpy(w_inout, vals.data(), (size_t)n * 8);
+    }
+    HIP_TRY(c, hipMemcpyAsync(Vr_inout, Vr, vn * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(Vi_inout, Vi, vn * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, hipGetLastError());
+    return SDPSR_OK;
+}
+
+extern "C" int sdpsr_profile_cx_block_norms(sdpsr_ctx* c, int route, int64_t n, const double* Hr_host, const double* Hi_host, const double* Vr_host,
+                                            const double* Vi_host, const int32_t* space_of, int32_t neig, double* norms_inout, int64_t guard) {
+    CHECK_CTX(c);
+    if (!Hr_host || !Hi_host || !Vr_host || !Vi_host || !space_of || !norms_inout || !cx_common_ok(route, n, guard) || neig < 1 || neig > n)
+        return ctx_fail(c, SDPSR_BAD_ARGUMENT, "cx_block_norms: bad arguments");
+    for (int64_t a = 0; a < n; ++a)
+        if (space_of[a] < 0 || space_of[a] >= neig) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "cx_block_norms: space_of points outside the norms");
+    hipStream_t s = c->stream;
+    const size_t nn = (size_t)((int64_t)neig * neig + guard);
+    double *Hr, *Hi, *Vr, *Vi;
+    int st = cx_upload_planes(c, n, n, Hr_host, Hi_host, Vr_host, Vi_host, &Hr, &Hi, &Vr, &Vi);
+    if (st) return st;
+    int32_t* dspace = (int32_t*)ctx_buf(c, "prof_cx_space", (size_t)n * 4);
+    unsigned long long* dnorms = (unsigned long long*)ctx_buf(c, "prof_cx_norms", nn * 8);
+    if (!dspace || !dnorms) return SDPSR_OUT_OF_MEMORY;
+    HIP_TRY(c, hipMemcpyAsync(dspace, space_of, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(dnorms, norms_inout, nn * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemsetAsync(dnorms, 0, (size_t)neig * neig * 8, s));  // the maxima start from the driver's zero fill
+    if (route == 0) launch_cx_block_norms(s, n, Hr, Hi, Vr, Vi, dspace, neig, dnorms);
+    else if ((st = cx_block_norms_general(c, n, Hr, Hi, Vr, Vi, dspace, neig, dnorms)) != SDPSR_OK) return st;
+    HIP_TRY(c, hipMemcpyAsync(norms_inout, dnorms, nn * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, hipGetLastError());
+    return SDPSR_OK;
+}
+
+extern "C" int sdpsr_profile_cx_irreducible(sdpsr_ctx* c, int route, int64_t n, int64_t vcols, const double* Hr_host, const double* Hi_host,
+                                            const double* Vr_host, const double* Vi_host, const int32_t* desc, int32_t ncols, double atol,
+                                            double* Qhat_inout, int64_t guard) {
+    CHECK_CTX(c);
+    if (!Hr_host || !Hi_host || !Vr_host || !Vi_host || !desc || !Qhat_inout || !cx_common_ok(route, n, guard) || vcols < 1 ||
+        vcols > SDPSR_CX_MAX_N || ncols < 1 || ncols > SDPSR_CX_MAX_N || !(atol >= 0))
+        return ctx_fail(c, SDPSR_BAD_ARGUMENT, "cx_irreducible: bad arguments");
+    for (int32_t j = 0; j < ncols; ++j) {
+        const int32_t* d = desc + 6 * (size_t)j;
+        const bool col_ok = d[5] >= 0 && d[5] < ncols;
+        const bool k0 = d[0] == 0 && d[1] >= 0 && d[1] < vcols;
+        const bool k1 = d[0] == 1 && d[1] >= 0 && d[2] >= 1 && d[2] <= n && (int64_t)d[1] + d[2] <= vcols && d[3] >= 0 && d[4] >= 1 && d[4] <= n &&
+                        (int64_t)d[3] + d[4] <= vcols;
+        if (!col_ok || !(k0 || k1)) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "cx_irreducible: a descriptor points outside V or Qhat");
+    }
+    if (route == 1 && !cx_irreducible_general_lds_bytes(n)) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "cx_irreducible: order not supported by the general kernel");
+    hipStream_t s = c->stream;
+    const size_t qn = (size_t)(2 * n * ncols + guard);
+    double *Hr, *Hi, *Vr, *Vi;
+    const int st = cx_upload_planes(c, n, vcols, Hr_host, Hi_host, Vr_host, Vi_host, &Hr, &Hi, &Vr, &Vi);
+    if (st) return st;
+    int32_t* ddesc = (int32_t*)ctx_buf(c, "prof_cx_desc", (size_t)6 * ncols * 4);
+    double* Qhat = (double*)ctx_buf(c, "prof_cx_qhat", qn * 8);
+    if (!ddesc || !Qhat) return SDPSR_OUT_OF_MEMORY;
+    HIP_TRY(c, hipMemcpyAsync(ddesc, desc, (size_t)6 * ncols * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(Qhat, Qhat_inout, qn * 8, hipMemcpyHostToDevice, s));
+    if (route == 0) launch_cx_irreducible(s, n, Hr, Hi, Vr, Vi, ddesc, ncols, atol, Qhat);
+    else if (!launch_cx_irreducible_general(s, n, Hr, Hi, Vr, Vi, ddesc, ncols, atol, Qhat))
+        return ctx_fail(c, SDPSR_BAD_ARGUMENT, "cx_irreducible: order not supported by the general kernel");
+    HIP_TRY(c, hipMemcpyAsync(Qhat_inout, Qhat, qn * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, hipGetLastError());
+    return SDPSR_OK;
+}
+
 extern "C" int sdpsr_profile_kernel(sdpsr_ctx* c, int kind, int64_t n, int64_t aux, int reps,
                                     double* ms_per_launch) {
     CHECK_CTX(c);

@@ -397,6 +397,9 @@ bool backtransform_set_device_attributes();
 bool complex_set_device_attributes();
 // kernels_complex.hip (complex path of blockDiagonalize, n <= 64; planes re / im, ld = n)
 void launch_cx_embed(hipStream_t s, int64_t n, const double* Hr, const double* Hi, int64_t ld2, double* M);
+void launch_cx_embed_adjoint(hipStream_t s, int64_t n, const double* Zr, const double* Zi, int64_t ld2, double* M);
+void launch_cx_newton_schulz_factor(hipStream_t s, int64_t m, int64_t ld, double* K);
+void launch_cx_unstack(hipStream_t s, int64_t n, int64_t cols, const double* E, int64_t ld2, double* Vr, double* Vi, int64_t ldv);
 void launch_cx_rot(hipStream_t s, int64_t n, int64_t cols, int64_t ld2, const double* E, double* R);
 void launch_cx_zero_pad(hipStream_t s, int64_t m, int64_t mc, int64_t ld, int64_t ldc, double* A);
 void launch_cx_combine(hipStream_t s, int64_t n, int64_t ld2, const double* E, const int32_t* desc, const double* coef, double* Vr,
@@ -404,7 +407,12 @@ void launch_cx_combine(hipStream_t s, int64_t n, int64_t ld2, const double* E, c
 void launch_cx_stack(hipStream_t s, int64_t n, int64_t cols, const double* Vr, const double* Vi, int64_t ldv, int64_t ld2, double* E);
 void launch_cx_block_norms_general(hipStream_t s, int64_t n, int64_t ldn, const double* Gr, const double* Gi, const int32_t* space_of,
                                    int neig, unsigned long long* norms);
-void launch_cx_irreducible_general(hipStream_t s, int64_t n, const double* Hr, const double* Hi, const double* Vr, const double* Vi,
+// the largest order of the complex path (sdpsr.h)
+constexpr int64_t SDPSR_CX_MAX_N = 4096;
+// dynamic LDS of cx_irreducible_general_kernel at order n, 0 when the order does not fit a workgroup's LDS; the launcher and the
+// kernel's function attribute both come from here.  The launcher returns false, with nothing launched, where this says 0.
+size_t cx_irreducible_general_lds_bytes(int64_t n);
+bool launch_cx_irreducible_general(hipStream_t s, int64_t n, const double* Hr, const double* Hi, const double* Vr, const double* Vi,
                                    const int32_t* desc, int ncols, double atol, double* Qhat);
 void launch_cx_basis_image_sorted(hipStream_t s, int64_t n, int64_t d, int64_t S, const uint32_t* ent, const int64_t* cls_ptr,
                                   const double* Qhat, const int32_t* descA, const int32_t* descB, double atol, double* out);
