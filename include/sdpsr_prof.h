@@ -70,6 +70,15 @@ int sdpsr_profile_gather_packed(sdpsr_ctx* ctx, int64_t n, int T, int64_t d, uin
    differs), out[1] = the class count up to which the pass is a single launch. */
 int sdpsr_profile_verify(sdpsr_ctx* ctx, int64_t n, int T, int64_t d, int mode, const uint32_t* Lp_host, const uint32_t* first_idx_host,
                          const int32_t* C_host, const double* U_host, double coef, uint64_t key, double atol, uint32_t* out);
+/* The pair check of the loop's guessed initial partition: "would the refinement of the value pairs (a, b) over the packed lower triangle write
+   the labels Lp_host and the representatives first_idx_host (d of them, packed indices) again?"  a_host, b_host: n x n, column-major, the
+   lower triangle is read.  out[0] = verdict word (0: it would, bit for bit), out[1] = the largest d the pass takes; a larger d is refused
+   with SDPSR_BAD_ARGUMENT. */
+int sdpsr_profile_verify_pair(sdpsr_ctx* ctx, int64_t n, int64_t d, const uint32_t* Lp_host, const uint32_t* first_idx_host,
+                              const double* a_host, const double* b_host, uint32_t* out);
+/* Guessed initial partitions of ctx (restart 0) or of batch restart `restart` (as sdpsr_profile_loop_counts): out[0] = reductions that checked
+   the recorded initial partition instead of rebuilding it, out[1] = of those, the ones whose check failed (reduction repeated). */
+int sdpsr_profile_initial_guess(sdpsr_ctx* ctx, int32_t restart, uint64_t* out);
 
 /* ---- The kernels of the module-compression driver on caller-made inputs (tests/test_gpu_module_kernels.py). ----
    All matrices are column-major host arrays of doubles; labels are n x n uint32, column-major.  Every *_inout array is uploaded as the caller

@@ -233,6 +233,10 @@ def load_prof_library():
     lib.sdpsr_profile_verify.restype = C.c_int
     lib.sdpsr_profile_verify.argtypes = [vp, i64, C.c_int, i64, C.c_int, vp, vp, vp, vp, C.c_double, C.c_uint64, C.c_double,
                                          C.POINTER(C.c_uint32)]
+    lib.sdpsr_profile_verify_pair.restype = C.c_int
+    lib.sdpsr_profile_verify_pair.argtypes = [vp, i64, i64, vp, vp, vp, vp, C.POINTER(C.c_uint32)]
+    lib.sdpsr_profile_initial_guess.restype = C.c_int
+    lib.sdpsr_profile_initial_guess.argtypes = [vp, C.c_int32, C.POINTER(C.c_uint64)]
     # the module-compression kernels on caller-made inputs (tests)
     f64, rep = C.c_double, C.POINTER(C.c_int32)
     lib.sdpsr_profile_gram.restype = C.c_int

@@ -251,6 +251,7 @@ constexpr PinnedWords PINNED_SMALL_FLAG{0, 1};                   // c->pinned_sm
 constexpr PinnedWords PINNED_SMALL_LABEL_CHECK{2, 2};             // sdpsr_basis_image: [0] != 0 the caller's P is not symmetric, [1] != 0 a label exceeds d
 constexpr PinnedWords PINNED_SMALL_DEFERRED_VERIFY{8, 1};        // sdpsr_jordan_reduce: the two verdicts the loop left unread (c->deferred_verdict)
 constexpr PinnedWords PINNED_SMALL_DEFERRED_SPECULATIVE{24, 1};
+constexpr PinnedWords PINNED_SMALL_DEFERRED_INITIAL{16, 1};       // ... and the one of the guessed initial partition (c->initial_guess_pending)
 constexpr PinnedWords PINNED_SMALL_GRAM_STAMP{32, 1};            // module growth: the stamp behind a round's Gram products (compress.cpp, ortho_step)
 constexpr PinnedWords PINNED_SMALL_CANON{44, 18};                // sdpsr_sparse_create: the nine 64-bit words of CanonVerdict (csr_canon.h)
 constexpr PinnedWords PINNED_SMALL_NARROW{40, 1};                // != 0: a label did not fit the narrow type (kernels_labels.hip); cleared by the host before each pass
@@ -264,7 +265,7 @@ constexpr bool pinned_words_disjoint(std::initializer_list<PinnedWords> w, size_
 }
 static_assert(pinned_words_disjoint({PINNED_REFINE, PINNED_SYMMETRY, PINNED_BASIS_IMAGE_VERDICTS, PINNED_VERIFY, PINNED_SPECULATIVE, PINNED_BASIS_CONSTANT, PINNED_SAMPLE}, PINNED_FIXED_BYTES) &&
               PINNED_FIXED_BYTES % sizeof(double) == 0, "two reports share a word of c->pinned, or one reaches into the symmetry probe's doubles");
-static_assert(pinned_words_disjoint({PINNED_SMALL_FLAG, PINNED_SMALL_LABEL_CHECK, PINNED_SMALL_DEFERRED_VERIFY, PINNED_SMALL_DEFERRED_SPECULATIVE, PINNED_SMALL_GRAM_STAMP, PINNED_SMALL_NARROW, PINNED_SMALL_CANON}, 256) &&
+static_assert(pinned_words_disjoint({PINNED_SMALL_FLAG, PINNED_SMALL_LABEL_CHECK, PINNED_SMALL_DEFERRED_VERIFY, PINNED_SMALL_DEFERRED_SPECULATIVE, PINNED_SMALL_DEFERRED_INITIAL, PINNED_SMALL_GRAM_STAMP, PINNED_SMALL_NARROW, PINNED_SMALL_CANON}, 256) &&
               (PINNED_SMALL_CANON.first * 4) % 8 == 0 && PINNED_SMALL_CANON.count * 4 == sizeof(CanonVerdict), "two reports share a word of c->pinned_small");
 inline uint32_t* pinned_report(sdpsr_ctx* c, PinnedWords w) {  // the pinned words of one report (nullptr: no pinned buffer)
     uint32_t* p = (uint32_t*)ctx_pinned(c, PINNED_FIXED_BYTES);

@@ -2219,6 +2219,77 @@ bool launch_basis_constant_on_classes(hipStream_t s, int64_t n, int64_t r, const
 #undef SDPSR_UCONST_CASE
     return true;
 }
+// "Is the initial partition S = Part(a) ^ Part(b) of this call the one that Lp and first_idx already describe?"  (the restarts of one
+// problem: a, b are what they were, and a call that found its input closed has left the initial partition in place).  Lp, first_idx: the
+// canonical labels of a refinement and the first occurrences of its d <= VERIFY_LDS_CAP classes.  flag[0] stays 0 exactly when the
+// refinement of SrcPair{a, b, n, packed} would write the same labels and representatives again:
+//   every entry of label l >= 1 has the signature of first_idx[l - 1]; no representative has the zero signature (its class would be
+//   label 0); the representatives' signatures are pairwise distinct; every entry of label 0 has the zero signature
+// -- then the classes of the signatures ARE the classes of Lp, and the canonical numbering depends on the partition alone.  The signature
+// is the refinement's own (SrcPair::fetch / sig): -0.0, NaN payloads and equal hashes count as they do in the insert pass.  Layout as
+// uconst_check_kernel<R, true>; flag[0] cleared by the launcher.  (A representative outside the triangle or a label > d: violated.)
+__global__ void __launch_bounds__(256)
+verify_pair_kernel(SrcPair src, const uint32_t* __restrict__ Lp, uint32_t* __restrict__ flag, int d, const uint32_t* __restrict__ first_idx) {
+    __shared__ uint64_t sref[VERIFY_LDS_CAP];
+    const int n = src.n;
+    const int64_t np = (int64_t)n * (n + 1) / 2;
+    bool bad = false;
+    for (int cls = threadIdx.x; cls < d; cls += blockDim.x) {
+        const int64_t e = (int64_t)first_idx[cls];
+        uint64_t sg = 0;  // (the zero signature: violated below)
+        if (e < np) {
+            uint32_t i, j;
+            packed_lower_ij(n, e, i, j);
+            sg = src.sig(src.fetch(i, j, e));
+        }
+        bad = bad || sg == 0;
+        sref[cls] = sg;
+    }
+    __syncthreads();
+    if (blockIdx.x == 0) {  // pairwise distinct: one workgroup's finding is enough (every lane reads the same word: a broadcast)
+        for (int cls = threadIdx.x; cls < d; cls += blockDim.x) {
+            const uint64_t mine = sref[cls];
+            for (int k = 0; k < cls; ++k) bad = bad || sref[k] == mine;
+        }
+    }
+    for (int j = blockIdx.x; j < n; j += gridDim.x) {
+        const int64_t poff = (int64_t)j * n - (int64_t)j * (j - 1) / 2 - j;
+        const uint32_t* Lj = Lp + poff;
+        constexpr int VB = 4;  // entries per trip: labels and values first, then the classes' signatures (see verify_lower_kernel)
+        for (int i0 = j + threadIdx.x; i0 < n; i0 += 256 * VB) {
+            uint32_t l[VB];
+            SrcPair::Raw v[VB];
+#pragma unroll
+            for (int b = 0; b < VB; ++b) {
+                const int i = i0 + 256 * b;
+                const bool ok = i < n;
+                l[b] = ok ? __builtin_nontemporal_load(&Lj[i]) : 0u;
+                v[b] = ok ? src.fetch((uint32_t)i, (uint32_t)j, poff + i) : SrcPair::Raw{0.0, 0.0};
+            }
+            uint64_t rc[VB];
+#pragma unroll
+            for (int b = 0; b < VB; ++b) {
+                rc[b] = 0;  // label 0 (and the slots past the column): the zero signature
+                if (l[b] > (uint32_t)d) bad = true;
+                else if (l[b]) rc[b] = sref[l[b] - 1];
+            }
+#pragma unroll
+            for (int b = 0; b < VB; ++b) bad = bad || src.sig(v[b]) != rc[b];
+        }
+    }
+    if (bad) flag[0] = 1u;
+}
+// a, b: symmetric n x n, column-major (the lower triangle is read); Lp, first_idx: as above; flag: a word of pinned host memory whose last
+// verdict has been read (cleared from the host).  false: more classes than the one-launch form holds (nothing is enqueued)
+bool launch_verify_pair(hipStream_t s, int64_t n, const double* a, const double* b, const uint32_t* Lp, int64_t d, const uint32_t* first_idx,
+                        uint32_t* flag) {
+    if (n < 1 || n >= (int64_t(1) << 31) || d < 1 || d > VERIFY_LDS_CAP) return false;
+    const int g = n < 256 * 8 ? (int)n : 256 * 8;
+    *(volatile uint32_t*)flag = 0u;
+    verify_pair_kernel<<<g, 256, 0, s>>>(SrcPair{a, b, (int)n, 1}, Lp, flag, (int)d, first_idx);
+    return true;
+}
+
 // q: SIG_JOINT_I32 or SIG_CHAN_I32 on the packed lower triangle with packed labels (q.L = Lp); flag[0] = verdict.
 // Returns false when there is no instance for the shape (the caller runs the refinement).
 bool verify_no_split_supports(const SigSource& q, int64_t d) {

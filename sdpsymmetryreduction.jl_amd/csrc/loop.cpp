@@ -1,4 +1,5 @@
 // admissible_subspace (src/partitions.jl:109-190): the Jordan-reduction loop on the device, and desymmetrize (:197-223).
+#include <algorithm>
 #include <cmath>
 
 #include "host_internal.h"
@@ -41,6 +42,7 @@ public:
         return st;
     }
     int refine_full(const SigSource& src, int64_t* d, bool with_symmetry_verdict) {
+        if (with_symmetry_verdict) c->symflag_zero = false;  // (the check pass stores its verdict into symflag[0])
         const int st = with_symmetry_verdict ? refine_signatures(c, n * n, src, L, d, n, symflag, &sym) : refine_signatures(c, n * n, src, L, d);
         full_valid = true, packed_valid = false;
         return st;
@@ -279,7 +281,7 @@ struct Loop {
             st = verify_round(qj, confirming, jl2, tail, &v);
             if (st) return st;
             if (v.unchanged) dj = current;  // labels (packed, and full where a gather has written them), class representatives and table hints stay as they are
-            else st = lab.refine_packed(qj, &dj);
+            else if (!(st = initial_guess_settled())) st = lab.refine_packed(qj, &dj);  // (never a refinement of labels that were only guessed)
             tm.end();
             if (st) return st;
             tm.collect();
@@ -395,15 +397,44 @@ struct Loop {
     }
     // S = Part(CL); S = refine!(S, Part(X0L))   (:145-146): both refinements in one canonical relabel; the pair signature is computed inside the
     // insert pass
-    int initial_partition(const double* dCL, const double* dX0, int hint, int64_t* d) {
+    // guess (admissible_subspace_impl decides): "adm_lpacked" / "ref_first" still hold the initial partition of the last call on this ctx, which
+    // found its input closed -- the restarts of one problem hand in the same C_L, X0_L again.  Then the partition is not rebuilt but CHECKED: one
+    // streaming compare of every entry's pair signature with its class representative's (launch_verify_pair: the word stays 0 exactly when the
+    // refinement would write the same labels and representatives again), no table, no ranking, no label pass, no host wait.  The verdict goes to a
+    // word of its own and is read with the loop's two deferred ones, behind the reduction's last wait (reduce.cpp); the loop goes on from the
+    // state a rebuild would have left.  Before anything REFINES these labels the word is read here (initial_guess_settled).
+    int initial_partition(const double* dCL, const double* dX0, int hint, const InitialRecord* guess, int64_t* d) {
         SigSource q;
         q.kind = SIG_PAIR, q.sig = sig, q.a = dCL, q.b = dX0;
         if (!((hint & 2) && lab.Lp && len < (int64_t(1) << 32))) return lab.refine_full(q, d, true);  // + symmetry verdict of the initial partition
         // the caller vouches for symmetric CL / X0L (the reference symmetrises both, src/partitions.jl:128-141): the initial partition from the lower
         // triangle, mirrored
         q.n = n, q.packed = 1, lab.sym = 1;
+        initial_packed = true;
+        if (guess && launch_verify_pair(s, n, dCL, dX0, lab.Lp, guess->d0, guess->first, c->pinned_small + PINNED_SMALL_DEFERRED_INITIAL.first)) {
+            c->initial_guess_pending = true;
+            ++c->initial_guesses;
+            HIP_TRY(c, hipGetLastError());
+            *d = guess->d0;
+            lab.packed_refined();
+            // (the hint a refinement that found d0 classes leaves, primitives.cpp; first_idx_labels is Lp already)
+            const int full = std::max(12, ceil_log2((uint64_t)(n * (n + 1) / 2) * 2));
+            c->table_log2_hint = std::min(full, std::max(12, ceil_log2((uint64_t)guess->d0 * 8 + 1)));
+            return SDPSR_OK;
+        }
         return lab.refine_packed(q, d);
     }
+    // The guessed initial partition's verdict, where the loop cannot go on without it: waits for the stream.  Violated: the loop ends with
+    // STATUS_REPEAT_REDUCTION (the word stays pending: reduce.cpp reads it again and repeats the reduction).
+    int initial_guess_settled() {
+        if (!c->initial_guess_pending) return SDPSR_OK;
+        HIP_TRY(c, ctx_sync_stream(c, s));
+        HIP_TRY(c, hipGetLastError());
+        if (((const volatile uint32_t*)c->pinned_small)[PINNED_SMALL_DEFERRED_INITIAL.first] != 0) return STATUS_REPEAT_REDUCTION;
+        c->initial_guess_pending = false;
+        return SDPSR_OK;
+    }
+    bool initial_packed = false;  // the initial partition was formed (or guessed) on the packed lower triangle
     // The square mode's buffers (same names and sizes for every call of a mode; T = 1 in the fp64 mode)
     int square_buffers() {
         static const struct { const char *x, *c; size_t xb, cb; } B[] = {{"adm_xi8", "adm_ci32", 1, 4}, {"adm_xf32", "adm_cf32", 4, 4}, {"adm_xf64", "adm_cf64", 8, 8}};
@@ -449,6 +480,8 @@ int admissible_subspace_impl(sdpsr_ctx* c, int64_t n, const double* CL, const do
     c->hint_symmetric_basis = 0;
     c->hint_used = hint;
     c->adm_dims.clear();
+    const InitialRecord rec = c->initial_record;  // whatever this call does, it ends with its own record or with none
+    c->initial_record = InitialRecord{};
     if (!CL || !X0L || !P_out || !dim_out || n < 1 || r < 0 || (r > 0 && !U) || !(atol > 0))
         return ctx_fail(c, SDPSR_BAD_ARGUMENT, "bad arguments");
     const int64_t len = n * n;
@@ -473,7 +506,9 @@ int admissible_subspace_impl(sdpsr_ctx* c, int64_t n, const double* CL, const do
     lp.coef = (double*)ctx_buf(c, "proj_coef", (size_t)2 * std::max<int64_t>(r, 1) * 8);
     lp.symflag = (uint32_t*)ctx_buf(c, "adm_symflag", 64);
     if (st || !lp.sig || !lp.partial || !lp.coef || !lp.symflag) return st ? st : SDPSR_OUT_OF_MEMORY;
-    HIP_TRY(c, hipMemsetAsync(lp.symflag, 0, 64, s));
+    // (the words are zero already when the last call on this ctx wrote none of them: one fill launch less)
+    if (!c->symflag_zero) HIP_TRY(c, hipMemsetAsync(lp.symflag, 0, 64, s));
+    c->symflag_zero = true;  // until somebody writes a verdict there (LoopLabels::refine_full) or the buffer is replaced (ctx_buf)
     lp.zero_flag = lp.symflag + 8;
     lp.mode = c->opts.square_mode, lp.T = (lp.mode == SDPSR_SQUARE_F64) ? 1 : c->opts.channels;
     st = lp.square_buffers();
@@ -485,9 +520,17 @@ int admissible_subspace_impl(sdpsr_ctx* c, int64_t n, const double* CL, const do
     lp.keep_packed = lp.mode == SDPSR_SQUARE_I8 && (lp.T == 1 || lp.T == 2 || lp.T == 4) && !(c->opts.flags & SDPSR_FLAG_UNPACK_EVERY_STEP);
     lp.lab.init(c, n, lp.symflag, lp.keep_packed, lp.early_ok);
 
+    // The initial partition is guessed (Loop::initial_partition) inside sdpsr_jordan_reduce only, where a wrong guess repeats the reduction, for
+    // an input predicted closed whose record is this call's: same order, same buffers, the packed route -- and only where the first iteration is
+    // the joint one with its verify pass, which looks at the guessed labels before anything refines them.
+    const bool first_joint = !(c->opts.flags & (SDPSR_FLAG_SEPARATE_REFINEMENTS | SDPSR_FLAG_NO_VERIFY_SHORTCUT)) && lp.keep_packed && (lp.T == 2 || lp.T == 4) &&
+                             (r == 0 || (hint & 1)) && r <= 4 && len < (int64_t(1) << 32) && c->opts.max_iters >= 1;
+    const bool guess_initial = c->allow_deferred_verdict && c->pinned_small && lp.early_ok && c->predict_closed && c->predict_n == n && (hint & 2) && first_joint &&
+                               rec.valid && rec.n == n && rec.Lp == lp.lab.Lp && rec.sym == 1 && rec.d0 >= 1 && rec.d0 <= (int64_t)verify_lds_cap() &&
+                               c->first_idx_labels == lp.lab.Lp && rec.first == (const uint32_t*)ctx_buf(c, "ref_first", (size_t)refine_first_cap() * 4);
     int64_t d = 0;
     tm.begin(SDPSR_T_REFINE);
-    st = lp.initial_partition(dCL, dX0, hint, &d);
+    st = lp.initial_partition(dCL, dX0, hint, guess_initial ? &rec : nullptr, &d);
     tm.end();
     if (st) return st;
     tm.collect();  // (intervals whose end has not passed yet stay pending: the refinement may have returned on its label pass's report)
@@ -524,6 +567,14 @@ int admissible_subspace_impl(sdpsr_ctx* c, int64_t n, const double* CL, const do
     HIP_TRY(c, hipGetLastError());
     c->predict_closed = converged && lp.it == 1 && c->adm_dims.size() == 2 && c->adm_dims[0] == c->adm_dims[1];
     c->predict_n = n;
+    // a call that refined nothing after its initial partition leaves that partition, and its representatives, where the next call looks for them
+    if (converged && lp.initial_packed && c->first_idx_labels == lp.lab.Lp && c->adm_dims[0] >= 1 && c->adm_dims[0] <= (int64_t)verify_lds_cap() &&
+        std::all_of(c->adm_dims.begin(), c->adm_dims.end(), [&](int64_t x) { return x == c->adm_dims[0]; })) {
+        InitialRecord& ir = c->initial_record;
+        ir.first = (const uint32_t*)ctx_buf(c, "ref_first", (size_t)refine_first_cap() * 4);  // (before `valid`: ctx_buf drops the record of a buffer it replaces)
+        ir.n = n, ir.d0 = c->adm_dims[0], ir.Lp = lp.lab.Lp, ir.sym = lp.lab.sym;
+        ir.valid = ir.first != nullptr;
+    }
     *dim_out = lp.current;
     if (iters_out) *iters_out = lp.it;
     if (labels_sym_out) *labels_sym_out = lp.lab.sym;

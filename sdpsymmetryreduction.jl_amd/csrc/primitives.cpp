@@ -40,6 +40,7 @@ int refine_signatures(sdpsr_ctx* c, int64_t len, const SigSource& src_in, uint32
     const int64_t nblk = (len + rb - 1) / rb;
     bool mispredicted = false, sampled = false, cub_fallback = false;
     c->first_idx_labels = nullptr;  // whatever happens below, the old representatives no longer describe `labels`
+    c->initial_record = InitialRecord{};  // ... nor does "ref_first" go with the last call's initial partition
     // Which relabel?  Few classes: a hash table (LDS level + a global one that stays in L2).  Many classes (problems
     // without symmetry: ~len / 2 distinct signatures): a table that large is one global atomic per entry into memory no
     // cache holds -- the bucketed grouping of kernels_refine_bucket.hip streams instead.  The choice is made BEFORE a

@@ -254,6 +254,48 @@ extern "C" int sdpsr_profile_verify(sdpsr_ctx* c, int64_t n, int T, int64_t d, i
     return SDPSR_OK;
 }
 
+// The pair check "would the initial refinement of (a, b) write these labels and representatives again?" on caller-made inputs
+// (tests/test_gpu_verify_pair.py).  Lp_host: packed labels <= d of order n, first_idx_host: the d packed indices of the representatives,
+// a_host, b_host: n x n column-major (the lower triangle is read).  out[0] = the verdict word (0xDEAD before the pass is enqueued: the pass has
+// to clear it), out[1] = the largest class count the pass takes; more classes are refused.
+extern "C" int sdpsr_profile_verify_pair(sdpsr_ctx* c, int64_t n, int64_t d, const uint32_t* Lp_host, const uint32_t* first_idx_host,
+                                         const double* a_host, const double* b_host, uint32_t* out) {
+    CHECK_CTX(c);
+    if (!Lp_host || !first_idx_host || !a_host || !b_host || !out || n < 1 || n > 8192 || d < 1 || d > (int64_t)verify_lds_cap())
+        return ctx_fail(c, SDPSR_BAD_ARGUMENT, "bad arguments");
+    const int64_t np = n * (n + 1) / 2;
+    for (int64_t k = 0; k < d; ++k)
+        if ((int64_t)first_idx_host[k] >= np) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "a representative outside the packed triangle");
+    hipStream_t s = c->stream;
+    uint32_t* Lp = (uint32_t*)ctx_buf(c, "prof_lp", (size_t)np * 4);
+    uint32_t* first = (uint32_t*)ctx_buf(c, "prof_first", (size_t)d * 4);
+    double* ab = (double*)ctx_buf(c, "prof_pair_ab", (size_t)2 * n * n * 8);
+    uint32_t* hv = pinned_report(c, PINNED_VERIFY);
+    if (!Lp || !first || !ab || !hv) return SDPSR_OUT_OF_MEMORY;
+    HIP_TRY(c, hipMemcpyAsync(Lp, Lp_host, (size_t)np * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(first, first_idx_host, (size_t)d * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(ab, a_host, (size_t)n * n * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(ab + n * n, b_host, (size_t)n * n * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipStreamSynchronize(s));  // (nothing may be in flight on the verdict word)
+    hv[0] = 0xDEADu;
+    const bool ran = launch_verify_pair(s, n, ab, ab + n * n, Lp, d, first, hv);
+    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, hipGetLastError());
+    if (!ran) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "no pair check for this shape");
+    out[0] = ((const volatile uint32_t*)hv)[0];
+    out[1] = (uint32_t)verify_lds_cap();
+    return SDPSR_OK;
+}
+
+extern "C" int sdpsr_profile_initial_guess(sdpsr_ctx* c, int32_t restart, uint64_t* out) {
+    CHECK_CTX(c);
+    if (!out || restart < 0 || restart > (int32_t)c->batch_children.size()) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "bad arguments");
+    const sdpsr_ctx* ci = restart == 0 ? c : c->batch_children[restart - 1];
+    out[0] = ci->initial_guesses;
+    out[1] = ci->initial_guesses_violated;
+    return SDPSR_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------
 // The kernels of the module-compression driver on caller-made inputs (tests/test_gpu_module_kernels.py): host arrays in, the
 // product's own launcher called the way compress.cpp calls it, everything back.  Every output array is in/out: uploaded as the

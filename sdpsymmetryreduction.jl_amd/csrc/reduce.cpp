@@ -41,24 +41,61 @@ int jordan_reduce_impl(sdpsr_ctx* c, int64_t n, const double* CL, const double* 
     double pm_a[SDPSR_T_COUNT] = {}, pm_b[SDPSR_T_COUNT] = {}, pm_i[SDPSR_T_COUNT] = {};
     int labels_sym = 0;
     c->deferred_verdict = false;
+    c->initial_guess_pending = false;
     // the loop's deferred tail lives inside this call: on the successful path it has been enqueued (below) well before the last host wait; an
     // error return drops what is left of it, so that no later call on the ctx enqueues segments that point into this call's arguments
     struct DropTail {
         sdpsr_ctx* c;
         ~DropTail() { c->deferred_tail.count = c->deferred_tail.next = 0; }
     } drop_tail{c};
+    // A wrong guess of the loop (its input closed, its initial partition the recorded one) voids the run: the reduction is done again from the
+    // caller's seed position with the caller's hint, and this time nothing is guessed (predict_closed is off, the record is gone).
+    auto repeat_without_guesses = [&](uint32_t dv, uint32_t dv_spec, uint32_t dv_init) -> int {
+        c->predict_closed = false;
+        c->initial_record = InitialRecord{};
+        if (dv_init != 0) ++c->initial_guesses_violated;
+        if (dbg_on())
+            fprintf(stderr, "[sdpsr] jordan_reduce: %s%s%s (deferred verdicts: verify %u, speculative %u, initial partition %u): reduction repeated\n",
+                    dv_init != 0 ? "the initial partition was not the recorded one" : "", dv_init != 0 && (dv != 0 || dv_spec != 0) ? "; " : "",
+                    dv != 0 ? "the input was not closed after all" : (dv_spec != 0 ? "the confirm round found a split" : ""), dv, dv_spec, dv_init);
+        // the repeat makes the draws of a call that took no guess, with the caller's hint
+        c->stream_counter = stream_at_entry;
+        c->hint_symmetric_basis = hint_at_entry;
+        if (mem_in != SDPSR_MEM_DEVICE) {  // host inputs: the loop's copies in its input buffers (loop.cpp, same names and sizes), no second upload
+            CL = (const double*)ctx_buf(c, "adm_cl", (size_t)len * 8);
+            X0L = (const double*)ctx_buf(c, "adm_x0", (size_t)len * 8);
+            if (U) U = (const double*)ctx_buf(c, "adm_u", (size_t)len * std::max<int64_t>(r, 1) * 8);
+            if (!CL || !X0L || (r > 0 && !U)) return SDPSR_OUT_OF_MEMORY;
+            mem_in = SDPSR_MEM_DEVICE;
+        }
+        return jordan_reduce_impl(c, n, CL, X0L, U, r, atol, epsilon, P_out, dim_out, iters_out, nblocks, sum_sq, sum_s, blks, blks_capacity, Q_hat,
+                                  qhat_capacity, phase_ms, mem_in, mem_out);
+    };
+    // An early way out while the guessed initial partition's verdict is unread: with stale labels the loop or a later step may report an error
+    // that is not real.  The rest of the tail is enqueued (nothing may stay registered), the stream waited for and the word read; violated:
+    // the reduction is repeated instead of the error reported.
+    auto leave = [&](int st_err) -> int {
+        if (!c->initial_guess_pending) return st_err;
+        c->initial_guess_pending = false;
+        c->deferred_verdict = false;
+        flush_deferred_tail(c);
+        if (ctx_sync_stream(c, s) != hipSuccess) return st_err == STATUS_REPEAT_REDUCTION ? ctx_fail(c, SDPSR_HIP_ERROR, "hipStreamSynchronize failed") : st_err;
+        const uint32_t dv_init = ((const volatile uint32_t*)c->pinned_small)[PINNED_SMALL_DEFERRED_INITIAL.first];
+        if (dv_init != 0) return repeat_without_guesses(0, 0, dv_init);
+        return st_err == STATUS_REPEAT_REDUCTION ? ctx_fail(c, SDPSR_BAD_STATE, "jordan_reduce: a repeat was asked for without a violated verdict") : st_err;
+    };
     c->allow_deferred_verdict = !(c->opts.flags & SDPSR_FLAG_WAIT_FOR_EVERY_VERDICT);  // (the loop's last verdicts may ride on this reduction's later host waits, see sdpsr_internal.h)
     st = admissible_subspace_impl(c, n, CL, X0L, U, r, atol, L, dim_out, iters_out, phase_ms ? pm_a : nullptr, mem_in, SDPSR_MEM_DEVICE,
                                   /*final_sync=*/false, &labels_sym);
     c->allow_deferred_verdict = false;
     const int st_loop = st;
-    if (st && st != SDPSR_NOT_CONVERGED) return st;
+    if (st && st != SDPSR_NOT_CONVERGED) return leave(st);
     // more classes than the ctx's label width holds (the reference's InexactError of Partition{T}): the reduction stops behind the loop,
     // P_out untouched -- reported below, once the stream has been waited for and the loop's deferred verdicts are in
     const bool overflow = P_out && label_width_overflows(c, (uint64_t)*dim_out);
     if (P_out && !in_place && !overflow) {  // stream-ordered; complete when the call returns (it ends with a synchronisation on every path)
         st = labels_deliver(c, P_out, L, (size_t)len, mem);
-        if (st) return st;
+        if (st) return leave(st);
     }
     const int64_t d = *dim_out;
     int32_t nb = 0;
@@ -92,8 +129,9 @@ int jordan_reduce_impl(sdpsr_ctx* c, int64_t n, const double* CL, const double* 
         } forget{c};
         if (!images_done && c->bd_valid) {
             uint32_t* keep = (uint32_t*)ctx_buf(c, "bd_labels", (size_t)len * 4);
-            if (!keep) return SDPSR_OUT_OF_MEMORY;
-            HIP_TRY(c, hipMemcpyAsync(keep, P_out, (size_t)len * 4, hipMemcpyDeviceToDevice, s));
+            if (!keep) return leave(SDPSR_OUT_OF_MEMORY);
+            const hipError_t ek = hipMemcpyAsync(keep, P_out, (size_t)len * 4, hipMemcpyDeviceToDevice, s);
+            if (ek != hipSuccess) return leave(ctx_fail(c, SDPSR_HIP_ERROR, std::string("hipMemcpyAsync: ") + hipGetErrorString(ek)));
         } else if (images_done) {
             c->bd_valid = false;  // nothing left for a second sdpsr_block_images to work on (sizes and Q_hat stay available)
         }
@@ -104,28 +142,18 @@ int jordan_reduce_impl(sdpsr_ctx* c, int64_t n, const double* CL, const double* 
         const hipError_t e = ctx_sync_stream(c, s);
         if (e != hipSuccess && st == SDPSR_OK) st = ctx_fail(c, SDPSR_HIP_ERROR, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
     }
-    if (c->deferred_verdict) {
-        // The stream has been waited for: the verdicts the loop left unread are in.  A violated one means the loop stopped on a
-        // partition that one more step would have refined -- whatever blockDiagonalize made of it (a failure included) is void;
-        // the reduction is done again, this time reading the verdicts where they arise.
+    if (c->deferred_verdict || c->initial_guess_pending) {
+        // The stream has been waited for: the verdicts the loop left unread are in.  A violated one means the loop started from a partition
+        // that is not this input's (the initial guess), or stopped on one that one more step would have refined -- whatever blockDiagonalize
+        // made of it (a failure included) is void; the reduction is done again, this time reading the verdicts where they arise.
         const volatile uint32_t* ps = c->pinned_small;
-        const uint32_t dv = ps[PINNED_SMALL_DEFERRED_VERIFY.first], dv_spec = ps[PINNED_SMALL_DEFERRED_SPECULATIVE.first];
+        const uint32_t dv = c->deferred_verdict ? ps[PINNED_SMALL_DEFERRED_VERIFY.first] : 0u;
+        const uint32_t dv_spec = c->deferred_verdict ? ps[PINNED_SMALL_DEFERRED_SPECULATIVE.first] : 0u;
+        const uint32_t dv_init = c->initial_guess_pending ? ps[PINNED_SMALL_DEFERRED_INITIAL.first] : 0u;
         c->deferred_verdict = false;
-        if (dv != 0 || dv_spec != 0) {
-            c->predict_closed = false;
-            if (dbg_on()) fprintf(stderr, "[sdpsr] jordan_reduce: the input was not closed after all (deferred verdicts %u %u): reduction repeated\n", dv, dv_spec);
-            // the repeat makes the draws of a call that took no guess, with the caller's hint
-            c->stream_counter = stream_at_entry;
-            c->hint_symmetric_basis = hint_at_entry;
-            if (mem_in != SDPSR_MEM_DEVICE) {  // host inputs: the loop's copies in its input buffers (loop.cpp, same names and sizes), no second upload
-                CL = (const double*)ctx_buf(c, "adm_cl", (size_t)len * 8);
-                X0L = (const double*)ctx_buf(c, "adm_x0", (size_t)len * 8);
-                if (U) U = (const double*)ctx_buf(c, "adm_u", (size_t)len * std::max<int64_t>(r, 1) * 8);
-                if (!CL || !X0L || (r > 0 && !U)) return SDPSR_OUT_OF_MEMORY;
-                mem_in = SDPSR_MEM_DEVICE;
-            }
-            const int st2 = jordan_reduce_impl(c, n, CL, X0L, U, r, atol, epsilon, P_out, dim_out, iters_out, nblocks, sum_sq, sum_s, blks, blks_capacity,
-                                               Q_hat, qhat_capacity, phase_ms, mem_in, mem_out);
+        c->initial_guess_pending = false;
+        if (dv != 0 || dv_spec != 0 || dv_init != 0) {
+            const int st2 = repeat_without_guesses(dv, dv_spec, dv_init);
             if (phase_ms)  // the voided run's time was spent too
                 for (int i = 0; i < SDPSR_T_COUNT; ++i) phase_ms[i] += pm_a[i] + pm_b[i] + pm_i[i];
             return st2;

@@ -70,6 +70,15 @@ struct DeferredTail {
     const uint32_t* first = nullptr;  // "ref_first" of the packed labels
 };
 constexpr uint32_t DEFERRED_NEVER_RAN = 0xDEFE44EDu;  // what a verdict word holds until its segment is enqueued: reads as "violated"
+// "adm_lpacked" (Lp) and "ref_first" (first) describe the initial partition of the last loop call: order n, d0 classes, labels symmetric
+struct InitialRecord {
+    bool valid = false;
+    int64_t n = 0, d0 = 0;
+    const uint32_t *Lp = nullptr, *first = nullptr;
+    int sym = 0;
+};
+// the loop's outcome "the initial partition was not the recorded one: repeat the reduction" -- never leaves jordan_reduce_impl
+constexpr int STATUS_REPEAT_REDUCTION = -0x5250;
 }  // namespace sdpsr
 
 struct sdpsr_ctx {
@@ -142,6 +151,14 @@ struct sdpsr_ctx {
     bool allow_deferred_verdict = false;
     bool deferred_verdict = false;  // both wait in c->pinned_small (host_internal.h: PINNED_SMALL_DEFERRED_*) and must be 0
     sdpsr::DeferredTail deferred_tail;  // ... and the squares and verify passes that produce them, while they are not enqueued yet
+    // The loop's second guess (loop.cpp, initial_partition): the last loop call on this ctx found its input closed, so "adm_lpacked" /
+    // "ref_first" still hold its INITIAL partition -- the next call of sdpsr_jordan_reduce checks that partition against its inputs
+    // (launch_verify_pair) instead of rebuilding it, and the verdict rides with the two above.  Dropped by every refinement, by a
+    // violated verdict, and by ctx_buf when it frees either buffer.
+    sdpsr::InitialRecord initial_record;
+    bool initial_guess_pending = false;  // this reduction took the guess; its word (PINNED_SMALL_DEFERRED_INITIAL) has not been read
+    uint64_t initial_guesses = 0, initial_guesses_violated = 0;  // sdpsr_profile_initial_guess
+    bool symflag_zero = false;  // every word of "adm_symflag" is 0 (the loop's last call wrote none of them)
 };
 
 // sdpsr_problem_create: the loop's inputs, device-resident, shared (read-only) by every reduction / restart that names them
@@ -322,6 +339,10 @@ bool launch_basis_constant_on_classes(hipStream_t s, int64_t n, int64_t r, const
                                       const uint32_t* first_idx, double atol, double scale, void* ref, uint32_t* flag);
 bool launch_verify_no_split(hipStream_t s, const SigSource& q, int64_t d, const uint32_t* first_idx, void* ref, uint32_t* flag);
 bool verify_no_split_supports(const SigSource& q, int64_t d);  // launch_verify_no_split has an instance for this shape
+// "would the refinement of SIG_PAIR (a, b; packed lower triangle) write Lp and first_idx again?"  d <= verify_lds_cap() classes: one launch,
+// flag[0] (pinned host memory, cleared from the host) stays 0 exactly then.  false: d outside [1, verify_lds_cap()], nothing enqueued
+bool launch_verify_pair(hipStream_t s, int64_t n, const double* a, const double* b, const uint32_t* Lp, int64_t d, const uint32_t* first_idx,
+                        uint32_t* flag);
 // loop.cpp: enqueue the next max_segments segments of the ctx's deferred tail on c->stream (none pending: nothing happens)
 void flush_deferred_tail(sdpsr_ctx* c, int max_segments = DEFERRED_SEGMENTS);
 inline bool deferred_tail_pending(const sdpsr_ctx* c) { return c->deferred_tail.next < c->deferred_tail.count; }
