@@ -475,6 +475,33 @@ int sdpsr_admissible_subspace_sparse(sdpsr_ctx* ctx, int64_t n, const sdpsr_spar
 int sdpsr_reduce_constraints_sparse(sdpsr_ctx* ctx, const sdpsr_sparse* A, const uint32_t* labels, int64_t d, double* out,
                                     int mem);
 
+/* ---- removing the linearly dependent reduced constraints, docs/src/examples/ReduceAndSolveJuMP.jl:44-50 ----
+   ("Removing linearly dependent constraints", docs/src/examples/QuadraticAssignmentProblems.jl:116-122)
+     newConstraints = hcat(A * PMat, b)
+     newConstraints = sparse(svd(Matrix(newConstraints)').U[:, 1:rank(newConstraints)]');  droptol!(newConstraints, 1e-8)
+   M = [newA | b] is m x ncols, ncols = d + 1 (d when b == NULL: newA alone).  newA: m x d, column-major -- what the three
+   sdpsr_reduce_constraints* entries write -- in `mem`; b: m doubles, HOST memory, may be NULL; out: m x ncols, column-major
+   with leading dimension m, in `mem`, never aliasing newA.  1 <= m <= 1024 (m = 0: nothing to do, rank 0); m > ncols is fine.
+     rows 0 .. r-1 of out   an orthonormal basis of rowspace(M): row k is the right singular vector of M for its k-th largest
+                            singular value (the rows of svd(M').U[:, 1:r]'; within a repeated singular value any orthonormal
+                            basis of its space), normalised, its sign fixed so that its first entry of largest magnitude is
+                            positive, and every entry with |v| <= droptol set to exactly 0.0 afterwards (droptol!; 0 keeps all)
+     rows r .. m-1 of out   exactly 0.0 -- every element of out is written
+     *rank_out = r          the number of singular values > rtol * sigma_1; rtol = 0: Julia's dense rank(M) default
+                            min(m, ncols) * eps.  rtol < 0, NaN or Inf, droptol < 0 or NaN: SDPSR_BAD_ARGUMENT
+     sv                     m doubles, host memory, may be NULL: all computed singular values, descending
+     *nnz_out               may be NULL: the non-zeros left in rows 0 .. r-1 after the drop (sizes a sparse copy)
+     *passes_out            may be NULL: outer passes made (Gram matrix on the device, Jacobi rotations of it on the host, rows
+                            rotated on the device; DESIGN.md "Dependent reduced constraints"); host waits: passes + 1, and for m > 64
+                            one more per rotating pass (the upload of the rotations)
+   A non-finite entry of newA or b: SDPSR_BAD_ARGUMENT ("non-finite value"), out untouched.  An all-zero M: r = 0, SDPSR_OK.
+   Pass limit (16) reached: SDPSR_NOT_CONVERGED, every output written as it stands.  Every sum has an order fixed by
+   (m, ncols) and there are no floating-point atomics: equal inputs give equal bytes, on any ctx.  The ctx stays usable
+   after every error. */
+int sdpsr_compress_constraints(sdpsr_ctx* ctx, int64_t m, int64_t d, const double* newA, const double* b, double rtol,
+                               double droptol, double* out, int64_t* rank_out, double* sv, int64_t* nnz_out,
+                               int32_t* passes_out, int mem);
+
 /* ---- blockDiagonalize, src/compat.jl:46-68 ---------------------------------- */
 /* Phase 1 = diagonalize(Float64, P; atol=epsilon) (src/diagonalize.jl:25-40) +
    check_block_sizes (:1-11).  Keeps Q_hat on the device inside ctx.

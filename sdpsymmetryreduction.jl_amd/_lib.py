@@ -160,6 +160,7 @@ def load_library():
         "sdpsr_admissible_setup_sparse": (C.c_int, [vp, i64, vp, vp, vp, dbl, vp, vp, vp, pi64, C.POINTER(C.c_int), pi32, C.c_int]),
         "sdpsr_admissible_subspace_sparse": (C.c_int, [vp, i64, vp, vp, vp, dbl, vp, pi64, pi32, vp, C.c_int]),
         "sdpsr_reduce_constraints_sparse": (C.c_int, [vp, vp, vp, i64, vp, C.c_int]),
+        "sdpsr_compress_constraints": (C.c_int, [vp, i64, i64, vp, vp, dbl, dbl, vp, pi64, vp, pi64, pi32, C.c_int]),
         "sdpsr_desymmetrize": (C.c_int, [vp, i64, vp, pi64, pi32, C.c_int]),
         "sdpsr_block_diagonalize": (C.c_int, [vp, i64, vp, i64, dbl, pi32, pi64, pi64, vp, C.c_int]),
         "sdpsr_block_sizes": (C.c_int, [vp, vp]),

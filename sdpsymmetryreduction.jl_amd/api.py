@@ -953,7 +953,8 @@ def reduce_constraints(P, A, ctx=None):
     return out[0] if vec else out
 
 
-def _reduce_constraints_sparse(P, A, ln, ctx):
+def _reduce_constraints_sparse(P, A, ln, ctx, keep_on_device=False):
+    """keep_on_device (device labels only): the flat m * d device buffer the entry filled comes back as it is."""
     if ln != A.len:
         raise ValueError(f"A has {A.len} columns, P has {ln} entries")
     m, d = A.m, int(P.nparts)
@@ -966,6 +967,8 @@ def _reduce_constraints_sparse(P, A, ln, ctx):
         t_out = torch.empty(m * d, dtype=torch.float64, device=lab.device)
         ctx.wait_for(lab, t_out)
         ctx.check(ctx._lib.sdpsr_reduce_constraints_sparse(ctx._h, A._h, _ptr(lab), d, _ptr(t_out), mem))
+        if keep_on_device:
+            return t_out
         return t_out.cpu().numpy().reshape(m, d, order="F")
     out = np.zeros((m, d), order="F")
     ctx.check(ctx._lib.sdpsr_reduce_constraints_sparse(ctx._h, A._h, _ptr(lab), d, _ptr(out), mem))
@@ -1011,6 +1014,109 @@ def reduce_constraints_csr(P, A, ctx=None, index_base=0):
         ctx.check(ctx._lib.sdpsr_reduce_constraints_csr(ctx._h, ln, _ptr(lab), d, m, _ptr(rowptr), _ptr(colind), _ptr(val), 0,
                                                         _ptr(out), mem))
     return out[0] if vec else out
+
+
+def compress_constraints(newA, b=None, rtol=0.0, droptol=1e-8, ctx=None, return_info=False, m=None):
+    """The independent part of the reduced constraints ``newA * x = b``: an orthonormal basis of the row space of
+    ``[newA b]`` (docs/src/examples/ReduceAndSolveJuMP.jl:44-50: ``svd(Matrix(hcat(A * PMat, b))').U[:, 1:rank]'``, then
+    ``droptol!``; ``sdpsr_compress_constraints``).  Returns ``(newA2, newB2)`` of shapes r x d and r -- ``newA2`` alone when
+    ``b`` is None -- with r the number of singular values above ``rtol * sigma_1`` (``rtol = 0``: Julia's ``rank`` default
+    ``min(size) * eps``); row k belongs to the k-th largest singular value, is normalised, has its first entry of largest
+    magnitude positive, and its entries with ``|v| <= droptol`` are exactly 0.  ``return_info=True`` adds a dict with ``rank``,
+    ``sv`` (all m singular values, descending), ``nnz`` and ``passes``.
+
+    ``newA``: an m x d NumPy array, or a torch CUDA tensor -- m x d with column-major strides, or the flat ``m * d`` buffer the
+    sparse assembly fills (then ``m`` names the row count).  Device input is read where it lies and the result comes back as
+    device tensors; ``b`` is host data either way."""
+    ctx = _ctx(ctx)
+    lib = ctx._lib
+    bh = None if b is None else np.ascontiguousarray(np.asarray(b, dtype=np.float64).reshape(-1))
+    if _is_torch(newA):
+        import torch
+        if not newA.is_cuda or newA.dtype != torch.float64:
+            raise TypeError("a torch newA is a float64 CUDA tensor")
+        if newA.dim() == 1:
+            if m is None:
+                if bh is None:
+                    raise ValueError("a flat newA needs m (or b, whose length is m)")
+                m = bh.size
+            mm = int(m)
+            if mm < 0 or (mm == 0 and newA.numel()) or (mm and newA.numel() % mm):
+                raise ValueError(f"a flat newA of {newA.numel()} entries has no {mm} rows")
+            d = newA.numel() // mm if mm else 0
+            flat = newA.contiguous()
+        else:
+            if newA.dim() != 2:
+                raise ValueError("newA is a matrix")
+            mm, d = int(newA.shape[0]), int(newA.shape[1])
+            flat = newA.t().contiguous().view(-1)  # (no copy when newA has column-major strides)
+        mem = L.MEM_DEVICE
+    else:
+        A2 = np.asfortranarray(np.asarray(_dense(newA), dtype=np.float64))
+        if A2.ndim != 2:
+            raise ValueError("newA is a matrix")
+        mm, d = A2.shape
+        flat, mem = A2, L.MEM_HOST
+    if bh is not None and bh.size != mm:
+        raise ValueError(f"b has {bh.size} entries, newA has {mm} rows")
+    ncols = d + (bh is not None)
+    if mem == L.MEM_DEVICE:
+        import torch
+        out = torch.empty(mm * ncols, dtype=torch.float64, device=flat.device)
+        ctx.wait_for(flat, out)
+    else:
+        out = np.zeros((mm, ncols), order="F")
+    rank, nnz, passes = C.c_int64(0), C.c_int64(0), C.c_int32(0)
+    sv = np.zeros(mm)
+    ctx.check(lib.sdpsr_compress_constraints(ctx._h, mm, d, _ptr(flat) if mm * d else None, _ptr(bh), float(rtol), float(droptol),
+                                             _ptr(out) if mm * ncols else None, C.byref(rank), _ptr(sv), C.byref(nnz),
+                                             C.byref(passes), mem))
+    r = int(rank.value)
+    if mem == L.MEM_DEVICE:
+        M2 = out.view(ncols, mm).t()[:r]  # (the r x ncols view of the column-major buffer)
+    else:
+        M2 = out[:r]
+    res = M2 if bh is None else (M2[:, :d], M2[:, d])
+    if not return_info:
+        return res
+    info = {"rank": r, "sv": sv, "nnz": int(nnz.value), "passes": int(passes.value)}
+    return (res, info) if bh is None else res + (info,)
+
+
+def reduced_sdp(P, A, b, C_, compress=True, rtol=0.0, droptol=1e-8, ctx=None):
+    """The whole hand-over of docs/src/examples/ReduceAndSolveJuMP.jl:42-51 in one call: ``(newA, newB, newC)`` with
+    ``newC = C' * PMat`` and ``[newA newB]`` the independent rows of ``[A * PMat  b]`` (``compress_constraints``;
+    ``compress=False``: ``A * PMat`` and ``b`` as they are).  ``A`` decides the assembly: a ``SparseConstraints`` is read
+    where it lies, SciPy-sparse input or a ``(rowptr, colind, val)`` triple goes through ``reduce_constraints_csr``, a dense
+    array through ``reduce_constraints``; ``newC`` takes the same route.  With a ``SparseConstraints`` and device-resident
+    labels ``A * PMat`` stays on the device between the assembly and the compression, and ``newA`` / ``newB`` come back as
+    device tensors."""
+    ln = int(P.shape[0]) * int(P.shape[1])
+    bh = np.ascontiguousarray(np.asarray(b, dtype=np.float64).reshape(-1))
+    c = np.asarray(_dense(C_), dtype=np.float64).reshape(-1, order="F")
+    if isinstance(A, SparseConstraints):
+        cx = A.ctx if ctx is None else ctx
+        with SparseConstraints(c.reshape(1, -1), ln, ctx=cx) as Cs:
+            newC = _reduce_constraints_sparse(P, Cs, ln, cx)[0]
+        on_device = _is_torch(P.matrix)
+        newA = _reduce_constraints_sparse(P, A, ln, cx, keep_on_device=on_device)
+        m = A.m
+    elif isinstance(A, tuple) or hasattr(A, "tocsr"):
+        cx = _ctx(ctx)
+        newA, newC = reduce_constraints_csr(P, A, ctx=cx), reduce_constraints_csr(P, c, ctx=cx)
+        m = newA.shape[0]
+    else:
+        cx = _ctx(ctx)
+        newA, newC = reduce_constraints(P, A, ctx=cx), reduce_constraints(P, c, ctx=cx)
+        m = newA.shape[0]
+    if bh.size != m:
+        raise ValueError(f"b has {bh.size} entries, A has {m} rows")
+    if not compress:
+        if _is_torch(newA):
+            newA = newA.view(-1, m).t()
+        return newA, bh, newC
+    newA2, newB2 = compress_constraints(newA, bh, rtol=rtol, droptol=droptol, ctx=cx, m=m)
+    return newA2, newB2, newC
 
 
 def desymmetrize(P, ctx=None):

@@ -249,6 +249,7 @@ constexpr size_t PINNED_FIXED_BYTES = 1024;
 constexpr PinnedWords PINNED_BASIS_IMAGE_VERDICTS{64, 1};
 constexpr PinnedWords PINNED_SMALL_FLAG{0, 1};                   // c->pinned_small (256 B): the flag of the one-shot entries ("a label exceeds d", symmetry)
 constexpr PinnedWords PINNED_SMALL_LABEL_CHECK{2, 2};             // sdpsr_basis_image: [0] != 0 the caller's P is not symmetric, [1] != 0 a label exceeds d
+constexpr PinnedWords PINNED_SMALL_ROWSPACE_NNZ{4, 2};            // sdpsr_compress_constraints: the 64-bit count of non-zeros left in the kept rows
 constexpr PinnedWords PINNED_SMALL_DEFERRED_VERIFY{8, 1};        // sdpsr_jordan_reduce: the two verdicts the loop left unread (c->deferred_verdict)
 constexpr PinnedWords PINNED_SMALL_DEFERRED_SPECULATIVE{24, 1};
 constexpr PinnedWords PINNED_SMALL_DEFERRED_INITIAL{16, 1};       // ... and the one of the guessed initial partition (c->initial_guess_pending)
@@ -265,7 +266,7 @@ constexpr bool pinned_words_disjoint(std::initializer_list<PinnedWords> w, size_
 }
 static_assert(pinned_words_disjoint({PINNED_REFINE, PINNED_SYMMETRY, PINNED_BASIS_IMAGE_VERDICTS, PINNED_VERIFY, PINNED_SPECULATIVE, PINNED_BASIS_CONSTANT, PINNED_SAMPLE}, PINNED_FIXED_BYTES) &&
               PINNED_FIXED_BYTES % sizeof(double) == 0, "two reports share a word of c->pinned, or one reaches into the symmetry probe's doubles");
-static_assert(pinned_words_disjoint({PINNED_SMALL_FLAG, PINNED_SMALL_LABEL_CHECK, PINNED_SMALL_DEFERRED_VERIFY, PINNED_SMALL_DEFERRED_SPECULATIVE, PINNED_SMALL_DEFERRED_INITIAL, PINNED_SMALL_GRAM_STAMP, PINNED_SMALL_NARROW, PINNED_SMALL_CANON}, 256) &&
+static_assert(pinned_words_disjoint({PINNED_SMALL_FLAG, PINNED_SMALL_LABEL_CHECK, PINNED_SMALL_ROWSPACE_NNZ, PINNED_SMALL_DEFERRED_VERIFY, PINNED_SMALL_DEFERRED_SPECULATIVE, PINNED_SMALL_DEFERRED_INITIAL, PINNED_SMALL_GRAM_STAMP, PINNED_SMALL_NARROW, PINNED_SMALL_CANON}, 256) &&
               (PINNED_SMALL_CANON.first * 4) % 8 == 0 && PINNED_SMALL_CANON.count * 4 == sizeof(CanonVerdict), "two reports share a word of c->pinned_small");
 inline uint32_t* pinned_report(sdpsr_ctx* c, PinnedWords w) {  // the pinned words of one report (nullptr: no pinned buffer)
     uint32_t* p = (uint32_t*)ctx_pinned(c, PINNED_FIXED_BYTES);
@@ -425,6 +426,17 @@ void launch_csr_entry_labels(hipStream_t s, int64_t nnz, const uint32_t* col, co
 size_t csr_class_sums_carry_bytes(int64_t nnz);
 void launch_csr_class_sums(hipStream_t s, int64_t nnz, int64_t m, const int64_t* rowptr, const uint32_t* key_sorted,
                            const uint32_t* idx_sorted, const double* val, void* carry, double* out);
+// kernels_rowspace.hip / host_gram_jacobi.cpp: the row space of [newA | b] (rowspace.cpp, sdpsr_compress_constraints)
+double rowspace_scale(double max_abs);
+int rowspace_absmax_blocks(int64_t total);
+size_t rowspace_gram_partial_doubles(int64_t m, int64_t ncols);
+void launch_rowspace_scale(hipStream_t s, int64_t total, int64_t md, const double* A, const double* b, double* pmax, uint32_t* flag,
+                           double* W, double* info);
+void launch_rowspace_gram(hipStream_t s, int64_t m, int64_t ncols, const double* W, double* P, double* G);
+void launch_rowspace_rotate(hipStream_t s, int64_t m, int64_t ncols, const double* J, double* W);
+void launch_rowspace_finish(hipStream_t s, int64_t m, int64_t ncols, int64_t r, const double* W, const int32_t* perm,
+                            const double* sigma, double* sig, double droptol, double* out, unsigned long long* nnz);
+int64_t host_gram_jacobi(int m, double* G, double* J, double tau, double floor2, int max_sweeps, int* sweeps_out, double* max_rel_out);
 // complex.cpp, the complex path through the real embedding (the driver takes it for n > 64; any n >= 1 works).  cx_heev_general:
 // eigenpairs of the Hermitian H (device planes, ld = n) into Vr, Vi (device) and vals (ascending, host); eigenvalues of the
 // embedding within atol of each other are one cluster.  cx_block_norms_general: dnorms[sa * neig + sb] (device, zeroed by the

@@ -272,6 +272,20 @@ function reduce_constraints(P::HIPPartition, S::SparseConstraints)
     return out
 end
 
+# newA2, newB2 = compress_constraints(newA, b) in place of docs/src/examples/ReduceAndSolveJuMP.jl:44-50
+#   newConstraints = sparse(svd(Matrix(hcat(A * PMat, b))').U[:, 1:rank(newConstraints)]'); droptol!(newConstraints, 1e-8)
+# (sdpsr_compress_constraints): the r independent rows, by descending singular value.  WRITTEN BLIND like the rest of this file: never run.
+function compress_constraints(newA::Matrix{Float64}, b::Vector{Float64}; rtol=0.0, droptol=1e-8)
+    m, d = size(newA); @assert length(b) == m
+    out = Matrix{Float64}(undef, m, d + 1); sv = Vector{Float64}(undef, m); cx = ctx()
+    r = Ref{Int64}(0); nnz = Ref{Int64}(0); passes = Ref{Int32}(0)
+    check(cx, ccall((:sdpsr_compress_constraints, libsdpsr), Cint,
+                    (Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Float64, Float64, Ptr{Float64}, Ref{Int64}, Ptr{Float64},
+                     Ref{Int64}, Ref{Int32}, Cint),
+                    cx.handle, m, d, newA, b, Float64(rtol), Float64(droptol), out, r, sv, nnz, passes, MEM_HOST))
+    return out[1:r[], 1:d], out[1:r[], d + 1]
+end
+
 # ---- the whole reduction in ONE call (sdpsr_jordan_reduce): admissible_subspace + blockDiagonalize with the
 # partition staying on the device; the images are fetched with sdpsr_block_images once their size is known ----
 function jordan_reduce(C::AbstractVector{Float64}, A::AbstractMatrix{Float64}, b::AbstractVector{Float64};
