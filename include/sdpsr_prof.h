@@ -171,6 +171,49 @@ int sdpsr_profile_cx_irreducible(sdpsr_ctx* ctx, int route, int64_t n, int64_t v
                                  const double* Vr_host, const double* Vi_host, const int32_t* desc, int32_t ncols, double atol,
                                  double* Qhat_inout, int64_t guard);
 
+/* ---- The steps of the real dense blockDiagonalize on caller-made inputs (tests/test_gpu_dense_steps.py). ----
+   Conventions of the module-kernel entries above: column-major host arrays of doubles, every *_inout array uploaded as the caller filled it,
+   handed to the launcher or step eigdec.cpp itself calls, and downloaded whole, the `guard` elements (8 bytes each) behind it included.
+   SDPSR_BAD_ARGUMENT, before anything is uploaded, for: a null pointer (where none is allowed), a dimension < 1 or above its cap (orders,
+   leading dimensions, column and pair counts <= 4096; guard <= 2^20), a leading dimension smaller than its rows, a space_of entry outside
+   [0, neig), a descriptor or a column index that points outside its arrays. */
+
+/* The coupling matrix: norms[sa * neig + sb] = max(what was there, max |M[a, b]| over space_of[a] == sa, space_of[b] == sb), M = Q' A Q, as
+   bit patterns of non-negative doubles (norms_inout: neig * neig + guard, 1 <= neig <= n); an entry of M that is +-0 writes nothing.
+   Route 0: launch_small_qtaq_block_norms, n <= 64; A_host, Q_host: ld x n; M_inout, T_inout (ld * n + guard each; either may be null):
+   rows < n of the n columns receive M resp. T = A Q.  Route 1: EigDec::couple() on the driver's padded squares: ld a multiple of 128,
+   A_host, Q_host: ld x ld with whatever padding the caller made (the driver's is zero), M_inout, T_inout (ld * ld + guard, both needed):
+   all ld x ld of each are written.  Route 2: launch_block_norms alone on M_inout (ld x n, read only; A_host, Q_host, T_inout unused). */
+int sdpsr_profile_dense_block_norms(sdpsr_ctx* ctx, int route, int64_t n, int64_t ld, const double* A_host, const double* Q_host,
+                                    const int32_t* space_of, int32_t neig, double* norms_inout, double* M_inout, double* T_inout, int64_t guard);
+/* launch_small_cluster_qtaq_block_norms (n <= 64): the eigenvalues evals_host (n) are clustered -- a new eigenspace where !(|dv| <= atol) --
+   and the coupling matrix of Q' A Q over those eigenspaces is formed from a zero fill.  pack_inout: small_cluster_pack_bytes(n) bytes =
+   [einfo[0], einfo[1], 2 int32 untouched, neig, 11 int32 untouched][space_of: n int32, padded to a multiple of 64 bytes, padding untouched]
+   [evals: n doubles][norms: neig * neig written of n * n], then guard * 8 bytes.  T_inout: ld * n + guard or null. */
+int sdpsr_profile_dense_cluster_norms(sdpsr_ctx* ctx, int64_t n, int64_t ld, const double* A_host, const double* Q_host,
+                                      const double* evals_host, double atol, const int32_t* einfo, void* pack_inout, double* T_inout, int64_t guard);
+/* isomorphism_classes_device on the raw coupling matrix norms_inout (neig * neig + guard, [i * neig + j]; the upper triangle i <= j is read)
+   and the eigenspace dimensions dims_host (neig, each >= 1), for any 1 <= neig <= 4096.  Back come: the matrix symmetrised under the dimension
+   rule; stat_out[20]: [0] = ~bits(min), [1] = bits(max), [2 + c] = entries with exactly c edges <= them; edges_out[17] and *thr_out as the
+   host formed them; bits_inout (neig * W + guard words, W = ceil(neig / 64)): bit b of word [i * W + w] = pair (i, j = 64 w + b), j > i,
+   coupling >= threshold, every other bit of the neig * W words 0; kpart_out[neig]: the root of every eigenspace.  The step's own status,
+   SDPSR_OK or SDPSR_NUMERICAL_INCONSISTENCY, is returned with all outputs filled. */
+int sdpsr_profile_dense_classes(sdpsr_ctx* ctx, int32_t neig, double* norms_inout, const int32_t* dims_host, double atol, uint64_t* stat_out,
+                                double* edges_out, double* thr_out, uint64_t* bits_inout, int32_t* kpart_out, int64_t guard);
+/* The columns of Q-hat of npairs pair descriptors desc = {c_i, m_i, c_j, m_j, f_i, f_j, col} (the driver's 7 ints): column col of Qhat
+   (leading dimension n; Qhat_inout: n * ncols + guard) = Q_j (Q_j' b_i) / |Q_i' b_j|, Q_x = Q[:, c_x .. c_x + m_x), b_x = Bf[:, f_x];
+   Q_host: ldq x vcols, Bf_host: ldq x nf, n rows of each used; 1 <= m_x <= n.  Through Irreducible::launch_pairs(): route 0 = launch_irreducible_pairs
+   (refused when max (m_i + m_j) + 2 doubles exceed the 60 KiB of LDS the driver's rule allows), route 1 = the four launches per pair
+   (gemv_t twice, inv_norm, gemv_n_scaled), route -1 = the driver's rule chooses.  report[0] = the route that ran. */
+int sdpsr_profile_dense_irreducible(sdpsr_ctx* ctx, int route, int64_t n, int64_t ldq, int64_t vcols, const double* Q_host, const double* Bf_host,
+                                    int64_t nf, const int32_t* desc, int32_t npairs, double* Qhat_inout, int64_t ncols, int64_t guard,
+                                    int32_t* report);
+/* launch_copy_cols: dst[:, dst_cols[k]] = src[:, src_cols[k]] (n rows) for k < count, in launches of 128 columns.  src_host: ld_src x scols,
+   dst_inout: ld_dst * dcols + guard.  launch_clamptol: a[e] = +0.0 where |a[e]| < atol, e < len <= 4096^2 (a_inout: len + guard). */
+int sdpsr_profile_copy_cols(sdpsr_ctx* ctx, int64_t n, int64_t count, const int32_t* src_cols, const int32_t* dst_cols, const double* src_host,
+                            int64_t ld_src, int64_t scols, double* dst_inout, int64_t ld_dst, int64_t dcols, int64_t guard);
+int sdpsr_profile_clamptol(sdpsr_ctx* ctx, int64_t len, double* a_inout, double atol, int64_t guard);
+
 #ifdef __cplusplus
 }
 #endif

@@ -269,5 +269,18 @@ def load_prof_library():
     lib.sdpsr_profile_cx_block_norms.argtypes = [vp, C.c_int, i64, vp, vp, vp, vp, vp, C.c_int32, vp, i64]
     lib.sdpsr_profile_cx_irreducible.restype = C.c_int
     lib.sdpsr_profile_cx_irreducible.argtypes = [vp, C.c_int, i64, i64, vp, vp, vp, vp, vp, C.c_int32, f64, vp, i64]
+    # the steps of the real dense path on caller-made inputs (tests)
+    lib.sdpsr_profile_dense_block_norms.restype = C.c_int
+    lib.sdpsr_profile_dense_block_norms.argtypes = [vp, C.c_int, i64, i64, vp, vp, vp, C.c_int32, vp, vp, vp, i64]
+    lib.sdpsr_profile_dense_cluster_norms.restype = C.c_int
+    lib.sdpsr_profile_dense_cluster_norms.argtypes = [vp, i64, i64, vp, vp, vp, f64, vp, vp, vp, i64]
+    lib.sdpsr_profile_dense_classes.restype = C.c_int
+    lib.sdpsr_profile_dense_classes.argtypes = [vp, C.c_int32, vp, vp, f64, vp, vp, vp, vp, vp, i64]
+    lib.sdpsr_profile_dense_irreducible.restype = C.c_int
+    lib.sdpsr_profile_dense_irreducible.argtypes = [vp, C.c_int, i64, i64, i64, vp, vp, i64, vp, C.c_int32, vp, i64, i64, rep]
+    lib.sdpsr_profile_copy_cols.restype = C.c_int
+    lib.sdpsr_profile_copy_cols.argtypes = [vp, i64, i64, vp, vp, vp, i64, i64, vp, i64, i64, i64]
+    lib.sdpsr_profile_clamptol.restype = C.c_int
+    lib.sdpsr_profile_clamptol.argtypes = [vp, i64, vp, f64, i64]
     _prof = lib
     return lib

@@ -34,8 +34,9 @@ int isomorphism_classes(sdpsr_ctx* c, const std::vector<double>& norms, int neig
 // The same with the coupling matrix on the device (kernels_blockdiag.hip coupling_*): the matrix is symmetrised with the
 // dimension rule there, the host sees its extrema, the 18 counts and one bit per pair.  The union-find visits the
 // pairs in the reference's order (i, then j > i); a pair whose ends already share a root is a no-op there too.
+// `trace` (tests): the edges and the threshold the host formed on the way.
 int isomorphism_classes_device(sdpsr_ctx* c, unsigned long long* dnorms, int neig, const std::vector<int32_t>& dims, double atol,
-                               std::vector<int>& kpart) {
+                               std::vector<int>& kpart, CouplingTrace* trace) {
     hipStream_t s = c->stream;
     const int W = (neig + 63) / 64;
     int32_t* ddims = (int32_t*)ctx_buf(c, "bd_dims", (size_t)neig * 4);
@@ -61,6 +62,10 @@ int isomorphism_classes_device(sdpsr_ctx* c, unsigned long long* dnorms, int nei
     int64_t cnt[OTSU_NB + 2];
     for (int q = 0; q <= 17; ++q) cnt[q] = (int64_t)hs[2 + q];
     const double thr = otsu_pick(edges, cnt);
+    if (trace) {
+        memcpy(trace->edges, edges, sizeof(edges));
+        trace->thr = thr;
+    }
     launch_coupling_bits(s, neig, dnorms, thr, dbits);
     const unsigned long long* hb = (const unsigned long long*)ctx_pinned(c, (size_t)neig * W * 8);
     if (!hb) return ctx_fail(c, SDPSR_OUT_OF_MEMORY, "pinned staging");
@@ -238,11 +243,13 @@ int EigDec::cluster_on_host() {
 }
 
 // the coupling matrix of the element in Ap: block_norms accumulates maxima, so a further element can only raise it
-void EigDec::couple() {
+void couple_block_norms(hipStream_t s, int64_t n, int64_t ld, double* Ap, const double* Q, double* Tp, const int32_t* dspace, int neig,
+                        unsigned long long* dnorms) {
     launch_gemm_tn_f64(s, ld, ld, ld, Ap, ld, Q, ld, Tp, ld, 1, 0, 0, 0);  // T = A Q (A symmetric)
     launch_gemm_tn_f64(s, ld, ld, ld, Q, ld, Tp, ld, Ap, ld, 1, 0, 0, 0);  // M = Q' T  (into Ap)
     launch_block_norms(s, n, ld, Ap, dspace, neig, dnorms);
 }
+void EigDec::couple() { couple_block_norms(s, n, ld, Ap, Q, Tp, dspace, neig, dnorms); }
 
 // one more independent generic element raises the coupling matrix
 int EigDec::raise_coupling() {
@@ -353,7 +360,6 @@ struct Irreducible {
     int fresh_b(double* A3, double* F, int64_t nfp);
     void describe_pairs();
     int launch_pairs();
-    int pairs_one_by_one();
 };
 
 // classes -> block sizes, Q_hat's buffer, and the first eigenvector of every eigenspace that sits in a merged class -> F
@@ -431,19 +437,31 @@ void Irreducible::describe_pairs() {
     }
 }
 
-int Irreducible::launch_pairs() {
+// the pair kernel keeps w (m_j), c (m_i) and one scalar in LDS: it takes the pairs whose m_i + m_j + 2 doubles fit in 60 KiB
+bool irreducible_pairs_fit_lds(int64_t max_m2) { return !((size_t)(max_m2 + 2) * 8 > 60 * 1024); }
+
+int Irreducible::launch_pairs() { return irreducible_pairs(c, n, ld, Q, Bf, pairs, max_m2, Qhat, -1, nullptr); }
+
+// route -1: the pair kernel where its LDS allows, else one by one; 0 / 1 (tests) ask for one of the two; *ran = the route taken
+int irreducible_pairs(sdpsr_ctx* c, int64_t n, int64_t ld, const double* Q, const double* Bf, const std::vector<int32_t>& pairs,
+                      int64_t max_m2, double* Qhat, int route, int* ran) {
     if (pairs.empty()) return SDPSR_OK;
     int32_t* d_pairs = (int32_t*)ctx_buf(c, "bd_pairs", pairs.size() * 4);
     if (!d_pairs) return SDPSR_OUT_OF_MEMORY;
     const int st = h2d_sync(c, d_pairs, pairs.data(), pairs.size() * 4);
     if (st) return st;
-    if ((size_t)(max_m2 + 2) * 8 > 60 * 1024) return pairs_one_by_one();
-    launch_irreducible_pairs(s, n, ld, Q, Bf, (int)(pairs.size() / 7), (int)max_m2, d_pairs, Qhat);
+    const bool one_by_one = route < 0 ? !irreducible_pairs_fit_lds(max_m2) : route == 1;
+    if (ran) *ran = one_by_one ? 1 : 0;
+    if (one_by_one) return irreducible_pairs_one_by_one(c, n, ld, Q, Bf, pairs, Qhat);
+    if (!irreducible_pairs_fit_lds(max_m2)) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "irreducible pairs: eigenspaces too large for the pair kernel");
+    launch_irreducible_pairs(c->stream, n, ld, Q, Bf, (int)(pairs.size() / 7), (int)max_m2, d_pairs, Qhat);
     return SDPSR_OK;
 }
 
 // eigenspaces too large for the LDS of the pair kernel: four small launches per pair
-int Irreducible::pairs_one_by_one() {
+int irreducible_pairs_one_by_one(sdpsr_ctx* c, int64_t n, int64_t ld, const double* Q, const double* Bf, const std::vector<int32_t>& pairs,
+                                 double* Qhat) {
+    hipStream_t s = c->stream;
     double* wv = (double*)ctx_buf(c, "bd_wv", (size_t)n * 8);
     double* cv = (double*)ctx_buf(c, "bd_cv", (size_t)n * 8);
     double* inv = (double*)ctx_buf(c, "bd_inv", 64);

@@ -326,6 +326,22 @@ struct ElemGen {
 int make_element(sdpsr_ctx* c, const ElemGen* gen, int64_t n, int64_t ld, const uint32_t* L, double* dst);
 // iso_classes.h holds the host arithmetic (Otsu threshold, union-find, class structure, layouts); this adds the one error message
 int isomorphism_classes(sdpsr_ctx* c, const std::vector<double>& norms, int neig, double atol, std::vector<int>& kpart);
+// the same with the coupling matrix on the device (symmetrised in place there); trace: what the host formed on the way (tests)
+struct CouplingTrace {
+    double edges[17];
+    double thr;
+};
+int isomorphism_classes_device(sdpsr_ctx* c, unsigned long long* dnorms, int neig, const std::vector<int32_t>& dims, double atol,
+                               std::vector<int>& kpart, CouplingTrace* trace = nullptr);
+// EigDec::couple(): T = A Q into Tp, M = Q' T into Ap (all ld x ld, padded), then the block maxima of M raise dnorms
+void couple_block_norms(hipStream_t s, int64_t n, int64_t ld, double* Ap, const double* Q, double* Tp, const int32_t* dspace, int neig,
+                        unsigned long long* dnorms);
+// Irreducible::launch_pairs(): the columns of Q-hat of the 7-int pair descriptors, by the pair kernel or one by one
+bool irreducible_pairs_fit_lds(int64_t max_m2);
+int irreducible_pairs(sdpsr_ctx* c, int64_t n, int64_t ld, const double* Q, const double* Bf, const std::vector<int32_t>& pairs,
+                      int64_t max_m2, double* Qhat, int route = -1, int* ran = nullptr);
+int irreducible_pairs_one_by_one(sdpsr_ctx* c, int64_t n, int64_t ld, const double* Q, const double* Bf, const std::vector<int32_t>& pairs,
+                                 double* Qhat);
 int eigen_decomposition_device(sdpsr_ctx* c, int64_t n, const uint32_t* L, double atol, EigInfo& info, PhaseTimer& tm,
                                const ElemGen* gen = nullptr, int64_t expect_dim = -1);
 // status used internally when a driver of diagonalize hands over to the dense one

@@ -712,6 +712,211 @@ extern "C" int sdpsr_profile_cx_irreducible(sdpsr_ctx* c, int route, int64_t n, 
     return SDPSR_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// The steps of the real dense blockDiagonalize (eigdec.cpp; the kernels at the head of kernels_blockdiag.hip) on caller-made
+// inputs (tests/test_gpu_dense_steps.py), by the conventions of the entries above: column-major host arrays in, every *_inout
+// array uploaded as the caller filled it and downloaded whole, the launcher or step eigdec.cpp itself calls, nothing measured,
+// every argument that could index outside a buffer refused before any upload.
+// ---------------------------------------------------------------------------------------------------------------------------
+namespace {
+constexpr int64_t DS_MAX_N = 4096;
+bool ds_guard_ok(int64_t guard) { return guard >= 0 && guard <= MK_MAX_GUARD; }
+// upload / download of one in/out array of `count` 8-byte elements
+int ds_up(sdpsr_ctx* c, void* dev, const void* host, size_t count) {
+    HIP_TRY(c, hipMemcpyAsync(dev, host, count * 8, hipMemcpyHostToDevice, c->stream));
+    return SDPSR_OK;
+}
+int ds_down(sdpsr_ctx* c, void* host, const void* dev, size_t count) {
+    HIP_TRY(c, hipMemcpyAsync(host, dev, count * 8, hipMemcpyDeviceToHost, c->stream));
+    return SDPSR_OK;
+}
+int ds_finish(sdpsr_ctx* c) {
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    return SDPSR_OK;
+}
+}  // namespace
+
+extern "C" int sdpsr_profile_dense_block_norms(sdpsr_ctx* c, int route, int64_t n, int64_t ld, const double* A_host, const double* Q_host,
+                                               const int32_t* space_of, int32_t neig, double* norms_inout, double* M_inout, double* T_inout,
+                                               int64_t guard) {
+    CHECK_CTX(c);
+    if (route < 0 || route > 2 || n < 1 || n > DS_MAX_N || ld < n || ld > DS_MAX_N || !space_of || !norms_inout || neig < 1 || neig > n ||
+        !ds_guard_ok(guard))
+        return ctx_fail(c, SDPSR_BAD_ARGUMENT, "dense_block_norms: bad arguments");
+    if (route != 2 && (!A_host || !Q_host)) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "dense_block_norms: bad arguments");
+    if (route == 0 && n > 64) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "dense_block_norms: route 0 takes n <= 64");
+    if (route == 1 && (ld % 128 || !M_inout || !T_inout))
+        return ctx_fail(c, SDPSR_BAD_ARGUMENT, "dense_block_norms: route 1 works on padded ld x ld buffers, ld a multiple of 128");
+    if (route == 2 && !M_inout) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "dense_block_norms: route 2 reads M_inout");
+    for (int64_t a = 0; a < n; ++a)
+        if (space_of[a] < 0 || space_of[a] >= neig) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "dense_block_norms: space_of points outside the norms");
+    hipStream_t s = c->stream;
+    const int64_t cols = route == 1 ? ld : n;  // route 1: the padded squares of the driver
+    const size_t in = (size_t)ld * cols, mn = in + (size_t)guard, nn = (size_t)neig * neig + (size_t)guard;
+    double* A = route == 0 ? (double*)ctx_buf(c, "prof_ds_a", in * 8) : nullptr;
+    double* Q = route != 2 ? (double*)ctx_buf(c, "prof_ds_q", in * 8) : nullptr;
+    double* M = M_inout ? (double*)ctx_buf(c, "prof_ds_m", mn * 8) : nullptr;
+    double* T = T_inout ? (double*)ctx_buf(c, "prof_ds_t", mn * 8) : nullptr;
+    int32_t* dspace = (int32_t*)ctx_buf(c, "prof_ds_space", (size_t)n * 4);
+    unsigned long long* dnorms = (unsigned long long*)ctx_buf(c, "prof_ds_norms", nn * 8);
+    if ((route == 0 && !A) || (route != 2 && !Q) || (M_inout && !M) || (T_inout && !T) || !dspace || !dnorms) return SDPSR_OUT_OF_MEMORY;
+    int st = SDPSR_OK;
+    if (M) st = ds_up(c, M, M_inout, mn);
+    if (!st && T) st = ds_up(c, T, T_inout, mn);
+    if (!st && route == 0) st = ds_up(c, A, A_host, in);
+    if (!st && route == 1) st = ds_up(c, M, A_host, in);  // the driver's Ap: the element goes in, M = Q'AQ comes out
+    if (!st && route != 2) st = ds_up(c, Q, Q_host, in);
+    if (!st) st = ds_up(c, dnorms, norms_inout, nn);
+    if (st) return st;
+    HIP_TRY(c, hipMemcpyAsync(dspace, space_of, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    if (route == 0) launch_small_qtaq_block_norms(s, n, ld, A, Q, dspace, neig, dnorms, M, T);
+    else if (route == 1) couple_block_norms(s, n, ld, M, Q, T, dspace, neig, dnorms);
+    else launch_block_norms(s, n, ld, M, dspace, neig, dnorms);
+    if (M) st = ds_down(c, M_inout, M, mn);
+    if (!st && T) st = ds_down(c, T_inout, T, mn);
+    if (!st) st = ds_down(c, norms_inout, dnorms, nn);
+    return st ? st : ds_finish(c);
+}
+
+extern "C" int sdpsr_profile_dense_cluster_norms(sdpsr_ctx* c, int64_t n, int64_t ld, const double* A_host, const double* Q_host,
+                                                 const double* evals_host, double atol, const int32_t* einfo, void* pack_inout, double* T_inout,
+                                                 int64_t guard) {
+    CHECK_CTX(c);
+    if (!A_host || !Q_host || !evals_host || !einfo || !pack_inout || n < 1 || n > 64 || ld < n || ld > DS_MAX_N || !ds_guard_ok(guard))
+        return ctx_fail(c, SDPSR_BAD_ARGUMENT, "dense_cluster_norms: bad arguments");
+    hipStream_t s = c->stream;
+    const size_t in = (size_t)ld * n, tn = in + (size_t)guard, pn = small_cluster_pack_bytes(n) / 8 + (size_t)guard;
+    double* A = (double*)ctx_buf(c, "prof_ds_a", in * 8);
+    double* Q = (double*)ctx_buf(c, "prof_ds_q", in * 8);
+    double* T = T_inout ? (double*)ctx_buf(c, "prof_ds_t", tn * 8) : nullptr;
+    double* w = (double*)ctx_buf(c, "prof_ds_w", (size_t)n * 8);
+    int* dinfo = (int*)ctx_buf(c, "prof_ds_info", 64);
+    char* pack = (char*)ctx_buf(c, "prof_ds_pack", pn * 8);
+    if (!A || !Q || (T_inout && !T) || !w || !dinfo || !pack) return SDPSR_OUT_OF_MEMORY;
+    int st = ds_up(c, A, A_host, in);
+    if (!st) st = ds_up(c, Q, Q_host, in);
+    if (!st) st = ds_up(c, w, evals_host, (size_t)n);
+    if (!st) st = ds_up(c, dinfo, einfo, 1);
+    if (!st) st = ds_up(c, pack, pack_inout, pn);
+    if (!st && T) st = ds_up(c, T, T_inout, tn);
+    if (st) return st;
+    launch_small_cluster_qtaq_block_norms(s, n, ld, A, Q, w, atol, dinfo, pack, T);
+    st = ds_down(c, pack_inout, pack, pn);
+    if (!st && T) st = ds_down(c, T_inout, T, tn);
+    return st ? st : ds_finish(c);
+}
+
+extern "C" int sdpsr_profile_dense_classes(sdpsr_ctx* c, int32_t neig, double* norms_inout, const int32_t* dims_host, double atol,
+                                           uint64_t* stat_out, double* edges_out, double* thr_out, uint64_t* bits_inout, int32_t* kpart_out,
+                                           int64_t guard) {
+    CHECK_CTX(c);
+    if (!norms_inout || !dims_host || !stat_out || !edges_out || !thr_out || !bits_inout || !kpart_out || neig < 1 || neig > DS_MAX_N ||
+        !(atol > 0) || !ds_guard_ok(guard))
+        return ctx_fail(c, SDPSR_BAD_ARGUMENT, "dense_classes: bad arguments");
+    for (int32_t i = 0; i < neig; ++i)
+        if (dims_host[i] < 1) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "dense_classes: a dimension < 1");
+    const int W = (neig + 63) / 64;
+    const size_t nn = (size_t)neig * neig + (size_t)guard, bn = (size_t)neig * W + (size_t)guard;
+    unsigned long long* dnorms = (unsigned long long*)ctx_buf(c, "prof_ds_norms", nn * 8);
+    // the step's own buffers, sized with the guard: it asks for them by name and gets these
+    unsigned long long* dbits = (unsigned long long*)ctx_buf(c, "bd_cbits", bn * 8);
+    unsigned long long* stat = (unsigned long long*)ctx_buf(c, "bd_cstat", 32 * 8);
+    if (!dnorms || !dbits || !stat) return SDPSR_OUT_OF_MEMORY;
+    int st = ds_up(c, dnorms, norms_inout, nn);
+    if (!st) st = ds_up(c, dbits, bits_inout, bn);
+    if (st) return st;
+    const std::vector<int32_t> dims(dims_host, dims_host + neig);
+    std::vector<int> kpart;
+    CouplingTrace tr;
+    const int verdict = isomorphism_classes_device(c, dnorms, neig, dims, atol, kpart, &tr);
+    if (verdict != SDPSR_OK && verdict != SDPSR_NUMERICAL_INCONSISTENCY) return verdict;
+    st = ds_down(c, norms_inout, dnorms, nn);
+    if (!st) st = ds_down(c, bits_inout, dbits, bn);
+    if (!st) st = ds_down(c, stat_out, stat, 20);
+    if (!st) st = ds_finish(c);
+    if (st) return st;
+    memcpy(edges_out, tr.edges, sizeof(tr.edges));
+    *thr_out = tr.thr;
+    for (int32_t i = 0; i < neig; ++i) kpart_out[i] = kpart[i];
+    return verdict;
+}
+
+extern "C" int sdpsr_profile_dense_irreducible(sdpsr_ctx* c, int route, int64_t n, int64_t ldq, int64_t vcols, const double* Q_host,
+                                               const double* Bf_host, int64_t nf, const int32_t* desc, int32_t npairs, double* Qhat_inout,
+                                               int64_t ncols, int64_t guard, int32_t* report) {
+    CHECK_CTX(c);
+    if (!Q_host || !Bf_host || !desc || !Qhat_inout || !report || route < -1 || route > 1 || n < 1 || n > DS_MAX_N || ldq < n || ldq > DS_MAX_N ||
+        vcols < 1 || vcols > DS_MAX_N || nf < 1 || nf > DS_MAX_N || npairs < 1 || npairs > DS_MAX_N || ncols < 1 || ncols > DS_MAX_N ||
+        !ds_guard_ok(guard))
+        return ctx_fail(c, SDPSR_BAD_ARGUMENT, "dense_irreducible: bad arguments");
+    int64_t max_m2 = 0;
+    for (int32_t p = 0; p < npairs; ++p) {
+        const int32_t* d = desc + 7 * (size_t)p;
+        // (m_i, m_j <= n as for eigenspaces: the one-by-one route keeps Q_j' b_i and Q_i' b_j in n doubles each)
+        const bool ok = d[0] >= 0 && d[1] >= 1 && d[1] <= n && (int64_t)d[0] + d[1] <= vcols && d[2] >= 0 && d[3] >= 1 && d[3] <= n &&
+                        (int64_t)d[2] + d[3] <= vcols &&
+                        d[4] >= 0 && d[4] < nf && d[5] >= 0 && d[5] < nf && d[6] >= 0 && d[6] < ncols;
+        if (!ok) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "dense_irreducible: a descriptor points outside Q, B or Qhat");
+        max_m2 = std::max<int64_t>(max_m2, (int64_t)d[1] + d[3]);
+    }
+    if (route == 0 && !irreducible_pairs_fit_lds(max_m2))
+        return ctx_fail(c, SDPSR_BAD_ARGUMENT, "dense_irreducible: eigenspaces too large for the pair kernel");
+    const size_t qn = (size_t)ldq * vcols, bn = (size_t)ldq * nf, hn = (size_t)n * ncols + (size_t)guard;
+    double* Q = (double*)ctx_buf(c, "prof_ds_q", qn * 8);
+    double* Bf = (double*)ctx_buf(c, "prof_ds_a", bn * 8);
+    double* Qhat = (double*)ctx_buf(c, "prof_ds_m", hn * 8);
+    if (!Q || !Bf || !Qhat) return SDPSR_OUT_OF_MEMORY;
+    int st = ds_up(c, Q, Q_host, qn);
+    if (!st) st = ds_up(c, Bf, Bf_host, bn);
+    if (!st) st = ds_up(c, Qhat, Qhat_inout, hn);
+    if (st) return st;
+    const std::vector<int32_t> pairs(desc, desc + 7 * (size_t)npairs);
+    int ran = -1;
+    st = irreducible_pairs(c, n, ldq, Q, Bf, pairs, max_m2, Qhat, route, &ran);
+    if (st) return st;
+    st = ds_down(c, Qhat_inout, Qhat, hn);
+    if (!st) st = ds_finish(c);
+    if (!st) report[0] = ran;
+    return st;
+}
+
+extern "C" int sdpsr_profile_copy_cols(sdpsr_ctx* c, int64_t n, int64_t count, const int32_t* src_cols, const int32_t* dst_cols,
+                                       const double* src_host, int64_t ld_src, int64_t scols, double* dst_inout, int64_t ld_dst, int64_t dcols,
+                                       int64_t guard) {
+    CHECK_CTX(c);
+    if (!src_cols || !dst_cols || !src_host || !dst_inout || n < 1 || n > DS_MAX_N || count < 1 || count > DS_MAX_N || ld_src < n ||
+        ld_src > DS_MAX_N || ld_dst < n || ld_dst > DS_MAX_N || scols < 1 || scols > DS_MAX_N || dcols < 1 || dcols > DS_MAX_N || !ds_guard_ok(guard))
+        return ctx_fail(c, SDPSR_BAD_ARGUMENT, "copy_cols: bad arguments");
+    for (int64_t k = 0; k < count; ++k)
+        if (src_cols[k] < 0 || src_cols[k] >= scols || dst_cols[k] < 0 || dst_cols[k] >= dcols)
+            return ctx_fail(c, SDPSR_BAD_ARGUMENT, "copy_cols: a column outside its matrix");
+    const size_t sn = (size_t)ld_src * scols, dn = (size_t)ld_dst * dcols + (size_t)guard;
+    double* src = (double*)ctx_buf(c, "prof_ds_q", sn * 8);
+    double* dst = (double*)ctx_buf(c, "prof_ds_m", dn * 8);
+    if (!src || !dst) return SDPSR_OUT_OF_MEMORY;
+    int st = ds_up(c, src, src_host, sn);
+    if (!st) st = ds_up(c, dst, dst_inout, dn);
+    if (st) return st;
+    launch_copy_cols(c->stream, n, count, src_cols, dst_cols, src, ld_src, dst, ld_dst);
+    st = ds_down(c, dst_inout, dst, dn);
+    return st ? st : ds_finish(c);
+}
+
+extern "C" int sdpsr_profile_clamptol(sdpsr_ctx* c, int64_t len, double* a_inout, double atol, int64_t guard) {
+    CHECK_CTX(c);
+    if (!a_inout || len < 1 || len > DS_MAX_N * DS_MAX_N || !(atol >= 0) || !ds_guard_ok(guard))
+        return ctx_fail(c, SDPSR_BAD_ARGUMENT, "clamptol: bad arguments");
+    const size_t an = (size_t)len + (size_t)guard;
+    double* a = (double*)ctx_buf(c, "prof_ds_m", an * 8);
+    if (!a) return SDPSR_OUT_OF_MEMORY;
+    int st = ds_up(c, a, a_inout, an);
+    if (st) return st;
+    launch_clamptol(c->stream, len, a, atol);
+    st = ds_down(c, a_inout, a, an);
+    return st ? st : ds_finish(c);
+}
+
 extern "C" int sdpsr_profile_kernel(sdpsr_ctx* c, int kind, int64_t n, int64_t aux, int reps,
                                     double* ms_per_launch) {
     CHECK_CTX(c);

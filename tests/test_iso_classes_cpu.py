@@ -13,7 +13,8 @@ CSRC = os.path.join(ROOT, "sdpsymmetryreduction.jl_amd", "csrc")
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import sdpsr_oracle as O  # noqa: E402
 
-ATOL = 1e-9
+# the matrices and the restatement of the oracle's chain live with the references of the GPU test of the same steps
+from dense_steps_ref import ATOL, _expected_classes, _matrix_cases, _oracle_chain  # noqa: E402
 
 SRC = r'''
 #include <cstdio>
@@ -97,89 +98,6 @@ int main(int argc, char** argv) {
     return 0;
 }
 '''
-
-
-def _two_clusters(rng, dims, classes, lo=1e-7, hi=1.0):
-    """Raw coupling matrix of eigenspaces with the given dimensions: large (hi * U(0.5, 1.5)) inside a class -- also between
-    its eigenspaces of different dimension, which only the dimension rule separates --, small (lo * U(0.5, 1.5)) elsewhere; the
-    lower triangle is large throughout: only the upper one may be read."""
-    ne = len(dims)
-    M = lo * rng.uniform(0.5, 1.5, size=(ne, ne))
-    for i in range(ne):
-        for j in range(ne):
-            if classes[i] == classes[j]:
-                M[i, j] = hi * rng.uniform(0.5, 1.5)
-    M[np.tril_indices(ne, -1)] = hi * rng.uniform(0.5, 1.5, size=ne * (ne - 1) // 2)  # never read
-    return M
-
-
-def _matrix_cases():
-    """(name, dims, raw matrix): neig = 1, 2, 17, 300; two well-separated clusters; all values equal; values below atol; a
-    value equal to an edge; mixed dimensions; the inconsistent chain."""
-    rng = np.random.default_rng(5)
-    cases = [("one", [3], np.array([[1.0]])),  # (1.0: exact edges, as in `equal`)
-             ("two_merged", [1, 1], _two_clusters(rng, [1, 1], [0, 0])),
-             ("two_apart", [2, 2], _two_clusters(rng, [2, 2], [0, 1]))]
-    dims17 = [1, 2, 1, 3, 2, 1, 1, 2, 3, 1, 2, 1, 1, 3, 2, 1, 1]
-    cls17 = [i % 4 for i in range(17)]  # classes mix dimensions: the dimension rule zeroes entries and splits them
-    cases.append(("mixed17", dims17, _two_clusters(rng, dims17, cls17)))
-    cls300 = list(rng.integers(0, 40, size=300))
-    cases.append(("clusters300", [1] * 300, _two_clusters(rng, [1] * 300, cls300)))
-    # all values equal (1.0: log and exp are exact, every edge is 1.0): counts end in the last bin, every variance is 0 / 0,
-    # Julia's argmax returns the first NaN
-    cases.append(("equal", [1] * 5, np.ones((5, 5))))
-    # values below atol (and zeros, from the dimension rule): the minimum is clamped to atol; one value EQUAL to atol, the first
-    # edge, and the maximum equal to the last (exp(log(x)) may round to either side of x: both sides fall into the same bin, the
-    # first and the last respectively)
-    M = _two_clusters(rng, [1, 1, 2, 1, 1, 2], [0, 0, 1, 2, 2, 1], lo=1e-12)
-    M[0, 3] = ATOL
-    cases.append(("below_atol", [1, 1, 2, 1, 1, 2], M))
-    # the inconsistent chain: 0-3, 1-2, 2-3 coupled -> union by rank makes 1 the root of {0, 1, 2, 3}, whose first member is 0
-    M = 1e-7 * rng.uniform(0.5, 1.5, size=(5, 5))
-    for i, j in ((0, 3), (1, 2), (2, 3)):
-        M[i, j] = rng.uniform(0.5, 1.5)
-    M[np.arange(5), np.arange(5)] = rng.uniform(0.5, 1.5, size=5)
-    cases.append(("chain", [1] * 5, M))
-    return cases
-
-
-def _oracle_chain(dims, raw):
-    """The oracle's own steps on a raw matrix: the dimension rule (block_norms_inf's), log_histogram, otsu_threshold, the
-    merge order of isomorphism_partition, __isconsistent."""
-    ne = len(dims)
-    sym = np.zeros((ne, ne))
-    for i in range(ne):
-        for j in range(i, ne):
-            sym[i, j] = sym[j, i] = 0.0 if dims[i] != dims[j] else raw[i, j]
-    counts, edges = O.log_histogram(sym, 16, ATOL)
-    thr = O.otsu_threshold(sym, ATOL)
-    pdf = counts / counts.sum()  # the chosen bin, as otsu_threshold picks it
-    w, mu0 = np.cumsum(pdf), np.cumsum(np.log(edges[:-1]) * pdf)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        cand = ((mu0[-1] * w - mu0) ** 2 / (w * (1 - w)))[:-1]
-    best = int(np.nonzero(np.isnan(cand))[0][0]) if np.isnan(cand).any() else int(np.argmax(cand))
-    assert edges[best + 1] == thr
-    K = O.IntDisjointSets(ne)
-    for i in range(ne):
-        for j in range(i + 1, ne):
-            if sym[i, j] >= thr:
-                K.union(i, j)
-    return sym, counts, edges, best, thr, K
-
-
-def _expected_classes(K, expect):
-    kp = [K.find_root(i) for i in range(len(K))]
-    roots = list(dict.fromkeys(kp))
-    members = [[j for j, r in enumerate(kp) if r == i] for i in roots]
-    sizes = [len(m) for m in members]
-    S1, S, fd = sum(sizes), sum(s * s for s in sizes), sum(s * (s + 1) // 2 for s in sizes)
-    col = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(int)
-    off = np.concatenate([[0], np.cumsum([s * s for s in sizes])[:-1]]).astype(int)
-    da = [c + a for c, s in zip(col, sizes) for b in range(s) for a in range(s)]
-    db = [c + b for c, s in zip(col, sizes) for b in range(s) for a in range(s)]
-    return {"verdict": [int(O.is_consistent(K))], "kpart": kp, "roots": roots, "members": members, "sizes": sizes,
-            "sums": [S1, S, fd, len(roots)], "settled": [int(fd == expect), 0, 1, 1, 1],
-            "colsz": list(col) + sizes, "off": list(off), "laymax": [len(sizes), max(sizes)], "desc": da + db}
 
 
 def _parse(lines):
