@@ -145,7 +145,12 @@ enum {
     /* A/B: every host wait of the loop is a wait for the stream and every verdict is read where it arises (rounds 1-4) --
        no return on the label pass's report, no speculated confirm round, no verdicts deferred to the reduction's later
        waits (round 5).  Same partition, iterations, dimension trajectory and random draws either way. */
-    SDPSR_FLAG_WAIT_FOR_EVERY_VERDICT = 1u << 15
+    SDPSR_FLAG_WAIT_FOR_EVERY_VERDICT = 1u << 15,
+    /* A/B: the guessed-closed path of sdpsr_jordan_reduce never makes or reads the 8-bit shadow of its packed labels: every
+       pass streams the 32-bit labels.  By default a reduction that checks the recorded initial partition (<= 255 classes)
+       instead of rebuilding it narrows the packed labels to bytes once, and the pair check, the dot-product pass, the
+       channel gathers and the verify passes of that and the following restarts stream the bytes.  Same results bit for bit. */
+    SDPSR_FLAG_WIDE_LOOP_LABELS = 1u << 16
 };
 
 typedef struct sdpsr_opts {

@@ -79,6 +79,24 @@ int sdpsr_profile_verify_pair(sdpsr_ctx* ctx, int64_t n, int64_t d, const uint32
 /* Guessed initial partitions of ctx (restart 0) or of batch restart `restart` (as sdpsr_profile_loop_counts): out[0] = reductions that checked
    the recorded initial partition instead of rebuilding it, out[1] = of those, the ones whose check failed (reduction repeated). */
 int sdpsr_profile_initial_guess(sdpsr_ctx* ctx, int32_t restart, uint64_t* out);
+/* ... out[0] = launches that made the 8-bit shadow of the packed labels behind such a guess (once per recorded partition of <= 255 classes). */
+int sdpsr_profile_narrow_labels(sdpsr_ctx* ctx, int32_t restart, uint64_t* out);
+/* The four consumers of the loop's packed labels at either label width (tests/test_gpu_narrow_loop_labels.py).  width 32: the kernels stream
+   Lp_host as uploaded; width 8: the library's narrowing pass makes the byte copy on the device (a label > 255: SDPSR_BAD_ARGUMENT) and the
+   kernels stream that.  Everything else as the entries above.
+   gather_packed_w: plain and label-writing form of the packed channel gather (X_plain, X_writing: T * ld * ld bytes, 0x5A where no kernel
+   wrote; L_inout: n * n + guard words).
+   verify_w: r = -1 the channels alone, r = 0 .. 4 joint with the r basis matrices U_host (r * n * n) and coefficients coef_host (r).
+   proj_coef_lower: the dot-product pass <U_k, x> over the packed triangle, x drawn from the labels and key: partial_out (r * 2048, the
+   per-workgroup sums as stored) and coef_out (r), 1 <= r <= 4. */
+int sdpsr_profile_gather_packed_w(sdpsr_ctx* ctx, int64_t n, int T, int64_t d, uint64_t key, int width, const uint32_t* Lp_host, int8_t* X_plain,
+                                  int8_t* X_writing, uint32_t* L_inout, int64_t guard);
+int sdpsr_profile_verify_w(sdpsr_ctx* ctx, int64_t n, int T, int64_t d, int r, int width, const uint32_t* Lp_host, const uint32_t* first_idx_host,
+                           const int32_t* C_host, const double* U_host, const double* coef_host, uint64_t key, double atol, uint32_t* out);
+int sdpsr_profile_verify_pair_w(sdpsr_ctx* ctx, int64_t n, int64_t d, int width, const uint32_t* Lp_host, const uint32_t* first_idx_host,
+                                const double* a_host, const double* b_host, uint32_t* out);
+int sdpsr_profile_proj_coef_lower(sdpsr_ctx* ctx, int64_t n, int64_t r, uint64_t key, int width, const uint32_t* Lp_host, const double* U_host,
+                                  double* partial_out, double* coef_out);
 
 /* ---- The kernels of the module-compression driver on caller-made inputs (tests/test_gpu_module_kernels.py). ----
    All matrices are column-major host arrays of doubles; labels are n x n uint32, column-major.  Every *_inout array is uploaded as the caller

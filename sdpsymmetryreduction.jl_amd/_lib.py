@@ -37,6 +37,7 @@ FLAG_SYTRD_PANELS = 1 << 12
 FLAG_COUPLING_ON_HOST = 1 << 13
 FLAG_SYTRD_ONE_LAUNCH = 1 << 14
 FLAG_WAIT_FOR_EVERY_VERDICT = 1 << 15
+FLAG_WIDE_LOOP_LABELS = 1 << 16
 BASIS_IMAGE_KERNELS = {"auto": 0, "two_stage": 1, "outer": 2, "chunk": 3}
 # sdpsr_basis_image: *route
 BI_ROUTE_COMMUTATIVE, BI_ROUTE_BLOCKS, BI_ROUTE_TWO_STAGE, BI_ROUTE_OUTER, BI_ROUTE_CHUNK = 1, 2, 3, 4, 5
@@ -238,6 +239,17 @@ def load_prof_library():
     lib.sdpsr_profile_verify_pair.argtypes = [vp, i64, i64, vp, vp, vp, vp, C.POINTER(C.c_uint32)]
     lib.sdpsr_profile_initial_guess.restype = C.c_int
     lib.sdpsr_profile_initial_guess.argtypes = [vp, C.c_int32, C.POINTER(C.c_uint64)]
+    # the loop's label consumers at either label width (32, or 8: the shadow of the guessed-closed path)
+    lib.sdpsr_profile_narrow_labels.restype = C.c_int
+    lib.sdpsr_profile_narrow_labels.argtypes = [vp, C.c_int32, C.POINTER(C.c_uint64)]
+    lib.sdpsr_profile_gather_packed_w.restype = C.c_int
+    lib.sdpsr_profile_gather_packed_w.argtypes = [vp, i64, C.c_int, i64, C.c_uint64, C.c_int, vp, vp, vp, vp, i64]
+    lib.sdpsr_profile_verify_w.restype = C.c_int
+    lib.sdpsr_profile_verify_w.argtypes = [vp, i64, C.c_int, i64, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_uint64, C.c_double, C.POINTER(C.c_uint32)]
+    lib.sdpsr_profile_verify_pair_w.restype = C.c_int
+    lib.sdpsr_profile_verify_pair_w.argtypes = [vp, i64, i64, C.c_int, vp, vp, vp, vp, C.POINTER(C.c_uint32)]
+    lib.sdpsr_profile_proj_coef_lower.restype = C.c_int
+    lib.sdpsr_profile_proj_coef_lower.argtypes = [vp, i64, i64, C.c_uint64, C.c_int, vp, vp, vp, vp]
     # the module-compression kernels on caller-made inputs (tests)
     f64, rep = C.c_double, C.POINTER(C.c_int32)
     lib.sdpsr_profile_gram.restype = C.c_int

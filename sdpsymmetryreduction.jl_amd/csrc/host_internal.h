@@ -253,7 +253,8 @@ constexpr PinnedWords PINNED_SMALL_ROWSPACE_NNZ{4, 2};            // sdpsr_compr
 constexpr PinnedWords PINNED_SMALL_DEFERRED_VERIFY{8, 1};        // sdpsr_jordan_reduce: the two verdicts the loop left unread (c->deferred_verdict)
 constexpr PinnedWords PINNED_SMALL_DEFERRED_SPECULATIVE{24, 1};
 constexpr PinnedWords PINNED_SMALL_DEFERRED_INITIAL{16, 1};       // ... and the one of the guessed initial partition (c->initial_guess_pending)
-constexpr PinnedWords PINNED_SMALL_GRAM_STAMP{32, 1};            // module growth: the stamp behind a round's Gram products (compress.cpp, ortho_step)
+constexpr PinnedWords PINNED_SMALL_DEFERRED_NARROW{20, 1};        // ... != 0: a label did not fit the 8-bit shadow made behind that guess (read with it: "violated")
+constexpr PinnedWords PINNED_SMALL_GRAM_STAMP{32, 1};           // module growth: the stamp behind a round's Gram products (compress.cpp, ortho_step)
 constexpr PinnedWords PINNED_SMALL_CANON{44, 18};                // sdpsr_sparse_create: the nine 64-bit words of CanonVerdict (csr_canon.h)
 constexpr PinnedWords PINNED_SMALL_NARROW{40, 1};                // != 0: a label did not fit the narrow type (kernels_labels.hip); cleared by the host before each pass
 constexpr bool pinned_words_disjoint(std::initializer_list<PinnedWords> w, size_t bytes) {
@@ -266,11 +267,17 @@ constexpr bool pinned_words_disjoint(std::initializer_list<PinnedWords> w, size_
 }
 static_assert(pinned_words_disjoint({PINNED_REFINE, PINNED_SYMMETRY, PINNED_BASIS_IMAGE_VERDICTS, PINNED_VERIFY, PINNED_SPECULATIVE, PINNED_BASIS_CONSTANT, PINNED_SAMPLE}, PINNED_FIXED_BYTES) &&
               PINNED_FIXED_BYTES % sizeof(double) == 0, "two reports share a word of c->pinned, or one reaches into the symmetry probe's doubles");
-static_assert(pinned_words_disjoint({PINNED_SMALL_FLAG, PINNED_SMALL_LABEL_CHECK, PINNED_SMALL_ROWSPACE_NNZ, PINNED_SMALL_DEFERRED_VERIFY, PINNED_SMALL_DEFERRED_SPECULATIVE, PINNED_SMALL_DEFERRED_INITIAL, PINNED_SMALL_GRAM_STAMP, PINNED_SMALL_NARROW, PINNED_SMALL_CANON}, 256) &&
+static_assert(pinned_words_disjoint({PINNED_SMALL_FLAG, PINNED_SMALL_LABEL_CHECK, PINNED_SMALL_ROWSPACE_NNZ, PINNED_SMALL_DEFERRED_VERIFY, PINNED_SMALL_DEFERRED_SPECULATIVE, PINNED_SMALL_DEFERRED_INITIAL, PINNED_SMALL_DEFERRED_NARROW, PINNED_SMALL_GRAM_STAMP, PINNED_SMALL_NARROW, PINNED_SMALL_CANON}, 256) &&
               (PINNED_SMALL_CANON.first * 4) % 8 == 0 && PINNED_SMALL_CANON.count * 4 == sizeof(CanonVerdict), "two reports share a word of c->pinned_small");
 inline uint32_t* pinned_report(sdpsr_ctx* c, PinnedWords w) {  // the pinned words of one report (nullptr: no pinned buffer)
     uint32_t* p = (uint32_t*)ctx_pinned(c, PINNED_FIXED_BYTES);
     return p ? p + w.first : nullptr;
+}
+// The verdict of a guessed initial partition (c->initial_guess_pending), once the stream has been waited for: the pair check's word, and
+// the overflow word of the narrowing launch made behind that guess (cleared with the guess; it stays 0 where no shadow was made)
+inline uint32_t initial_guess_violated(const sdpsr_ctx* c) {
+    const volatile uint32_t* ps = c->pinned_small;
+    return ps[PINNED_SMALL_DEFERRED_INITIAL.first] | ps[PINNED_SMALL_DEFERRED_NARROW.first];
 }
 
 // canonical refinement of a signature source / array (primitives.cpp)

@@ -173,9 +173,11 @@ __device__ __forceinline__ void bytes_4x4_transpose(uint32_t a, uint32_t b, uint
 // unpack_symmetric_labels_kernel without its pass over Lp.  The lower tile is stored as read, the mirrored one through the SAME LDS tile in a phase
 // of its own before the channel bytes are staged (a second tile would halve the resident workgroups); diagonal tiles hold every entry of the tile
 // by symmetry and are stored whole.  Nothing is stored at or beyond row / column n.
-template <int T, bool WRITE_L>
+// LT: the element type of Lp -- uint32_t, or uint8_t for the loop's 8-bit shadow of labels <= 255 (a quarter of the label bytes; the
+// sentinel and Lfull stay 32-bit words).
+template <int T, bool WRITE_L, typename LT>
 __global__ void __launch_bounds__(256)
-gather_i8_sym_packed_kernel(int n, int64_t ld, const uint32_t* __restrict__ Lp, uint64_t key, int8_t* __restrict__ X, int dlut,
+gather_i8_sym_packed_kernel(int n, int64_t ld, const LT* __restrict__ Lp, uint64_t key, int8_t* __restrict__ X, int dlut,
                             uint32_t* __restrict__ Lfull) {
     __shared__ uint32_t lut[GATHER_LUT + 1];
     __shared__ uint32_t tile[64][65];  // [column][row]: channel bytes of element (i0 + row, j0 + column) (WRITE_L: its label first)
@@ -194,7 +196,7 @@ gather_i8_sym_packed_kernel(int n, int64_t ld, const uint32_t* __restrict__ Lp, 
         lab[q] = 0xFFFFFFFFu;
         if (i < n && j < n) {
             const int hi = i > j ? i : j, lo = i > j ? j : i;  // (diagonal tiles: the upper half by symmetry)
-            lab[q] = Lp[(int64_t)lo * n - (int64_t)lo * (lo - 1) / 2 + (hi - lo)];
+            lab[q] = (uint32_t)Lp[(int64_t)lo * n - (int64_t)lo * (lo - 1) / 2 + (hi - lo)];
         }
     }
     if (WRITE_L) {
@@ -249,14 +251,17 @@ gather_i8_sym_packed_kernel(int n, int64_t ld, const uint32_t* __restrict__ Lp, 
 }
 // Lfull != nullptr: the full n x n label matrix is written as well (leading dimension n)
 void launch_gather_i8_sym_packed(hipStream_t s, int64_t n, int64_t ld, int T, const uint32_t* Lp, uint64_t key, int8_t* X,
-                                 int64_t dmax, uint32_t* Lfull) {
+                                 int64_t dmax, uint32_t* Lfull, const uint8_t* Lp8) {
     const int dlut = (dmax > 0 && dmax <= GATHER_LUT) ? (int)dmax : 0;
     const unsigned t = (unsigned)(ld / 64);  // ld is a multiple of 128
     dim3 g(t, t);
-#define SDPSR_GATHER_PACKED_CASE(TT)                                                                                    \
-    case TT:                                                                                                            \
-        if (Lfull) gather_i8_sym_packed_kernel<TT, true><<<g, 256, 0, s>>>((int)n, ld, Lp, key, X, dlut, Lfull);        \
-        else gather_i8_sym_packed_kernel<TT, false><<<g, 256, 0, s>>>((int)n, ld, Lp, key, X, dlut, nullptr);           \
+    if (T == 1) Lp8 = nullptr;  // (one channel: the plain byte form has occupancy 6 against the wide form's 8; no guess runs with one channel)
+#define SDPSR_GATHER_PACKED_CASE(TT)                                                                                            \
+    case TT:                                                                                                                       \
+        if (Lp8 && Lfull) gather_i8_sym_packed_kernel<TT, true, uint8_t><<<g, 256, 0, s>>>((int)n, ld, Lp8, key, X, dlut, Lfull);  \
+        else if (Lp8) gather_i8_sym_packed_kernel<TT, false, uint8_t><<<g, 256, 0, s>>>((int)n, ld, Lp8, key, X, dlut, nullptr);   \
+        else if (Lfull) gather_i8_sym_packed_kernel<TT, true, uint32_t><<<g, 256, 0, s>>>((int)n, ld, Lp, key, X, dlut, Lfull);    \
+        else gather_i8_sym_packed_kernel<TT, false, uint32_t><<<g, 256, 0, s>>>((int)n, ld, Lp, key, X, dlut, nullptr);            \
         break;
     switch (T) {
         SDPSR_GATHER_PACKED_CASE(1)
@@ -509,7 +514,10 @@ __device__ __forceinline__ void packed_lower_ij(int n, int64_t e, uint32_t& i, u
 }
 
 // grid = (nblk, r): workgroups stride over the columns, threads over the rows i >= j of a column
-__global__ void proj_coef_lower_kernel(int n, const double* __restrict__ U, const uint32_t* __restrict__ L, int lab_packed,
+// LT: the labels' element type (uint8_t: the loop's 8-bit shadow of packed labels <= 255).  Only the loads differ: every thread adds the same
+// entries in the same order whatever the width, so partial and coef are bit for bit the same.
+template <typename LT>
+__global__ void proj_coef_lower_kernel(int n, const double* __restrict__ U, const LT* __restrict__ L, int lab_packed,
                                        uint64_t key, double* __restrict__ partial) {
     __shared__ double sh[8];
     const int k = blockIdx.y;
@@ -518,17 +526,17 @@ __global__ void proj_coef_lower_kernel(int n, const double* __restrict__ U, cons
     for (int j = blockIdx.x; j < n; j += gridDim.x) {
         const double* Uj = Uk + (int64_t)j * n;
         // labels: the full matrix, or its packed lower triangle (column j at offset j n - j (j - 1) / 2, rows j ..)
-        const uint32_t* Lj = lab_packed ? L + ((int64_t)j * n - (int64_t)j * (j - 1) / 2 - j) : L + (int64_t)j * n;
+        const LT* Lj = lab_packed ? L + ((int64_t)j * n - (int64_t)j * (j - 1) / 2 - j) : L + (int64_t)j * n;
         int i = j + threadIdx.x;
         for (; i + (int)blockDim.x < n; i += 2 * blockDim.x) {
             const double u0 = Uj[i], u1 = Uj[i + blockDim.x];
-            const uint32_t l0 = Lj[i], l1 = Lj[i + blockDim.x];
+            const uint32_t l0 = (uint32_t)Lj[i], l1 = (uint32_t)Lj[i + blockDim.x];
             const double x0 = l0 ? sdpsr_class_uniform(key, l0) : 0.0, x1 = l1 ? sdpsr_class_uniform(key, l1) : 0.0;
             a0 = fma(i == j ? u0 : 2.0 * u0, x0, a0);
             a1 = fma(2.0 * u1, x1, a1);
         }
         if (i < n) {
-            const uint32_t l0 = Lj[i];
+            const uint32_t l0 = (uint32_t)Lj[i];
             const double u0 = Uj[i], x0 = l0 ? sdpsr_class_uniform(key, l0) : 0.0;
             a0 = fma(i == j ? u0 : 2.0 * u0, x0, a0);
         }
@@ -536,11 +544,13 @@ __global__ void proj_coef_lower_kernel(int n, const double* __restrict__ U, cons
     const double r = block_reduce_sum(a0 + a1, sh);
     if (threadIdx.x == 0) partial[(int64_t)k * gridDim.x + blockIdx.x] = r;
 }
+// Lp8 (packed labels only): see sdpsr_internal.h
 void launch_proj_coef_lower(hipStream_t s, int64_t n, int64_t r, const double* U, const uint32_t* L, int lab_packed,
-                            uint64_t key, double* partial, int nblk, double* coef) {
+                            uint64_t key, double* partial, int nblk, double* coef, const uint8_t* Lp8) {
     if (r <= 0) return;
     dim3 g(nblk, (unsigned)r);
-    proj_coef_lower_kernel<<<g, 256, 0, s>>>((int)n, U, L, lab_packed, key, partial);
+    if (Lp8 && lab_packed) proj_coef_lower_kernel<uint8_t><<<g, 256, 0, s>>>((int)n, U, Lp8, 1, key, partial);
+    else proj_coef_lower_kernel<uint32_t><<<g, 256, 0, s>>>((int)n, U, L, lab_packed, key, partial);
     proj_coef_final_kernel<<<(unsigned)r, 256, 0, s>>>(nblk, partial, coef);
 }
 
@@ -2032,9 +2042,10 @@ __global__ void verify_ref_kernel(int n, int64_t ld, int d, const uint32_t* __re
 }
 // LDSREF (d <= VERIFY_LDS_CAP): the table is built here from first_idx (ref unused) and nobody zeroes flag[0] on the device -- a workgroup
 // could set the word before another one clears it: the launcher stores the 0 from the host before it enqueues the pass.
-template <int R, int T, bool JOINT, bool LDSREF>
+// LT: the element type of Lp (uint8_t: the loop's 8-bit shadow of labels <= 255, LDSREF only); the loads and the widening differ, nothing else.
+template <int R, int T, bool JOINT, bool LDSREF, typename LT = uint32_t>
 __global__ void __launch_bounds__(256)
-verify_lower_kernel(int n, int64_t ld, const uint32_t* __restrict__ Lp, const double* __restrict__ U, const double* __restrict__ coef,
+verify_lower_kernel(int n, int64_t ld, const LT* __restrict__ Lp, const double* __restrict__ U, const double* __restrict__ coef,
                     double atol, double scale, const int32_t* __restrict__ C, const VerifyRef* __restrict__ ref,
                     uint32_t* __restrict__ flag, int d, const uint32_t* __restrict__ first_idx, uint64_t key) {
     __shared__ VerifyRef sref[LDSREF ? VERIFY_LDS_CAP : 1];
@@ -2050,7 +2061,7 @@ verify_lower_kernel(int n, int64_t ld, const uint32_t* __restrict__ Lp, const do
     const int64_t nn = (int64_t)n * n;
     for (int j = blockIdx.x; j < n; j += gridDim.x) {
         const int64_t poff = (int64_t)j * n - (int64_t)j * (j - 1) / 2 - j;
-        const uint32_t* Lj = Lp + poff;
+        const LT* Lj = Lp + poff;
         const int32_t* Cj = C + (int64_t)j * ld;
         const double* Uj = U + (int64_t)j * n;
         // VB entries of a thread per trip: their labels and values in one batch of loads, then the representatives of their
@@ -2064,7 +2075,7 @@ verify_lower_kernel(int n, int64_t ld, const uint32_t* __restrict__ Lp, const do
             for (int b = 0; b < VB; ++b) {
                 const int i = i0 + 256 * b;
                 const bool ok = i < n;
-                l[b] = ok ? __builtin_nontemporal_load(&Lj[i]) : 0u;
+                l[b] = ok ? (uint32_t)__builtin_nontemporal_load(&Lj[i]) : 0u;
 #pragma unroll
                 for (int t = 0; t < T; ++t) c[b][t] = ok ? __builtin_nontemporal_load(&Cj[(int64_t)t * ld * ld + i]) : 0;
                 if (JOINT) {
@@ -2108,6 +2119,16 @@ static void launch_verify_rt(hipStream_t s, const SigSource& q, int64_t d, const
     const int g = n < 256 * 8 ? n : 256 * 8;
     if (d <= VERIFY_LDS_CAP) {
         *(volatile uint32_t*)flag = 0u;
+        // the labels' 8-bit shadow -- except in the two joint instances whose byte form needs 4 more VGPRs than a wave per SIMD allows
+        // (74 against 70, 97 against 93: occupancy 6 against 7 and 4 against 5): those keep the wide labels
+        constexpr bool byte_form = !(JOINT && T == 2 && (R == 2 || R == 4));
+        if constexpr (byte_form) {
+            if (q.L8 && d <= 255) {
+                verify_lower_kernel<R, T, JOINT, true, uint8_t><<<g, 256, 0, s>>>(n, q.ld, q.L8, q.U, q.coef, q.atol, q.scale, (const int32_t*)q.C,
+                                                                                 nullptr, flag, (int)d, first_idx, q.key);
+                return;
+            }
+        }
         verify_lower_kernel<R, T, JOINT, true><<<g, 256, 0, s>>>(n, q.ld, q.L, q.U, q.coef, q.atol, q.scale, (const int32_t*)q.C, nullptr, flag,
                                                                 (int)d, first_idx, q.key);
         return;
@@ -2228,8 +2249,10 @@ bool launch_basis_constant_on_classes(hipStream_t s, int64_t n, int64_t r, const
 // -- then the classes of the signatures ARE the classes of Lp, and the canonical numbering depends on the partition alone.  The signature
 // is the refinement's own (SrcPair::fetch / sig): -0.0, NaN payloads and equal hashes count as they do in the insert pass.  Layout as
 // uconst_check_kernel<R, true>; flag[0] cleared by the launcher.  (A representative outside the triangle or a label > d: violated.)
+// LT: the element type of Lp (uint8_t: the loop's 8-bit shadow of labels <= 255).
+template <typename LT>
 __global__ void __launch_bounds__(256)
-verify_pair_kernel(SrcPair src, const uint32_t* __restrict__ Lp, uint32_t* __restrict__ flag, int d, const uint32_t* __restrict__ first_idx) {
+verify_pair_kernel(SrcPair src, const LT* __restrict__ Lp, uint32_t* __restrict__ flag, int d, const uint32_t* __restrict__ first_idx) {
     __shared__ uint64_t sref[VERIFY_LDS_CAP];
     const int n = src.n;
     const int64_t np = (int64_t)n * (n + 1) / 2;
@@ -2254,7 +2277,7 @@ verify_pair_kernel(SrcPair src, const uint32_t* __restrict__ Lp, uint32_t* __res
     }
     for (int j = blockIdx.x; j < n; j += gridDim.x) {
         const int64_t poff = (int64_t)j * n - (int64_t)j * (j - 1) / 2 - j;
-        const uint32_t* Lj = Lp + poff;
+        const LT* Lj = Lp + poff;
         constexpr int VB = 4;  // entries per trip: labels and values first, then the classes' signatures (see verify_lower_kernel)
         for (int i0 = j + threadIdx.x; i0 < n; i0 += 256 * VB) {
             uint32_t l[VB];
@@ -2263,7 +2286,7 @@ verify_pair_kernel(SrcPair src, const uint32_t* __restrict__ Lp, uint32_t* __res
             for (int b = 0; b < VB; ++b) {
                 const int i = i0 + 256 * b;
                 const bool ok = i < n;
-                l[b] = ok ? __builtin_nontemporal_load(&Lj[i]) : 0u;
+                l[b] = ok ? (uint32_t)__builtin_nontemporal_load(&Lj[i]) : 0u;
                 v[b] = ok ? src.fetch((uint32_t)i, (uint32_t)j, poff + i) : SrcPair::Raw{0.0, 0.0};
             }
             uint64_t rc[VB];
@@ -2282,11 +2305,12 @@ verify_pair_kernel(SrcPair src, const uint32_t* __restrict__ Lp, uint32_t* __res
 // a, b: symmetric n x n, column-major (the lower triangle is read); Lp, first_idx: as above; flag: a word of pinned host memory whose last
 // verdict has been read (cleared from the host).  false: more classes than the one-launch form holds (nothing is enqueued)
 bool launch_verify_pair(hipStream_t s, int64_t n, const double* a, const double* b, const uint32_t* Lp, int64_t d, const uint32_t* first_idx,
-                        uint32_t* flag) {
+                        uint32_t* flag, const uint8_t* Lp8) {
     if (n < 1 || n >= (int64_t(1) << 31) || d < 1 || d > VERIFY_LDS_CAP) return false;
     const int g = n < 256 * 8 ? (int)n : 256 * 8;
     *(volatile uint32_t*)flag = 0u;
-    verify_pair_kernel<<<g, 256, 0, s>>>(SrcPair{a, b, (int)n, 1}, Lp, flag, (int)d, first_idx);
+    if (Lp8 && d <= 255) verify_pair_kernel<uint8_t><<<g, 256, 0, s>>>(SrcPair{a, b, (int)n, 1}, Lp8, flag, (int)d, first_idx);
+    else verify_pair_kernel<uint32_t><<<g, 256, 0, s>>>(SrcPair{a, b, (int)n, 1}, Lp, flag, (int)d, first_idx);
     return true;
 }
 

@@ -12,11 +12,14 @@ namespace {  // ---- the admissible_subspace loop, src/partitions.jl:145-185 ---
 // formed by the channel gather of a round that is expected not to refine (a confirm round, the speculative square of a guess): that kernel holds
 // every tile in both orientations anyway, and when the round's verdict is "unchanged" L is the call's output as it stands.  A refinement
 // invalidates it; the unpack pass forms it where no such gather ran (no confirm rounds), or whenever a step needs it (non-symmetric basis, other
-// square modes).  Only the methods below write the two validity bits.
+// square modes).  Only the methods below write the validity bits.
+// The guessed-closed path also keeps Lp8, a byte copy of Lp (labels <= 255), valid from the guess that made or found it until anything
+// refines: the streaming passes of that path read a quarter of the label bytes.  Lp stays the truth; the shadow never outlives it.
 class LoopLabels {
 public:
     uint32_t* L = nullptr;   // the full matrix (the call's output)
     uint32_t* Lp = nullptr;  // the packed lower triangle (integer modes)
+    uint8_t* Lp8 = nullptr;  // its 8-bit shadow ("adm_lpacked8"; nullptr: this call keeps none)
     int sym = 0;             // the labels are symmetric: by construction, or by the verdict of the last refine_full
     void init(sdpsr_ctx* ctx, int64_t order, uint32_t* symflag_dev, bool keep, bool early) { c = ctx, n = order, symflag = symflag_dev, keep_packed = keep, early_ok = early; }
     bool packed() const { return packed_valid; }
@@ -31,7 +34,11 @@ public:
         full_valid = true;
         return L;
     }
-    void packed_refined() { packed_valid = true, full_valid = false; }
+    void packed_refined() { packed_valid = true, full_valid = false, narrow_valid = false; }
+    // the shadow holds the packed labels (made by this call's narrowing launch, or recorded by the last call): right after the guess
+    void shadow_current() { narrow_valid = packed_valid && Lp8 != nullptr; }
+    bool narrow() const { return narrow_valid; }
+    const uint8_t* shadow(bool from_packed = true) const { return from_packed && packed_valid && narrow_valid ? Lp8 : nullptr; }
     // symmetric by construction: refine the n (n + 1) / 2 entries of the packed lower triangle (same relative order, same canonical numbering; in
     // place when the labels were packed); the full matrix is formed right away only where the loop does not keep packed labels (the joint iteration
     // runs with keep_packed alone: nothing to form there)
@@ -44,14 +51,14 @@ public:
     int refine_full(const SigSource& src, int64_t* d, bool with_symmetry_verdict) {
         if (with_symmetry_verdict) c->symflag_zero = false;  // (the check pass stores its verdict into symflag[0])
         const int st = with_symmetry_verdict ? refine_signatures(c, n * n, src, L, d, n, symflag, &sym) : refine_signatures(c, n * n, src, L, d);
-        full_valid = true, packed_valid = false;
+        full_valid = true, packed_valid = false, narrow_valid = false;
         return st;
     }
 private:
     sdpsr_ctx* c = nullptr;
     int64_t n = 0;
     uint32_t* symflag = nullptr;
-    bool keep_packed = false, early_ok = false, full_valid = true, packed_valid = false;
+    bool keep_packed = false, early_ok = false, full_valid = true, packed_valid = false, narrow_valid = false;
 };
 
 // Extra independent draws before a stall is believed: a round that did not refine spends one of the confirm rounds left and asks for another square
@@ -117,6 +124,7 @@ struct Loop {
     SigSource joint_source(bool from_packed) {
         SigSource q = proj_source(lab.current(from_packed), 1, from_packed ? 1 : 0);
         q.kind = proj_dead ? SIG_CHAN_I32 : SIG_JOINT_I32, q.ld = ld, q.T = T, q.C = Cp;
+        q.L8 = lab.shadow(from_packed);  // (the verify passes' label stream while the shadow is current; a refinement reads q.L)
         return q;
     }
     // The symmetric int8 square of a fresh random element of S: X from the packed or the full labels, X'X = X X on the lower-triangle tiles only (X
@@ -124,7 +132,7 @@ struct Loop {
     // write_full (packed labels only): the gather forms the full label matrix as well, unless it is current (LoopLabels).
     // gather_only: the product itself is a segment of the ctx's deferred tail (verify_round), enqueued and counted by flush_deferred_tail.
     void launch_square(bool from_packed, uint64_t key, void* X, void* C, int64_t dim, bool write_full = false, bool gather_only = false) {
-        if (from_packed) launch_gather_i8_sym_packed(s, n, ld, T, lab.Lp, key, (int8_t*)X, dim, write_full ? lab.full_from_gather() : nullptr);
+        if (from_packed) launch_gather_i8_sym_packed(s, n, ld, T, lab.Lp, key, (int8_t*)X, dim, write_full ? lab.full_from_gather() : nullptr, lab.shadow());
         else launch_gather_i8(s, n, ld, T, lab.L, key, (int8_t*)X, dim);
         if (gather_only) return;
         launch_gemm_tn_i8_sym(s, ld, ld, (const int8_t*)X, ld, (int32_t*)C, ld, T, ld * ld, ld * ld, zero_flag, c->num_cus, c->opts.square_kernel);
@@ -262,7 +270,7 @@ struct Loop {
         // (Round 3 measured this dot-product pass on the side stream BESIDE the channel gather and the int8 square -- two independent readers of the
         // same labels: theta_c32xk128 477 against 480 reductions/s in sequence, closed_scheme 1016 against 1028.  The square slows by what the
         // overlapped pass takes from it; kept in sequence.)
-        if (!proj_dead) launch_proj_coef_lower(s, n, r, dU, lab.current(jl), jl ? 1 : 0, key, partial, nblk, coef);
+        if (!proj_dead) launch_proj_coef_lower(s, n, r, dU, lab.current(jl), jl ? 1 : 0, key, partial, nblk, coef, lab.shadow(jl));
         tm.end();
         int64_t dj = current;
         bool confirming = false;  // this round repeats the square after a round that did not refine
@@ -411,12 +419,25 @@ struct Loop {
         // triangle, mirrored
         q.n = n, q.packed = 1, lab.sym = 1;
         initial_packed = true;
-        if (guess && launch_verify_pair(s, n, dCL, dX0, lab.Lp, guess->d0, guess->first, c->pinned_small + PINNED_SMALL_DEFERRED_INITIAL.first)) {
+        // The labels' 8-bit shadow (lab.Lp8 set: this call keeps one) is made here once, in front of the first pass that streams it, unless
+        // the record says that it is there already.  Its overflow word is nobody's to wait for -- d0 <= 255 says that every label fits --
+        // and is read with the guess's verdict (initial_guess_violated), as "violated".
+        const uint8_t* Lp8 = guess ? lab.Lp8 : nullptr;
+        if (guess) {
+            uint32_t* over = c->pinned_small + PINNED_SMALL_DEFERRED_NARROW.first;
+            *(volatile uint32_t*)over = 0u;
+            if (Lp8 && !(guess->narrow && guess->Lp8 == Lp8)) {
+                launch_labels_narrow(s, n * (n + 1) / 2, lab.Lp, lab.Lp8, 8, over, c->num_cus);
+                ++c->label_narrowings;
+            }
+        }
+        if (guess && launch_verify_pair(s, n, dCL, dX0, lab.Lp, guess->d0, guess->first, c->pinned_small + PINNED_SMALL_DEFERRED_INITIAL.first, Lp8)) {
             c->initial_guess_pending = true;
             ++c->initial_guesses;
             HIP_TRY(c, hipGetLastError());
             *d = guess->d0;
             lab.packed_refined();
+            lab.shadow_current();
             // (the hint a refinement that found d0 classes leaves, primitives.cpp; first_idx_labels is Lp already)
             const int full = std::max(12, ceil_log2((uint64_t)(n * (n + 1) / 2) * 2));
             c->table_log2_hint = std::min(full, std::max(12, ceil_log2((uint64_t)guess->d0 * 8 + 1)));
@@ -430,7 +451,7 @@ struct Loop {
         if (!c->initial_guess_pending) return SDPSR_OK;
         HIP_TRY(c, ctx_sync_stream(c, s));
         HIP_TRY(c, hipGetLastError());
-        if (((const volatile uint32_t*)c->pinned_small)[PINNED_SMALL_DEFERRED_INITIAL.first] != 0) return STATUS_REPEAT_REDUCTION;
+        if (initial_guess_violated(c) != 0) return STATUS_REPEAT_REDUCTION;
         c->initial_guess_pending = false;
         return SDPSR_OK;
     }
@@ -454,7 +475,7 @@ struct Loop {
 
 namespace sdpsr {
 // The deferred tail's segments, in order, on the ctx's stream; squares are counted here, where they are enqueued.  A segment reads
-// "adm_xi8" / "adm_xi8_spec" (its gathered element), "adm_lpacked" and "ref_first" (labels and class representatives), "proj_coef" and
+// "adm_xi8" / "adm_xi8_spec" (its gathered element), "adm_lpacked" or its shadow "adm_lpacked8" and "ref_first" (labels and class representatives), "proj_coef" and
 // the caller's U (joint verify), "adm_symflag" (the constant zero); it writes "adm_ci32" / "adm_ci32_spec", "adm_vref" / "adm_vref2"
 // and its verdict word.  Whoever enqueues work of its own while segments are pending must touch none of these -- in particular run no
 // refinement (refine_signatures rewrites "ref_first") and request none of these buffers with another size (ctx_buf would free them).
@@ -528,6 +549,14 @@ int admissible_subspace_impl(sdpsr_ctx* c, int64_t n, const double* CL, const do
     const bool guess_initial = c->allow_deferred_verdict && c->pinned_small && lp.early_ok && c->predict_closed && c->predict_n == n && (hint & 2) && first_joint &&
                                rec.valid && rec.n == n && rec.Lp == lp.lab.Lp && rec.sym == 1 && rec.d0 >= 1 && rec.d0 <= (int64_t)verify_lds_cap() &&
                                c->first_idx_labels == lp.lab.Lp && rec.first == (const uint32_t*)ctx_buf(c, "ref_first", (size_t)refine_first_cap() * 4);
+    if (dbg_on() && c->allow_deferred_verdict && !guess_initial)
+        fprintf(stderr, "[sdpsr] loop: initial partition not guessed (predicted closed %d at n %lld, hint %d, joint first iteration %d, record %d: n %lld, d0 %lld, "
+                        "labels %d, representatives of them %d)\n", (int)c->predict_closed, (long long)c->predict_n, hint, (int)first_joint, (int)rec.valid,
+                (long long)rec.n, (long long)rec.d0, (int)(rec.Lp == lp.lab.Lp), (int)(c->first_idx_labels == lp.lab.Lp));
+    // ... and such a call streams the labels' 8-bit shadow where every label fits a byte (a record of 256 classes takes the guess with the wide
+    // labels; SDPSR_FLAG_WIDE_LOOP_LABELS: never).  No buffer: the wide labels.
+    if (guess_initial && rec.d0 <= 255 && !(c->opts.flags & SDPSR_FLAG_WIDE_LOOP_LABELS))
+        lp.lab.Lp8 = (uint8_t*)ctx_buf(c, "adm_lpacked8", (size_t)(n * (n + 1) / 2));
     int64_t d = 0;
     tm.begin(SDPSR_T_REFINE);
     st = lp.initial_partition(dCL, dX0, hint, guess_initial ? &rec : nullptr, &d);
@@ -573,6 +602,7 @@ int admissible_subspace_impl(sdpsr_ctx* c, int64_t n, const double* CL, const do
         InitialRecord& ir = c->initial_record;
         ir.first = (const uint32_t*)ctx_buf(c, "ref_first", (size_t)refine_first_cap() * 4);  // (before `valid`: ctx_buf drops the record of a buffer it replaces)
         ir.n = n, ir.d0 = c->adm_dims[0], ir.Lp = lp.lab.Lp, ir.sym = lp.lab.sym;
+        ir.narrow = lp.lab.narrow(), ir.Lp8 = ir.narrow ? lp.lab.Lp8 : nullptr;  // (the shadow, where the call ends with a current one)
         ir.valid = ir.first != nullptr;
     }
     *dim_out = lp.current;

@@ -296,6 +296,165 @@ extern "C" int sdpsr_profile_initial_guess(sdpsr_ctx* c, int32_t restart, uint64
     return SDPSR_OK;
 }
 
+extern "C" int sdpsr_profile_narrow_labels(sdpsr_ctx* c, int32_t restart, uint64_t* out) {
+    CHECK_CTX(c);
+    if (!out || restart < 0 || restart > (int32_t)c->batch_children.size()) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "bad arguments");
+    out[0] = (restart == 0 ? c : c->batch_children[restart - 1])->label_narrowings;
+    return SDPSR_OK;
+}
+
+// ---- the consumers of the loop's packed labels at either label width (tests/test_gpu_narrow_loop_labels.py) ----
+namespace {
+// width 8: *Lp8 = the byte copy of the np packed labels Lp (device), made by the library's own narrowing pass; width 32: nullptr.  d: the
+// labels' bound (the byte forms take <= 255 classes)
+int prof_label_shadow(sdpsr_ctx* c, const uint32_t* Lp, int64_t np, int64_t d, int width, const uint8_t** Lp8) {
+    *Lp8 = nullptr;
+    if (width == 32) return SDPSR_OK;
+    if (width != 8 || d > 255) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "label width: 32, or 8 with at most 255 classes");
+    uint8_t* p = (uint8_t*)ctx_buf(c, "prof_lp8", (size_t)np);
+    if (!p || !c->pinned_small) return SDPSR_OUT_OF_MEMORY;
+    uint32_t* over = c->pinned_small + PINNED_SMALL_NARROW.first;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));  // (the labels' upload; nothing in flight on the word)
+    *(volatile uint32_t*)over = 0u;
+    launch_labels_narrow(c->stream, np, Lp, p, 8, over, c->num_cus);
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    if (*(volatile uint32_t*)over != 0) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "a label does not fit 8 bits");
+    *Lp8 = p;
+    return SDPSR_OK;
+}
+}  // namespace
+
+extern "C" int sdpsr_profile_gather_packed_w(sdpsr_ctx* c, int64_t n, int T, int64_t d, uint64_t key, int width, const uint32_t* Lp_host,
+                                             int8_t* X_plain, int8_t* X_writing, uint32_t* L_inout, int64_t guard) {
+    CHECK_CTX(c);
+    if (!Lp_host || !X_plain || !X_writing || !L_inout || n < 1 || n > 8192 || d < 0 || guard < 0 || (T != 1 && T != 2 && T != 4))
+        return ctx_fail(c, SDPSR_BAD_ARGUMENT, "bad arguments");
+    hipStream_t s = c->stream;
+    const int64_t ld = round_up(n, 128), np = n * (n + 1) / 2;
+    const size_t xb = (size_t)T * ld * ld;
+    uint32_t* Lp = (uint32_t*)ctx_buf(c, "prof_lp", (size_t)np * 4);
+    uint32_t* Lw = (uint32_t*)ctx_buf(c, "prof_lwritten", (size_t)(n * n + guard) * 4);
+    int8_t* X = (int8_t*)ctx_buf(c, "prof_gx", 2 * xb);
+    if (!Lp || !Lw || !X) return SDPSR_OUT_OF_MEMORY;
+    HIP_TRY(c, hipMemcpyAsync(Lp, Lp_host, (size_t)np * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(Lw, L_inout, (size_t)(n * n + guard) * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemsetAsync(X, 0x5A, 2 * xb, s));
+    const uint8_t* Lp8 = nullptr;
+    const int st = prof_label_shadow(c, Lp, np, d, width, &Lp8);
+    if (st) return st;
+    launch_gather_i8_sym_packed(s, n, ld, T, Lp, key, X, d, nullptr, Lp8);
+    launch_gather_i8_sym_packed(s, n, ld, T, Lp, key, X + xb, d, Lw, Lp8);
+    HIP_TRY(c, hipMemcpyAsync(X_plain, X, xb, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(X_writing, X + xb, xb, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(L_inout, Lw, (size_t)(n * n + guard) * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, hipGetLastError());
+    return SDPSR_OK;
+}
+
+extern "C" int sdpsr_profile_verify_w(sdpsr_ctx* c, int64_t n, int T, int64_t d, int r, int width, const uint32_t* Lp_host,
+                                      const uint32_t* first_idx_host, const int32_t* C_host, const double* U_host, const double* coef_host,
+                                      uint64_t key, double atol, uint32_t* out) {
+    CHECK_CTX(c);
+    if (!Lp_host || !first_idx_host || !C_host || !out || n < 1 || n > 8192 || d < 1 || d > (int64_t)refine_first_cap() || r < -1 || r > 4 ||
+        (T != 2 && T != 4) || (r > 0 && (!U_host || !coef_host)) || !(atol > 0))
+        return ctx_fail(c, SDPSR_BAD_ARGUMENT, "bad arguments");
+    const int64_t ld = round_up(n, 128), np = n * (n + 1) / 2, rr = r > 0 ? r : 0;
+    for (int64_t k = 0; k < d; ++k)
+        if ((int64_t)first_idx_host[k] >= np) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "a representative outside the packed triangle");
+    hipStream_t s = c->stream;
+    const size_t cb = (size_t)T * ld * ld * 4;
+    uint32_t* Lp = (uint32_t*)ctx_buf(c, "prof_lp", (size_t)np * 4);
+    uint32_t* first = (uint32_t*)ctx_buf(c, "prof_first", (size_t)d * 4);
+    int32_t* Cd = (int32_t*)ctx_buf(c, "prof_vc", cb);
+    double* Ud = (double*)ctx_buf(c, "prof_vu", (size_t)(n * n + 1) * 4 * 8);  // + the coefficients
+    void* ref = ctx_buf(c, "prof_vref", std::max(verify_ref_bytes(d), uconst_ref_bytes(d, 1)));
+    uint32_t* hv = pinned_report(c, PINNED_VERIFY);
+    if (!Lp || !first || !Cd || !Ud || !ref || !hv) return SDPSR_OUT_OF_MEMORY;
+    double* coef = Ud + 4 * n * n;
+    HIP_TRY(c, hipMemcpyAsync(Lp, Lp_host, (size_t)np * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(first, first_idx_host, (size_t)d * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(Cd, C_host, cb, hipMemcpyHostToDevice, s));
+    if (rr > 0) {
+        HIP_TRY(c, hipMemcpyAsync(Ud, U_host, (size_t)rr * n * n * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(coef, coef_host, (size_t)rr * 8, hipMemcpyHostToDevice, s));
+    }
+    HIP_TRY(c, hipStreamSynchronize(s));  // (nothing may be in flight on the verdict word)
+    const uint8_t* Lp8 = nullptr;
+    const int st = prof_label_shadow(c, Lp, np, d, width, &Lp8);
+    if (st) return st;
+    hv[0] = 0xDEADu;
+    SigSource q;
+    q.kind = r >= 0 ? SIG_JOINT_I32 : SIG_CHAN_I32, q.U = Ud, q.coef = coef, q.r = (int)rr, q.key = key, q.atol = atol, q.scale = round_scale(c, atol);
+    q.n = n, q.ld = ld, q.T = T, q.C = Cd, q.L = Lp, q.L8 = Lp8, q.packed = 1, q.lab_packed = 1;
+    const bool ran = launch_verify_no_split(s, q, d, first, ref, hv);
+    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, hipGetLastError());
+    if (!ran) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "no verify pass for this shape");
+    out[0] = ((const volatile uint32_t*)hv)[0];
+    out[1] = (uint32_t)verify_lds_cap();
+    return SDPSR_OK;
+}
+
+extern "C" int sdpsr_profile_verify_pair_w(sdpsr_ctx* c, int64_t n, int64_t d, int width, const uint32_t* Lp_host, const uint32_t* first_idx_host,
+                                           const double* a_host, const double* b_host, uint32_t* out) {
+    CHECK_CTX(c);
+    if (!Lp_host || !first_idx_host || !a_host || !b_host || !out || n < 1 || n > 8192 || d < 1 || d > (int64_t)verify_lds_cap())
+        return ctx_fail(c, SDPSR_BAD_ARGUMENT, "bad arguments");
+    const int64_t np = n * (n + 1) / 2;
+    for (int64_t k = 0; k < d; ++k)
+        if ((int64_t)first_idx_host[k] >= np) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "a representative outside the packed triangle");
+    hipStream_t s = c->stream;
+    uint32_t* Lp = (uint32_t*)ctx_buf(c, "prof_lp", (size_t)np * 4);
+    uint32_t* first = (uint32_t*)ctx_buf(c, "prof_first", (size_t)d * 4);
+    double* ab = (double*)ctx_buf(c, "prof_pair_ab", (size_t)2 * n * n * 8);
+    uint32_t* hv = pinned_report(c, PINNED_VERIFY);
+    if (!Lp || !first || !ab || !hv) return SDPSR_OUT_OF_MEMORY;
+    HIP_TRY(c, hipMemcpyAsync(Lp, Lp_host, (size_t)np * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(first, first_idx_host, (size_t)d * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(ab, a_host, (size_t)n * n * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(ab + n * n, b_host, (size_t)n * n * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipStreamSynchronize(s));  // (nothing may be in flight on the verdict word)
+    const uint8_t* Lp8 = nullptr;
+    const int st = prof_label_shadow(c, Lp, np, d, width, &Lp8);
+    if (st) return st;
+    hv[0] = 0xDEADu;
+    const bool ran = launch_verify_pair(s, n, ab, ab + n * n, Lp, d, first, hv, Lp8);
+    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, hipGetLastError());
+    if (!ran) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "no pair check for this shape");
+    out[0] = ((const volatile uint32_t*)hv)[0];
+    out[1] = (uint32_t)verify_lds_cap();
+    return SDPSR_OK;
+}
+
+extern "C" int sdpsr_profile_proj_coef_lower(sdpsr_ctx* c, int64_t n, int64_t r, uint64_t key, int width, const uint32_t* Lp_host,
+                                             const double* U_host, double* partial_out, double* coef_out) {
+    CHECK_CTX(c);
+    if (!Lp_host || !U_host || !partial_out || !coef_out || n < 1 || n > 8192 || r < 1 || r > 4) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "bad arguments");
+    constexpr int nblk = 2048;  // the loop's (loop.cpp)
+    hipStream_t s = c->stream;
+    const int64_t np = n * (n + 1) / 2;
+    uint32_t* Lp = (uint32_t*)ctx_buf(c, "prof_lp", (size_t)np * 4);
+    double* Ud = (double*)ctx_buf(c, "prof_vu", (size_t)(n * n + 1) * 4 * 8);
+    double* partial = (double*)ctx_buf(c, "prof_partial", (size_t)(r * nblk + r) * 8);
+    if (!Lp || !Ud || !partial) return SDPSR_OUT_OF_MEMORY;
+    double* coef = partial + r * nblk;
+    HIP_TRY(c, hipMemcpyAsync(Lp, Lp_host, (size_t)np * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(Ud, U_host, (size_t)r * n * n * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemsetAsync(partial, 0xFF, (size_t)(r * nblk + r) * 8, s));
+    const uint8_t* Lp8 = nullptr;
+    const int st = prof_label_shadow(c, Lp, np, 0, width, &Lp8);  // (the narrowing pass itself refuses a label above 255)
+    if (st) return st;
+    launch_proj_coef_lower(s, n, r, Ud, Lp, 1, key, partial, nblk, coef, Lp8);
+    HIP_TRY(c, hipMemcpyAsync(partial_out, partial, (size_t)r * nblk * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(coef_out, coef, (size_t)r * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, hipGetLastError());
+    return SDPSR_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------
 // The kernels of the module-compression driver on caller-made inputs (tests/test_gpu_module_kernels.py): host arrays in, the
 // product's own launcher called the way compress.cpp calls it, everything back.  Every output array is in/out: uploaded as the

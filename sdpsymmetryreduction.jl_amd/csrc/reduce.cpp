@@ -80,7 +80,7 @@ int jordan_reduce_impl(sdpsr_ctx* c, int64_t n, const double* CL, const double* 
         c->deferred_verdict = false;
         flush_deferred_tail(c);
         if (ctx_sync_stream(c, s) != hipSuccess) return st_err == STATUS_REPEAT_REDUCTION ? ctx_fail(c, SDPSR_HIP_ERROR, "hipStreamSynchronize failed") : st_err;
-        const uint32_t dv_init = ((const volatile uint32_t*)c->pinned_small)[PINNED_SMALL_DEFERRED_INITIAL.first];
+        const uint32_t dv_init = initial_guess_violated(c);
         if (dv_init != 0) return repeat_without_guesses(0, 0, dv_init);
         return st_err == STATUS_REPEAT_REDUCTION ? ctx_fail(c, SDPSR_BAD_STATE, "jordan_reduce: a repeat was asked for without a violated verdict") : st_err;
     };
@@ -149,7 +149,7 @@ int jordan_reduce_impl(sdpsr_ctx* c, int64_t n, const double* CL, const double* 
         const volatile uint32_t* ps = c->pinned_small;
         const uint32_t dv = c->deferred_verdict ? ps[PINNED_SMALL_DEFERRED_VERIFY.first] : 0u;
         const uint32_t dv_spec = c->deferred_verdict ? ps[PINNED_SMALL_DEFERRED_SPECULATIVE.first] : 0u;
-        const uint32_t dv_init = c->initial_guess_pending ? ps[PINNED_SMALL_DEFERRED_INITIAL.first] : 0u;
+        const uint32_t dv_init = c->initial_guess_pending ? initial_guess_violated(c) : 0u;  // (with the overflow word of the labels' 8-bit shadow)
         c->deferred_verdict = false;
         c->initial_guess_pending = false;
         if (dv != 0 || dv_spec != 0 || dv_init != 0) {

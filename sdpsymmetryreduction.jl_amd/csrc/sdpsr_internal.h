@@ -45,6 +45,7 @@ struct SigSource {
     const void* C = nullptr;
     int packed = 0;                                               // lower triangle only, densely packed (symmetric labels; SIG_PROJ: and symmetric basis, needs n)
     int lab_packed = 0;                                           // (with packed) L is the packed lower triangle itself: label of packed entry e = L[e]
+    const uint8_t* L8 = nullptr;                                  // (with lab_packed) a byte copy of L, every label <= 255: the verify passes read it instead (the label width of the source: 8 when set)
 };
 
 // The tail of the loop's guessed-closed path that sdpsr_jordan_reduce defers (loop.cpp, verify_round): two segments, each the
@@ -71,11 +72,14 @@ struct DeferredTail {
 };
 constexpr uint32_t DEFERRED_NEVER_RAN = 0xDEFE44EDu;  // what a verdict word holds until its segment is enqueued: reads as "violated"
 // "adm_lpacked" (Lp) and "ref_first" (first) describe the initial partition of the last loop call: order n, d0 classes, labels symmetric
+// narrow: "adm_lpacked8" (Lp8) is a byte copy of Lp (d0 <= 255) -- the 8-bit shadow the guessed-closed path streams instead of Lp
 struct InitialRecord {
     bool valid = false;
     int64_t n = 0, d0 = 0;
     const uint32_t *Lp = nullptr, *first = nullptr;
     int sym = 0;
+    bool narrow = false;
+    const uint8_t* Lp8 = nullptr;
 };
 // the loop's outcome "the initial partition was not the recorded one: repeat the reduction" -- never leaves jordan_reduce_impl
 constexpr int STATUS_REPEAT_REDUCTION = -0x5250;
@@ -154,10 +158,11 @@ struct sdpsr_ctx {
     // The loop's second guess (loop.cpp, initial_partition): the last loop call on this ctx found its input closed, so "adm_lpacked" /
     // "ref_first" still hold its INITIAL partition -- the next call of sdpsr_jordan_reduce checks that partition against its inputs
     // (launch_verify_pair) instead of rebuilding it, and the verdict rides with the two above.  Dropped by every refinement, by a
-    // violated verdict, and by ctx_buf when it frees either buffer.
+    // violated verdict, and by ctx_buf when it frees either buffer (or "adm_lpacked8", the labels' 8-bit shadow).
     sdpsr::InitialRecord initial_record;
     bool initial_guess_pending = false;  // this reduction took the guess; its word (PINNED_SMALL_DEFERRED_INITIAL) has not been read
     uint64_t initial_guesses = 0, initial_guesses_violated = 0;  // sdpsr_profile_initial_guess
+    uint64_t label_narrowings = 0;  // launches that made the 8-bit shadow of the packed labels (loop.cpp, initial_partition); sdpsr_profile_narrow_labels
     bool symflag_zero = false;  // every word of "adm_symflag" is 0 (the loop's last call wrote none of them)
 };
 
@@ -275,10 +280,11 @@ void launch_proj_coef(hipStream_t s, int64_t len, int64_t r, const double* U, co
 // y[e] = x[e] - sum_k U[e,k] coef[k]; optional outputs: yout (rounded value, fp64),
 // sig (signature chained on L).  x as above.
 // Lfull != nullptr: the kernel also writes the full n x n label matrix (leading dimension n) that the packed triangle describes
+// Lp8 != nullptr (here and below): a byte copy of the packed labels, every label <= 255 -- the kernel streams it instead of Lp, same results
 void launch_gather_i8_sym_packed(hipStream_t s, int64_t n, int64_t ld, int T, const uint32_t* Lp, uint64_t key, int8_t* X,
-                                 int64_t dmax, uint32_t* Lfull = nullptr);
+                                 int64_t dmax, uint32_t* Lfull = nullptr, const uint8_t* Lp8 = nullptr);
 void launch_proj_coef_lower(hipStream_t s, int64_t n, int64_t r, const double* U, const uint32_t* L, int lab_packed,
-                            uint64_t key, double* partial, int nblk, double* coef);
+                            uint64_t key, double* partial, int nblk, double* coef, const uint8_t* Lp8 = nullptr);
 void launch_proj_coef_probe(hipStream_t s, int64_t len, int64_t n, int64_t r, const double* U, const uint32_t* L, uint64_t key,
                             double* partial, int nblk, double* coef);
 void launch_proj_apply(hipStream_t s, int64_t len, int64_t r, const double* U, const uint32_t* L,
@@ -342,7 +348,7 @@ bool verify_no_split_supports(const SigSource& q, int64_t d);  // launch_verify_
 // "would the refinement of SIG_PAIR (a, b; packed lower triangle) write Lp and first_idx again?"  d <= verify_lds_cap() classes: one launch,
 // flag[0] (pinned host memory, cleared from the host) stays 0 exactly then.  false: d outside [1, verify_lds_cap()], nothing enqueued
 bool launch_verify_pair(hipStream_t s, int64_t n, const double* a, const double* b, const uint32_t* Lp, int64_t d, const uint32_t* first_idx,
-                        uint32_t* flag);
+                        uint32_t* flag, const uint8_t* Lp8 = nullptr);
 // loop.cpp: enqueue the next max_segments segments of the ctx's deferred tail on c->stream (none pending: nothing happens)
 void flush_deferred_tail(sdpsr_ctx* c, int max_segments = DEFERRED_SEGMENTS);
 inline bool deferred_tail_pending(const sdpsr_ctx* c) { return c->deferred_tail.next < c->deferred_tail.count; }
