@@ -70,6 +70,10 @@ int sdpsr_profile_gather_packed(sdpsr_ctx* ctx, int64_t n, int T, int64_t d, uin
    differs), out[1] = the class count up to which the pass is a single launch. */
 int sdpsr_profile_verify(sdpsr_ctx* ctx, int64_t n, int T, int64_t d, int mode, const uint32_t* Lp_host, const uint32_t* first_idx_host,
                          const int32_t* C_host, const double* U_host, double coef, uint64_t key, double atol, uint32_t* out);
+/* The basis check of mode 2 for r = 1 .. 4 basis matrices U_host (r * n * n): "is every one of them constant on the classes, and 0 on label
+   0?"  Wide labels; out as above. */
+int sdpsr_profile_basis_constant(sdpsr_ctx* ctx, int64_t n, int r, int64_t d, const uint32_t* Lp_host, const uint32_t* first_idx_host,
+                                 const double* U_host, double atol, uint32_t* out);
 /* The pair check of the loop's guessed initial partition: "would the refinement of the value pairs (a, b) over the packed lower triangle write
    the labels Lp_host and the representatives first_idx_host (d of them, packed indices) again?"  a_host, b_host: n x n, column-major, the
    lower triangle is read.  out[0] = verdict word (0: it would, bit for bit), out[1] = the largest d the pass takes; a larger d is refused
@@ -83,7 +87,8 @@ int sdpsr_profile_initial_guess(sdpsr_ctx* ctx, int32_t restart, uint64_t* out);
 int sdpsr_profile_narrow_labels(sdpsr_ctx* ctx, int32_t restart, uint64_t* out);
 /* The four consumers of the loop's packed labels at either label width (tests/test_gpu_narrow_loop_labels.py).  width 32: the kernels stream
    Lp_host as uploaded; width 8: the library's narrowing pass makes the byte copy on the device (a label > 255: SDPSR_BAD_ARGUMENT) and the
-   kernels stream that.  Everything else as the entries above.
+   kernels stream that.  Everything else as the entries above: each pass has one body, and the entries without a width are its width-32 form,
+   so every entry refuses what either refuses (a representative outside the triangle, d above its cap, width 8 with more than 255 classes).
    gather_packed_w: plain and label-writing form of the packed channel gather (X_plain, X_writing: T * ld * ld bytes, 0x5A where no kernel
    wrote; L_inout: n * n + guard words).
    verify_w: r = -1 the channels alone, r = 0 .. 4 joint with the r basis matrices U_host (r * n * n) and coefficients coef_host (r).

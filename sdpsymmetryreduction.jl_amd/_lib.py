@@ -235,6 +235,8 @@ def load_prof_library():
     lib.sdpsr_profile_verify.restype = C.c_int
     lib.sdpsr_profile_verify.argtypes = [vp, i64, C.c_int, i64, C.c_int, vp, vp, vp, vp, C.c_double, C.c_uint64, C.c_double,
                                          C.POINTER(C.c_uint32)]
+    lib.sdpsr_profile_basis_constant.restype = C.c_int
+    lib.sdpsr_profile_basis_constant.argtypes = [vp, i64, C.c_int, i64, vp, vp, vp, C.c_double, C.POINTER(C.c_uint32)]
     lib.sdpsr_profile_verify_pair.restype = C.c_int
     lib.sdpsr_profile_verify_pair.argtypes = [vp, i64, i64, vp, vp, vp, vp, C.POINTER(C.c_uint32)]
     lib.sdpsr_profile_initial_guess.restype = C.c_int

@@ -1999,7 +1999,24 @@ static void launch_insert(hipStream_t s, int g_chunks_cap, int64_t len, const SR
 // representative of its class -- raw values (rounded projection, channel products), no signature
 // hashing, no atomics; flag[0] = 1 as soon as some entry differs (the caller then runs the full
 // refinement).  Packed lower triangle, int32 channels (the default loop).
+// The same pass answers two more questions, with other values per entry and per class: "is every basis
+// matrix constant on the classes?" (ChkBasis) and "would Part(a) ^ Part(b) write these labels again?"
+// (ChkPair).  There is ONE table kernel and ONE compare kernel (class_ref_kernel, class_compare_kernel);
+// what a question loads, keeps per class and compares is its check, a functor like the Src* sources above:
+//   Raw                    what one entry loads;            Ref   what the table holds per class
+//   ref_of(cls, first_idx) the record of class cls, taken at its representative
+//   zero_ref()             the record that label 0 and the slots past a column compare with
+//   fetch(i, j, e, ok)     the loads of entry (i, j), packed number e (ok = 0: past the column, zeros)
+//   differs(raw, ref)      THE comparison
+//   load_uniforms()        what differs reads for every entry alike, into registers once
+//   order()                n;   kUntrusted: labels and representatives are a guess (see ChkPair)
 // ---------------------------------------------------------------------------
+// f(std::integral_constant<int, v>) for the v of the list that equals x; false when none does
+template <int... Vs, class F>
+static bool with_constant(int x, F&& f) {
+    return ((x == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...);
+}
+
 struct VerifyRef {  // one per class: the step's values at the class representative
     double x;        // the class's uniform draw (depends on the label only)
     uint64_t ybits;  // code of the rounded projected value there (sdpsr_round_key)
@@ -2007,239 +2024,130 @@ struct VerifyRef {  // one per class: the step's values at the class representat
 };
 // Up to this many classes the compare pass builds the table of representatives itself, in LDS, in a prologue of every workgroup (8 KiB: the
 // kernel's occupancy stays where it is): no launch of its own for the table, no gather from global memory per entry.  More classes: the table
-// kernel and the compare pass as two launches.  The same cap serves the basis check below (<= 4 codes of 8 bytes per class).
+// kernel and the compare pass as two launches.  The same cap serves the basis check (<= 4 codes of 8 bytes per class) and the pair check.
 constexpr int VERIFY_LDS_CAP = 256;
 int verify_lds_cap() { return VERIFY_LDS_CAP; }
-template <int R, int T, bool JOINT>
-__device__ __forceinline__ VerifyRef verify_ref_of(int cls, int n, int64_t ld, const uint32_t* __restrict__ first_idx, const double* __restrict__ U,
-                                                   uint64_t key, const double* __restrict__ coef, double atol, double scale,
-                                                   const int32_t* __restrict__ C) {
-    uint32_t i, j;
-    packed_lower_ij(n, (int64_t)first_idx[cls], i, j);
-    const int64_t ef = (int64_t)i + (int64_t)j * n;
-    VerifyRef r;
-    r.x = 0;
-    r.ybits = 0;
-    if (JOINT) {
-        r.x = sdpsr_class_uniform(key, (uint32_t)cls + 1u);
-        double p = 0;
-#pragma unroll
-        for (int k = 0; k < R; ++k) p = fma(U[(int64_t)k * n * n + ef], coef[k], p);
-        r.ybits = sdpsr_round_key(r.x - p, atol, scale);
-    }
-#pragma unroll
-    for (int t = 0; t < 4; ++t) r.c[t] = t < T ? C[(int64_t)t * ld * ld + (int64_t)j * ld + i] : 0;
-    return r;
-}
-template <int R, int T, bool JOINT>
-__global__ void verify_ref_kernel(int n, int64_t ld, int d, const uint32_t* __restrict__ first_idx, const double* __restrict__ U,
-                                  uint64_t key, const double* __restrict__ coef, double atol, double scale,
-                                  const int32_t* __restrict__ C, VerifyRef* __restrict__ ref, uint32_t* __restrict__ flag) {
-    const int cls = blockIdx.x * blockDim.x + threadIdx.x;
-    if (cls == 0) flag[0] = 0u;  // the verdict of the compare pass that follows in stream order
-    if (cls >= d) return;
-    ref[cls] = verify_ref_of<R, T, JOINT>(cls, n, ld, first_idx, U, key, coef, atol, scale, C);
-}
-// LDSREF (d <= VERIFY_LDS_CAP): the table is built here from first_idx (ref unused) and nobody zeroes flag[0] on the device -- a workgroup
-// could set the word before another one clears it: the launcher stores the 0 from the host before it enqueues the pass.
-// LT: the element type of Lp (uint8_t: the loop's 8-bit shadow of labels <= 255, LDSREF only); the loads and the widening differ, nothing else.
-template <int R, int T, bool JOINT, bool LDSREF, typename LT = uint32_t>
-__global__ void __launch_bounds__(256)
-verify_lower_kernel(int n, int64_t ld, const LT* __restrict__ Lp, const double* __restrict__ U, const double* __restrict__ coef,
-                    double atol, double scale, const int32_t* __restrict__ C, const VerifyRef* __restrict__ ref,
-                    uint32_t* __restrict__ flag, int d, const uint32_t* __restrict__ first_idx, uint64_t key) {
-    __shared__ VerifyRef sref[LDSREF ? VERIFY_LDS_CAP : 1];
-    if (LDSREF) {
-        for (int cls = threadIdx.x; cls < d; cls += blockDim.x)
-            sref[cls] = verify_ref_of<R, T, JOINT>(cls, n, ld, first_idx, U, key, coef, atol, scale, C);
-        __syncthreads();
-    }
-    bool bad = false;
-    double cf[R > 0 ? R : 1];
-#pragma unroll
-    for (int k = 0; k < R; ++k) cf[k] = coef[k];
-    const int64_t nn = (int64_t)n * n;
-    for (int j = blockIdx.x; j < n; j += gridDim.x) {
-        const int64_t poff = (int64_t)j * n - (int64_t)j * (j - 1) / 2 - j;
-        const LT* Lj = Lp + poff;
-        const int32_t* Cj = C + (int64_t)j * ld;
-        const double* Uj = U + (int64_t)j * n;
-        // VB entries of a thread per trip: their labels and values in one batch of loads, then the representatives of their
-        // classes in a second one (entry by entry it was two dependent memory round trips per entry, round 4)
-        constexpr int VB = 4;
-        for (int i0 = j + threadIdx.x; i0 < n; i0 += 256 * VB) {
-            uint32_t l[VB];
-            int32_t c[VB][T];
-            double u[VB][R > 0 ? R : 1];
-#pragma unroll
-            for (int b = 0; b < VB; ++b) {
-                const int i = i0 + 256 * b;
-                const bool ok = i < n;
-                l[b] = ok ? (uint32_t)__builtin_nontemporal_load(&Lj[i]) : 0u;
-#pragma unroll
-                for (int t = 0; t < T; ++t) c[b][t] = ok ? __builtin_nontemporal_load(&Cj[(int64_t)t * ld * ld + i]) : 0;
-                if (JOINT) {
-#pragma unroll
-                    for (int k = 0; k < R; ++k) u[b][k] = ok ? __builtin_nontemporal_load(&Uj[(int64_t)k * nn + i]) : 0.0;
-                }
-            }
-            VerifyRef r[VB];
-#pragma unroll
-            for (int b = 0; b < VB; ++b) {
-                r[b].x = 0;
-                r[b].ybits = 0;
-                r[b].c[0] = r[b].c[1] = r[b].c[2] = r[b].c[3] = 0;
-                // label 0 (and the slots past the column): the zero class stays together only while every value is zero
-                if (l[b]) {
-                    if (LDSREF) r[b] = sref[l[b] - 1];
-                    else r[b] = ref[l[b] - 1];
-                }
-            }
-#pragma unroll
-            for (int b = 0; b < VB; ++b) {
-                if (JOINT) {
-                    double p = 0;
-#pragma unroll
-                    for (int k = 0; k < R; ++k) p = fma(u[b][k], cf[k], p);
-                    const uint64_t yb = sdpsr_round_key(r[b].x - p, atol, scale);
-                    bad = bad || yb != r[b].ybits;
-                }
-#pragma unroll
-                for (int t = 0; t < T; ++t) bad = bad || c[b][t] != r[b].c[t];
-            }
-        }
-    }
-    if (bad) flag[0] = 1u;
-}
 
-// flag: a word of pinned host memory whose last verdict has been read (the one-launch form clears it from the host)
+// "Does this step split a class?": the T int32 channels and, JOINT, the rounded projection x - sum_k coef[k] U_k of the class draws x.
+// The zero record is all zero bits (ybits = 0 is what sdpsr_round_key gives below atol, not a code of its own).
 template <int R, int T, bool JOINT>
-static void launch_verify_rt(hipStream_t s, const SigSource& q, int64_t d, const uint32_t* first_idx, void* ref, uint32_t* flag) {
-    const int n = (int)q.n;
-    const int g = n < 256 * 8 ? n : 256 * 8;
-    if (d <= VERIFY_LDS_CAP) {
-        *(volatile uint32_t*)flag = 0u;
-        // the labels' 8-bit shadow -- except in the two joint instances whose byte form needs 4 more VGPRs than a wave per SIMD allows
-        // (74 against 70, 97 against 93: occupancy 6 against 7 and 4 against 5): those keep the wide labels
-        constexpr bool byte_form = !(JOINT && T == 2 && (R == 2 || R == 4));
-        if constexpr (byte_form) {
-            if (q.L8 && d <= 255) {
-                verify_lower_kernel<R, T, JOINT, true, uint8_t><<<g, 256, 0, s>>>(n, q.ld, q.L8, q.U, q.coef, q.atol, q.scale, (const int32_t*)q.C,
-                                                                                 nullptr, flag, (int)d, first_idx, q.key);
-                return;
-            }
-        }
-        verify_lower_kernel<R, T, JOINT, true><<<g, 256, 0, s>>>(n, q.ld, q.L, q.U, q.coef, q.atol, q.scale, (const int32_t*)q.C, nullptr, flag,
-                                                                (int)d, first_idx, q.key);
-        return;
+struct ChkStep {
+    using Ref = VerifyRef;
+    static constexpr bool kUntrusted = false;
+    struct Raw {
+        int32_t c[T];
+        double u[R > 0 ? R : 1];
+    };
+    int n;
+    int64_t ld;
+    const double* __restrict__ U;
+    const double* __restrict__ coef;
+    double atol, scale;
+    const int32_t* __restrict__ C;  // T channels, ld x ld each
+    uint64_t key;
+    double cf[R > 0 ? R : 1];  // coef, once load_uniforms() has run
+    __host__ __device__ __forceinline__ int order() const { return n; }
+    __device__ __forceinline__ void load_uniforms() {
+#pragma unroll
+        for (int k = 0; k < R; ++k) cf[k] = coef[k];
     }
-    verify_ref_kernel<R, T, JOINT><<<(unsigned)((d + 255) / 256), 256, 0, s>>>(n, q.ld, (int)d, first_idx, q.U, q.key, q.coef, q.atol, q.scale,
-                                                                             (const int32_t*)q.C, (VerifyRef*)ref, flag);
-    verify_lower_kernel<R, T, JOINT, false><<<g, 256, 0, s>>>(n, q.ld, q.L, q.U, q.coef, q.atol, q.scale, (const int32_t*)q.C,
-                                                             (const VerifyRef*)ref, flag, (int)d, first_idx, q.key);
-}
+    __device__ __forceinline__ Ref ref_of(int cls, const uint32_t* __restrict__ first_idx) const {
+        uint32_t i, j;
+        packed_lower_ij(n, (int64_t)first_idx[cls], i, j);
+        const int64_t ef = (int64_t)i + (int64_t)j * n;
+        Ref r;
+        r.x = 0;
+        r.ybits = 0;
+        if (JOINT) {
+            r.x = sdpsr_class_uniform(key, (uint32_t)cls + 1u);
+            double p = 0;
+#pragma unroll
+            for (int k = 0; k < R; ++k) p = fma(U[(int64_t)k * n * n + ef], coef[k], p);
+            r.ybits = sdpsr_round_key(r.x - p, atol, scale);
+        }
+#pragma unroll
+        for (int t = 0; t < 4; ++t) r.c[t] = t < T ? C[(int64_t)t * ld * ld + (int64_t)j * ld + i] : 0;
+        return r;
+    }
+    __device__ __forceinline__ Ref zero_ref() const { return Ref{0.0, 0ull, {0, 0, 0, 0}}; }
+    __device__ __forceinline__ Raw fetch(int i, int j, int64_t, bool ok) const {
+        Raw v;
+        const int32_t* Cij = C + (int64_t)j * ld + i;
+#pragma unroll
+        for (int t = 0; t < T; ++t) v.c[t] = ok ? __builtin_nontemporal_load(&Cij[(int64_t)t * ld * ld]) : 0;
+        if (JOINT) {
+            const double* Uij = U + (int64_t)j * n + i;
+#pragma unroll
+            for (int k = 0; k < R; ++k) v.u[k] = ok ? __builtin_nontemporal_load(&Uij[(int64_t)k * n * n]) : 0.0;
+        }
+        return v;
+    }
+    __device__ __forceinline__ bool differs(const Raw& v, const Ref& r) const {
+        bool bad = false;
+        if (JOINT) {
+            double p = 0;
+#pragma unroll
+            for (int k = 0; k < R; ++k) p = fma(v.u[k], cf[k], p);
+            bad = sdpsr_round_key(r.x - p, atol, scale) != r.ybits;
+        }
+#pragma unroll
+        for (int t = 0; t < T; ++t) bad = bad || v.c[t] != r.c[t];
+        return bad;
+    }
+};
 size_t verify_ref_bytes(int64_t d) { return (size_t)(d > 0 ? d : 1) * sizeof(VerifyRef); }
 
 // "Can the projection step still split a class?"  x - U U'x of an x that is constant on the classes of S is constant on
 // them for EVERY x exactly when every basis matrix U_k is (U_k in span(S) => U U'x in span(S)), and a finer S keeps the
 // property: once it holds, the projection half of the loop (src/partitions.jl:159-164) cannot refine S any more.  The
 // check compares the rounded codes of U_k (the rounding of the projection's own signatures, sdpsr_round_key) at every
-// entry of the packed lower triangle with those at the class representative (first_idx, as the verify pass); label 0
-// (structural zeros) needs U_k = 0.  flag[0] = 1 <=> some U_k is NOT constant on some class.
+// entry of the packed lower triangle with those at the class representative; label 0 (structural zeros) needs U_k = 0:
+// the zero record holds the code of 0.0.  flag[0] = 1 <=> some U_k is NOT constant on some class.
 template <int R>
-__device__ __forceinline__ void uconst_ref_of(int cls, int n, const uint32_t* __restrict__ first_idx, const double* __restrict__ U, double atol,
-                                              double scale, uint64_t* ref) {
-    uint32_t i, j;
-    packed_lower_ij(n, (int64_t)first_idx[cls], i, j);
-    const int64_t ef = (int64_t)i + (int64_t)j * n;
+struct ChkBasis {
+    struct Ref {
+        uint64_t code[R];  // (8 R bytes per class: uconst_ref_bytes)
+    };
+    static constexpr bool kUntrusted = false;
+    struct Raw {
+        double u[R];
+    };
+    int n;
+    const double* __restrict__ U;  // symmetric basis matrices U_k, n x n, column-major
+    double atol, scale;
+    __host__ __device__ __forceinline__ int order() const { return n; }
+    __device__ __forceinline__ void load_uniforms() {}
+    __device__ __forceinline__ Ref ref_of(int cls, const uint32_t* __restrict__ first_idx) const {
+        uint32_t i, j;
+        packed_lower_ij(n, (int64_t)first_idx[cls], i, j);
+        const int64_t ef = (int64_t)i + (int64_t)j * n;
+        Ref r;
 #pragma unroll
-    for (int k = 0; k < R; ++k) ref[(int64_t)cls * R + k] = sdpsr_round_key(U[(int64_t)k * n * n + ef], atol, scale);
-}
-template <int R>
-__global__ void uconst_ref_kernel(int n, int d, const uint32_t* __restrict__ first_idx, const double* __restrict__ U, double atol, double scale,
-                                  uint64_t* __restrict__ ref, uint32_t* __restrict__ flag) {
-    const int cls = blockIdx.x * blockDim.x + threadIdx.x;
-    if (cls == 0) flag[0] = 0u;
-    if (cls >= d) return;
-    uconst_ref_of<R>(cls, n, first_idx, U, atol, scale, ref);
-}
-// LDSREF: as verify_lower_kernel (the codes of d <= VERIFY_LDS_CAP classes from first_idx into LDS; flag[0] cleared by the launcher)
-template <int R, bool LDSREF>
-__global__ void __launch_bounds__(256)
-uconst_check_kernel(int n, const uint32_t* __restrict__ Lp, const double* __restrict__ U, double atol, double scale,
-                    const uint64_t* __restrict__ ref, uint32_t* __restrict__ flag, int d, const uint32_t* __restrict__ first_idx) {
-    __shared__ uint64_t sref[LDSREF ? VERIFY_LDS_CAP * R : 1];
-    if (LDSREF) {
-        for (int cls = threadIdx.x; cls < d; cls += blockDim.x) uconst_ref_of<R>(cls, n, first_idx, U, atol, scale, sref);
-        __syncthreads();
+        for (int k = 0; k < R; ++k) r.code[k] = sdpsr_round_key(U[(int64_t)k * n * n + ef], atol, scale);
+        return r;
     }
-    bool bad = false;
-    const int64_t nn = (int64_t)n * n;
-    const uint64_t zero_code = sdpsr_round_key(0.0, atol, scale);
-    for (int j = blockIdx.x; j < n; j += gridDim.x) {
-        const int64_t poff = (int64_t)j * n - (int64_t)j * (j - 1) / 2 - j;
-        const uint32_t* Lj = Lp + poff;
-        const double* Uj = U + (int64_t)j * n;
-        constexpr int VB = 4;  // entries per trip: labels and values first, then the classes' reference codes (see verify_lower_kernel)
-        for (int i0 = j + threadIdx.x; i0 < n; i0 += 256 * VB) {
-            uint32_t l[VB];
-            double uv[VB][R];
+    __device__ __forceinline__ Ref zero_ref() const {
+        Ref r;
 #pragma unroll
-            for (int b = 0; b < VB; ++b) {
-                const int i = i0 + 256 * b;
-                const bool ok = i < n;
-                l[b] = ok ? __builtin_nontemporal_load(&Lj[i]) : 0u;
-#pragma unroll
-                for (int k = 0; k < R; ++k) uv[b][k] = ok ? __builtin_nontemporal_load(&Uj[(int64_t)k * nn + i]) : 0.0;
-            }
-            uint64_t rc[VB][R];
-#pragma unroll
-            for (int b = 0; b < VB; ++b)
-#pragma unroll
-                for (int k = 0; k < R; ++k) {
-                    rc[b][k] = zero_code;
-                    if (l[b]) {
-                        if (LDSREF) rc[b][k] = sref[(l[b] - 1) * R + k];
-                        else rc[b][k] = ref[(int64_t)(l[b] - 1) * R + k];
-                    }
-                }
-#pragma unroll
-            for (int b = 0; b < VB; ++b)
-#pragma unroll
-                for (int k = 0; k < R; ++k) bad = bad || sdpsr_round_key(uv[b][k], atol, scale) != rc[b][k];
-        }
+        for (int k = 0; k < R; ++k) r.code[k] = sdpsr_round_key(0.0, atol, scale);
+        return r;
     }
-    if (bad) flag[0] = 1u;
-}
+    __device__ __forceinline__ Raw fetch(int i, int j, int64_t, bool ok) const {
+        Raw v;
+        const double* Uij = U + (int64_t)j * n + i;
+#pragma unroll
+        for (int k = 0; k < R; ++k) v.u[k] = ok ? __builtin_nontemporal_load(&Uij[(int64_t)k * n * n]) : 0.0;
+        return v;
+    }
+    __device__ __forceinline__ bool differs(const Raw& v, const Ref& r) const {
+        bool bad = false;
+#pragma unroll
+        for (int k = 0; k < R; ++k) bad = bad || sdpsr_round_key(v.u[k], atol, scale) != r.code[k];
+        return bad;
+    }
+};
 size_t uconst_ref_bytes(int64_t d, int64_t r) { return (size_t)(d > 0 ? d : 1) * (size_t)(r > 0 ? r : 1) * 8; }
-// symmetric basis matrices U_k (n x n, column-major, r <= 4 of them), packed labels Lp of d <= REFINE_FIRST_CAP classes
-// with their representatives first_idx; flag: a word of pinned host memory whose last verdict has been read (d <= VERIFY_LDS_CAP: one launch,
-// the word is cleared from the host)
-bool launch_basis_constant_on_classes(hipStream_t s, int64_t n, int64_t r, const double* U, const uint32_t* Lp, int64_t d,
-                                      const uint32_t* first_idx, double atol, double scale, void* ref, uint32_t* flag) {
-    if (r < 1 || r > 4 || d < 1 || d > (int64_t)REFINE_FIRST_CAP) return false;
-    const unsigned gr = (unsigned)((d + 255) / 256);
-    const int g = n < 256 * 8 ? (int)n : 256 * 8;
-    const bool lds = d <= VERIFY_LDS_CAP;
-    if (lds) *(volatile uint32_t*)flag = 0u;
-#define SDPSR_UCONST_CASE(RR)                                                                                                                  \
-    case RR:                                                                                                                                   \
-        if (lds) {                                                                                                                             \
-            uconst_check_kernel<RR, true><<<g, 256, 0, s>>>((int)n, Lp, U, atol, scale, nullptr, flag, (int)d, first_idx);                      \
-        } else {                                                                                                                               \
-            uconst_ref_kernel<RR><<<gr, 256, 0, s>>>((int)n, (int)d, first_idx, U, atol, scale, (uint64_t*)ref, flag);                          \
-            uconst_check_kernel<RR, false><<<g, 256, 0, s>>>((int)n, Lp, U, atol, scale, (const uint64_t*)ref, flag, (int)d, first_idx);        \
-        }                                                                                                                                      \
-        break;
-    switch (r) {
-        SDPSR_UCONST_CASE(1)
-        SDPSR_UCONST_CASE(2)
-        SDPSR_UCONST_CASE(3)
-        SDPSR_UCONST_CASE(4)
-    }
-#undef SDPSR_UCONST_CASE
-    return true;
-}
+
 // "Is the initial partition S = Part(a) ^ Part(b) of this call the one that Lp and first_idx already describe?"  (the restarts of one
 // problem: a, b are what they were, and a call that found its input closed has left the initial partition in place).  Lp, first_idx: the
 // canonical labels of a refinement and the first occurrences of its d <= VERIFY_LDS_CAP classes.  flag[0] stays 0 exactly when the
@@ -2247,70 +2155,139 @@ bool launch_basis_constant_on_classes(hipStream_t s, int64_t n, int64_t r, const
 //   every entry of label l >= 1 has the signature of first_idx[l - 1]; no representative has the zero signature (its class would be
 //   label 0); the representatives' signatures are pairwise distinct; every entry of label 0 has the zero signature
 // -- then the classes of the signatures ARE the classes of Lp, and the canonical numbering depends on the partition alone.  The signature
-// is the refinement's own (SrcPair::fetch / sig): -0.0, NaN payloads and equal hashes count as they do in the insert pass.  Layout as
-// uconst_check_kernel<R, true>; flag[0] cleared by the launcher.  (A representative outside the triangle or a label > d: violated.)
-// LT: the element type of Lp (uint8_t: the loop's 8-bit shadow of labels <= 255).
-template <typename LT>
-__global__ void __launch_bounds__(256)
-verify_pair_kernel(SrcPair src, const LT* __restrict__ Lp, uint32_t* __restrict__ flag, int d, const uint32_t* __restrict__ first_idx) {
-    __shared__ uint64_t sref[VERIFY_LDS_CAP];
-    const int n = src.n;
-    const int64_t np = (int64_t)n * (n + 1) / 2;
-    bool bad = false;
-    for (int cls = threadIdx.x; cls < d; cls += blockDim.x) {
+// is the refinement's own (SrcPair::fetch / sig): -0.0, NaN payloads and equal hashes count as they do in the insert pass.
+// kUntrusted: labels and representatives are a guess, so the compare kernel adds what the list above needs beyond the entry compare: a
+// representative outside the triangle (ref_of gives it the zero signature) or with the zero signature, two classes of one signature,
+// a label > d: violated.  The table is checked where it is built, in LDS: one launch, d <= VERIFY_LDS_CAP.
+struct ChkPair {
+    using Ref = uint64_t;
+    using Raw = SrcPair::Raw;
+    static constexpr bool kUntrusted = true;
+    SrcPair src;
+    __host__ __device__ __forceinline__ int order() const { return src.n; }
+    __device__ __forceinline__ void load_uniforms() {}
+    __device__ __forceinline__ Ref ref_of(int cls, const uint32_t* __restrict__ first_idx) const {
         const int64_t e = (int64_t)first_idx[cls];
-        uint64_t sg = 0;  // (the zero signature: violated below)
-        if (e < np) {
+        uint64_t sg = 0;
+        if (e < (int64_t)src.n * (src.n + 1) / 2) {
             uint32_t i, j;
-            packed_lower_ij(n, e, i, j);
+            packed_lower_ij(src.n, e, i, j);
             sg = src.sig(src.fetch(i, j, e));
         }
-        bad = bad || sg == 0;
-        sref[cls] = sg;
+        return sg;
     }
-    __syncthreads();
-    if (blockIdx.x == 0) {  // pairwise distinct: one workgroup's finding is enough (every lane reads the same word: a broadcast)
+    __device__ __forceinline__ Ref zero_ref() const { return 0; }
+    __device__ __forceinline__ Raw fetch(int i, int j, int64_t e, bool ok) const {
+        return ok ? src.fetch((uint32_t)i, (uint32_t)j, e) : Raw{0.0, 0.0};
+    }
+    __device__ __forceinline__ bool differs(const Raw& v, const Ref& r) const { return src.sig(v) != r; }
+};
+
+// The table of the two-launch form: one record per class, and the verdict word of the compare pass that follows in stream order cleared.
+template <class CHK>
+__global__ void class_ref_kernel(CHK chk, int d, const uint32_t* __restrict__ first_idx, typename CHK::Ref* __restrict__ ref,
+                                 uint32_t* __restrict__ flag) {
+    const int cls = blockIdx.x * blockDim.x + threadIdx.x;
+    if (cls == 0) flag[0] = 0u;
+    if (cls >= d) return;
+    ref[cls] = chk.ref_of(cls, first_idx);
+}
+// Column j over the workgroups, rows over the threads; flag[0] = 1 when some entry differs from the record of its class.
+// LDSREF (d <= VERIFY_LDS_CAP): the table is built here from first_idx (ref unused) and nobody zeroes flag[0] on the device -- a workgroup
+// could set the word before another one clears it: the launcher stores the 0 from the host before it enqueues the pass.
+// LT: the element type of Lp (uint8_t: the loop's 8-bit shadow of labels <= 255, LDSREF only); the loads and the widening differ, nothing else.
+template <class CHK, bool LDSREF, typename LT>
+__global__ void __launch_bounds__(256)
+class_compare_kernel(CHK chk, const LT* __restrict__ Lp, const typename CHK::Ref* __restrict__ ref, uint32_t* __restrict__ flag, int d,
+                     const uint32_t* __restrict__ first_idx) {
+    using Ref = typename CHK::Ref;
+    static_assert(LDSREF || !CHK::kUntrusted, "an untrusted table is checked in LDS");
+    __shared__ Ref sref[LDSREF ? VERIFY_LDS_CAP : 1];
+    const int n = chk.order();
+    const Ref zero = chk.zero_ref();
+    bool bad = false;
+    if (LDSREF) {
         for (int cls = threadIdx.x; cls < d; cls += blockDim.x) {
-            const uint64_t mine = sref[cls];
-            for (int k = 0; k < cls; ++k) bad = bad || sref[k] == mine;
+            sref[cls] = chk.ref_of(cls, first_idx);
+            if constexpr (CHK::kUntrusted) bad = bad || sref[cls] == zero;
+        }
+        __syncthreads();
+        if constexpr (CHK::kUntrusted) {
+            if (blockIdx.x == 0) {  // pairwise distinct: one workgroup's finding is enough (every lane reads the same word: a broadcast)
+                for (int cls = threadIdx.x; cls < d; cls += blockDim.x) {
+                    const Ref mine = sref[cls];
+                    for (int k = 0; k < cls; ++k) bad = bad || sref[k] == mine;
+                }
+            }
         }
     }
+    chk.load_uniforms();
     for (int j = blockIdx.x; j < n; j += gridDim.x) {
         const int64_t poff = (int64_t)j * n - (int64_t)j * (j - 1) / 2 - j;
         const LT* Lj = Lp + poff;
-        constexpr int VB = 4;  // entries per trip: labels and values first, then the classes' signatures (see verify_lower_kernel)
+        // VB entries of a thread per trip: their labels and values in one batch of loads, then the records of their
+        // classes in a second one (entry by entry it was two dependent memory round trips per entry, round 4)
+        constexpr int VB = 4;
         for (int i0 = j + threadIdx.x; i0 < n; i0 += 256 * VB) {
             uint32_t l[VB];
-            SrcPair::Raw v[VB];
+            typename CHK::Raw v[VB];
 #pragma unroll
             for (int b = 0; b < VB; ++b) {
                 const int i = i0 + 256 * b;
                 const bool ok = i < n;
                 l[b] = ok ? (uint32_t)__builtin_nontemporal_load(&Lj[i]) : 0u;
-                v[b] = ok ? src.fetch((uint32_t)i, (uint32_t)j, poff + i) : SrcPair::Raw{0.0, 0.0};
+                v[b] = chk.fetch(i, j, poff + i, ok);
             }
-            uint64_t rc[VB];
+            Ref r[VB];
 #pragma unroll
             for (int b = 0; b < VB; ++b) {
-                rc[b] = 0;  // label 0 (and the slots past the column): the zero signature
-                if (l[b] > (uint32_t)d) bad = true;
-                else if (l[b]) rc[b] = sref[l[b] - 1];
+                // label 0 (and the slots past the column): the zero class stays together only while every value is the zero record's
+                r[b] = zero;
+                if (CHK::kUntrusted && l[b] > (uint32_t)d) bad = true;
+                else if (l[b]) {
+                    if (LDSREF) r[b] = sref[l[b] - 1];
+                    else r[b] = ref[l[b] - 1];
+                }
             }
 #pragma unroll
-            for (int b = 0; b < VB; ++b) bad = bad || src.sig(v[b]) != rc[b];
+            for (int b = 0; b < VB; ++b) bad = bad || chk.differs(v[b], r[b]);
         }
     }
     if (bad) flag[0] = 1u;
 }
-// a, b: symmetric n x n, column-major (the lower triangle is read); Lp, first_idx: as above; flag: a word of pinned host memory whose last
-// verdict has been read (cleared from the host).  false: more classes than the one-launch form holds (nothing is enqueued)
+// THE launcher of the three checks.  Up to VERIFY_LDS_CAP classes: one launch, flag[0] cleared from the host (flag: a word of pinned host
+// memory whose last verdict has been read).  More: the table kernel, which clears the word, and the compare pass; that form exists for wide
+// labels and trusted tables only, and the callers ask for no other.
+template <class CHK, typename LT>
+static void launch_class_compare(hipStream_t s, const CHK& chk, const LT* Lp, int64_t d, const uint32_t* first_idx, void* ref, uint32_t* flag) {
+    const int n = chk.order();
+    const int g = n < 256 * 8 ? n : 256 * 8;
+    if (d <= VERIFY_LDS_CAP) {
+        *(volatile uint32_t*)flag = 0u;
+        class_compare_kernel<CHK, true, LT><<<g, 256, 0, s>>>(chk, Lp, nullptr, flag, (int)d, first_idx);
+    } else if constexpr (std::is_same_v<LT, uint32_t> && !CHK::kUntrusted) {
+        class_ref_kernel<CHK><<<(unsigned)((d + 255) / 256), 256, 0, s>>>(chk, (int)d, first_idx, (typename CHK::Ref*)ref, flag);
+        class_compare_kernel<CHK, false, LT><<<g, 256, 0, s>>>(chk, Lp, (const typename CHK::Ref*)ref, flag, (int)d, first_idx);
+    }
+}
+
+// symmetric basis matrices U_k (n x n, column-major, r <= 4 of them), packed labels Lp of d <= REFINE_FIRST_CAP classes
+// with their representatives first_idx.  Wide labels only.
+bool launch_basis_constant_on_classes(hipStream_t s, int64_t n, int64_t r, const double* U, const uint32_t* Lp, int64_t d,
+                                      const uint32_t* first_idx, double atol, double scale, void* ref, uint32_t* flag) {
+    if (d < 1 || d > (int64_t)REFINE_FIRST_CAP) return false;
+    return with_constant<1, 2, 3, 4>((int)r, [&](auto R) {
+        launch_class_compare(s, ChkBasis<decltype(R)::value>{(int)n, U, atol, scale}, Lp, d, first_idx, ref, flag);
+    });
+}
+// a, b: symmetric n x n, column-major (the lower triangle is read); Lp, first_idx: as above (Lp8: the labels' 8-bit shadow, or null).
+// false: more classes than the one-launch form holds (nothing is enqueued)
 bool launch_verify_pair(hipStream_t s, int64_t n, const double* a, const double* b, const uint32_t* Lp, int64_t d, const uint32_t* first_idx,
                         uint32_t* flag, const uint8_t* Lp8) {
     if (n < 1 || n >= (int64_t(1) << 31) || d < 1 || d > VERIFY_LDS_CAP) return false;
-    const int g = n < 256 * 8 ? (int)n : 256 * 8;
-    *(volatile uint32_t*)flag = 0u;
-    if (Lp8 && d <= 255) verify_pair_kernel<uint8_t><<<g, 256, 0, s>>>(SrcPair{a, b, (int)n, 1}, Lp8, flag, (int)d, first_idx);
-    else verify_pair_kernel<uint32_t><<<g, 256, 0, s>>>(SrcPair{a, b, (int)n, 1}, Lp, flag, (int)d, first_idx);
+    const ChkPair chk{SrcPair{a, b, (int)n, 1}};
+    if (Lp8 && d <= 255) launch_class_compare(s, chk, Lp8, d, first_idx, nullptr, flag);
+    else launch_class_compare(s, chk, Lp, d, first_idx, nullptr, flag);
     return true;
 }
 
@@ -2320,34 +2297,27 @@ bool verify_no_split_supports(const SigSource& q, int64_t d) {
     if (!q.packed || !q.lab_packed || d < 1 || d > (int64_t)REFINE_FIRST_CAP || (q.T != 2 && q.T != 4)) return false;
     return q.kind == SIG_CHAN_I32 || (q.kind == SIG_JOINT_I32 && q.r >= 0 && q.r <= 4);
 }
+template <int R, int T, bool JOINT>
+static void launch_verify_rt(hipStream_t s, const SigSource& q, int64_t d, const uint32_t* first_idx, void* ref, uint32_t* flag) {
+    const ChkStep<R, T, JOINT> chk{(int)q.n, q.ld, q.U, q.coef, q.atol, q.scale, (const int32_t*)q.C, q.key, {}};
+    // the labels' 8-bit shadow -- except in the two joint instances whose byte form needs 4 more VGPRs than a wave per SIMD allows
+    // (74 against 70, 97 against 93: occupancy 6 against 7 and 4 against 5): those keep the wide labels
+    constexpr bool byte_form = !(JOINT && T == 2 && (R == 2 || R == 4));
+    if constexpr (byte_form) {
+        if (q.L8 && d <= 255) {
+            launch_class_compare(s, chk, q.L8, d, first_idx, ref, flag);
+            return;
+        }
+    }
+    launch_class_compare(s, chk, q.L, d, first_idx, ref, flag);
+}
 bool launch_verify_no_split(hipStream_t s, const SigSource& q, int64_t d, const uint32_t* first_idx, void* ref, uint32_t* flag) {
     if (!verify_no_split_supports(q, d)) return false;
-    if (q.kind == SIG_CHAN_I32) {
-        if (q.T == 2) launch_verify_rt<0, 2, false>(s, q, d, first_idx, ref, flag);
-        else launch_verify_rt<0, 4, false>(s, q, d, first_idx, ref, flag);
-        return true;
-    }
-    if (q.kind != SIG_JOINT_I32 || q.r < 0 || q.r > 4) return false;
-#define SDPSR_VERIFY_CASE(RR)                                                       \
-    case RR:                                                                        \
-        if (q.T == 2) launch_verify_rt<RR, 2, true>(s, q, d, first_idx, ref, flag); \
-        else launch_verify_rt<RR, 4, true>(s, q, d, first_idx, ref, flag);          \
-        break;
-    switch (q.r) {
-        SDPSR_VERIFY_CASE(0)
-        SDPSR_VERIFY_CASE(1)
-        SDPSR_VERIFY_CASE(2)
-        SDPSR_VERIFY_CASE(3)
-        SDPSR_VERIFY_CASE(4)
-    }
-#undef SDPSR_VERIFY_CASE
+    with_constant<2, 4>(q.T, [&](auto T) {
+        if (q.kind == SIG_CHAN_I32) launch_verify_rt<0, decltype(T)::value, false>(s, q, d, first_idx, ref, flag);
+        else with_constant<0, 1, 2, 3, 4>(q.r, [&](auto R) { launch_verify_rt<decltype(R)::value, decltype(T)::value, true>(s, q, d, first_idx, ref, flag); });
+    });
     return true;
-}
-
-// f(std::integral_constant<int, v>) for the v of the list that equals x; false when none does
-template <int... Vs, class F>
-static bool with_constant(int x, F&& f) {
-    return ((x == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...);
 }
 
 // THE map from a SigSource to its functor: f(src) with the Src* instance of q.  false (f not called) when q's shape has

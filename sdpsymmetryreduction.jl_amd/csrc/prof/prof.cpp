@@ -173,120 +173,6 @@ extern "C" int sdpsr_profile_loop_counts(sdpsr_ctx* c, int32_t restart, uint64_t
     return SDPSR_OK;
 }
 
-// The loop's label passes on caller-made inputs (tests/test_gpu_label_passes.py).  Gather: the packed triangle Lp (order n, labels <= d) through
-// the plain and the label-writing form of the packed channel gather, and the mirrored full labels Lfull through the full-matrix gather; the three
-// X (T channels of ld x ld, ld = n rounded up to 128; every buffer filled with 0x5A first, so padding nobody wrote shows) come back with the full
-// matrix the writing form made.  L_inout: n * n + guard words, uploaded as they are (the test's fill) and downloaded after the kernel.
-extern "C" int sdpsr_profile_gather_packed(sdpsr_ctx* c, int64_t n, int T, int64_t d, uint64_t key, const uint32_t* Lp_host, const uint32_t* Lfull_host,
-                                           int8_t* X_plain, int8_t* X_writing, int8_t* X_full, uint32_t* L_inout, int64_t guard) {
-    CHECK_CTX(c);
-    if (!Lp_host || !Lfull_host || !X_plain || !X_writing || !X_full || !L_inout || n < 1 || n > 8192 || guard < 0 || (T != 1 && T != 2 && T != 4))
-        return ctx_fail(c, SDPSR_BAD_ARGUMENT, "bad arguments");
-    hipStream_t s = c->stream;
-    const int64_t ld = round_up(n, 128), np = n * (n + 1) / 2;
-    const size_t xb = (size_t)T * ld * ld;
-    uint32_t* Lp = (uint32_t*)ctx_buf(c, "prof_lp", (size_t)np * 4);
-    uint32_t* Lf = (uint32_t*)ctx_buf(c, "prof_lfull", (size_t)n * n * 4);
-    uint32_t* Lw = (uint32_t*)ctx_buf(c, "prof_lwritten", (size_t)(n * n + guard) * 4);
-    int8_t* X = (int8_t*)ctx_buf(c, "prof_gx", 3 * xb);
-    if (!Lp || !Lf || !Lw || !X) return SDPSR_OUT_OF_MEMORY;
-    HIP_TRY(c, hipMemcpyAsync(Lp, Lp_host, (size_t)np * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(Lf, Lfull_host, (size_t)n * n * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(Lw, L_inout, (size_t)(n * n + guard) * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemsetAsync(X, 0x5A, 3 * xb, s));
-    launch_gather_i8_sym_packed(s, n, ld, T, Lp, key, X, d);
-    launch_gather_i8_sym_packed(s, n, ld, T, Lp, key, X + xb, d, Lw);
-    launch_gather_i8(s, n, ld, T, Lf, key, X + 2 * xb, d);
-    HIP_TRY(c, hipMemcpyAsync(X_plain, X, xb, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipMemcpyAsync(X_writing, X + xb, xb, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipMemcpyAsync(X_full, X + 2 * xb, xb, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipMemcpyAsync(L_inout, Lw, (size_t)(n * n + guard) * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    HIP_TRY(c, hipGetLastError());
-    return SDPSR_OK;
-}
-
-// Verify: "does any entry of the packed triangle differ from the representative of its class?" on caller-made inputs.  Lp: packed labels <= d,
-// first_idx: the d packed indices of the representatives, C_host: T (2 or 4) int32 channels of ld x ld.  mode 0: the channels alone; 1: joint
-// with the one basis matrix U_host (n x n) and coefficient coef (the class draws come from key); 2: the basis check "is U constant on the
-// classes" (C_host unused).  out[0] = the verdict word (it holds 0xDEAD before the pass is enqueued: the pass has to clear it),
-// out[1] = the class count up to which the pass is one launch.
-extern "C" int sdpsr_profile_verify(sdpsr_ctx* c, int64_t n, int T, int64_t d, int mode, const uint32_t* Lp_host, const uint32_t* first_idx_host,
-                                    const int32_t* C_host, const double* U_host, double coef, uint64_t key, double atol, uint32_t* out) {
-    CHECK_CTX(c);
-    if (!Lp_host || !first_idx_host || !out || n < 1 || n > 8192 || d < 1 || d > (int64_t)refine_first_cap() || mode < 0 || mode > 2 ||
-        (mode != 2 && (!C_host || (T != 2 && T != 4))) || (mode != 0 && !U_host) || !(atol > 0))
-        return ctx_fail(c, SDPSR_BAD_ARGUMENT, "bad arguments");
-    hipStream_t s = c->stream;
-    const int64_t ld = round_up(n, 128), np = n * (n + 1) / 2;
-    const size_t cb = (size_t)(mode == 2 ? 1 : T) * ld * ld * 4;
-    uint32_t* Lp = (uint32_t*)ctx_buf(c, "prof_lp", (size_t)np * 4);
-    uint32_t* first = (uint32_t*)ctx_buf(c, "prof_first", (size_t)d * 4);
-    int32_t* Cd = (int32_t*)ctx_buf(c, "prof_vc", cb);
-    double* Ud = (double*)ctx_buf(c, "prof_vu", (size_t)(n * n + 1) * 8);  // + the coefficient
-    void* ref = ctx_buf(c, "prof_vref", std::max(verify_ref_bytes(d), uconst_ref_bytes(d, 1)));
-    uint32_t* hv = pinned_report(c, PINNED_VERIFY);
-    if (!Lp || !first || !Cd || !Ud || !ref || !hv) return SDPSR_OUT_OF_MEMORY;
-    HIP_TRY(c, hipMemcpyAsync(Lp, Lp_host, (size_t)np * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(first, first_idx_host, (size_t)d * 4, hipMemcpyHostToDevice, s));
-    if (mode != 2) HIP_TRY(c, hipMemcpyAsync(Cd, C_host, cb, hipMemcpyHostToDevice, s));
-    if (mode != 0) {
-        HIP_TRY(c, hipMemcpyAsync(Ud, U_host, (size_t)n * n * 8, hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemcpyAsync(Ud + n * n, &coef, 8, hipMemcpyHostToDevice, s));
-    }
-    HIP_TRY(c, hipStreamSynchronize(s));  // (coef is a stack variable; and nothing may be in flight on the verdict word)
-    hv[0] = 0xDEADu;
-    const double scale = round_scale(c, atol);
-    bool ran;
-    if (mode == 2) {
-        ran = launch_basis_constant_on_classes(s, n, 1, Ud, Lp, d, first, atol, scale, ref, hv);
-    } else {
-        SigSource q;
-        q.kind = mode == 1 ? SIG_JOINT_I32 : SIG_CHAN_I32, q.U = Ud, q.coef = Ud + n * n, q.r = mode == 1 ? 1 : 0, q.key = key, q.atol = atol, q.scale = scale;
-        q.n = n, q.ld = ld, q.T = T, q.C = Cd, q.L = Lp, q.packed = 1, q.lab_packed = 1;
-        ran = launch_verify_no_split(s, q, d, first, ref, hv);
-    }
-    HIP_TRY(c, hipStreamSynchronize(s));
-    HIP_TRY(c, hipGetLastError());
-    if (!ran) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "no verify pass for this shape");
-    out[0] = ((const volatile uint32_t*)hv)[0];
-    out[1] = (uint32_t)verify_lds_cap();
-    return SDPSR_OK;
-}
-
-// The pair check "would the initial refinement of (a, b) write these labels and representatives again?" on caller-made inputs
-// (tests/test_gpu_verify_pair.py).  Lp_host: packed labels <= d of order n, first_idx_host: the d packed indices of the representatives,
-// a_host, b_host: n x n column-major (the lower triangle is read).  out[0] = the verdict word (0xDEAD before the pass is enqueued: the pass has
-// to clear it), out[1] = the largest class count the pass takes; more classes are refused.
-extern "C" int sdpsr_profile_verify_pair(sdpsr_ctx* c, int64_t n, int64_t d, const uint32_t* Lp_host, const uint32_t* first_idx_host,
-                                         const double* a_host, const double* b_host, uint32_t* out) {
-    CHECK_CTX(c);
-    if (!Lp_host || !first_idx_host || !a_host || !b_host || !out || n < 1 || n > 8192 || d < 1 || d > (int64_t)verify_lds_cap())
-        return ctx_fail(c, SDPSR_BAD_ARGUMENT, "bad arguments");
-    const int64_t np = n * (n + 1) / 2;
-    for (int64_t k = 0; k < d; ++k)
-        if ((int64_t)first_idx_host[k] >= np) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "a representative outside the packed triangle");
-    hipStream_t s = c->stream;
-    uint32_t* Lp = (uint32_t*)ctx_buf(c, "prof_lp", (size_t)np * 4);
-    uint32_t* first = (uint32_t*)ctx_buf(c, "prof_first", (size_t)d * 4);
-    double* ab = (double*)ctx_buf(c, "prof_pair_ab", (size_t)2 * n * n * 8);
-    uint32_t* hv = pinned_report(c, PINNED_VERIFY);
-    if (!Lp || !first || !ab || !hv) return SDPSR_OUT_OF_MEMORY;
-    HIP_TRY(c, hipMemcpyAsync(Lp, Lp_host, (size_t)np * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(first, first_idx_host, (size_t)d * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(ab, a_host, (size_t)n * n * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(ab + n * n, b_host, (size_t)n * n * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipStreamSynchronize(s));  // (nothing may be in flight on the verdict word)
-    hv[0] = 0xDEADu;
-    const bool ran = launch_verify_pair(s, n, ab, ab + n * n, Lp, d, first, hv);
-    HIP_TRY(c, hipStreamSynchronize(s));
-    HIP_TRY(c, hipGetLastError());
-    if (!ran) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "no pair check for this shape");
-    out[0] = ((const volatile uint32_t*)hv)[0];
-    out[1] = (uint32_t)verify_lds_cap();
-    return SDPSR_OK;
-}
-
 extern "C" int sdpsr_profile_initial_guess(sdpsr_ctx* c, int32_t restart, uint64_t* out) {
     CHECK_CTX(c);
     if (!out || restart < 0 || restart > (int32_t)c->batch_children.size()) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "bad arguments");
@@ -303,7 +189,8 @@ extern "C" int sdpsr_profile_narrow_labels(sdpsr_ctx* c, int32_t restart, uint64
     return SDPSR_OK;
 }
 
-// ---- the consumers of the loop's packed labels at either label width (tests/test_gpu_narrow_loop_labels.py) ----
+// ---- the consumers of the loop's packed labels on caller-made inputs, at either label width (tests/test_gpu_label_passes.py,
+// test_gpu_verify_pair.py, test_gpu_narrow_loop_labels.py) ----
 namespace {
 // width 8: *Lp8 = the byte copy of the np packed labels Lp (device), made by the library's own narrowing pass; width 32: nullptr.  d: the
 // labels' bound (the byte forms take <= 255 classes)
@@ -323,28 +210,69 @@ int prof_label_shadow(sdpsr_ctx* c, const uint32_t* Lp, int64_t np, int64_t d, i
     *Lp8 = p;
     return SDPSR_OK;
 }
-}  // namespace
+// What the three checks of the class-compare kernel share.  Up: the packed labels, their d representatives (each inside the triangle: the
+// step and basis checks index with them unguarded) and the labels' shadow on the device, the stream idle, the verdict word holding 0xDEAD (the
+// pass has to clear it).  Down: out[0] = the verdict word, out[1] = the class count up to which a check is one launch.
+struct ProfClasses {
+    uint32_t *Lp, *first, *flag;
+    const uint8_t* Lp8;
+};
+int prof_classes_up(sdpsr_ctx* c, int64_t n, int64_t d, int width, const uint32_t* Lp_host, const uint32_t* first_idx_host, ProfClasses* p) {
+    const int64_t np = n * (n + 1) / 2;
+    for (int64_t k = 0; k < d; ++k)
+        if ((int64_t)first_idx_host[k] >= np) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "a representative outside the packed triangle");
+    p->Lp = (uint32_t*)ctx_buf(c, "prof_lp", (size_t)np * 4);
+    p->first = (uint32_t*)ctx_buf(c, "prof_first", (size_t)d * 4);
+    p->flag = pinned_report(c, PINNED_VERIFY);
+    if (!p->Lp || !p->first || !p->flag) return SDPSR_OUT_OF_MEMORY;
+    HIP_TRY(c, hipMemcpyAsync(p->Lp, Lp_host, (size_t)np * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(p->first, first_idx_host, (size_t)d * 4, hipMemcpyHostToDevice, c->stream));
+    const int st = prof_label_shadow(c, p->Lp, np, d, width, &p->Lp8);
+    if (st) return st;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));  // (nothing may be in flight on the verdict word)
+    p->flag[0] = 0xDEADu;
+    return SDPSR_OK;
+}
+int prof_verdict_down(sdpsr_ctx* c, bool ran, const ProfClasses& p, uint32_t* out) {
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    if (!ran) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "no check for this shape");
+    out[0] = ((const volatile uint32_t*)p.flag)[0];
+    out[1] = (uint32_t)verify_lds_cap();
+    return SDPSR_OK;
+}
 
-extern "C" int sdpsr_profile_gather_packed_w(sdpsr_ctx* c, int64_t n, int T, int64_t d, uint64_t key, int width, const uint32_t* Lp_host,
-                                             int8_t* X_plain, int8_t* X_writing, uint32_t* L_inout, int64_t guard) {
+// Gather: the packed triangle Lp (order n, labels <= d) through the plain and the label-writing form of the packed channel gather and, where
+// Lfull_host / X_full are given, the mirrored full labels through the full-matrix gather; the X (T channels of ld x ld, ld = n rounded up to
+// 128; every buffer filled with 0x5A first, so padding nobody wrote shows) come back with the full matrix the writing form made.  L_inout:
+// n * n + guard words, uploaded as they are (the test's fill) and downloaded after the kernel.
+int prof_gather_packed(sdpsr_ctx* c, int64_t n, int T, int64_t d, uint64_t key, int width, const uint32_t* Lp_host, const uint32_t* Lfull_host,
+                       int8_t* X_plain, int8_t* X_writing, int8_t* X_full, uint32_t* L_inout, int64_t guard) {
     CHECK_CTX(c);
-    if (!Lp_host || !X_plain || !X_writing || !L_inout || n < 1 || n > 8192 || d < 0 || guard < 0 || (T != 1 && T != 2 && T != 4))
+    if (!Lp_host || !X_plain || !X_writing || !L_inout || !Lfull_host != !X_full || n < 1 || n > 8192 || d < 0 || guard < 0 ||
+        (T != 1 && T != 2 && T != 4))
         return ctx_fail(c, SDPSR_BAD_ARGUMENT, "bad arguments");
     hipStream_t s = c->stream;
     const int64_t ld = round_up(n, 128), np = n * (n + 1) / 2;
     const size_t xb = (size_t)T * ld * ld;
     uint32_t* Lp = (uint32_t*)ctx_buf(c, "prof_lp", (size_t)np * 4);
+    uint32_t* Lf = (uint32_t*)ctx_buf(c, "prof_lfull", (size_t)n * n * 4);
     uint32_t* Lw = (uint32_t*)ctx_buf(c, "prof_lwritten", (size_t)(n * n + guard) * 4);
-    int8_t* X = (int8_t*)ctx_buf(c, "prof_gx", 2 * xb);
-    if (!Lp || !Lw || !X) return SDPSR_OUT_OF_MEMORY;
+    int8_t* X = (int8_t*)ctx_buf(c, "prof_gx", 3 * xb);
+    if (!Lp || !Lf || !Lw || !X) return SDPSR_OUT_OF_MEMORY;
     HIP_TRY(c, hipMemcpyAsync(Lp, Lp_host, (size_t)np * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(c, hipMemcpyAsync(Lw, L_inout, (size_t)(n * n + guard) * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemsetAsync(X, 0x5A, 2 * xb, s));
+    HIP_TRY(c, hipMemsetAsync(X, 0x5A, 3 * xb, s));
     const uint8_t* Lp8 = nullptr;
     const int st = prof_label_shadow(c, Lp, np, d, width, &Lp8);
     if (st) return st;
     launch_gather_i8_sym_packed(s, n, ld, T, Lp, key, X, d, nullptr, Lp8);
     launch_gather_i8_sym_packed(s, n, ld, T, Lp, key, X + xb, d, Lw, Lp8);
+    if (X_full) {
+        HIP_TRY(c, hipMemcpyAsync(Lf, Lfull_host, (size_t)n * n * 4, hipMemcpyHostToDevice, s));
+        launch_gather_i8(s, n, ld, T, Lf, key, X + 2 * xb, d);
+        HIP_TRY(c, hipMemcpyAsync(X_full, X + 2 * xb, xb, hipMemcpyDeviceToHost, s));
+    }
     HIP_TRY(c, hipMemcpyAsync(X_plain, X, xb, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipMemcpyAsync(X_writing, X + xb, xb, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipMemcpyAsync(L_inout, Lw, (size_t)(n * n + guard) * 4, hipMemcpyDeviceToHost, s));
@@ -353,80 +281,108 @@ extern "C" int sdpsr_profile_gather_packed_w(sdpsr_ctx* c, int64_t n, int T, int
     return SDPSR_OK;
 }
 
-extern "C" int sdpsr_profile_verify_w(sdpsr_ctx* c, int64_t n, int T, int64_t d, int r, int width, const uint32_t* Lp_host,
-                                      const uint32_t* first_idx_host, const int32_t* C_host, const double* U_host, const double* coef_host,
-                                      uint64_t key, double atol, uint32_t* out) {
+// The step check "does any entry of the packed triangle differ from the representative of its class?" on caller-made inputs.  Lp: packed
+// labels <= d, first_idx: the d packed indices of the representatives, C_host: T (2 or 4) int32 channels of ld x ld.  r = -1: the channels
+// alone; r = 0 .. 4: joint with the r basis matrices U_host (r * n * n) and coefficients coef_host (r); the class draws come from key.
+int prof_verify(sdpsr_ctx* c, int64_t n, int T, int64_t d, int r, int width, const uint32_t* Lp_host, const uint32_t* first_idx_host,
+                const int32_t* C_host, const double* U_host, const double* coef_host, uint64_t key, double atol, uint32_t* out) {
     CHECK_CTX(c);
     if (!Lp_host || !first_idx_host || !C_host || !out || n < 1 || n > 8192 || d < 1 || d > (int64_t)refine_first_cap() || r < -1 || r > 4 ||
         (T != 2 && T != 4) || (r > 0 && (!U_host || !coef_host)) || !(atol > 0))
         return ctx_fail(c, SDPSR_BAD_ARGUMENT, "bad arguments");
-    const int64_t ld = round_up(n, 128), np = n * (n + 1) / 2, rr = r > 0 ? r : 0;
-    for (int64_t k = 0; k < d; ++k)
-        if ((int64_t)first_idx_host[k] >= np) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "a representative outside the packed triangle");
     hipStream_t s = c->stream;
+    const int64_t ld = round_up(n, 128), rr = r > 0 ? r : 0;
     const size_t cb = (size_t)T * ld * ld * 4;
-    uint32_t* Lp = (uint32_t*)ctx_buf(c, "prof_lp", (size_t)np * 4);
-    uint32_t* first = (uint32_t*)ctx_buf(c, "prof_first", (size_t)d * 4);
     int32_t* Cd = (int32_t*)ctx_buf(c, "prof_vc", cb);
     double* Ud = (double*)ctx_buf(c, "prof_vu", (size_t)(n * n + 1) * 4 * 8);  // + the coefficients
-    void* ref = ctx_buf(c, "prof_vref", std::max(verify_ref_bytes(d), uconst_ref_bytes(d, 1)));
-    uint32_t* hv = pinned_report(c, PINNED_VERIFY);
-    if (!Lp || !first || !Cd || !Ud || !ref || !hv) return SDPSR_OUT_OF_MEMORY;
+    void* ref = ctx_buf(c, "prof_vref", verify_ref_bytes(d));
+    if (!Cd || !Ud || !ref) return SDPSR_OUT_OF_MEMORY;
     double* coef = Ud + 4 * n * n;
-    HIP_TRY(c, hipMemcpyAsync(Lp, Lp_host, (size_t)np * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(first, first_idx_host, (size_t)d * 4, hipMemcpyHostToDevice, s));
+    ProfClasses p;
+    const int st = prof_classes_up(c, n, d, width, Lp_host, first_idx_host, &p);
+    if (st) return st;
+    // (after the last early return: coef_host may be a caller's stack variable, and prof_verdict_down waits for the stream)
     HIP_TRY(c, hipMemcpyAsync(Cd, C_host, cb, hipMemcpyHostToDevice, s));
     if (rr > 0) {
         HIP_TRY(c, hipMemcpyAsync(Ud, U_host, (size_t)rr * n * n * 8, hipMemcpyHostToDevice, s));
         HIP_TRY(c, hipMemcpyAsync(coef, coef_host, (size_t)rr * 8, hipMemcpyHostToDevice, s));
     }
-    HIP_TRY(c, hipStreamSynchronize(s));  // (nothing may be in flight on the verdict word)
-    const uint8_t* Lp8 = nullptr;
-    const int st = prof_label_shadow(c, Lp, np, d, width, &Lp8);
-    if (st) return st;
-    hv[0] = 0xDEADu;
     SigSource q;
     q.kind = r >= 0 ? SIG_JOINT_I32 : SIG_CHAN_I32, q.U = Ud, q.coef = coef, q.r = (int)rr, q.key = key, q.atol = atol, q.scale = round_scale(c, atol);
-    q.n = n, q.ld = ld, q.T = T, q.C = Cd, q.L = Lp, q.L8 = Lp8, q.packed = 1, q.lab_packed = 1;
-    const bool ran = launch_verify_no_split(s, q, d, first, ref, hv);
-    HIP_TRY(c, hipStreamSynchronize(s));
-    HIP_TRY(c, hipGetLastError());
-    if (!ran) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "no verify pass for this shape");
-    out[0] = ((const volatile uint32_t*)hv)[0];
-    out[1] = (uint32_t)verify_lds_cap();
-    return SDPSR_OK;
+    q.n = n, q.ld = ld, q.T = T, q.C = Cd, q.L = p.Lp, q.L8 = p.Lp8, q.packed = 1, q.lab_packed = 1;
+    return prof_verdict_down(c, launch_verify_no_split(s, q, d, p.first, ref, p.flag), p, out);
 }
 
-extern "C" int sdpsr_profile_verify_pair_w(sdpsr_ctx* c, int64_t n, int64_t d, int width, const uint32_t* Lp_host, const uint32_t* first_idx_host,
-                                           const double* a_host, const double* b_host, uint32_t* out) {
+// The basis check "is every one of the r (1 .. 4) basis matrices U_host (r * n * n) constant on the classes, and 0 on label 0?"; wide labels.
+int prof_basis_constant(sdpsr_ctx* c, int64_t n, int r, int64_t d, const uint32_t* Lp_host, const uint32_t* first_idx_host, const double* U_host,
+                        double atol, uint32_t* out) {
+    CHECK_CTX(c);
+    if (!Lp_host || !first_idx_host || !U_host || !out || n < 1 || n > 8192 || d < 1 || d > (int64_t)refine_first_cap() || r < 1 || r > 4 ||
+        !(atol > 0))
+        return ctx_fail(c, SDPSR_BAD_ARGUMENT, "bad arguments");
+    double* Ud = (double*)ctx_buf(c, "prof_vu", (size_t)(n * n + 1) * 4 * 8);
+    void* ref = ctx_buf(c, "prof_vref", uconst_ref_bytes(d, r));
+    if (!Ud || !ref) return SDPSR_OUT_OF_MEMORY;
+    HIP_TRY(c, hipMemcpyAsync(Ud, U_host, (size_t)r * n * n * 8, hipMemcpyHostToDevice, c->stream));
+    ProfClasses p;
+    const int st = prof_classes_up(c, n, d, 32, Lp_host, first_idx_host, &p);
+    if (st) return st;
+    const bool ran = launch_basis_constant_on_classes(c->stream, n, r, Ud, p.Lp, d, p.first, atol, round_scale(c, atol), ref, p.flag);
+    return prof_verdict_down(c, ran, p, out);
+}
+
+// The pair check "would the initial refinement of (a, b) write these labels and representatives again?" on caller-made inputs
+// (tests/test_gpu_verify_pair.py).  a_host, b_host: n x n column-major (the lower triangle is read).  More classes than one launch takes
+// (out[1]) are refused.
+int prof_verify_pair(sdpsr_ctx* c, int64_t n, int64_t d, int width, const uint32_t* Lp_host, const uint32_t* first_idx_host, const double* a_host,
+                     const double* b_host, uint32_t* out) {
     CHECK_CTX(c);
     if (!Lp_host || !first_idx_host || !a_host || !b_host || !out || n < 1 || n > 8192 || d < 1 || d > (int64_t)verify_lds_cap())
         return ctx_fail(c, SDPSR_BAD_ARGUMENT, "bad arguments");
-    const int64_t np = n * (n + 1) / 2;
-    for (int64_t k = 0; k < d; ++k)
-        if ((int64_t)first_idx_host[k] >= np) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "a representative outside the packed triangle");
-    hipStream_t s = c->stream;
-    uint32_t* Lp = (uint32_t*)ctx_buf(c, "prof_lp", (size_t)np * 4);
-    uint32_t* first = (uint32_t*)ctx_buf(c, "prof_first", (size_t)d * 4);
     double* ab = (double*)ctx_buf(c, "prof_pair_ab", (size_t)2 * n * n * 8);
-    uint32_t* hv = pinned_report(c, PINNED_VERIFY);
-    if (!Lp || !first || !ab || !hv) return SDPSR_OUT_OF_MEMORY;
-    HIP_TRY(c, hipMemcpyAsync(Lp, Lp_host, (size_t)np * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(first, first_idx_host, (size_t)d * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(ab, a_host, (size_t)n * n * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(ab + n * n, b_host, (size_t)n * n * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipStreamSynchronize(s));  // (nothing may be in flight on the verdict word)
-    const uint8_t* Lp8 = nullptr;
-    const int st = prof_label_shadow(c, Lp, np, d, width, &Lp8);
+    if (!ab) return SDPSR_OUT_OF_MEMORY;
+    HIP_TRY(c, hipMemcpyAsync(ab, a_host, (size_t)n * n * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(ab + n * n, b_host, (size_t)n * n * 8, hipMemcpyHostToDevice, c->stream));
+    ProfClasses p;
+    const int st = prof_classes_up(c, n, d, width, Lp_host, first_idx_host, &p);
     if (st) return st;
-    hv[0] = 0xDEADu;
-    const bool ran = launch_verify_pair(s, n, ab, ab + n * n, Lp, d, first, hv, Lp8);
-    HIP_TRY(c, hipStreamSynchronize(s));
-    HIP_TRY(c, hipGetLastError());
-    if (!ran) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "no pair check for this shape");
-    out[0] = ((const volatile uint32_t*)hv)[0];
-    out[1] = (uint32_t)verify_lds_cap();
-    return SDPSR_OK;
+    return prof_verdict_down(c, launch_verify_pair(c->stream, n, ab, ab + n * n, p.Lp, d, p.first, p.flag, p.Lp8), p, out);
+}
+}  // namespace
+
+// The entries (include/sdpsr_prof.h): each pass has ONE body above; the entries without a width argument are its width-32 form.
+extern "C" int sdpsr_profile_gather_packed(sdpsr_ctx* c, int64_t n, int T, int64_t d, uint64_t key, const uint32_t* Lp_host, const uint32_t* Lfull_host,
+                                           int8_t* X_plain, int8_t* X_writing, int8_t* X_full, uint32_t* L_inout, int64_t guard) {
+    if (!Lfull_host || !X_full) return c ? ctx_fail(c, SDPSR_BAD_ARGUMENT, "bad arguments") : SDPSR_BAD_ARGUMENT;
+    return prof_gather_packed(c, n, T, d, key, 32, Lp_host, Lfull_host, X_plain, X_writing, X_full, L_inout, guard);
+}
+extern "C" int sdpsr_profile_gather_packed_w(sdpsr_ctx* c, int64_t n, int T, int64_t d, uint64_t key, int width, const uint32_t* Lp_host,
+                                             int8_t* X_plain, int8_t* X_writing, uint32_t* L_inout, int64_t guard) {
+    return prof_gather_packed(c, n, T, d, key, width, Lp_host, nullptr, X_plain, X_writing, nullptr, L_inout, guard);
+}
+// mode 0: the channels alone; 1: joint with the one basis matrix U_host and coefficient coef; 2: the basis check of U_host (C_host unused)
+extern "C" int sdpsr_profile_verify(sdpsr_ctx* c, int64_t n, int T, int64_t d, int mode, const uint32_t* Lp_host, const uint32_t* first_idx_host,
+                                    const int32_t* C_host, const double* U_host, double coef, uint64_t key, double atol, uint32_t* out) {
+    if (mode == 2) return prof_basis_constant(c, n, 1, d, Lp_host, first_idx_host, U_host, atol, out);
+    if (mode != 0 && mode != 1) return c ? ctx_fail(c, SDPSR_BAD_ARGUMENT, "bad arguments") : SDPSR_BAD_ARGUMENT;
+    return prof_verify(c, n, T, d, mode == 1 ? 1 : -1, 32, Lp_host, first_idx_host, C_host, U_host, &coef, key, atol, out);
+}
+extern "C" int sdpsr_profile_verify_w(sdpsr_ctx* c, int64_t n, int T, int64_t d, int r, int width, const uint32_t* Lp_host,
+                                      const uint32_t* first_idx_host, const int32_t* C_host, const double* U_host, const double* coef_host,
+                                      uint64_t key, double atol, uint32_t* out) {
+    return prof_verify(c, n, T, d, r, width, Lp_host, first_idx_host, C_host, U_host, coef_host, key, atol, out);
+}
+extern "C" int sdpsr_profile_basis_constant(sdpsr_ctx* c, int64_t n, int r, int64_t d, const uint32_t* Lp_host, const uint32_t* first_idx_host,
+                                            const double* U_host, double atol, uint32_t* out) {
+    return prof_basis_constant(c, n, r, d, Lp_host, first_idx_host, U_host, atol, out);
+}
+extern "C" int sdpsr_profile_verify_pair(sdpsr_ctx* c, int64_t n, int64_t d, const uint32_t* Lp_host, const uint32_t* first_idx_host,
+                                         const double* a_host, const double* b_host, uint32_t* out) {
+    return prof_verify_pair(c, n, d, 32, Lp_host, first_idx_host, a_host, b_host, out);
+}
+extern "C" int sdpsr_profile_verify_pair_w(sdpsr_ctx* c, int64_t n, int64_t d, int width, const uint32_t* Lp_host, const uint32_t* first_idx_host,
+                                           const double* a_host, const double* b_host, uint32_t* out) {
+    return prof_verify_pair(c, n, d, width, Lp_host, first_idx_host, a_host, b_host, out);
 }
 
 extern "C" int sdpsr_profile_proj_coef_lower(sdpsr_ctx* c, int64_t n, int64_t r, uint64_t key, int width, const uint32_t* Lp_host,

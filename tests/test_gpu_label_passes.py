@@ -2,9 +2,9 @@
 gather in its plain and in its label-writing form, and the verify pass with its table of class representatives built in LDS
 (one launch up to a class-count cap) or by a kernel of its own (above the cap).
 
-The kernels are driven on made-up inputs through libsdpsr_prof.so (sdpsr_profile_gather_packed, sdpsr_profile_verify); every
-expectation is a NumPy restatement.  The last test goes through the product ABI: the full label matrix that a gather wrote
-must be the call's output on every route that claims it valid -- in place in a device buffer filled with garbage, on the
+The kernels are driven on made-up inputs through libsdpsr_prof.so (sdpsr_profile_gather_packed, sdpsr_profile_verify and, for
+more than one basis matrix, sdpsr_profile_verify_w and sdpsr_profile_basis_constant); every expectation is a NumPy restatement.
+The last test goes through the product ABI: the full label matrix that a gather wrote must be the call's output on every route that claims it valid -- in place in a device buffer filled with garbage, on the
 guess, on the deferred guess, and on the wrong guess."""
 import ctypes as C
 
@@ -192,6 +192,116 @@ def test_basis_constant_on_classes_verdict(pkg, gpu_ctx, d):
         U2[j, i] += 0.5
         assert _expected(n, Lp, first, Cm, U2, True) == 1
         assert _run_verify(pkg, gpu_ctx, n, 2, d, 2, Lp, first, Cm, U2)[0] == 1, (name, i, j)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the instances of the compare kernel that the cases above do not launch: r basis matrices
+# ---------------------------------------------------------------------------------------------------------------------------
+COEF = np.array([0.75, -0.5, 1.25, 0.625])  # (a needle of 0.5 in any U_k moves the projected value by far more than the rounding)
+
+
+def _basis_stack(n, d, r, Lp, rng):
+    """r basis matrices [k][column][row], each constant on the classes of Lp and 0 on label 0 (noise above the diagonal)."""
+    uvals = rng.standard_normal((r, d + 1))
+    uvals[:, 0] = 0.0
+    U = np.full((r, n, n), 12345.0)
+    for j in range(n):
+        U[:, j, j:] = uvals[:, Lp[_col_off(n, j):_col_off(n, j) + n - j]]
+    return U
+
+
+def _expected_stack(n, Lp, first, Cm, U, joint):
+    """_expected for a stack of basis matrices: any of them off is off."""
+    return int(_expected(n, Lp, first, Cm, U[0], False) or (joint and any(_expected(n, Lp, first, Cm, Uk, True) for Uk in U)))
+
+
+def _run_step(pkg, ctx, n, T, d, r, Lp, first, Cm, U, width=32):
+    """The step check: r = -1 the channels alone, r = 0 .. 4 joint with the first r matrices of U."""
+    prof = pkg._lib.load_prof_library()
+    out = (C.c_uint32 * 2)()
+    U = np.ascontiguousarray(U)
+    ctx.check(prof.sdpsr_profile_verify_w(ctx._h, n, T, d, r, width, _vp(Lp), _vp(first), _vp(Cm), _vp(U), _vp(COEF), KEY, 1e-6, out))
+    return int(out[0]), int(out[1])
+
+
+def _run_basis(pkg, ctx, n, d, r, Lp, first, U):
+    prof = pkg._lib.load_prof_library()
+    out = (C.c_uint32 * 2)()
+    U = np.ascontiguousarray(U)
+    ctx.check(prof.sdpsr_profile_basis_constant(ctx._h, n, r, d, _vp(Lp), _vp(first), _vp(U), 1e-6, out))
+    return int(out[0]), int(out[1])
+
+
+def _basis_needles(n, r, Lp, first, Cm, U, places, run):
+    """One entry of one U_k off at each place, k going round so that every one of the r matrices is hit; run(U) = the GPU's verdict."""
+    for idx, (name, e) in enumerate(places.items()):
+        i, j = _ij(n, e)
+        U2 = U.copy()
+        U2[idx % r, j, i] += 0.5
+        assert _expected_stack(n, Lp, first, Cm, U2, True) == 1, name
+        assert run(U2) == 1, (name, i, j, idx % r)
+
+
+@pytest.mark.parametrize("r", [1, 2, 3, 4])
+@pytest.mark.parametrize("d", [1, 34, CAP, CAP + 1])
+def test_basis_check_of_r_matrices(pkg, gpu_ctx, r, d):
+    """Every instance of the basis check, in both forms (table in LDS up to CAP classes, a table kernel above): 0 on matrices that are
+    constant on the classes and 0 on label 0; 1 with one entry of one U_k off, each k and each place at least once."""
+    n = 57
+    rng = np.random.default_rng(9000 + 10 * d + r)
+    Lp, first, Cm, _, places = _verify_case(n, 2, d, rng)
+    U = _basis_stack(n, d, r, Lp, rng)
+    assert len(places) == 4 >= r
+    assert _expected_stack(n, Lp, first, Cm, U, True) == 0
+    assert _run_basis(pkg, gpu_ctx, n, d, r, Lp, first, U) == (0, CAP)
+    _basis_needles(n, r, Lp, first, Cm, U, places, lambda U2: _run_basis(pkg, gpu_ctx, n, d, r, Lp, first, U2)[0])
+
+
+def test_basis_check_where_a_workgroup_walks_two_columns(pkg, gpu_ctx):
+    n, d = 2049, 34  # 2048 workgroups: the first one takes columns 0 and 2048
+    rng = np.random.default_rng(2049)
+    Lp, first, Cm, _, places = _verify_case(n, 2, d, rng)
+    U = _basis_stack(n, d, 1, Lp, rng)
+    assert _run_basis(pkg, gpu_ctx, n, d, 1, Lp, first, U)[0] == 0
+    _basis_needles(n, 1, Lp, first, Cm, U, places, lambda U2: _run_basis(pkg, gpu_ctx, n, d, 1, Lp, first, U2)[0])
+
+
+def _step_case(pkg, ctx, n, T, d, r, width, seed):
+    """Clean -> 0; one channel entry off -> 1 at each place; r >= 1: one basis entry off -> 1.  The NumPy expectation flips first."""
+    rng = np.random.default_rng(seed)
+    Lp, first, Cm, _, places = _verify_case(n, T, d, rng)
+    assert all(np.count_nonzero(Lp == Lp[e]) >= 2 for name, e in places.items() if name != "label_zero")
+    joint = r >= 0
+    U = _basis_stack(n, d, max(r, 1), Lp, rng)
+    assert _expected_stack(n, Lp, first, Cm, U, joint) == 0
+    verdict, cap = _run_step(pkg, ctx, n, T, d, r, Lp, first, Cm, U, width)
+    assert verdict == 0
+    for name, e in places.items():
+        i, j = _ij(n, e)
+        t = (i + j) % T
+        C2 = Cm.copy()
+        C2[t, j, i] += 1 if name != "label_zero" else 5
+        assert _expected_stack(n, Lp, first, C2, U, joint) == 1, name
+        assert _run_step(pkg, ctx, n, T, d, r, Lp, first, C2, U, width)[0] == 1, (name, i, j, t)
+    if r >= 1:
+        _basis_needles(n, r, Lp, first, Cm, U, places, lambda U2: _run_step(pkg, ctx, n, T, d, r, Lp, first, Cm, U2, width)[0])
+    return cap
+
+
+@pytest.mark.parametrize("r", [-1, 0, 2, 3, 4], ids=["channels", "joint_r0", "joint_r2", "joint_r3", "joint_r4"])
+@pytest.mark.parametrize("T", [2, 4])
+def test_two_launch_step_check_of_every_r(pkg, gpu_ctx, T, r):
+    """One class above the cap, where a kernel of its own builds the table: the instances that test_verify_verdict (r = 1) leaves out.
+    57 * 58 / 2 = 1653 packed entries hold 257 classes with the needle places in classes of two entries or more (_verify_case)."""
+    d = CAP + 1
+    assert d > _step_case(pkg, gpu_ctx, 57, T, d, r, 32, seed=7000 + 10 * T + r)
+
+
+@pytest.mark.parametrize("width", [32, 8])
+@pytest.mark.parametrize("T", [2, 4])
+def test_one_launch_step_check_joint_with_three_matrices(pkg, gpu_ctx, T, width):
+    """r = 3 in the one-launch form, at either label width: the only r that no other test launches there."""
+    assert 34 <= _step_case(pkg, gpu_ctx, 57, T, 34, 3, width, seed=7300 + 10 * T + width)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
