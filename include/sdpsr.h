@@ -764,7 +764,12 @@ int sdpsr_eigen_decomposition_batched(sdpsr_ctx* ctx, int64_t n, const uint32_t*
                                       int64_t count, const double* values, int32_t* status, int32_t* neig,
                                       int32_t* nclasses, int mem);
 /* Symmetric eigendecomposition used by the path (eigen(A), :246): ascending values,
-   orthonormal vectors (column-major n x n, overwrites nothing of A). */
+   orthonormal vectors (column-major n x n, overwrites nothing of A).  Only the lower triangle of A is referenced.
+   Range: the solver's norms are sums of squares, so the copy the entry point makes of A is multiplied by a power of two -- exact --
+   when max |a| over the lower triangle lies outside [2^-400, 2^400], and the eigenvalues are multiplied back (on the device, no host
+   wait): every finite input whose eigenvalues are representable is solved to the same relative accuracy, subnormal entries
+   included; inside the window no bit of the result differs from a solver without the scaling.  A NaN or Inf entry
+   is not scaled away: the solver's own checks see it (n > 128: SDPSR_SOLVER_ERROR from the check of the tridiagonal matrix). */
 int sdpsr_syev_f64(sdpsr_ctx* ctx, int64_t n, const double* A, double* values, double* vectors,
                    int mem);
 

@@ -237,6 +237,32 @@ int sdpsr_profile_copy_cols(sdpsr_ctx* ctx, int64_t n, int64_t count, const int3
                             int64_t ld_src, int64_t scols, double* dst_inout, int64_t ld_dst, int64_t dcols, int64_t guard);
 int sdpsr_profile_clamptol(sdpsr_ctx* ctx, int64_t len, double* a_inout, double atol, int64_t guard);
 
+/* ---- The stages of the dense symmetric eigensolver on caller-made inputs (tests/test_gpu_eigen_stages.py). ----
+   Conventions of the dense-step entries above.  2 <= n <= ld <= 4096, ld a multiple of 128: the padded column-major square that
+   sdpsr_syev_f64 makes (padding rows and columns n .. ld-1 zero).  Anything else: SDPSR_BAD_ARGUMENT before any upload. */
+
+/* launch_sytrd (A = Q T Q', Q = H_0 ... H_{n-2}, H_j = I - tau_j v_j v_j', v_j = [0 .. 0, 1 in row j+1, A[j+2 .., j]]: LAPACK dsytrd,
+   uplo = 'L') on the ctx's own buffers, in the form the ctx's flags choose (default: row form up to 2048 and the panel / row hybrid
+   beyond; SDPSR_FLAG_SYTRD_PANELS; SDPSR_FLAG_SYTRD_ONE_LAUNCH); a second call of the same shape in one ctx replays the cached graph.
+   A_inout: ld * ld + guard, lower triangle referenced; d_inout, e_inout, tau_inout: n + guard each.
+   May write: the leading n x n of A (the row form mirrors the lower triangle into the upper one; the reflectors go below the
+   subdiagonal, the diagonal and subdiagonal are NOT kept up to date), d[0 .. n), e[0 .. n-1), tau[0 .. n-1).
+   Never written: rows and columns n .. ld-1 of A, e[n-1], tau[n-1], the guards. */
+int sdpsr_profile_sytrd(sdpsr_ctx* ctx, int64_t n, int64_t ld, double* A_inout, double* d_inout, double* e_inout, double* tau_inout,
+                        int64_t guard);
+/* backtransform_prepare, then backtransform_apply, both on the ctx's main stream: Z <- H_0 ... H_{n-2} Z in compact-WY blocks of 128
+   reflectors, last block first.  A_host: ld x ld, only the reflector entries (rows j+2 .. n-1 of column j <= n-3) are read;
+   tau_host: n - 1.  Z_inout: ld * ld + guard, uploaded as the caller filled it; the products run over all ld x ld of it.  What may
+   CHANGE is rows 1 .. n-1: row 0, rows n .. ld-1 and -- zero on entry -- columns n .. ld-1 come back as they were.  Never the guards. */
+int sdpsr_profile_backtransform(sdpsr_ctx* ctx, int64_t n, int64_t ld, const double* A_host, const double* tau_host, double* Z_inout,
+                                int64_t guard);
+/* The tridiagonal problem d_host (n), e_host (n - 1) as syev_device issues it: zero fill of Z, descriptor upload, launch_stedc_check,
+   launch_stedc, launch_stedc_check.  w_inout: n + guard, w[0 .. n) written (ascending).  Z_inout: ld * ld + guard, all ld x ld
+   written: eigenvectors in the leading n x n, exact zeros in rows and columns n .. ld-1.  Never the guards.
+   SDPSR_SOLVER_ERROR, with the outputs filled, when a check raises its flag. */
+int sdpsr_profile_stedc(sdpsr_ctx* ctx, int64_t n, int64_t ld, const double* d_host, const double* e_host, double* w_inout, double* Z_inout,
+                        int64_t guard);
+
 #ifdef __cplusplus
 }
 #endif

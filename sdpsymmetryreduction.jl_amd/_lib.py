@@ -296,5 +296,12 @@ def load_prof_library():
     lib.sdpsr_profile_copy_cols.argtypes = [vp, i64, i64, vp, vp, vp, i64, i64, vp, i64, i64, i64]
     lib.sdpsr_profile_clamptol.restype = C.c_int
     lib.sdpsr_profile_clamptol.argtypes = [vp, i64, vp, f64, i64]
+    # the stages of the dense symmetric eigensolver on caller-made inputs (tests)
+    lib.sdpsr_profile_sytrd.restype = C.c_int
+    lib.sdpsr_profile_sytrd.argtypes = [vp, i64, i64, vp, vp, vp, vp, i64]
+    lib.sdpsr_profile_backtransform.restype = C.c_int
+    lib.sdpsr_profile_backtransform.argtypes = [vp, i64, i64, vp, vp, vp, i64]
+    lib.sdpsr_profile_stedc.restype = C.c_int
+    lib.sdpsr_profile_stedc.argtypes = [vp, i64, i64, vp, vp, vp, vp, i64]
     _prof = lib
     return lib

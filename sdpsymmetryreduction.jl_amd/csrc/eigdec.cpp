@@ -609,11 +609,16 @@ int sdpsr_syev_f64(sdpsr_ctx* c, int64_t n, const double* A, double* values, dou
     if (st) return st;
     const int64_t ld = round_up(n, 128);
     double* Ap = (double*)ctx_buf(c, "ev_pad", (size_t)ld * ld * 8);
-    if (!Ap) return SDPSR_OUT_OF_MEMORY;
+    void* scale = ctx_buf(c, "ev_scale", 64);
+    if (!Ap || !scale) return SDPSR_OUT_OF_MEMORY;
     HIP_TRY(c, hipMemsetAsync(Ap, 0, (size_t)ld * ld * 8, c->stream));
-    HIP_TRY(c, hipMemcpy2DAsync(Ap, ld * 8, dA, n * 8, n * 8, n, hipMemcpyDeviceToDevice, c->stream));
+    // the copy into the padded buffer brings max |a| into [2^-400, 2^400] by a power of two (kernels_sytrd.hip: the solver's
+    // norms are sums of squares); the factor stays on the device and is 1 for every input inside the window
+    launch_syev_scaled_copy(c->stream, n, dA, ld, Ap, scale);
+    HIP_TRY(c, hipGetLastError());
     st = syev_device(c, n, Ap, ld, dW);
     if (st) return st;
+    launch_syev_unscale_values(c->stream, n, dW, scale);
     HIP_TRY(c, hipMemcpy2DAsync(dV, n * 8, Ap, ld * 8, n * 8, n, hipMemcpyDeviceToDevice, c->stream));
     st = out_finish(c, vectors, dV, (size_t)n * n, mem);
     if (st) return st;

@@ -20,13 +20,6 @@ bool launch_small_syev(hipStream_t s, int64_t n, double* A, int64_t lda, double*
 void launch_bt_extract_panel(hipStream_t s, int64_t n, int64_t ld, const double* A, int64_t j0, int64_t r0, double* Vp,
                              double* VpT);
 void launch_bt_larft(hipStream_t s, const double* G, const double* tau, int64_t nblk, int64_t n, double* T);
-// kernels_stedc.hip: divide and conquer for the tridiagonal problem
-size_t stedc_workspace_bytes(int64_t ld);
-size_t stedc_descriptors(int64_t ld, std::vector<int>& out);
-void* stedc_descriptor_slot(void* ws, int64_t ld);
-bool launch_stedc(hipStream_t s, int64_t n, int64_t ld, const double* d, const double* e, double* w, double* Z, double* W1, double* W2,
-                  void* ws);
-void launch_stedc_check(hipStream_t s, int64_t n, const double* a, const double* b, int pre, int* info);
 
 // Z <- Q Z with Q = H_0 ... H_{n-2} from the tridiagonalisation (reflectors below the subdiagonal of
 // A, tau): compact-WY blocks of 128 reflectors, last block first, every product on the fp64
@@ -34,7 +27,7 @@ void launch_stedc_check(hipStream_t s, int64_t n, const double* a, const double*
 // Two halves: what depends on the reflectors only -- the panels V_b, their Gram matrices, every T_b, X_b = T_b' V_b' --
 // is launched by backtransform_prepare and runs on the side stream BESIDE the tridiagonal solver (which touches neither
 // A nor these buffers); backtransform_apply then needs two products per block, W = V_b' Z and Z -= X_b' W.
-static int backtransform_prepare(sdpsr_ctx* c, int64_t n, const double* A, int64_t ld, const double* tau) {
+int backtransform_prepare(sdpsr_ctx* c, int64_t n, const double* A, int64_t ld, const double* tau) {
     hipStream_t s = c->stream;
     const int64_t nblk = (n - 1 + 127) / 128;
     const size_t per = (size_t)ld * 128 * 8;
@@ -61,7 +54,7 @@ static int backtransform_prepare(sdpsr_ctx* c, int64_t n, const double* A, int64
     if (hipGetLastError() != hipSuccess) return ctx_fail(c, SDPSR_HIP_ERROR, "back-transformation launch failed");
     return SDPSR_OK;
 }
-static int backtransform_apply(sdpsr_ctx* c, int64_t n, int64_t ld, double* Z) {
+int backtransform_apply(sdpsr_ctx* c, int64_t n, int64_t ld, double* Z) {
     hipStream_t s = c->stream;
     const int64_t nblk = (n - 1 + 127) / 128;
     double* VpAll = (double*)ctx_buf(c, "bt_vp_all", (size_t)ld * 128 * 8 * std::max<int64_t>(nblk, 1));

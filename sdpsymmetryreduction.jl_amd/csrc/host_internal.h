@@ -406,6 +406,22 @@ size_t gram_tall_partial_doubles(int64_t len, int64_t m);
 void launch_gram_tall(hipStream_t s, int64_t len, int64_t m, const double* W, double* partials, double* host_G);
 void launch_apply_upper_inverse(hipStream_t s, int64_t len, int64_t m, double* W, const int32_t* piv, const double* Xrow);
 bool launch_small_syev(hipStream_t s, int64_t n, double* A, int64_t lda, double* w, double* Vtmp, int* info);
+// kernels_sytrd.hip: the range of sdpsr_syev_f64.  dst (ld x ld, padding zeroed by the caller) <- src (n x n) with the lower triangle
+// times 2^-e, e chosen on the device from max |a| (0 inside [2^-400, 2^400]); slot: 16 bytes of device memory that keep 2^e for
+// launch_syev_unscale_values (w *= 2^e).  With e = 0 neither changes a bit.
+void launch_syev_scaled_copy(hipStream_t s, int64_t n, const double* src, int64_t ld, double* dst, void* slot);
+void launch_syev_unscale_values(hipStream_t s, int64_t n, double* w, const void* slot);
+// kernels_stedc.hip: divide and conquer for the tridiagonal problem (eigen.cpp has the calling sequence)
+size_t stedc_workspace_bytes(int64_t ld);
+size_t stedc_descriptors(int64_t ld, std::vector<int>& out);
+void* stedc_descriptor_slot(void* ws, int64_t ld);
+bool launch_stedc(hipStream_t s, int64_t n, int64_t ld, const double* d, const double* e, double* w, double* Z, double* W1, double* W2,
+                  void* ws);
+void launch_stedc_check(hipStream_t s, int64_t n, const double* a, const double* b, int pre, int* info);
+// eigen.cpp: the two halves of the back-transformation Z <- Q Z, both issued on c->stream (syev_device points c->stream at the
+// side stream around the first half when it can fork; the test entry sdpsr_profile_backtransform runs both on the main stream)
+int backtransform_prepare(sdpsr_ctx* c, int64_t n, const double* A, int64_t ld, const double* tau);
+int backtransform_apply(sdpsr_ctx* c, int64_t n, int64_t ld, double* Z);
 
 // setup_csr.cpp: what a CSR input means, for every entry that takes one (the setup entries, sdpsr_reduce_constraints_csr).
 // Validates (SDPSR_BAD_ARGUMENT with a message, before any kernel) and brings the rows into canonical form.

@@ -1614,4 +1614,68 @@ bool launch_small_syev(hipStream_t s, int64_t n, double* A, int64_t lda, double*
     return true;
 }
 
+// ---------------------------------------------------------------------------
+// Range of sdpsr_syev_f64.  The reflector norms of the tridiagonalisation and the stopping rule of the Jacobi kernels are
+// plain sums of squares: with entries below 2^-511 every square is 0, every column takes the H = I branch (the Jacobi
+// kernel stops before its first rotation) and the answer is wrong with a clean status.  So the entry point's copy into the
+// padded buffer multiplies by a power of two -- exact -- when max |a| over the referenced (lower) triangle lies outside
+// [2^-400, 2^400], and the eigenvalues are multiplied back at the end.  Everything stays on the device: slot[0] = bit pattern
+// of max |a| (zeroed by the caller), slot[1] = the factor the eigenvalues are multiplied by (1.0 inside the window, where
+// both multiplications change no bit).  A NaN or Inf entry leaves the factor at 1: the solver's own checks report it.
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) syev_absmax_kernel(int64_t n, const double* __restrict__ A, unsigned long long* __restrict__ slot) {
+    unsigned long long m = 0;
+    const int64_t tot = n * n;
+    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < tot; t += (int64_t)gridDim.x * 256) {
+        const int64_t j = t / n, i = t - j * n;
+        if (i < j) continue;  // only the lower triangle is referenced
+        const unsigned long long b = (unsigned long long)__double_as_longlong(A[t]) & 0x7FFFFFFFFFFFFFFFull;
+        m = b > m ? b : m;  // non-negative doubles order like their bit patterns (NaN above Inf)
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long x = __shfl_down(m, o, 64);
+        m = x > m ? x : m;
+    }
+    if ((threadIdx.x & 63) == 0 && m) atomicMax(slot, m);
+}
+
+__device__ __forceinline__ int syev_scale_exponent(unsigned long long amax_bits) {
+    if (amax_bits == 0 || amax_bits >= 0x7FF0000000000000ull) return 0;  // zero matrix; Inf / NaN
+    const int e = (int)(amax_bits >> 52) - 1023;                        // (subnormal: -1023)
+    if (e >= -400 && e <= 400) return 0;
+    return e < -1000 ? -1000 : (e > 1000 ? 1000 : e);  // 2^1000 brings every subnormal into the normal range; 2^-+e are normal numbers
+}
+
+// dst (ld x ld, column-major; the caller zeroed the padding) <- src (n x n) with the lower triangle times 2^-e
+__global__ void __launch_bounds__(256) syev_scaled_copy_kernel(int64_t n, const double* __restrict__ src, int64_t ld, double* __restrict__ dst,
+                                                               unsigned long long* __restrict__ slot) {
+    const int e = syev_scale_exponent(slot[0]);
+    const double f = __longlong_as_double((long long)(1023 - e) << 52);
+    const int64_t tot = n * n;
+    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < tot; t += (int64_t)gridDim.x * 256) {
+        const int64_t j = t / n, i = t - j * n;
+        const double v = src[t];
+        dst[i + j * ld] = i >= j ? v * f : v;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) slot[1] = (unsigned long long)(1023 + e) << 52;  // 2^e, for the eigenvalues
+}
+
+__global__ void __launch_bounds__(256) syev_unscale_values_kernel(int64_t n, double* __restrict__ w, const unsigned long long* __restrict__ slot) {
+    const double f = __longlong_as_double((long long)slot[1]);
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) w[i] *= f;
+}
+
+void launch_syev_scaled_copy(hipStream_t s, int64_t n, const double* src, int64_t ld, double* dst, void* slot) {
+    const int64_t tot = n * n;
+    const unsigned grid = (unsigned)std::min<int64_t>((tot + 255) / 256, 4096);
+    hipMemsetAsync(slot, 0, 16, s);
+    syev_absmax_kernel<<<grid, 256, 0, s>>>(n, src, (unsigned long long*)slot);
+    syev_scaled_copy_kernel<<<grid, 256, 0, s>>>(n, src, ld, dst, (unsigned long long*)slot);
+}
+void launch_syev_unscale_values(hipStream_t s, int64_t n, double* w, const void* slot) {
+    syev_unscale_values_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(n, w, (const unsigned long long*)slot);
+}
+
 }  // namespace sdpsr

@@ -1032,6 +1032,106 @@ extern "C" int sdpsr_profile_clamptol(sdpsr_ctx* c, int64_t len, double* a_inout
     return st ? st : ds_finish(c);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// The stages of the dense symmetric eigensolver (eigen.cpp: syev_device) on caller-made inputs (tests/test_gpu_eigen_stages.py), by
+// the conventions of the entries above.  Orders 2 <= n <= ld <= 4096, ld a multiple of 128 (the padded square sdpsr_syev_f64 makes).
+// ---------------------------------------------------------------------------------------------------------------------------
+namespace {
+bool es_shape_ok(int64_t n, int64_t ld, int64_t guard) { return n >= 2 && ld >= n && ld <= DS_MAX_N && ld % 128 == 0 && ds_guard_ok(guard); }
+}  // namespace
+
+// launch_sytrd on the buffers syev_device itself hands it ("ev_pad", "ev_val", "eig_E", "eig_tau", "eig_sytrd_ws"), so that a second
+// call of the same shape in one ctx replays the cached graph.  May write: the leading n x n of A (the row form mirrors the lower
+// triangle into the upper one first; d, e stay in the arrays, the reflectors go below the subdiagonal), d[0 .. n), e[0 .. n-1),
+// tau[0 .. n-1).  Never: rows / columns n .. ld-1 of A, e[n-1], tau[n-1], the guards.
+extern "C" int sdpsr_profile_sytrd(sdpsr_ctx* c, int64_t n, int64_t ld, double* A_inout, double* d_inout, double* e_inout, double* tau_inout,
+                                   int64_t guard) {
+    CHECK_CTX(c);
+    if (!A_inout || !d_inout || !e_inout || !tau_inout || !es_shape_ok(n, ld, guard)) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "sytrd: bad arguments");
+    const size_t an = (size_t)ld * ld + (size_t)guard, vn = (size_t)n + (size_t)guard;
+    double* A = (double*)ctx_buf(c, "ev_pad", an * 8);
+    double* d = (double*)ctx_buf(c, "ev_val", vn * 8);
+    double* e = (double*)ctx_buf(c, "eig_E", vn * 8);
+    double* tau = (double*)ctx_buf(c, "eig_tau", vn * 8);
+    double* ws = (double*)ctx_buf(c, "eig_sytrd_ws", sytrd_workspace_doubles(n, ld) * sizeof(double));
+    if (!A || !d || !e || !tau || !ws) return SDPSR_OUT_OF_MEMORY;
+    int st = ds_up(c, A, A_inout, an);
+    if (!st) st = ds_up(c, d, d_inout, vn);
+    if (!st) st = ds_up(c, e, e_inout, vn);
+    if (!st) st = ds_up(c, tau, tau_inout, vn);
+    if (st) return st;
+    launch_sytrd(c, n, A, ld, d, e, tau, ws);
+    st = ds_down(c, A_inout, A, an);
+    if (!st) st = ds_down(c, d_inout, d, vn);
+    if (!st) st = ds_down(c, e_inout, e, vn);
+    if (!st) st = ds_down(c, tau_inout, tau, vn);
+    return st ? st : ds_finish(c);
+}
+
+// backtransform_prepare, then backtransform_apply, both on the main stream (the branch syev_device takes when the side stream cannot
+// be forked): Z <- H_0 ... H_{n-2} Z, reflectors below the subdiagonal of A_host (ld x ld; nothing else of it is read), tau_host: n - 1.
+// Z_inout: ld x ld + guard, uploaded as the caller filled it (the driver's padding rows and columns are zero).  The products run over
+// all ld x ld of Z; what can CHANGE is rows 1 .. n-1 of it -- row 0, rows n .. ld-1 and, with zero padding columns, those columns
+// come back with the values they had -- and never the guards.
+extern "C" int sdpsr_profile_backtransform(sdpsr_ctx* c, int64_t n, int64_t ld, const double* A_host, const double* tau_host, double* Z_inout,
+                                           int64_t guard) {
+    CHECK_CTX(c);
+    if (!A_host || !tau_host || !Z_inout || !es_shape_ok(n, ld, guard)) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "backtransform: bad arguments");
+    const size_t in = (size_t)ld * ld, zn = in + (size_t)guard;
+    double* A = (double*)ctx_buf(c, "prof_es_a", in * 8);
+    double* tau = (double*)ctx_buf(c, "prof_es_tau", (size_t)n * 8);
+    double* Z = (double*)ctx_buf(c, "prof_es_z", zn * 8);
+    if (!A || !tau || !Z) return SDPSR_OUT_OF_MEMORY;
+    int st = ds_up(c, A, A_host, in);
+    if (!st) st = ds_up(c, tau, tau_host, (size_t)n - 1);
+    if (!st) st = ds_up(c, Z, Z_inout, zn);
+    if (!st) st = backtransform_prepare(c, n, A, ld, tau);
+    if (!st) st = backtransform_apply(c, n, ld, Z);
+    if (!st) st = ds_down(c, Z_inout, Z, zn);
+    return st ? st : ds_finish(c);
+}
+
+// The tridiagonal problem T = tridiag(e_host (n - 1), d_host (n), e_host) as syev_device issues it: zero fill of Z, upload of the merge
+// descriptors, launch_stedc_check, launch_stedc, launch_stedc_check.  w_inout (n + guard): w[0 .. n) written, ascending.  Z_inout
+// (ld x ld + guard): all ld x ld written -- the eigenvectors in the leading n x n, exact zeros in rows and columns n .. ld-1.
+// SDPSR_SOLVER_ERROR (outputs filled) when a check raises the flag.
+extern "C" int sdpsr_profile_stedc(sdpsr_ctx* c, int64_t n, int64_t ld, const double* d_host, const double* e_host, double* w_inout, double* Z_inout,
+                                   int64_t guard) {
+    CHECK_CTX(c);
+    if (!d_host || !e_host || !w_inout || !Z_inout || !es_shape_ok(n, ld, guard)) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "stedc: bad arguments");
+    hipStream_t s = c->stream;
+    const size_t in = (size_t)ld * ld, zn = in + (size_t)guard, wn = (size_t)n + (size_t)guard;
+    double* d = (double*)ctx_buf(c, "prof_es_d", (size_t)n * 8);
+    double* e = (double*)ctx_buf(c, "eig_E", (size_t)n * 8);
+    double* w = (double*)ctx_buf(c, "prof_es_w", wn * 8);
+    double* Z = (double*)ctx_buf(c, "prof_es_z", zn * 8);
+    int* info = (int*)ctx_buf(c, "eig_info", 64);
+    void* dws = ctx_buf(c, "eig_dc_ws", stedc_workspace_bytes(ld));
+    double* W1 = (double*)ctx_buf(c, "eig_dc_w1", in * 8);
+    double* W2 = (double*)ctx_buf(c, "eig_dc_w2", in * 8);
+    if (!d || !e || !w || !Z || !info || !dws || !W1 || !W2) return SDPSR_OUT_OF_MEMORY;
+    int st = ds_up(c, d, d_host, (size_t)n);
+    if (!st) st = ds_up(c, e, e_host, (size_t)n - 1);
+    if (!st) st = ds_up(c, w, w_inout, wn);
+    if (!st) st = ds_up(c, Z, Z_inout, zn);
+    if (st) return st;
+    HIP_TRY(c, hipMemsetAsync(Z, 0, in * 8, s));
+    std::vector<int> desc;
+    const size_t db = stedc_descriptors(ld, desc);
+    st = h2d_sync(c, stedc_descriptor_slot(dws, ld), desc.data(), db);
+    if (st) return st;
+    launch_stedc_check(s, n, d, e, 1, info);
+    if (!launch_stedc(s, n, ld, d, e, w, Z, W1, W2, dws)) return ctx_fail(c, SDPSR_HIP_ERROR, "stedc: launch failed");
+    launch_stedc_check(s, n, w, nullptr, 0, info);
+    int hinfo[2] = {0, 0};
+    HIP_TRY(c, hipMemcpyAsync(hinfo, info, 8, hipMemcpyDeviceToHost, s));
+    st = ds_down(c, w_inout, w, wn);
+    if (!st) st = ds_down(c, Z_inout, Z, zn);
+    if (!st) st = ds_finish(c);
+    if (st) return st;
+    return hinfo[0] ? ctx_fail(c, SDPSR_SOLVER_ERROR, "stedc: the checks raised info = " + std::to_string(hinfo[0])) : SDPSR_OK;
+}
+
 extern "C" int sdpsr_profile_kernel(sdpsr_ctx* c, int kind, int64_t n, int64_t aux, int reps,
                                     double* ms_per_launch) {
     CHECK_CTX(c);
