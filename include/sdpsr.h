@@ -150,7 +150,14 @@ enum {
        pass streams the 32-bit labels.  By default a reduction that checks the recorded initial partition (<= 255 classes)
        instead of rebuilding it narrows the packed labels to bytes once, and the pair check, the dot-product pass, the
        channel gathers and the verify passes of that and the following restarts stream the bytes.  Same results bit for bit. */
-    SDPSR_FLAG_WIDE_LOOP_LABELS = 1u << 16
+    SDPSR_FLAG_WIDE_LOOP_LABELS = 1u << 16,
+    /* A/B: the module growth of blockDiagonalize keeps its scratch the way it did before the small-module route stopped
+       needing it: whole-buffer zero fills of the basis, the candidate block and the scratch matrix, the stacked product into
+       the scratch matrix and a device copy back behind the basis, the seed vector and its normalisation as two launches, the
+       lift's clamp as a pass of its own, and the row-major copy of Q_hat made by sdpsr_block_images.  By default (small
+       modules, w <= 64, solved on the host) only the padding rows n .. ld-1 are zeroed, the stacked product is written in
+       place, the seed is one launch, and the lift stores Q_hat clamped in both layouts.  Same results bit for bit. */
+    SDPSR_FLAG_MODULE_SCRATCH_FILLS = 1u << 17
 };
 
 typedef struct sdpsr_opts {

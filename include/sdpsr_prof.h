@@ -160,6 +160,31 @@ int sdpsr_profile_normalize_columns(sdpsr_ctx* ctx, int64_t n, int64_t ldx, int6
                                     double* H_inout, double* norm_inout, int64_t guard);
 int sdpsr_profile_random_vector(sdpsr_ctx* ctx, int64_t n, uint64_t key, double* x_inout, int64_t guard);
 
+/* ---- The module growth's scratch discipline (tests/test_gpu_module_scratch.py). ----
+   Each of the three kernel entries runs the form the ctx's flags choose: by default the one-launch form, under
+   SDPSR_FLAG_MODULE_SCRATCH_FILLS the separate launches it replaced.  Conventions of the module-kernel entries above. */
+
+/* Every device buffer of the ctx whose name starts with "cm_" (the module growth's scratch), and "bd_qrm", is filled with the
+   NaN pattern 0x7FF85A5ADEADBEEF after a stream synchronisation: whatever a later call reads of them without writing it first
+   shows in its results. */
+int sdpsr_profile_poison_scratch(sdpsr_ctx* ctx);
+/* The stacked product written in place: M[:, w + c] = sum_{t < kk} M[:, t] S[t + c lds], c < ncols -- out = In + w ldi, ldo = ldi,
+   alpha = 1, beta = 0, as Module::apply_stacked calls it.  M_inout: ldi * mcols + guard with mcols >= max(kk, w + ncols); kk <= 512,
+   ncols <= 512, 1 <= w.  Default form: launch_tall_times_small_rows, report[0] = 1; where it refuses (ncols > 64) or under the flag:
+   launch_tall_times_small into a scratch matrix and a copy of rows < n back, report[0] = 0. */
+int sdpsr_profile_stacked_in_place(sdpsr_ctx* ctx, int64_t n, int64_t ldi, int64_t kk, int64_t lds, int64_t ncols, int64_t w, int64_t mcols,
+                                   double* M_inout, const double* S_host, int64_t guard, int32_t* report);
+/* The lift Qcm = clamptol(In S, atol) (n x S1, ld n) and its row-major copy Qrm[i S1 + c]; Qcm_inout, Qrm_inout: n * S1 + guard each.
+   Default: launch_lift_clamped (S1 <= 64, else SDPSR_BAD_ARGUMENT); under the flag: launch_tall_times_small, launch_clamptol,
+   launch_transpose_to_rowmajor. */
+int sdpsr_profile_lift(sdpsr_ctx* ctx, int64_t n, int64_t ldi, int64_t kk, int64_t lds, int64_t S1, double atol, const double* In_host,
+                       const double* S_host, double* Qcm_inout, double* Qrm_inout, int64_t guard);
+/* The seed: x[i] = 2 u(key, i + 1) - 1, h = x / |x|, norm[0] = |x|; x_inout, h_inout: n + guard, norm_inout: 1 + guard.  Default:
+   launch_seed_vector; under the flag: launch_random_vector, then launch_normalize_columns with one run. */
+int sdpsr_profile_seed_vector(sdpsr_ctx* ctx, int64_t n, uint64_t key, double* x_inout, double* h_inout, double* norm_inout, int64_t guard);
+/* *current = 1 when the ctx holds "bd_qrm" as the row-major copy of the Q_hat in "bd_qhat" (sdpsr_block_images then skips its transpose) */
+int sdpsr_profile_qrm_current(sdpsr_ctx* ctx, int32_t* current);
+
 /* ---- The steps of blockDiagonalize(P; complex = true) on caller-made inputs (tests/test_gpu_complex_steps.py). ----
    Conventions of the module-kernel entries above.  A complex matrix is two column-major planes of doubles (real, imaginary) with leading
    dimension n.  `route` 0 = the one-workgroup kernels the driver takes for n <= 64 (refused above 64), 1 = the route through the real symmetric

@@ -38,6 +38,7 @@ FLAG_COUPLING_ON_HOST = 1 << 13
 FLAG_SYTRD_ONE_LAUNCH = 1 << 14
 FLAG_WAIT_FOR_EVERY_VERDICT = 1 << 15
 FLAG_WIDE_LOOP_LABELS = 1 << 16
+FLAG_MODULE_SCRATCH_FILLS = 1 << 17
 BASIS_IMAGE_KERNELS = {"auto": 0, "two_stage": 1, "outer": 2, "chunk": 3}
 # sdpsr_basis_image: *route
 BI_ROUTE_COMMUTATIVE, BI_ROUTE_BLOCKS, BI_ROUTE_TWO_STAGE, BI_ROUTE_OUTER, BI_ROUTE_CHUNK = 1, 2, 3, 4, 5
@@ -274,6 +275,17 @@ def load_prof_library():
     lib.sdpsr_profile_normalize_columns.argtypes = [vp, i64, i64, i64, i64, vp, vp, vp, i64]
     lib.sdpsr_profile_random_vector.restype = C.c_int
     lib.sdpsr_profile_random_vector.argtypes = [vp, i64, C.c_uint64, vp, i64]
+    # the module growth's scratch discipline (tests): each runs the form the ctx's flags choose
+    lib.sdpsr_profile_poison_scratch.restype = C.c_int
+    lib.sdpsr_profile_poison_scratch.argtypes = [vp]
+    lib.sdpsr_profile_stacked_in_place.restype = C.c_int
+    lib.sdpsr_profile_stacked_in_place.argtypes = [vp, i64, i64, i64, i64, i64, i64, i64, vp, vp, i64, rep]
+    lib.sdpsr_profile_lift.restype = C.c_int
+    lib.sdpsr_profile_lift.argtypes = [vp, i64, i64, i64, i64, i64, f64, vp, vp, vp, vp, i64]
+    lib.sdpsr_profile_seed_vector.restype = C.c_int
+    lib.sdpsr_profile_seed_vector.argtypes = [vp, i64, C.c_uint64, vp, vp, vp, i64]
+    lib.sdpsr_profile_qrm_current.restype = C.c_int
+    lib.sdpsr_profile_qrm_current.argtypes = [vp, rep]
     # the steps of the complex path on caller-made inputs (tests)
     lib.sdpsr_profile_cx_gather_herm.restype = C.c_int
     lib.sdpsr_profile_cx_gather_herm.argtypes = [vp, i64, vp, C.c_uint64, vp, vp, i64]

@@ -71,6 +71,7 @@ int block_diagonalize_impl(sdpsr_ctx* c, int64_t n, const uint32_t* P, int64_t d
     hipStream_t s = c->stream;
     c->bd_valid = false;
     c->bd_q_valid = false;
+    c->bd_qrm_current = false;  // set again by the module lift, which stores the row-major copy itself
     PhaseTimer tm(c, phase_ms != nullptr);
     TotalEvents ev_total(phase_ms != nullptr, s);
     uint32_t* L = nullptr;
@@ -356,7 +357,7 @@ int sdpsr_block_images(sdpsr_ctx* c, double* blks, double* Q_hat, double* phase_
     // below: its host vectors are the sources of asynchronous uploads
     BasisImage bi(c, n, L, Qrm, c->bd_sizes, S1, S, 1, d, 1e-12 * (double)n, out);
     bi.own_labels = true;
-    launch_transpose_to_rowmajor(s, n, S1, Qhat, Qrm);
+    if (!c->bd_qrm_current) launch_transpose_to_rowmajor(s, n, S1, Qhat, Qrm);  // (the module lift has written Qrm beside Q_hat)
     bool done_synced = false;  // the stream was synchronised by a shortcut's verdict and nothing was enqueued since
     st = bi.run(done_synced);
     if (st) return st;

@@ -55,6 +55,16 @@ struct Module {
     bool spec_b2 = false;               // the second compressed element was formed behind the final round's product
     bool sym_pre = false, sym_trusted = false, sym_checked = false;  // the symmetric check's verdict: who made it, whether it was looked at
     bool forked = false;                // device tail: the fork point of the next prefetch is marked
+    // Scratch discipline (DESIGN.md "module scratch").  lean: the growth is on the small-module route -- small_on_host(), every
+    // product the fused label product, the skinny Gram kernel or the row-owning tall product -- whose kernels read exact shapes:
+    // only the padding rows n .. ld-1 of W are kept zero (seed_basis), nothing is filled per round and Q1 is not used.  The first
+    // step that needs more (a padded split-K product, the device tail) calls restore_fills(), which brings W and Q1 to what the
+    // whole-buffer fills would have left, and the growth goes on with those fills.  live: candidate columns behind the basis
+    // that hold data of the round at hand.
+    bool lean = false;
+    int live = 0;
+    bool parent_form() const { return (c->opts.flags & SDPSR_FLAG_MODULE_SCRATCH_FILLS) != 0; }
+    int restore_fills();
 
     bool fused_product(int wcols) const { return wcols <= 64 && d <= 4000; }
     // small modules: Murota's steps on the host (small_eigen_host.cpp)
@@ -104,16 +114,32 @@ int Module::setup() {
     return SDPSR_OK;
 }
 
+// leaving the lean route: everything but the basis and the live candidates zero, as the whole-buffer fills leave it
+// (rows >= n of every column are zero already)
+int Module::restore_fills() {
+    if (!lean) return SDPSR_OK;
+    lean = false;
+    HIP_TRY(c, hipMemsetAsync(W + (size_t)(w + live) * ld, 0, (size_t)ld * (wtot - w - live) * 8, c->stream));
+    HIP_TRY(c, hipMemsetAsync(Q1, 0, (size_t)ld * ycap * 8, c->stream));
+    return SDPSR_OK;
+}
+
 // W = [x / |x|, 0, ...] for a random x, and the buffers of the growth
 int Module::seed_basis() {
-    HIP_TRY(c, hipMemsetAsync(W, 0, (size_t)ld * wtot * 8, c->stream));
-    launch_random_vector(c->stream, n, next_key(c), zy);
-    launch_normalize_columns(c->stream, n, ld, W, 0, zy, ld, 1, dout);  // W[:,0] = x / |x|
+    lean = !parent_form() && small_on_host();  // (w == 1: what can still end it is the module's growth past 64 or a shape the exact-shape kernels refuse)
+    if (lean) launch_pad_rows(c->stream, n, ld, wtot, W);  // nothing at all when ld == n
+    else HIP_TRY(c, hipMemsetAsync(W, 0, (size_t)ld * wtot * 8, c->stream));
+    if (parent_form()) {
+        launch_random_vector(c->stream, n, next_key(c), zy);
+        launch_normalize_columns(c->stream, n, ld, W, 0, zy, ld, 1, dout);  // W[:,0] = x / |x|
+    } else {
+        launch_seed_vector(c->stream, n, next_key(c), zy, W, dout);  // the same two steps in one launch
+    }
     Cc = (double*)ctx_buf(c, "cm_c", (size_t)(wcap + ycap + 128) * ycap * 8);
     dSm = (double*)ctx_buf(c, "cm_sm", (size_t)(wcap + ycap) * ycap * 8);
     Q1 = (double*)ctx_buf(c, "cm_q1", (size_t)ld * ycap * 8);
     if (!Cc || !dSm || !Q1) return SDPSR_OUT_OF_MEMORY;
-    HIP_TRY(c, hipMemsetAsync(Q1, 0, (size_t)ld * ycap * 8, c->stream));  // rows >= n stay zero for good
+    if (!lean) HIP_TRY(c, hipMemsetAsync(Q1, 0, (size_t)ld * ycap * 8, c->stream));  // rows >= n stay zero for good
     return SDPSR_OK;
 }
 
@@ -126,6 +152,7 @@ int Module::apply_generic(int wcols, double* dst) {
         if (!part) return SDPSR_OUT_OF_MEMORY;
         if (launch_label_spmm(c->stream, n, L, key, d, W, ld, wcols, part, dst, ld)) return SDPSR_OK;
     }
+    { int e0 = restore_fills(); if (e0) return e0; }  // the padded product: not the lean route
     double* Afull = (double*)ctx_buf(c, "cm_a", (size_t)ld * ld * 8);
     const int64_t wcp = round_up(wcols, 128);
     double* tmpo = (double*)ctx_buf(c, "cm_tmpo", (size_t)ld * wcp * 8);
@@ -158,6 +185,10 @@ int Module::ortho_step(int mc, double tol, bool take_ref, const Rider* rider, Se
     // a ride that finds the upload ring wrapped (h2d_sync) waits for the stream behind the segment.  Both cost what the segment would have
     // cost in the loop, never more, and keep the rule that a segment is always enqueued before anything that could disturb it.)
     if (!ride) flush_deferred_tail(c);
+    if (lean && !gram_tn_is_skinny(w + mc, mc)) {  // the padded split-K product reads whole 128-column tiles
+        const int e0 = restore_fills();
+        if (e0) return e0;
+    }
     int st = hpin ? gram_tn(c, w + mc, mc, ld, W, ld, W + (size_t)w * ld, ld, Cc, ap, mp, hpin, &host_filled) : SDPSR_OUT_OF_MEMORY;
     if (st) return st;
     if (rider && (rider->have_t || apply_generic(w, T) == SDPSR_OK)) {  // T[:, 0:w) = A2 W
@@ -192,12 +223,21 @@ int Module::ortho_step(int mc, double tol, bool take_ref, const Rider* rider, Se
     return SDPSR_OK;
 }
 
-// V_new = [W V] S into Q1, then back behind the basis (the old V is dead by then)
+// V_new = [W V] S written straight behind the basis: the row-owning product reads its 64 rows of [W V] before it stores any
+// (the old V is dead by then).  More than 64 new columns, or SDPSR_FLAG_MODULE_SCRATCH_FILLS: into Q1, then copied back.
 int Module::apply_stacked(int mc, const Selection& sel) {
     int e2 = h2d_sync(c, dSm, sel.coef.data(), (size_t)(w + mc) * sel.rank * 8);
     if (e2) return e2;
-    launch_tall_times_small(c->stream, n, ld, W, w + mc, dSm, w + mc, sel.rank, 1.0, 0.0, Q1, ld);
-    HIP_TRY(c, hipMemcpyAsync(W + (size_t)w * ld, Q1, (size_t)ld * sel.rank * 8, hipMemcpyDeviceToDevice, c->stream));
+    double* V = W + (size_t)w * ld;
+    const bool in_place = !parent_form() && launch_tall_times_small_rows(c->stream, n, ld, W, w + mc, dSm, w + mc, sel.rank, 1.0, 0.0, V, ld);
+    if (!in_place) {
+        live = mc;  // the old V is still read by the product
+        e2 = restore_fills();  // Q1's padding rows travel with the copy
+        if (e2) return e2;
+        launch_tall_times_small(c->stream, n, ld, W, w + mc, dSm, w + mc, sel.rank, 1.0, 0.0, Q1, ld);
+        HIP_TRY(c, hipMemcpyAsync(V, Q1, (size_t)ld * sel.rank * 8, hipMemcpyDeviceToDevice, c->stream));
+    }
+    live = sel.rank;
     return SDPSR_OK;
 }
 
@@ -232,6 +272,7 @@ int Module::absorb(int m, const Rider* rider, int& got) {
         if (st) return st;
     }
     w += got;
+    live = 0;
     return SDPSR_OK;
 }
 
@@ -245,6 +286,7 @@ int Module::class_sum_round() {
     }
     launch_class_sums(c->stream, n, d, L, W, W + (size_t)w * ld, ld);  // W[:, w + i] = P_{i+1} x
     int got;
+    live = (int)d;
     return absorb((int)d, nullptr, got);
 }
 
@@ -259,7 +301,13 @@ int Module::growth_round(int& got) {
     if ((int64_t)G * w > ycap || w >= d) G = 1;
     const int m = G * w;
     double* Y = W + (size_t)w * ld;
-    HIP_TRY(c, hipMemsetAsync(Y, 0, (size_t)ld * round_up(m, 128) * 8, c->stream));
+    live = 0;
+    if (lean && !(fused && small_on_host())) {  // the module has outgrown the small-module route
+        const int e0 = restore_fills();
+        if (e0) return e0;
+    }
+    // lean: the label products write rows < n of exactly the m columns the round's Gram product reads; rows >= n are zero
+    if (!lean) HIP_TRY(c, hipMemsetAsync(Y, 0, (size_t)ld * round_up(m, 128) * 8, c->stream));
     bool batched = false;
     if (fused && G > 1 && G != 3 && G * w <= 64 && !(c->opts.flags & SDPSR_FLAG_SPMM_ONE_BY_ONE)) {
         // the G generic elements of the round in one pass over the labels
@@ -301,9 +349,11 @@ int Module::growth_round(int& got) {
         if (!rider.have_t) c->stream_counter = save;
     }
     for (int gidx = 0; gidx < G && !batched && !rider.have_t; ++gidx) {
+        live = gidx * w;
         int e2 = apply_generic(w, Y + (size_t)gidx * w * ld);
         if (e2) return e2;
     }
+    live = m;
     int st = absorb(m, armed ? &rider : nullptr, got);
     if (st) return st;
     if (got != 0) spec_b2 = false;
@@ -330,7 +380,12 @@ int Module::grow(PhaseTimer& tm) {
     if (st) return st;
     if (got != 0) return driver_fallback(c, "module growth did not close within 40 rounds");  // never diagonalise a module that no round has confirmed invariant
     // device tail: columns >= w must be zero for its padded products
-    if (!small_on_host()) HIP_TRY(c, hipMemsetAsync(W + (size_t)w * ld, 0, (size_t)ld * (wtot - w) * 8, c->stream));
+    live = 0;
+    if (!small_on_host()) {
+        st = restore_fills();
+        if (st) return st;
+        HIP_TRY(c, hipMemsetAsync(W + (size_t)w * ld, 0, (size_t)ld * (wtot - w) * 8, c->stream));
+    }
     return SDPSR_OK;
 }
 
@@ -466,6 +521,14 @@ int Module::lift(PhaseTimer& tm, const double* Qs_host, int64_t S1, double atol)
         if (st) return st;
     } else {
         HIP_TRY(c, hipMemcpyAsync(qs, Qhat, (size_t)w * S1 * 8, hipMemcpyDeviceToDevice, c->stream));
+    }
+    if (!parent_form() && tall_times_small_rows_supports((int)S1)) {
+        // the product's store clamps and writes the row-major copy sdpsr_block_images reads: no clamp pass, no transpose pass
+        double* Qrm = (double*)ctx_buf(c, "bd_qrm", (size_t)n * S1 * 8);
+        if (!Qrm) return SDPSR_OUT_OF_MEMORY;
+        launch_lift_clamped(c->stream, n, ld, W, w, qs, w, (int)S1, atol, Qhat, Qrm);
+        c->bd_qrm_current = true;
+        return SDPSR_OK;
     }
     launch_tall_times_small(c->stream, n, ld, W, w, qs, w, (int)S1, 1.0, 0.0, Qhat, n);
     launch_clamptol(c->stream, n * S1, Qhat, atol);

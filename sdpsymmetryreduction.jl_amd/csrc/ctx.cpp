@@ -31,6 +31,7 @@ void* ctx_buf(sdpsr_ctx* c, const char* name, size_t bytes) {
     const std::string_view nm(name);
     if (nm == "adm_lpacked" || nm == "adm_lpacked8" || nm == "ref_first") c->initial_record = InitialRecord{};
     if (nm == "adm_symflag") c->symflag_zero = false;
+    if (nm == "bd_qhat" || nm == "bd_qrm") c->bd_qrm_current = false;
     if (b.p) {
         ctx_sync_stream(c, c->stream);
         hipFree(b.p);

@@ -369,6 +369,7 @@ int Irreducible::layout(std::vector<int32_t>& sizes, int64_t& S1, int64_t& S) {
     Q = (double*)ctx_buf(c, "bd_q", (size_t)ld * ld * 8);
     Qhat = (double*)ctx_buf(c, "bd_qhat", (size_t)n * S1 * 8);
     if (!Q || !Qhat) return SDPSR_OUT_OF_MEMORY;
+    c->bd_qrm_current = false;  // Q_hat is rewritten here: "bd_qrm" no longer is its row-major copy
     fcol.assign(neig, -1);
     for (size_t p = 0; p < roots.size(); ++p)
         if (members[p].size() > 1)

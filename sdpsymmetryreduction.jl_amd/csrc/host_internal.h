@@ -396,6 +396,18 @@ void launch_sub_round(hipStream_t s, int64_t len, const double* a, const double*
 void launch_normalize_columns(hipStream_t s, int64_t n, int64_t ld, double* H, int64_t hstride, const double* X,
                          int64_t ldx, int nruns, double* norm0);
 void launch_random_vector(hipStream_t s, int64_t n, uint64_t key, double* x);
+// random_vector + normalize_columns (one run) as one single-workgroup launch: x, h = x / |x| and norm0[0] = |x|, bit for bit
+void launch_seed_vector(hipStream_t s, int64_t n, uint64_t key, double* x, double* h, double* norm0);
+// rows n .. ld-1 of `cols` columns of M <- 0 (nothing launched when ld == n)
+void launch_pad_rows(hipStream_t s, int64_t n, int64_t ld, int64_t cols, double* M);
+// launch_tall_times_small with a workgroup per 64 rows that owns every output column (ncols <= 64): `out` may alias columns of
+// In.  The same sums bit for bit.  false: ncols beyond the form, nothing launched.
+bool tall_times_small_rows_supports(int ncols);
+bool launch_tall_times_small_rows(hipStream_t s, int64_t n, int64_t ldi, const double* In, int kk, const double* S, int lds_, int ncols,
+                                  double alpha, double beta, double* out, int64_t ldo);
+// the lift in one launch: Qcm = clamptol(In S, atol) (ld n) and its row-major copy Qrm[i * ncols + c]; false: ncols > 64
+bool launch_lift_clamped(hipStream_t s, int64_t n, int64_t ldi, const double* In, int kk, const double* S, int lds_, int ncols, double atol,
+                         double* Qcm, double* Qrm);
 void launch_fill_test_sig(hipStream_t s, int64_t len, int64_t nclasses, uint64_t* sig);
 size_t sytrd_workspace_doubles(int64_t n, int64_t ld);
 void launch_sytrd(sdpsr_ctx* c, int64_t n, double* A, int64_t ld, double* d, double* e, double* tau, double* ws);

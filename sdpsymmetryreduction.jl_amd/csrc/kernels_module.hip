@@ -50,6 +50,57 @@ void launch_random_vector(hipStream_t s, int64_t n, uint64_t key, double* x) {
     random_vector_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>((int)n, key, x);
 }
 
+// The seed of the module growth in ONE launch: x = random_vector(key), h = x / ||x||, norm0[0] = ||x|| -- random_vector_kernel
+// and normalize_columns_kernel (one run) as a single workgroup.  The same generator call per element, and every thread of
+// the normalisation squares the elements i = tid, tid + LZ_THREADS, ... in that order, the same shuffle reduction, the same
+// sqrt and reciprocal: x, h and norm0 come out bit for bit as from the two launches.  No x needs to reach memory between
+// them for the sum (each thread squares what it drew itself); x is still stored, the scaling pass reads it back.
+__global__ void __launch_bounds__(LZ_THREADS)
+seed_vector_kernel(int n, uint64_t key, double* __restrict__ x, double* __restrict__ h, double* __restrict__ norm0) {
+    __shared__ double s_red[LZ_THREADS / 64];
+    const int tid = threadIdx.x;
+    double sq = 0;
+    for (int i = tid; i < n; i += LZ_THREADS) {
+        const double v = 2.0 * sdpsr_class_uniform(key, (uint32_t)(i + 1)) - 1.0;
+        x[i] = v;
+        sq = fma(v, v, sq);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sq += __shfl_down(sq, o, 64);
+    if ((tid & 63) == 0) s_red[tid >> 6] = sq;
+    __syncthreads();
+    if (tid == 0) {
+        double tot = 0;
+        for (int k = 0; k < LZ_THREADS / 64; ++k) tot += s_red[k];
+        s_red[0] = sqrt(tot);
+        norm0[0] = s_red[0];
+    }
+    __syncthreads();
+    const double inv = s_red[0] > 0 ? 1.0 / s_red[0] : 0.0;
+    for (int i = tid; i < n; i += LZ_THREADS) h[i] = x[i] * inv;  // x[i]: this thread's own store
+}
+void launch_seed_vector(hipStream_t s, int64_t n, uint64_t key, double* x, double* h, double* norm0) {
+    seed_vector_kernel<<<1, LZ_THREADS, 0, s>>>((int)n, key, x, h, norm0);
+}
+
+// M[r, j] = 0 for n <= r < ld, j < cols: the padding rows of a column-major scratch matrix.  The module growth's small-module
+// route keeps only these rows zero (its Gram products run over ld rows); ld == n: nothing to launch.
+__global__ void pad_rows_kernel(int n, int pad, int64_t ld, int cols, double* __restrict__ M) {
+    const int64_t total = (int64_t)pad * cols;
+    const int64_t step = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += step) {
+        const int64_t j = e / pad, r = e - j * pad;
+        M[n + r + j * ld] = 0.0;
+    }
+}
+void launch_pad_rows(hipStream_t s, int64_t n, int64_t ld, int64_t cols, double* M) {
+    const int64_t pad = ld - n;
+    if (pad <= 0 || cols <= 0) return;
+    int64_t g = (pad * cols + 255) / 256;
+    if (g > 1024) g = 1024;
+    pad_rows_kernel<<<(unsigned)g, 256, 0, s>>>((int)n, (int)pad, ld, (int)cols, M);
+}
+
 // B <- (B + B') / 2 on the leading m x m part (ld), in place
 __global__ void symmetrize_kernel(int m, int64_t ld, double* __restrict__ B) {
     const int j = blockIdx.y * blockDim.y + threadIdx.y;
@@ -126,6 +177,80 @@ void launch_tall_times_small(hipStream_t s, int64_t n, int64_t ldi, const double
     if (ncols <= 0) return;
     dim3 g((unsigned)((n + 63) / 64), (unsigned)((ncols + TS_COLS - 1) / TS_COLS));
     tall_times_small_kernel<<<g, 64, 0, s>>>((int)n, ldi, In, kk, S, lds_, ncols, alpha, beta, out, ldo);
+}
+
+// The same product with a workgroup that owns 64 rows and ALL output columns (ncols <= TS_ROWS_MAX_COLS): wave q of the
+// workgroup takes the columns [q TS_COLS, (q + 1) TS_COLS), every thread's sums are those of tall_times_small_kernel (the same
+// fma order over t), and a barrier separates the workgroup's last read of In from its first store.  So `out` may alias columns
+// of In -- out = In + w ldi, ldo = ldi is the stacked product [W V] S written straight behind the basis: no scratch matrix, no
+// copy back (a grid that splits the columns over workgroups could overwrite candidate columns a sibling still reads) -- and no
+// row outside the workgroup's 64 is read or written.
+// LIFT: the store clamps, v = |v| < atol ? 0 : v (clamptol_kernel's expression), and writes the value a second time into the
+// row-major copy rm[i * ncols + c] (transpose_to_rowmajor_kernel's layout): the lift Q_hat = W Q_small leaves both forms
+// that block_images reads, no clamp pass and no transpose pass over Q_hat.
+constexpr int TS_ROWS_MAX_COLS = 64;
+template <bool LIFT>
+__global__ void __launch_bounds__(64 * (TS_ROWS_MAX_COLS / TS_COLS))
+tall_times_small_rows_kernel(int n, int64_t ldi, const double* In, int kk, const double* __restrict__ S, int lds_, int ncols,
+                             double alpha, double beta, double* out, int64_t ldo, double atol, double* __restrict__ rm) {
+    const int c0 = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * TS_COLS;  // wave-uniform: the coefficients stay scalar loads
+    const int i = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int ic = i < n ? i : n - 1;
+    const double* in = In + ic;
+    double acc[TS_COLS];
+#pragma unroll
+    for (int q = 0; q < TS_COLS; ++q) acc[q] = 0.0;
+    const double* sc[TS_COLS];
+#pragma unroll
+    for (int q = 0; q < TS_COLS; ++q) sc[q] = S + (int64_t)(c0 + q < ncols ? c0 + q : ncols - 1) * lds_;
+    int t = 0;
+    for (; t + 8 <= kk; t += 8) {
+        double x[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) x[u] = in[(int64_t)(t + u) * ldi];
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+#pragma unroll
+            for (int q = 0; q < TS_COLS; ++q) acc[q] = fma(x[u], sc[q][t + u], acc[q]);
+    }
+    for (; t < kk; ++t) {
+        const double x = in[(int64_t)t * ldi];
+#pragma unroll
+        for (int q = 0; q < TS_COLS; ++q) acc[q] = fma(x, sc[q][t], acc[q]);
+    }
+    __syncthreads();  // every wave of the workgroup has read its rows of In: the stores below may land in columns of In
+    if (i < n) {
+#pragma unroll
+        for (int q = 0; q < TS_COLS; ++q)
+            if (c0 + q < ncols) {
+                double* o = out + i + (int64_t)(c0 + q) * ldo;
+                double v = (beta == 0.0 ? 0.0 : beta * *o) + alpha * acc[q];
+                if (LIFT) {
+                    v = (fabs(v) < atol) ? 0.0 : v;
+                    rm[(int64_t)i * ncols + c0 + q] = v;
+                }
+                *o = v;
+            }
+    }
+}
+bool tall_times_small_rows_supports(int ncols) { return ncols >= 1 && ncols <= TS_ROWS_MAX_COLS; }
+// false (nothing launched): more than TS_ROWS_MAX_COLS output columns -- the caller keeps launch_tall_times_small and a scratch output
+bool launch_tall_times_small_rows(hipStream_t s, int64_t n, int64_t ldi, const double* In, int kk, const double* S, int lds_, int ncols,
+                                  double alpha, double beta, double* out, int64_t ldo) {
+    if (!tall_times_small_rows_supports(ncols)) return false;
+    const int waves = (ncols + TS_COLS - 1) / TS_COLS;
+    tall_times_small_rows_kernel<false><<<(unsigned)((n + 63) / 64), 64 * waves, 0, s>>>((int)n, ldi, In, kk, S, lds_, ncols, alpha, beta, out,
+                                                                                         ldo, 0.0, nullptr);
+    return true;
+}
+// Qcm = clamp(In S) (n x ncols column-major, ld n) and Qrm = its row-major copy, one launch; false: ncols beyond the form
+bool launch_lift_clamped(hipStream_t s, int64_t n, int64_t ldi, const double* In, int kk, const double* S, int lds_, int ncols, double atol,
+                         double* Qcm, double* Qrm) {
+    if (!tall_times_small_rows_supports(ncols)) return false;
+    const int waves = (ncols + TS_COLS - 1) / TS_COLS;
+    tall_times_small_rows_kernel<true><<<(unsigned)((n + 63) / 64), 64 * waves, 0, s>>>((int)n, ldi, In, kk, S, lds_, ncols, 1.0, 0.0, Qcm, n,
+                                                                                        atol, Qrm);
+    return true;
 }
 
 // C[e] = sum_z P[z * stride + e]  (split-K partial sums, fixed order)

@@ -680,6 +680,118 @@ extern "C" int sdpsr_profile_random_vector(sdpsr_ctx* c, int64_t n, uint64_t key
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
+// The module growth's scratch discipline (tests/test_gpu_module_scratch.py): the form each entry runs is the one the ctx's
+// flags choose, as in compress.cpp.
+// ---------------------------------------------------------------------------------------------------------------------------
+static bool mk_parent_form(const sdpsr_ctx* c) { return (c->opts.flags & SDPSR_FLAG_MODULE_SCRATCH_FILLS) != 0; }
+
+extern "C" int sdpsr_profile_poison_scratch(sdpsr_ctx* c) {
+    CHECK_CTX(c);
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    std::vector<uint64_t> pat;
+    for (auto& kv : c->bufs) {
+        if (!kv.second.p || !(kv.first.rfind("cm_", 0) == 0 || kv.first == "bd_qrm")) continue;
+        const size_t words = kv.second.bytes / 8;
+        if (pat.size() < words) pat.assign(words, 0x7FF85A5ADEADBEEFull);
+        HIP_TRY(c, hipMemcpy(kv.second.p, pat.data(), words * 8, hipMemcpyHostToDevice));
+    }
+    return SDPSR_OK;
+}
+
+extern "C" int sdpsr_profile_stacked_in_place(sdpsr_ctx* c, int64_t n, int64_t ldi, int64_t kk, int64_t lds, int64_t ncols, int64_t w, int64_t mcols,
+                                              double* M_inout, const double* S_host, int64_t guard, int32_t* report) {
+    CHECK_CTX(c);
+    if (!M_inout || !S_host || !report || n < 1 || n > MK_MAX_N || ldi < n || ldi > MK_MAX_LD || kk < 1 || kk > 512 || lds < kk || lds > 1024 ||
+        ncols < 1 || ncols > 512 || w < 1 || w > 512 || mcols < kk || mcols < w + ncols || mcols > 1024 || guard < 0 || guard > MK_MAX_GUARD)
+        return ctx_fail(c, SDPSR_BAD_ARGUMENT, "stacked_in_place: bad arguments");
+    hipStream_t s = c->stream;
+    const size_t mn = (size_t)(ldi * mcols + guard);
+    double* M = (double*)ctx_buf(c, "prof_mk_a", mn * 8);
+    double* S = (double*)ctx_buf(c, "prof_mk_b", (size_t)lds * ncols * 8);
+    double* Q1 = (double*)ctx_buf(c, "prof_mk_c", (size_t)ldi * ncols * 8);
+    if (!M || !S || !Q1) return SDPSR_OUT_OF_MEMORY;
+    HIP_TRY(c, hipMemcpyAsync(M, M_inout, mn * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(S, S_host, (size_t)lds * ncols * 8, hipMemcpyHostToDevice, s));
+    double* V = M + (size_t)w * ldi;
+    const bool in_place = !mk_parent_form(c) && launch_tall_times_small_rows(s, n, ldi, M, (int)kk, S, (int)lds, (int)ncols, 1.0, 0.0, V, ldi);
+    if (!in_place) {
+        launch_tall_times_small(s, n, ldi, M, (int)kk, S, (int)lds, (int)ncols, 1.0, 0.0, Q1, ldi);
+        HIP_TRY(c, hipMemcpy2DAsync(V, (size_t)ldi * 8, Q1, (size_t)ldi * 8, (size_t)n * 8, (size_t)ncols, hipMemcpyDeviceToDevice, s));
+    }
+    HIP_TRY(c, hipMemcpyAsync(M_inout, M, mn * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, hipGetLastError());
+    report[0] = in_place ? 1 : 0;
+    return SDPSR_OK;
+}
+
+extern "C" int sdpsr_profile_lift(sdpsr_ctx* c, int64_t n, int64_t ldi, int64_t kk, int64_t lds, int64_t S1, double atol, const double* In_host,
+                                  const double* S_host, double* Qcm_inout, double* Qrm_inout, int64_t guard) {
+    CHECK_CTX(c);
+    if (!In_host || !S_host || !Qcm_inout || !Qrm_inout || n < 1 || n > MK_MAX_N || ldi < n || ldi > MK_MAX_LD || kk < 1 || kk > 512 || lds < kk ||
+        lds > 1024 || S1 < 1 || S1 > 512 || guard < 0 || guard > MK_MAX_GUARD || !(atol >= 0) ||
+        (!mk_parent_form(c) && !tall_times_small_rows_supports((int)S1)))
+        return ctx_fail(c, SDPSR_BAD_ARGUMENT, "lift: bad arguments");
+    hipStream_t s = c->stream;
+    const size_t qn = (size_t)(n * S1 + guard);
+    double* In = (double*)ctx_buf(c, "prof_mk_a", (size_t)ldi * kk * 8);
+    double* S = (double*)ctx_buf(c, "prof_mk_b", (size_t)lds * S1 * 8);
+    double* Qcm = (double*)ctx_buf(c, "prof_mk_c", qn * 8);
+    double* Qrm = (double*)ctx_buf(c, "prof_mk_d", qn * 8);
+    if (!In || !S || !Qcm || !Qrm) return SDPSR_OUT_OF_MEMORY;
+    HIP_TRY(c, hipMemcpyAsync(In, In_host, (size_t)ldi * kk * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(S, S_host, (size_t)lds * S1 * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(Qcm, Qcm_inout, qn * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(Qrm, Qrm_inout, qn * 8, hipMemcpyHostToDevice, s));
+    if (mk_parent_form(c)) {
+        launch_tall_times_small(s, n, ldi, In, (int)kk, S, (int)lds, (int)S1, 1.0, 0.0, Qcm, n);
+        launch_clamptol(s, n * S1, Qcm, atol);
+        launch_transpose_to_rowmajor(s, n, S1, Qcm, Qrm);
+    } else {
+        launch_lift_clamped(s, n, ldi, In, (int)kk, S, (int)lds, (int)S1, atol, Qcm, Qrm);
+    }
+    HIP_TRY(c, hipMemcpyAsync(Qcm_inout, Qcm, qn * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(Qrm_inout, Qrm, qn * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, hipGetLastError());
+    return SDPSR_OK;
+}
+
+extern "C" int sdpsr_profile_seed_vector(sdpsr_ctx* c, int64_t n, uint64_t key, double* x_inout, double* h_inout, double* norm_inout, int64_t guard) {
+    CHECK_CTX(c);
+    if (!x_inout || !h_inout || !norm_inout || n < 1 || n > MK_MAX_N || guard < 0 || guard > MK_MAX_GUARD)
+        return ctx_fail(c, SDPSR_BAD_ARGUMENT, "seed_vector: bad arguments");
+    hipStream_t s = c->stream;
+    const size_t xn = (size_t)(n + guard), nn = (size_t)(1 + guard);
+    double* x = (double*)ctx_buf(c, "prof_mk_a", xn * 8);
+    double* h = (double*)ctx_buf(c, "prof_mk_c", xn * 8);
+    double* nrm = (double*)ctx_buf(c, "prof_mk_b", nn * 8);
+    if (!x || !h || !nrm) return SDPSR_OUT_OF_MEMORY;
+    HIP_TRY(c, hipMemcpyAsync(x, x_inout, xn * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(h, h_inout, xn * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(nrm, norm_inout, nn * 8, hipMemcpyHostToDevice, s));
+    if (mk_parent_form(c)) {
+        launch_random_vector(s, n, key, x);
+        launch_normalize_columns(s, n, n, h, 0, x, n, 1, nrm);
+    } else {
+        launch_seed_vector(s, n, key, x, h, nrm);
+    }
+    HIP_TRY(c, hipMemcpyAsync(x_inout, x, xn * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(h_inout, h, xn * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(norm_inout, nrm, nn * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, hipGetLastError());
+    return SDPSR_OK;
+}
+
+extern "C" int sdpsr_profile_qrm_current(sdpsr_ctx* c, int32_t* current) {
+    CHECK_CTX(c);
+    if (!current) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "null pointer");
+    *current = c->bd_qrm_current ? 1 : 0;
+    return SDPSR_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
 // The steps of blockDiagonalize(P; complex = true) on caller-made inputs (tests/test_gpu_complex_steps.py), by the conventions
 // of the module-kernel entries above: host arrays in (column-major, real / imaginary planes with ld = n), every *_inout array
 // uploaded as the caller filled it and downloaded whole, the product's own launcher or host function called the way

@@ -37,6 +37,7 @@ int jordan_reduce_impl(sdpsr_ctx* c, int64_t n, const double* CL, const double* 
     if (!L) return SDPSR_OUT_OF_MEMORY;
     c->bd_valid = false;
     c->bd_q_valid = false;
+    c->bd_qrm_current = false;
     c->bd_labels_ext = nullptr;
     double pm_a[SDPSR_T_COUNT] = {}, pm_b[SDPSR_T_COUNT] = {}, pm_i[SDPSR_T_COUNT] = {};
     int labels_sym = 0;

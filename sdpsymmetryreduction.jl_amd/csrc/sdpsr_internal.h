@@ -129,6 +129,9 @@ struct sdpsr_ctx {
     std::vector<int64_t> adm_dims;        // dimension trajectory of the last admissible_subspace call (sdpsr_dimension_trajectory)
     bool bd_q_valid = false;  // "bd_qhat" holds Q_hat of the last diagonalize (even when check_block_sizes failed)
     bool bd_labels_owned = false;
+    // "bd_qrm" is the row-major copy of the Q_hat in "bd_qhat" (the module lift stores both): sdpsr_block_images skips its transpose.
+    // Cleared by every other writer of "bd_qhat" and when either buffer is reallocated.
+    bool bd_qrm_current = false;
     // hash table capacity hint (log2) for the next refine
     int table_log2_hint = 12;
     hipEvent_t ev[2 * SDPSR_T_COUNT] = {};
