@@ -157,7 +157,14 @@ enum {
        lift's clamp as a pass of its own, and the row-major copy of Q_hat made by sdpsr_block_images.  By default (small
        modules, w <= 64, solved on the host) only the padding rows n .. ld-1 are zeroed, the stacked product is written in
        place, the seed is one launch, and the lift stores Q_hat clamped in both layouts.  Same results bit for bit. */
-    SDPSR_FLAG_MODULE_SCRATCH_FILLS = 1u << 17
+    SDPSR_FLAG_MODULE_SCRATCH_FILLS = 1u << 17,
+    /* A/B: the guessed-closed rounds of the loop (first iteration of an input predicted closed: the joint round and the
+       speculated confirm round) form their int8 squares and compare every entry with its class representative, as every
+       other round does.  By default those two rounds, which are expected to report "no class splits" and nothing else,
+       check X_t^2 against its class constants with a random vector (v'X_t^2 v = v'C_t v, exact integers, one pass over the
+       labels, no product; a difference is missed w.p. <= 2^-15 per channel) and form the square only when the check of a
+       verdict read inside the loop says "violated".  Same results. */
+    SDPSR_FLAG_SQUARE_EVERY_VERDICT = 1u << 18
 };
 
 typedef struct sdpsr_opts {
@@ -166,7 +173,9 @@ typedef struct sdpsr_opts {
     int32_t channels;       /* independent int8 / f32 draws per square step (1..8).  0 = default: 2 channels AND
                                confirm_rounds >= 1 (a false stop needs confirm_rounds + 1 consecutive squares that
                                miss every needed split, each w.p. <= (2/256)^channels: the (2/256)^4 of four
-                               channels, at 2 (I + 1) instead of 4 I channel squares for I iterations) */
+                               channels, at 2 (I + 1) instead of 4 I channel squares for I iterations; the two rounds of
+                               a guessed-closed first iteration are judged by the square check, which adds at most
+                               2^-15 to a channel's 2/256: <= (2^-7 + 2^-15)^channels per round) */
     int32_t max_iters;      /* 0 = default (10000) */
     int32_t confirm_rounds; /* extra no-change square rounds demanded before stopping (default with channels = 0: 1) */
     int32_t eig_driver;     /* driver of diagonalize: 0 = default (module compression when dim(P) is small against n, else

@@ -41,8 +41,10 @@ int sdpsr_profile_clock(sdpsr_ctx* ctx, int kind, int64_t n, int64_t aux, int re
    trips of a reduction = the difference around it. */
 int sdpsr_profile_host_waits(sdpsr_ctx* ctx, uint64_t* out);
 /* Counters of ctx (restart 0) or of batch restart `restart` (as sdpsr_batch_block_sizes): out[0] = random draws so far
-   (the ctx's stream position, reset by sdpsr_set_seed), out[1] = squares the loop has launched, out[2] = of those, squares
-   launched speculatively, out[3] = the symmetric-basis hint bits the last admissible_subspace run used. */
+   (the ctx's stream position, reset by sdpsr_set_seed), out[1] = square rounds the loop has examined, out[2] = of those, rounds
+   examined speculatively -- a round is one int8 square, or one round of the square check that stands in for it (a square formed
+   behind a check's "violated" verdict belongs to the round already counted) --, out[3] = the symmetric-basis hint bits the last
+   admissible_subspace run used. */
 int sdpsr_profile_loop_counts(sdpsr_ctx* ctx, int32_t restart, uint64_t* out);
 /* Stage 2 of a two-stage tridiagonalisation (band -> tridiagonal by Householder bulge chasing, one workgroup per sweep,
    hand-offs through progress words), built to be measured: A_host n x n dense symmetric with bandwidth b (16, 32 or 64),
@@ -102,6 +104,21 @@ int sdpsr_profile_verify_pair_w(sdpsr_ctx* ctx, int64_t n, int64_t d, int width,
                                 const double* a_host, const double* b_host, uint32_t* out);
 int sdpsr_profile_proj_coef_lower(sdpsr_ctx* ctx, int64_t n, int64_t r, uint64_t key, int width, const uint32_t* Lp_host, const double* U_host,
                                   double* partial_out, double* coef_out);
+/* Guessed-closed first iterations of ctx (restart 0) or of batch restart `restart` whose two rounds were judged by the square check instead of
+   two int8 squares (out[0]), and those of them that formed a real square behind a "violated" verdict read inside the loop (out[1]). */
+int sdpsr_profile_square_checks(sdpsr_ctx* ctx, int32_t restart, uint64_t* out);
+/* The square check (csrc/kernels_square_check.hip) on caller-made inputs: "does X_t^2 take its class representative's value on every entry,
+   0 on label 0?" for G (1 or 2) rounds with keys[g], T (2 or 4) channels each, on the packed labels Lp_host (<= d <= 255, width 8 or 32 as
+   above) of order n <= 8192 with the representatives first_idx_host.  layout[0..6] = byte offsets of c (int32 [G T][d]), part_x (int32
+   [G T][nb][64 nb], nb = ceil(n / 64)), part_c (int64, same shape), y, w (int64 [G T][64 nb]), the 128-bit block sums (uint64 [G T][nb][2])
+   and the equality bits (uint32 [G T], 1: |X_t v|^2 == v'C_t v) inside the workspace, layout[7] = its bytes; 64 bytes in front of every
+   array and behind the last belong to nobody.  ws_inout == NULL: only layout is filled.  Otherwise ws_inout (layout[7] bytes) is uploaded as
+   the caller filled it, the kernels run as the loop launches them, and it is downloaded whole; verdicts_out[g] = round g's verdict word
+   (cleared by the host, 1 when a channel differs); write_full != 0: L_inout (n * n + guard words, uploaded, downloaded) receives the full
+   label matrix. */
+int sdpsr_profile_square_check(sdpsr_ctx* ctx, int64_t n, int64_t d, int G, int T, const uint64_t* keys, int width, int write_full,
+                               const uint32_t* Lp_host, const uint32_t* first_idx_host, uint8_t* ws_inout, uint64_t* layout,
+                               uint32_t* verdicts_out, uint32_t* L_inout, int64_t guard);
 
 /* ---- The kernels of the module-compression driver on caller-made inputs (tests/test_gpu_module_kernels.py). ----
    All matrices are column-major host arrays of doubles; labels are n x n uint32, column-major.  Every *_inout array is uploaded as the caller

@@ -2097,6 +2097,57 @@ struct ChkStep {
 };
 size_t verify_ref_bytes(int64_t d) { return (size_t)(d > 0 ? d : 1) * sizeof(VerifyRef); }
 
+// The projection half of ChkStep<R, T, true> alone, the same ybits rule: the channel half of such a round is settled without the
+// product (kernels_square_check.hip), so nothing of C is read here.
+template <int R>
+struct ChkProj {
+    struct Ref {
+        double x;
+        uint64_t ybits;
+    };
+    static constexpr bool kUntrusted = false;
+    struct Raw {
+        double u[R];
+    };
+    int n;
+    const double* __restrict__ U;
+    const double* __restrict__ coef;
+    double atol, scale;
+    uint64_t key;
+    double cf[R];  // coef, once load_uniforms() has run
+    __host__ __device__ __forceinline__ int order() const { return n; }
+    __device__ __forceinline__ void load_uniforms() {
+#pragma unroll
+        for (int k = 0; k < R; ++k) cf[k] = coef[k];
+    }
+    __device__ __forceinline__ Ref ref_of(int cls, const uint32_t* __restrict__ first_idx) const {
+        uint32_t i, j;
+        packed_lower_ij(n, (int64_t)first_idx[cls], i, j);
+        const int64_t ef = (int64_t)i + (int64_t)j * n;
+        Ref r;
+        r.x = sdpsr_class_uniform(key, (uint32_t)cls + 1u);
+        double p = 0;
+#pragma unroll
+        for (int k = 0; k < R; ++k) p = fma(U[(int64_t)k * n * n + ef], coef[k], p);
+        r.ybits = sdpsr_round_key(r.x - p, atol, scale);
+        return r;
+    }
+    __device__ __forceinline__ Ref zero_ref() const { return Ref{0.0, 0ull}; }
+    __device__ __forceinline__ Raw fetch(int i, int j, int64_t, bool ok) const {
+        Raw v;
+        const double* Uij = U + (int64_t)j * n + i;
+#pragma unroll
+        for (int k = 0; k < R; ++k) v.u[k] = ok ? __builtin_nontemporal_load(&Uij[(int64_t)k * n * n]) : 0.0;
+        return v;
+    }
+    __device__ __forceinline__ bool differs(const Raw& v, const Ref& r) const {
+        double p = 0;
+#pragma unroll
+        for (int k = 0; k < R; ++k) p = fma(v.u[k], cf[k], p);
+        return sdpsr_round_key(r.x - p, atol, scale) != r.ybits;
+    }
+};
+
 // "Can the projection step still split a class?"  x - U U'x of an x that is constant on the classes of S is constant on
 // them for EVERY x exactly when every basis matrix U_k is (U_k in span(S) => U U'x in span(S)), and a finer S keeps the
 // property: once it holds, the projection half of the loop (src/partitions.jl:159-164) cannot refine S any more.  The
@@ -2310,6 +2361,14 @@ static void launch_verify_rt(hipStream_t s, const SigSource& q, int64_t d, const
         }
     }
     launch_class_compare(s, chk, q.L, d, first_idx, ref, flag);
+}
+bool launch_verify_projection(hipStream_t s, const SigSource& q, int64_t d, const uint32_t* first_idx, uint32_t* flag) {
+    if (q.kind != SIG_JOINT_I32 || !q.packed || !q.lab_packed || d < 1 || d > VERIFY_LDS_CAP) return false;
+    return with_constant<1, 2, 3, 4>(q.r, [&](auto R) {
+        const ChkProj<decltype(R)::value> chk{(int)q.n, q.U, q.coef, q.atol, q.scale, q.key, {}};
+        if (q.L8 && d <= 255) launch_class_compare(s, chk, q.L8, d, first_idx, nullptr, flag);
+        else launch_class_compare(s, chk, q.L, d, first_idx, nullptr, flag);
+    });
 }
 bool launch_verify_no_split(hipStream_t s, const SigSource& q, int64_t d, const uint32_t* first_idx, void* ref, uint32_t* flag) {
     if (!verify_no_split_supports(q, d)) return false;

@@ -182,6 +182,58 @@ struct Loop {
                pinned_report(c, PINNED_VERIFY) && ctx_buf(c, "adm_xi8_spec", (size_t)T * ld * ld) &&
                ctx_buf(c, "adm_ci32_spec", (size_t)T * ld * ld * 4) && ctx_buf(c, "adm_vref2", verify_ref_bytes(current));
     }
+    // The guessed-closed first iteration without its two squares (kernels_square_check.hip, DESIGN section 2 dev. 15): both rounds are
+    // expected to answer "no class splits" and nothing else, and that answer -- X_t^2 equals its class constants -- is checked with a
+    // random vector in one pass over the labels.  Symmetric packed labels, int8 channels; the projection half of the joint verdict
+    // needs the LDS form of the compare (or no live projection at all).
+    bool check_applies(bool confirming, bool from_packed) const {
+        return guess_applies(confirming) && verify_applies(confirming, from_packed) && lab.sym && mode == SDPSR_SQUARE_I8 &&
+               square_check_supports(n, current, 2, T) && !(c->opts.flags & SDPSR_FLAG_SQUARE_EVERY_VERDICT) &&
+               (proj_dead || r == 0 || current <= (int64_t)verify_lds_cap());
+    }
+    // The checked rounds: key2 is the joint round's key, the confirm round's is drawn here, where verify_round draws it.  Stream order:
+    // class constants, the pass (which writes the full labels: expected to be the call's last label pass), the projection compare into
+    // the first verdict word, the verdicts.  Nothing is deferred to the ctx's tail: the label write cannot wait, and nothing long is left.
+    // Both rounds count as squares examined.  A "violated" first verdict read here forms the real square of key2 for the refinement
+    // that follows (not counted again).
+    int check_round(const SigSource& qj, uint64_t key2, Verdict* v) {
+        SquareCheck q;
+        q.n = n, q.d = current, q.G = 2, q.T = T;
+        void* ws = ctx_buf(c, "adm_sqcheck", square_check_ws_bytes(n, current, 2, T));
+        const uint32_t* first = (const uint32_t*)ctx_buf(c, "ref_first", (size_t)refine_first_cap() * 4);
+        uint32_t* hv = pinned_report(c, PINNED_VERIFY);
+        uint32_t* hv2 = pinned_report(c, PINNED_SPECULATIVE);
+        if (!ws || !first || !hv || !hv2) return SDPSR_OUT_OF_MEMORY;
+        const bool defer = c->allow_deferred_verdict && c->pinned_small != nullptr;
+        if (defer) hv = c->pinned_small + PINNED_SMALL_DEFERRED_VERIFY.first, hv2 = c->pinned_small + PINNED_SMALL_DEFERRED_SPECULATIVE.first;
+        square_check_ws_carve(q, ws);
+        q.key[0] = key2, q.key[1] = next_key(c);
+        q.Lp = lab.Lp, q.Lp8 = lab.shadow(), q.first_idx = first, q.Lfull = lab.full_from_gather();
+        q.flag[0] = hv, q.flag[1] = hv2;
+        *(volatile uint32_t*)hv = 0u;  // (the kernels only ever store 1; the last verdicts on these words have been read)
+        *(volatile uint32_t*)hv2 = 0u;
+        launch_square_check_ref_and_pass(s, q);
+        if (qj.kind == SIG_JOINT_I32 && r >= 1) launch_verify_projection(s, qj, current, first, hv);
+        launch_square_check_verdict(s, q);
+        c->squares_launched += 2, ++c->squares_speculative, ++c->square_checks;
+        if (defer) {
+            c->deferred_verdict = true;  // both words are read in reduce.cpp
+            HIP_TRY(c, hipGetLastError());
+            v->unchanged = v->spec_confirmed = true;
+            return SDPSR_OK;
+        }
+        HIP_TRY(c, ctx_sync_stream(c, s));
+        HIP_TRY(c, hipGetLastError());
+        v->unchanged = hv[0] == 0;
+        v->spec_confirmed = v->unchanged && hv2[0] == 0;
+        if (!v->spec_confirmed) --c->stream_counter;  // (a confirm round that follows redraws this key)
+        if (!v->unchanged) {
+            ++c->square_check_fallbacks;
+            --c->squares_launched;
+            launch_square(true, key2, Xp, Cp, current);
+        }
+        return SDPSR_OK;
+    }
     // tail (tail_applies): the round's square has not been launched
     int verify_round(const SigSource& qj, bool confirming, bool from_packed, bool tail, Verdict* v) {
         if (!verify_applies(confirming, from_packed)) return SDPSR_OK;
@@ -281,12 +333,13 @@ struct Loop {
             const bool jl2 = lab.packed();
             // a confirm round that the verify pass will judge is expected to leave the labels as they are: its gather writes the full matrix
             const SigSource qj = joint_source(jl2);
-            const bool tail = tail_applies(qj, confirming, jl2);  // this square and the speculative one go to the ctx's deferred tail
-            launch_square(jl2, key2, Xp, Cp, current, /*write_full=*/confirming && verify_applies(confirming, jl2), /*gather_only=*/tail);
+            const bool check = check_applies(confirming, jl2);             // this round and the speculative one are checked, not squared
+            const bool tail = !check && tail_applies(qj, confirming, jl2);  // this square and the speculative one go to the ctx's deferred tail
+            if (!check) launch_square(jl2, key2, Xp, Cp, current, /*write_full=*/confirming && verify_applies(confirming, jl2), /*gather_only=*/tail);
             tm.end();
             tm.begin(SDPSR_T_REFINE);
             Verdict v;
-            st = verify_round(qj, confirming, jl2, tail, &v);
+            st = check ? check_round(qj, key2, &v) : verify_round(qj, confirming, jl2, tail, &v);
             if (st) return st;
             if (v.unchanged) dj = current;  // labels (packed, and full where a gather has written them), class representatives and table hints stay as they are
             else if (!(st = initial_guess_settled())) st = lab.refine_packed(qj, &dj);  // (never a refinement of labels that were only guessed)

@@ -385,6 +385,59 @@ extern "C" int sdpsr_profile_verify_pair_w(sdpsr_ctx* c, int64_t n, int64_t d, i
     return prof_verify_pair(c, n, d, width, Lp_host, first_idx_host, a_host, b_host, out);
 }
 
+extern "C" int sdpsr_profile_square_checks(sdpsr_ctx* c, int32_t restart, uint64_t* out) {
+    CHECK_CTX(c);
+    if (!out || restart < 0 || restart > (int32_t)c->batch_children.size()) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "bad arguments");
+    const sdpsr_ctx* ci = restart == 0 ? c : c->batch_children[restart - 1];
+    out[0] = ci->square_checks;
+    out[1] = ci->square_check_fallbacks;
+    return SDPSR_OK;
+}
+
+// The square check on caller-made inputs (tests/test_gpu_square_check.py).  ws_inout == nullptr: only layout[] is filled.
+extern "C" int sdpsr_profile_square_check(sdpsr_ctx* c, int64_t n, int64_t d, int G, int T, const uint64_t* keys, int width, int write_full,
+                                          const uint32_t* Lp_host, const uint32_t* first_idx_host, uint8_t* ws_inout, uint64_t* layout,
+                                          uint32_t* verdicts_out, uint32_t* L_inout, int64_t guard) {
+    CHECK_CTX(c);
+    constexpr size_t gap = 64;
+    if (!layout || !square_check_supports(n, d, G, T) || n > 8192 || (width != 8 && width != 32) || guard < 0 || guard > (int64_t(1) << 20))
+        return ctx_fail(c, SDPSR_BAD_ARGUMENT, "bad arguments");
+    SquareCheck q;
+    q.n = n, q.d = d, q.G = G, q.T = T;
+    const size_t bytes = square_check_ws_carve(q, nullptr, gap);
+    void* ws = ctx_buf(c, "prof_sqcheck", bytes);
+    if (!ws) return SDPSR_OUT_OF_MEMORY;
+    square_check_ws_carve(q, ws, gap);
+    const void* parts[7] = {q.c, q.part_x, q.part_c, q.y, q.w, q.esum, q.bits};
+    for (int k = 0; k < 7; ++k) layout[k] = (uint64_t)((const char*)parts[k] - (const char*)ws);
+    layout[7] = bytes;
+    if (!ws_inout) return SDPSR_OK;
+    if (!keys || !Lp_host || !first_idx_host || !verdicts_out || (write_full && !L_inout)) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "null pointer");
+    hipStream_t s = c->stream;
+    uint32_t* Lw = write_full ? (uint32_t*)ctx_buf(c, "prof_lwritten", (size_t)(n * n + guard) * 4) : nullptr;
+    uint32_t* flag1 = pinned_report(c, PINNED_SPECULATIVE);
+    if ((write_full && !Lw) || !flag1) return SDPSR_OUT_OF_MEMORY;
+    ProfClasses p;
+    const int st = prof_classes_up(c, n, d, width, Lp_host, first_idx_host, &p);  // (p.flag: PINNED_VERIFY)
+    if (st) return st;
+    HIP_TRY(c, hipMemcpyAsync(ws, ws_inout, bytes, hipMemcpyHostToDevice, s));
+    if (write_full) HIP_TRY(c, hipMemcpyAsync(Lw, L_inout, (size_t)(n * n + guard) * 4, hipMemcpyHostToDevice, s));
+    for (int g = 0; g < G; ++g) q.key[g] = keys[g];
+    q.Lp = p.Lp, q.Lp8 = p.Lp8, q.first_idx = p.first, q.Lfull = Lw;
+    q.flag[0] = p.flag, q.flag[1] = flag1;
+    *(volatile uint32_t*)q.flag[0] = 0u;  // (the stream is idle: prof_classes_up waited)
+    *(volatile uint32_t*)q.flag[1] = 0u;
+    launch_square_check_ref_and_pass(s, q);
+    launch_square_check_verdict(s, q);
+    HIP_TRY(c, hipMemcpyAsync(ws_inout, ws, bytes, hipMemcpyDeviceToHost, s));
+    if (write_full) HIP_TRY(c, hipMemcpyAsync(L_inout, Lw, (size_t)(n * n + guard) * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, hipGetLastError());
+    verdicts_out[0] = ((const volatile uint32_t*)q.flag[0])[0];
+    verdicts_out[1] = ((const volatile uint32_t*)q.flag[1])[0];
+    return SDPSR_OK;
+}
+
 extern "C" int sdpsr_profile_proj_coef_lower(sdpsr_ctx* c, int64_t n, int64_t r, uint64_t key, int width, const uint32_t* Lp_host,
                                              const double* U_host, double* partial_out, double* coef_out) {
     CHECK_CTX(c);

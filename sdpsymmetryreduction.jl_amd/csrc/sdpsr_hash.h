@@ -33,6 +33,11 @@ SDPSR_HD double sdpsr_class_uniform(uint64_t key, uint32_t label) {
 // channel t (0..7) int8 value of the class: byte t of the 64 bits, as signed.
 SDPSR_HD int sdpsr_class_i8(uint64_t bits, int t) { return (int)(int8_t)(bits >> (8 * t)); }
 
+// The random vector v of the square check (kernels_square_check.hip), one per round: derived from the round's key without consuming a
+// draw.  v_i in [0, 2^16), i = 0 .. n - 1.
+SDPSR_HD uint64_t sdpsr_check_vector_key(uint64_t key) { return sdpsr_fmix64(key ^ 0xA24BAED4963EE407ULL); }
+SDPSR_HD uint32_t sdpsr_check_vector(uint64_t kv, uint32_t i) { return (uint32_t)(uint16_t)(sdpsr_class_bits(kv, i + 1u) >> 48); }
+
 // integer value in [-vmax, vmax] for the fp32-exact mode (7 bits per channel used).
 SDPSR_HD int sdpsr_class_small(uint64_t bits, int t, int vmax) {
     uint32_t b = (uint32_t)(bits >> (8 * t)) & 0xFFu;

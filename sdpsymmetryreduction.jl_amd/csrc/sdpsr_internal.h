@@ -148,6 +148,9 @@ struct sdpsr_ctx {
     // what the loop has done on this ctx (sdpsr_profile_loop_counts): squares launched by admissible_subspace, of those the
     // speculative ones, and the symmetric-basis hint bits its last run used
     uint64_t squares_launched = 0, squares_speculative = 0;
+    // guessed-closed first iterations judged by the square check (two rounds each, counted above as two squares, one speculative), and
+    // those of them that formed a real square behind a "violated" verdict read in the loop; sdpsr_profile_square_checks
+    uint64_t square_checks = 0, square_check_fallbacks = 0;
     int hint_used = 0;
     uint64_t host_waits = 0;                 // host waits for one of this ctx's streams (ctx_sync_stream); sdpsr_profile_host_waits
     uint32_t report_seq = 0;                 // stamps of the label passes' reports to pinned memory (ctx_wait_word)
@@ -352,6 +355,38 @@ bool verify_no_split_supports(const SigSource& q, int64_t d);  // launch_verify_
 // flag[0] (pinned host memory, cleared from the host) stays 0 exactly then.  false: d outside [1, verify_lds_cap()], nothing enqueued
 bool launch_verify_pair(hipStream_t s, int64_t n, const double* a, const double* b, const uint32_t* Lp, int64_t d, const uint32_t* first_idx,
                         uint32_t* flag, const uint8_t* Lp8 = nullptr);
+// the projection half of the joint verdict alone (q: SIG_JOINT_I32 with 1 <= q.r <= 4, packed labels, d <= verify_lds_cap()): the rounded
+// projected value of every entry against its class representative's; flag as above.  false: no instance, nothing enqueued
+bool launch_verify_projection(hipStream_t s, const SigSource& q, int64_t d, const uint32_t* first_idx, uint32_t* flag);
+// kernels_square_check.hip: "is X_t^2 constant on the classes (0 on label 0)?" for G rounds of T channels without forming X_t^2, from the
+// packed labels (Lp8: their byte copy, or null) and the representatives.  Stream order: ref_and_pass (class constants c, then the ONE pass
+// over the labels, which writes the full n x n label matrix to Lfull unless that is null), then verdict (y, w, the (round, channel)
+// equality bits, and a 1 into flag[g][0] -- pinned host words the caller has cleared -- for every round with a channel that differs).
+constexpr int SQUARE_CHECK_MAX_CLASSES = 255;
+constexpr int64_t SQUARE_CHECK_MAX_ORDER = 1 << 15;
+struct SquareCheck {
+    int64_t n = 0, d = 0;
+    int G = 0, T = 0;
+    uint64_t key[2] = {0, 0};
+    const uint32_t* Lp = nullptr;
+    const uint8_t* Lp8 = nullptr;
+    const uint32_t* first_idx = nullptr;
+    uint32_t* Lfull = nullptr;
+    uint32_t* flag[2] = {nullptr, nullptr};
+    // workspace (square_check_ws_carve): c [G T][d]; part_x, part_c [G T][nb][64 nb], nb = ceil(n / 64); y, w [G T][64 nb];
+    // esum [G T][nb][2]; bits [G T]
+    int32_t *c = nullptr, *part_x = nullptr;
+    int64_t *part_c = nullptr, *y = nullptr, *w = nullptr;
+    uint64_t* esum = nullptr;
+    uint32_t* bits = nullptr;
+};
+bool square_check_supports(int64_t n, int64_t d, int G, int T);
+size_t square_check_ws_bytes(int64_t n, int64_t d, int G, int T);
+// sets the workspace pointers (n, d, G, T set); returns the bytes.  gap (a multiple of 16): bytes left untouched in front of every array and
+// behind the last one (the test entry's sentinels)
+size_t square_check_ws_carve(SquareCheck& q, void* ws, size_t gap = 0);
+void launch_square_check_ref_and_pass(hipStream_t s, const SquareCheck& q);
+void launch_square_check_verdict(hipStream_t s, const SquareCheck& q);
 // loop.cpp: enqueue the next max_segments segments of the ctx's deferred tail on c->stream (none pending: nothing happens)
 void flush_deferred_tail(sdpsr_ctx* c, int max_segments = DEFERRED_SEGMENTS);
 inline bool deferred_tail_pending(const sdpsr_ctx* c) { return c->deferred_tail.next < c->deferred_tail.count; }
