@@ -236,7 +236,11 @@ int sdpsr_create(int device_id, uint64_t seed, const sdpsr_opts* opts, sdpsr_ctx
     attrs_ok &= refine_bucket_set_device_attributes();
     attrs_ok &= blockdiag_set_device_attributes();
     attrs_ok &= module_set_device_attributes();
-    attrs_ok &= partition_set_device_attributes();
+    attrs_ok &= dense_setup_set_device_attributes();
+    attrs_ok &= insert_array_pair_set_device_attributes();
+    attrs_ok &= insert_proj_set_device_attributes();
+    attrs_ok &= insert_chan_set_device_attributes();
+    attrs_ok &= insert_joint_set_device_attributes();
     attrs_ok &= sytrd_set_device_attributes();
     attrs_ok &= small_syev_set_device_attributes();
     attrs_ok &= stedc_set_device_attributes();

@@ -388,11 +388,6 @@ bool launch_label_spmm(hipStream_t s, int64_t n, const uint32_t* L, uint64_t key
                        int64_t ldw, int w, double* partials, double* Y, int64_t ldy);
 void launch_tall_times_small(hipStream_t s, int64_t n, int64_t ldi, const double* In, int kk, const double* S,
                              int lds_, int ncols, double alpha, double beta, double* out, int64_t ldo);
-void launch_transpose_rows(hipStream_t s, int64_t len, int64_t m, const double* A, double* R);
-void launch_col_norms2(hipStream_t s, int64_t len, int64_t k, const double* V, double* partial, int nblk, double* out);
-void launch_scale_copy(hipStream_t s, int64_t len, const double* v, double alpha, double* out);
-void launch_rank1_update(hipStream_t s, int64_t len, int64_t m, double* R, const double* u, const double* dots);
-void launch_sub_round(hipStream_t s, int64_t len, const double* a, const double* b, double atol, double scale, double* out);
 void launch_normalize_columns(hipStream_t s, int64_t n, int64_t ld, double* H, int64_t hstride, const double* X,
                          int64_t ldx, int nruns, double* norm0);
 void launch_random_vector(hipStream_t s, int64_t n, uint64_t key, double* x);

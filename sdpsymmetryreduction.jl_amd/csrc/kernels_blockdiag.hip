@@ -4,17 +4,11 @@
 #include <cstdlib>
 #include <type_traits>
 #include "host_internal.h"
+#include "kernel_util.h"
 
 namespace sdpsr {
 
 typedef double v4d __attribute__((ext_vector_type(4)));
-
-static inline int grid_for(int64_t work_items, int block, int max_blocks = 256 * 8) {
-    int64_t g = (work_items + block - 1) / block;
-    if (g < 1) g = 1;
-    if (g > max_blocks) g = max_blocks;
-    return (int)g;
-}
 
 // ---------------------------------------------------------------------------
 // block_norms(Q'AQ, eigdec, Inf), src/eigen_decomposition.jl:177-193: max |M[i,j]| per
@@ -333,16 +327,6 @@ __global__ void gemv_n_scaled_kernel(int64_t n, int64_t ld, const double* __rest
 void launch_gemv_n_scaled(hipStream_t s, int64_t n, int64_t ld, const double* Q, int64_t col0,
                           int64_t m, const double* w, const double* inv_norm, double* dst) {
     gemv_n_scaled_kernel<<<grid_for(n, 256), 256, 0, s>>>(n, ld, Q, col0, m, w, inv_norm, dst);
-}
-
-__global__ void copy_col_kernel(int64_t n, const double* __restrict__ src,
-                                double* __restrict__ dst) {
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
-        dst[i] = src[i];
-}
-void launch_copy_col(hipStream_t s, int64_t n, const double* src, double* dst) {
-    copy_col_kernel<<<grid_for(n, 256), 256, 0, s>>>(n, src, dst);
 }
 
 // many column copies in one launch: the (source, destination) column pairs travel by value in

@@ -11,15 +11,9 @@
 #include <cstdint>
 
 #include "sdpsr_internal.h"
+#include "kernel_util.h"
 
 namespace sdpsr {
-
-static inline int grid_for(int64_t work_items, int block, int max_blocks = 256 * 8) {
-    int64_t g = (work_items + block - 1) / block;
-    if (g < 1) g = 1;
-    if (g > max_blocks) g = max_blocks;
-    return (int)g;
-}
 
 // acc += conj(x) * y: four real FMAs
 __device__ __forceinline__ void cfma_conj(double2& acc, const double2 x, const double2 y) {

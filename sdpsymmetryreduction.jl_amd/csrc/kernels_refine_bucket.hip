@@ -1019,7 +1019,7 @@ bk_label_kernel(int64_t len, const uint32_t* __restrict__ first, uint32_t* __res
 }
 
 // ---------------------------------------------------------------------------
-// Ranks of the classes of a hash-table refinement from the TABLE's side (kernels_partition.hip, more than SMALL_K
+// Ranks of the classes of a hash-table refinement from the TABLE's side (kernels_refine.hip, more than SMALL_K
 // classes): one bit per first index, the rank records of the pass above, label of a slot = rank of its first index + 1.
 // Work on the d classes and on len / 64 words -- the entry-level count / scan / rank passes they replace read every
 // entry's slot and gathered its minimum twice (140 us at 16.7 M entries).

@@ -138,7 +138,7 @@ struct Loop {
         launch_gemm_tn_i8_sym(s, ld, ld, (const int8_t*)X, ld, (int32_t*)C, ld, T, ld * ld, ld * ld, zero_flag, c->num_cus, c->opts.square_kernel);
         ++c->squares_launched;
     }
-    // Is the projection half still able to split a class?  Not once every U_k is constant on the classes of S (kernels_partition.hip,
+    // Is the projection half still able to split a class?  Not once every U_k is constant on the classes of S (kernels_class_compare.hip,
     // launch_basis_constant_on_classes): x - U U'x of a class-constant x is then class-constant for every x, and a finer S keeps that.  Generically
     // this holds after the first projection refinement (entries of a class with different U_k get different projected values); it is CHECKED, once
     // per iteration until it holds, on the labels the last refinement made, and from then on the iteration is the square alone: no dot-product pass
@@ -156,7 +156,7 @@ struct Loop {
         return SDPSR_OK;
     }
     // Rounds that are expected NOT to refine -- a confirm round, and the first iteration (an input that is closed already) -- first ask the cheap
-    // question "does any entry differ from the representative of its class?" (one streaming compare pass, kernels_partition.hip verify_*); only a yes
+    // question "does any entry differ from the representative of its class?" (one streaming compare pass, kernels_class_compare.hip verify_*); only a yes
     // runs the insert / rank / label passes.  A confirm round re-checks the channels only: its projected element is the one the previous round has
     // cleared.
     bool verify_applies(bool confirming, bool from_packed) const {

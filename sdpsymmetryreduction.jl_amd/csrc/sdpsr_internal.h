@@ -27,7 +27,7 @@ struct DevBuf {
 namespace sdpsr {
 // Where the insert pass takes its signatures from: an array (SIG_ARRAY), or computed on the fly
 // (the signatures never travel through HBM).  Each kind is defined by one functor of
-// kernels_partition.hip (SrcPair, SrcProj<r>, SrcChan<CT, T>, SrcJoint<r, T>).
+// sig_sources.h (SrcPair, SrcProj<r>, SrcChan<CT, T>, SrcJoint<r, T>).
 // `sig` is the array (SIG_ARRAY) or len entries of scratch for the paths that need one
 // (launch_sig_materialize: sort / bucket, an overflowed table, a shape without a functor instance).
 enum { SIG_ARRAY = 0, SIG_PAIR = 1, SIG_PROJ = 2, SIG_CHAN_I32 = 3, SIG_CHAN_F32 = 4, SIG_JOINT_I32 = 5 };  // JOINT: SIG_PROJ and SIG_CHAN_I32 fields together (packed)
@@ -252,11 +252,11 @@ int ctx_fail(sdpsr_ctx* c, int status, const std::string& msg);
                             std::string(#expr) + ": " + hipGetErrorString(_e));       \
     } while (0)
 
-// ---------------------------------------------------------------------------
-// kernels_partition.hip
-// ---------------------------------------------------------------------------
 namespace sdpsr {
 
+// ---------------------------------------------------------------------------
+// kernels_gather.hip: fills, channel gathers, padded copies
+// ---------------------------------------------------------------------------
 // M[e] = values[L[e]-1] (0 -> 0.0)
 void launch_fill_f64(hipStream_t s, int64_t len, const uint32_t* L, const double* values, int64_t d,
                      double* M, uint32_t* bad_flag);
@@ -272,6 +272,10 @@ void launch_gather_f32(hipStream_t s, int64_t n, int64_t ld, int T, int vmax, co
                        uint64_t key, float* X);
 void launch_gather_f64_padded(hipStream_t s, int64_t n, int64_t ld, const uint32_t* L,
                               uint64_t key, double* X);
+// Lfull != nullptr: the kernel also writes the full n x n label matrix (leading dimension n) that the packed triangle describes
+// Lp8 != nullptr (here and below): a byte copy of the packed labels, every label <= 255 -- the kernel streams it instead of Lp, same results
+void launch_gather_i8_sym_packed(hipStream_t s, int64_t n, int64_t ld, int T, const uint32_t* Lp, uint64_t key, int8_t* X,
+                                 int64_t dmax, uint32_t* Lfull = nullptr, const uint8_t* Lp8 = nullptr);
 // dense copy with padding: dst[ld x ld] <- src[n x n], zero padding (templated by bytes)
 void launch_unpad_mirror_lower_i32(hipStream_t s, int64_t n, int64_t ld, const int32_t* src, int32_t* dst);
 void launch_pad_copy(hipStream_t s, int64_t n, int64_t ld, const void* src, void* dst,
@@ -279,24 +283,26 @@ void launch_pad_copy(hipStream_t s, int64_t n, int64_t ld, const void* src, void
 void launch_unpad_copy(hipStream_t s, int64_t n, int64_t ld, const void* src, void* dst,
                        int elem_bytes);
 
+// ---------------------------------------------------------------------------
+// kernels_projection.hip
+// ---------------------------------------------------------------------------
 // projection: coef[k] = sum_e U[e,k] * x[e] with x[e] = uniform(key, L[e]) (Lx == nullptr)
 // or x[e] = xin[e].  partial: r * nblk doubles scratch.
 void launch_proj_coef(hipStream_t s, int64_t len, int64_t r, const double* U, const uint32_t* L,
                       uint64_t key, const double* xin, double* partial, int nblk, double* coef);
-// y[e] = x[e] - sum_k U[e,k] coef[k]; optional outputs: yout (rounded value, fp64),
-// sig (signature chained on L).  x as above.
-// Lfull != nullptr: the kernel also writes the full n x n label matrix (leading dimension n) that the packed triangle describes
-// Lp8 != nullptr (here and below): a byte copy of the packed labels, every label <= 255 -- the kernel streams it instead of Lp, same results
-void launch_gather_i8_sym_packed(hipStream_t s, int64_t n, int64_t ld, int T, const uint32_t* Lp, uint64_t key, int8_t* X,
-                                 int64_t dmax, uint32_t* Lfull = nullptr, const uint8_t* Lp8 = nullptr);
 void launch_proj_coef_lower(hipStream_t s, int64_t n, int64_t r, const double* U, const uint32_t* L, int lab_packed,
                             uint64_t key, double* partial, int nblk, double* coef, const uint8_t* Lp8 = nullptr);
 void launch_proj_coef_probe(hipStream_t s, int64_t len, int64_t n, int64_t r, const double* U, const uint32_t* L, uint64_t key,
                             double* partial, int nblk, double* coef);
+// y[e] = x[e] - sum_k U[e,k] coef[k]; optional outputs: yout (rounded value, fp64),
+// sig (signature chained on L).  x as above.
 void launch_proj_apply(hipStream_t s, int64_t len, int64_t r, const double* U, const uint32_t* L,
                        uint64_t key, const double* xin, const double* coef, double atol,
                        double scale, int do_round, double* yout, uint64_t* sig);
 
+// ---------------------------------------------------------------------------
+// kernels_signature.hip
+// ---------------------------------------------------------------------------
 // signatures.  sig = 0 <=> (L == 0 and key == 0).  L may be nullptr (all zero labels).
 void launch_sig_f64(hipStream_t s, int64_t len, const uint32_t* L, const double* v, uint64_t* sig);
 void launch_sig_f64_rounded(hipStream_t s, int64_t n, int64_t ld, const uint32_t* L,
@@ -310,7 +316,12 @@ void launch_sig_i32(hipStream_t s, int64_t n, int64_t ld, int T, const uint32_t*
                     const int32_t* C, uint64_t* sig, int packed = 0, int lab_packed = 0);
 void launch_sig_f32(hipStream_t s, int64_t n, int64_t ld, int T, const uint32_t* L,
                     const float* C, uint64_t* sig, int packed = 0, int lab_packed = 0);
+bool sig_source_fusable(const SigSource& q);
+bool launch_sig_materialize(hipStream_t s, int64_t len, const SigSource& q, uint64_t* sig);  // false: nothing writes this source out
 
+// ---------------------------------------------------------------------------
+// kernels_refine.hip (the insert pass: kernels_insert_*.hip, one file per source family)
+// ---------------------------------------------------------------------------
 // canonical relabel of signatures (hash table + first-occurrence ranking).
 // Workspace layout is owned by the caller (see refine_workspace_bytes).
 // slot of the refinement's global table: signature and first index side by side -- ONE 16-byte gather per look-up (a gather that
@@ -339,8 +350,16 @@ struct RefineWs {
 size_t refine_block_entries();
 size_t refine_counters_bytes();
 uint32_t refine_small_k();
-bool sig_source_fusable(const SigSource& q);
 uint32_t refine_first_cap();
+// slot: len entries of scratch; labels_out may alias q.L (it is written only by a pass that succeeded)
+// sym_n > 0 (and len == sym_n^2): the label pass also checks the new labels for symmetry, counters[3] = 1 if NOT symmetric
+bool refine_mid_supports(const SigSource& q);  // RefineWs::mid is honoured for this source
+bool launch_refine(hipStream_t s, int64_t len, const SigSource& q, uint32_t* slot, uint32_t* labels_out,
+                   const RefineWs& ws, int64_t sym_n = 0);  // false: q is not sig_source_fusable
+
+// ---------------------------------------------------------------------------
+// kernels_class_compare.hip
+// ---------------------------------------------------------------------------
 size_t verify_ref_bytes(int64_t d);
 size_t uconst_ref_bytes(int64_t d, int64_t r);
 // The two checks below are ONE launch up to verify_lds_cap() classes (the table of representatives is built in LDS by every workgroup, `ref` is
@@ -393,12 +412,6 @@ inline bool deferred_tail_pending(const sdpsr_ctx* c) { return c->deferred_tail.
 // kernels_module.hip: one thread stores `seq` into a word of coherent pinned host memory, behind a system-scope fence: what the
 // kernels before it in the stream stored into pinned memory is complete when the host sees the stamp (ctx_wait_word)
 void launch_report_stamp(hipStream_t s, uint32_t* host_word, uint32_t seq);
-bool launch_sig_materialize(hipStream_t s, int64_t len, const SigSource& q, uint64_t* sig);  // false: nothing writes this source out
-// slot: len entries of scratch; labels_out may alias q.L (it is written only by a pass that succeeded)
-// sym_n > 0 (and len == sym_n^2): the label pass also checks the new labels for symmetry, counters[3] = 1 if NOT symmetric
-bool refine_mid_supports(const SigSource& q);  // RefineWs::mid is honoured for this source
-bool launch_refine(hipStream_t s, int64_t len, const SigSource& q, uint32_t* slot, uint32_t* labels_out,
-                   const RefineWs& ws, int64_t sym_n = 0);  // false: q is not sig_source_fusable
 
 // kernels_refine_sort.hip: radix-sort relabel for the many-classes regime
 size_t refine_bucketed_workspace_bytes(int64_t len);
@@ -416,21 +429,36 @@ size_t refine_sorted_workspace_bytes(int64_t len);
 bool launch_refine_sorted(hipStream_t s, int64_t len, const uint64_t* sig, uint32_t* labels_out, void* ws, size_t ws_bytes,
                           uint32_t* counters);
 
+// ---------------------------------------------------------------------------
+// kernels_label_util.hip
+// ---------------------------------------------------------------------------
 void launch_max_pair_code(hipStream_t s, int64_t len, const uint32_t* p1, const uint32_t* p2, uint64_t d1, uint64_t* out);
 void launch_transpose_labels(hipStream_t s, int64_t n, const uint32_t* L, uint32_t* Lt);
 void launch_labels_checksum(hipStream_t s, int64_t len, const uint32_t* L, uint64_t* partial, uint64_t* out);
+void launch_unpack_symmetric_labels(hipStream_t s, int64_t n, const uint32_t* Lp, uint32_t* L);
+// symmetric-labels check: flag[0] = 1 if some L[i,j] != L[j,i]
+void launch_check_symmetric(hipStream_t s, int64_t n, const uint32_t* L, uint32_t* flag);
+void launch_copy_check_symmetric(hipStream_t s, int64_t n, const uint32_t* src, uint32_t* dst, uint32_t* flag, uint32_t epoch);
+// dst = src (n x n labels; dst == src allowed) with two verdicts from the same tiles:
+// flag[0] = 1 if src is not symmetric, flag[1] = 1 if a label exceeds dmax.  The caller clears flag[0..1] first.
+void launch_copy_check_labels(hipStream_t s, int64_t n, const uint32_t* src, uint32_t* dst, uint32_t dmax, uint32_t* flag);
+
+// ---------------------------------------------------------------------------
+// kernels_dense_setup.hip: the small dense algebra of setup_dense.cpp and reduce_csr.cpp
+// ---------------------------------------------------------------------------
 int64_t reduce_columns_chunk(int64_t len, int64_t m, int64_t d);
 bool launch_reduce_columns(hipStream_t s, int64_t len, int64_t m, int64_t d, const uint32_t* L, const double* A,
                            double* partial, double* out, uint32_t* bad_flag);
-// kernels_module.hip / setup-stage helpers used across api.cpp
-void launch_symmetrize(hipStream_t s, int64_t m, int64_t ld, double* B);
-void launch_tall_times_small(hipStream_t s, int64_t n, int64_t ldi, const double* In, int kk, const double* S,
-                             int lds_, int ncols, double alpha, double beta, double* out, int64_t ldo);
 void launch_transpose_rows(hipStream_t s, int64_t len, int64_t m, const double* A, double* R);
 void launch_col_norms2(hipStream_t s, int64_t len, int64_t k, const double* V, double* partial, int nblk, double* out);
 void launch_scale_copy(hipStream_t s, int64_t len, const double* v, double alpha, double* out);
 void launch_rank1_update(hipStream_t s, int64_t len, int64_t m, double* R, const double* u, const double* dots);
 void launch_sub_round(hipStream_t s, int64_t len, const double* a, const double* b, double atol, double scale, double* out);
+
+// kernels_module.hip / setup-stage helpers used across api.cpp
+void launch_symmetrize(hipStream_t s, int64_t m, int64_t ld, double* B);
+void launch_tall_times_small(hipStream_t s, int64_t n, int64_t ldi, const double* In, int kk, const double* S,
+                             int lds_, int ncols, double alpha, double beta, double* out, int64_t ldo);
 // The form launch_label_spmm_multi gives a shape (kernels_module.hip): matrix cores (label_spmm_mfma_kernel<tile, G>, tile = JT
 // tiles of 16 columns of W) or VALU (label_spmm_sload_kernel<tile, G>, tile = WMAX), the column range split over z workgroups
 // of cols_per_block columns each.  false: shape not supported.
@@ -453,7 +481,11 @@ bool launch_label_spmm_pair(hipStream_t s, int64_t n, const uint32_t* L, const u
 bool gemm_set_device_attributes();
 bool blockdiag_set_device_attributes();
 bool module_set_device_attributes();
-bool partition_set_device_attributes();
+bool dense_setup_set_device_attributes();
+bool insert_array_pair_set_device_attributes();  // kernels_insert_*.hip: the mid kernels of the sources with SRC::kMid
+bool insert_proj_set_device_attributes();
+bool insert_chan_set_device_attributes();
+bool insert_joint_set_device_attributes();
 bool sytrd_set_device_attributes();
 bool small_syev_set_device_attributes();
 bool stedc_set_device_attributes();
@@ -522,10 +554,6 @@ const void* sytrd_look_kernel_fn(int mode, int64_t ld);
 void sytrd_graph_cache_destroy(SytrdGraphCache* g);
 void sytrd_graph_cache_stats(const SytrdGraphCache* g, uint64_t* hits, uint64_t* misses, double* instantiate_ms);
 
-// symmetric-labels check: flag[0] = 1 if some L[i,j] != L[j,i]
-void launch_check_symmetric(hipStream_t s, int64_t n, const uint32_t* L, uint32_t* flag);
-void launch_copy_check_symmetric(hipStream_t s, int64_t n, const uint32_t* src, uint32_t* dst, uint32_t* flag, uint32_t epoch);
-
 // ---------------------------------------------------------------------------
 // kernels_gemm.hip:  C = A' * B (column-major), MFMA tiles staged through LDS.
 // Operands must be padded: k multiple of KT, m and n multiples of 128, pointers 16-B
@@ -542,7 +570,6 @@ bool i8_symsquare_pays(int64_t n, int T, int num_cus);
 bool gemm_sym_set_device_attributes();
 void launch_gemm_tn_f32_sym(hipStream_t s, int64_t n, int64_t k, const float* X, int64_t ldx, float* C, int64_t ldc,
                             int batch, int64_t strideX, int64_t strideC, const uint32_t* nonsym_flag);
-void launch_unpack_symmetric_labels(hipStream_t s, int64_t n, const uint32_t* Lp, uint32_t* L);
 void launch_gemm_tn_i8(hipStream_t s, int64_t m, int64_t n, int64_t k, const int8_t* A,
                        int64_t lda, const int8_t* B, int64_t ldb, int32_t* C, int64_t ldc,
                        int batch, int64_t strideA, int64_t strideB, int64_t strideC);
@@ -574,17 +601,12 @@ void launch_coupling_count(hipStream_t s, int neig, const unsigned long long* no
 void launch_coupling_bits(hipStream_t s, int neig, const unsigned long long* norms, double thr, unsigned long long* bits);
 void launch_block_norms(hipStream_t s, int64_t n, int64_t ld, const double* M,
                         const int32_t* space_of, int neig, unsigned long long* norms);
-// y = A * x for symmetric A (n x n, ld) and nv vectors (columns of X, ldx): Y[:,v]
-void launch_symm_multi_gemv(hipStream_t s, int64_t n, int64_t ld, const double* A,
-                            const double* X, int64_t ldx, int nv, double* Y, int64_t ldy);
 // out[j] = sum_i Q[i, col0 + j] * a[i], j < m   (Q' a over a column range)
 void launch_gemv_t(hipStream_t s, int64_t n, int64_t ld, const double* Q, int64_t col0,
                    int64_t m, const double* a, double* out);
 // dst[i] (+)= alpha_dev[0] * sum_j Q[i, col0+j] * w[j]
 void launch_gemv_n_scaled(hipStream_t s, int64_t n, int64_t ld, const double* Q, int64_t col0,
                           int64_t m, const double* w, const double* inv_norm, double* dst);
-// copy column / clamp
-void launch_copy_col(hipStream_t s, int64_t n, const double* src, double* dst);
 void launch_irreducible_pairs(hipStream_t s, int64_t n, int64_t ld, const double* Q, const double* Bf, int npairs,
                               int max_m2, const int32_t* desc, double* Qhat);
 void launch_copy_cols(hipStream_t s, int64_t n, int64_t count, const int32_t* src_cols, const int32_t* dst_cols,
@@ -640,9 +662,6 @@ void launch_radix_sort_pairs(hipStream_t s, int64_t len, int bits, const uint32_
 // stable sort of entries by label (label 0 dropped): ent sorted, hist[d+1]; the d classes from `first` on
 int sort_entries_by_label(sdpsr_ctx* c, int64_t len, int64_t d, const uint32_t* L,
                           uint32_t** ent_out, std::vector<int64_t>& class_ptr_host, uint32_t first = 1);
-// kernels_partition.hip: dst = src (n x n labels; dst == src allowed) with two verdicts from the same tiles:
-// flag[0] = 1 if src is not symmetric, flag[1] = 1 if a label exceeds dmax.  The caller clears flag[0..1] first.
-void launch_copy_check_labels(hipStream_t s, int64_t n, const uint32_t* src, uint32_t* dst, uint32_t dmax, uint32_t* flag);
 
 // ---------------------------------------------------------------------------
 // eigen.cpp (rocSOLVER)

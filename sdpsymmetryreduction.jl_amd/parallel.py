@@ -35,7 +35,7 @@ def torch_checksum(labels):
     import torch
     idx = torch.arange(labels.numel(), dtype=torch.int64, device=labels.device)
     l = labels.reshape(-1).to(torch.int64) + 1
-    # same formula and constants as labels_checksum_kernel (csrc/kernels_partition.hip)
+    # same formula and constants as labels_checksum_kernel (csrc/kernels_label_util.hip)
     h1 = (l * (idx * _signed(0x9E3779B97F4A7C15) + _signed(0xD1342543DE82EF95))).sum()
     h2 = ((l * l + _signed(0x27D4EB2F165667C5)) *
           ((idx ^ (idx >> 13)) * _signed(0xBF58476D1CE4E5B9) + _signed(0x94D049BB133111EB))).sum()

@@ -129,7 +129,7 @@ def _verify_case(pkg, ctx, n, T, d, r, zero):
 def test_verify_pass_verdicts_and_single_entry_needles(pkg, gpu_ctx, T, r):
     """Every order with one class count and zero-class choice each (rotating, so that all of them occur for every T and r).
     (Joint with r = 2 or 4 and T = 2 the launcher keeps the wide labels at width 8 too -- the byte form would lose a wave per SIMD,
-    csrc/kernels_partition.hip: launch_verify_rt -- so those cases pin that the choice changes no verdict.)"""
+    csrc/kernels_class_compare.hip: launch_verify_rt -- so those cases pin that the choice changes no verdict.)"""
     for k, n in enumerate(SIZES):
         _verify_case(pkg, gpu_ctx, n, T, CLASSES[(k + T + r) % 3], r, zero=(k + r) % 2 == 0)
 

@@ -1836,7 +1836,7 @@ def _loop_run(pkg, setup, channels, flags=0, refine_path="auto"):
 @pytest.mark.parametrize("name", SIG_INSTANCES)
 def test_signature_array_path_equals_fused_path(pkg, sig_instances, name, channels):
     """A computed signature source (pair, projection, channels, joint) is defined once, by its functor in
-    kernels_partition.hip; the insert pass evaluates it entry by entry, and SDPSR_FLAG_REFINE_NO_FUSE writes it out as an array
+    sig_sources.h; the insert pass evaluates it entry by entry, and SDPSR_FLAG_REFINE_NO_FUSE writes it out as an array
     first (the materialise kernel, or the stand-alone kernel of a run-time shape: 3 channels, r > 4) and refines that.  Same
     seed and same control flow, so the same keys and the same signatures either way: labels BIT-IDENTICAL, and the same
     dimension after every iteration and the same iteration count -- in the default loop (joint iteration on packed labels), with

@@ -1,4 +1,4 @@
-"""The pair check of the loop's guessed initial partition (csrc/kernels_partition.hip: class_compare_kernel with ChkPair), driven on made-up
+"""The pair check of the loop's guessed initial partition (csrc/kernels_class_compare.hip: class_compare_kernel with ChkPair), driven on made-up
 inputs through libsdpsr_prof.so (sdpsr_profile_verify_pair).
 
 The check answers "would the refinement of the value pairs (a, b) over the packed lower triangle write these labels and these
