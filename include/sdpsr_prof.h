@@ -104,6 +104,31 @@ int sdpsr_profile_verify_pair_w(sdpsr_ctx* ctx, int64_t n, int64_t d, int width,
                                 const double* a_host, const double* b_host, uint32_t* out);
 int sdpsr_profile_proj_coef_lower(sdpsr_ctx* ctx, int64_t n, int64_t r, uint64_t key, int width, const uint32_t* Lp_host, const double* U_host,
                                   double* partial_out, double* coef_out);
+/* One refinement over a COMPUTED signature source on caller-made inputs (tests/test_gpu_refine_sources.py): the source is put together as the
+   loop does it and handed to the product's own refine_signatures, which refines through it in the form the ctx's flags and refine_path
+   choose (insert kernel of the source's functor, materialised array, sort, bucket, the mid kernel).  Conventions of the module-kernel entries
+   below: host arrays, every *_inout array uploaded as filled and downloaded whole (guard included), SDPSR_BAD_ARGUMENT before any upload.
+   kind: 0 = value pairs (a_host, b_host: n * n doubles; packed: column-major, the lower triangle is read; else flat), 1 = rounded projection
+   y = x(l) - sum_k U_k coef_k (U_host: r * n * n, coef_host: r, x drawn from the old label and key), 2 / 3 = T int32 / float channels
+   (C_host: T * ld * ld, ld a multiple of 128), 4 = projection and int32 channels together.  1 <= n <= 2048, ld <= 2048, T <= 8, r <= 8.
+   packed: the source runs over the lower triangle column by column (n (n + 1) / 2 entries), else over all n * n; lab_packed: the old labels
+   are that packed triangle themselves.  L_inout: the old labels, n (n + 1) / 2 or n * n words by lab_packed, + guard; the refinement runs IN
+   PLACE on its device copy -- except packed without lab_packed, where the loop reads the full labels and writes the packed ones: then the
+   new labels go to Lnew_inout (n (n + 1) / 2 + guard words; null otherwise) and L_inout comes back as it was.  kind 0 has no old labels:
+   L_inout (sized by packed) receives the result.
+   what 0: refine through the source.  what 1: the stand-alone kernel of run-time shape (sig_channels_kernel, proj_apply_kernel) writes the
+   signature array and that is refined; refused where no such kernel exists (kind 0 and 4, a packed projection).  A source that has neither
+   a functor instance nor a stand-alone kernel is refused (a packed projection with r > 4, kind 4 not packed or with T other than 2, 4).
+   sig_out (optional, one word per entry): the signatures as launch_sig_materialize (what 0) resp. the stand-alone kernel (what 1) writes
+   them, by a launch of its own before the refinement.  prev_classes: the ctx's class-count prediction is set to what a refinement that
+   ended with this many classes leaves.  sym != 0 (not packed): the symmetry verdict of the new n x n labels is asked for as well.
+   *nparts = the class count; first_out (optional, min(*nparts, 65536) words are written) = the head of "ref_first"; report[0] = relabel
+   passes the driver ran (repeats included), report[1] = symmetry verdict (1 symmetric, 0 not, -1 not asked for), report[2] = 1 when the
+   ctx records "ref_first" as describing the new labels. */
+int sdpsr_profile_refine_source(sdpsr_ctx* ctx, int kind, int what, int64_t n, int64_t ld, int T, int r, int packed, int lab_packed, uint64_t key,
+                                double atol, const double* a_host, const double* b_host, const double* U_host, const double* coef_host,
+                                const void* C_host, uint32_t* L_inout, uint32_t* Lnew_inout, int64_t guard, int64_t prev_classes, int sym,
+                                uint64_t* sig_out, int64_t* nparts, uint32_t* first_out, int32_t* report);
 /* Guessed-closed first iterations of ctx (restart 0) or of batch restart `restart` whose two rounds were judged by the square check instead of
    two int8 squares (out[0]), and those of them that formed a real square behind a "violated" verdict read inside the loop (out[1]). */
 int sdpsr_profile_square_checks(sdpsr_ctx* ctx, int32_t restart, uint64_t* out);

@@ -258,6 +258,10 @@ def load_prof_library():
     lib.sdpsr_profile_square_check.argtypes = [vp, i64, i64, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, i64]
     lib.sdpsr_profile_proj_coef_lower.restype = C.c_int
     lib.sdpsr_profile_proj_coef_lower.argtypes = [vp, i64, i64, C.c_uint64, C.c_int, vp, vp, vp, vp]
+    # one refinement over a computed signature source on caller-made inputs (tests)
+    lib.sdpsr_profile_refine_source.restype = C.c_int
+    lib.sdpsr_profile_refine_source.argtypes = [vp, C.c_int, C.c_int, i64, i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_double,
+                                                vp, vp, vp, vp, vp, vp, vp, i64, i64, C.c_int, vp, C.POINTER(i64), vp, C.POINTER(C.c_int32)]
     # the module-compression kernels on caller-made inputs (tests)
     f64, rep = C.c_double, C.POINTER(C.c_int32)
     lib.sdpsr_profile_gram.restype = C.c_int

@@ -119,6 +119,12 @@ inline int ceil_log2(uint64_t x) {
     while ((uint64_t(1) << l) < x) ++l;
     return l;
 }
+// sdpsr_ctx::table_log2_hint as a refinement of len entries that ended with `classes` classes leaves it: a table with at most an
+// eighth of its slots taken, between 2^12 slots and the full size of the input (two slots per entry)
+inline int refine_table_hint(int64_t len, uint64_t classes) {
+    const int full = std::max(12, ceil_log2((uint64_t)len * 2));
+    return std::min(full, std::max(12, ceil_log2(classes * 8 + 1)));
+}
 
 double round_scale(const sdpsr_ctx* c, double atol);
 bool label_overflows(const sdpsr_ctx* c, uint64_t value);

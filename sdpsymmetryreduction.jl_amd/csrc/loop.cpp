@@ -492,8 +492,7 @@ struct Loop {
             lab.packed_refined();
             lab.shadow_current();
             // (the hint a refinement that found d0 classes leaves, primitives.cpp; first_idx_labels is Lp already)
-            const int full = std::max(12, ceil_log2((uint64_t)(n * (n + 1) / 2) * 2));
-            c->table_log2_hint = std::min(full, std::max(12, ceil_log2((uint64_t)guess->d0 * 8 + 1)));
+            c->table_log2_hint = refine_table_hint(n * (n + 1) / 2, (uint64_t)guess->d0);
             return SDPSR_OK;
         }
         return lab.refine_packed(q, d);

@@ -59,6 +59,7 @@ int refine_signatures(sdpsr_ctx* c, int64_t len, const SigSource& src_in, uint32
     // (table_log2_hint = ceil(log2(8 d + 1)) of the previous refinement's class count d)
     bool use_sort = sort_ok && (forced_relabel || (c->table_log2_hint >= 4 && (int64_t(1) << (c->table_log2_hint - 4)) >= group_from));
     for (;;) {
+        ++c->refine_passes;
         if (use_sort) {
             // the hand-written bucketed grouping (kernels_refine_bucket.hip); hipCUB's radix sort behind refine_path = 2
             // and as the fallback for signatures the grouping reports it cannot resolve
@@ -93,7 +94,7 @@ int refine_signatures(sdpsr_ctx* c, int64_t len, const SigSource& src_in, uint32
             }
             if (sym_n > 0 && symflag_dev && sym_out) *sym_out = *hsym ? 0 : 1;
             *nparts = h[REFINE_CLASSES];
-            c->table_log2_hint = std::min(full, std::max(12, ceil_log2((uint64_t)h[REFINE_CLASSES] * 8 + 1)));
+            c->table_log2_hint = refine_table_hint(len, h[REFINE_CLASSES]);
             if (!cub && h[REFINE_CLASSES] <= refine_first_cap()) c->first_idx_labels = labels;  // "ref_first" describes these labels
             return SDPSR_OK;
         }
@@ -191,7 +192,7 @@ int refine_signatures(sdpsr_ctx* c, int64_t len, const SigSource& src_in, uint32
             continue;
         }
         *nparts = h[REFINE_CLASSES];
-        c->table_log2_hint = std::min(full, std::max(12, ceil_log2((uint64_t)h[REFINE_CLASSES] * 8 + 1)));
+        c->table_log2_hint = refine_table_hint(len, h[REFINE_CLASSES]);
         if (h[REFINE_CLASSES] <= refine_first_cap()) c->first_idx_labels = labels;  // "ref_first" describes these labels
         return SDPSR_OK;
     }

@@ -464,6 +464,99 @@ extern "C" int sdpsr_profile_proj_coef_lower(sdpsr_ctx* c, int64_t n, int64_t r,
     return SDPSR_OK;
 }
 
+// One refinement over a computed signature source on caller-made inputs (tests/test_gpu_refine_sources.py): the SigSource is put together
+// the way loop.cpp does it (proj_source, chan_source, joint_source, initial_partition) and handed to the product's refine_signatures, the
+// labels in place wherever the loop refines in place.  Conventions of the module-kernel entries below.
+extern "C" int sdpsr_profile_refine_source(sdpsr_ctx* c, int kind, int what, int64_t n, int64_t ld, int T, int r, int packed, int lab_packed,
+                                           uint64_t key, double atol, const double* a_host, const double* b_host, const double* U_host,
+                                           const double* coef_host, const void* C_host, uint32_t* L_inout, uint32_t* Lnew_inout, int64_t guard,
+                                           int64_t prev_classes, int sym, uint64_t* sig_out, int64_t* nparts, uint32_t* first_out, int32_t* report) {
+    CHECK_CTX(c);
+    enum { RS_PAIR = 0, RS_PROJ = 1, RS_CHAN_I32 = 2, RS_CHAN_F32 = 3, RS_JOINT = 4 };
+    const bool pair = kind == RS_PAIR, proj = kind == RS_PROJ || kind == RS_JOINT, chan = kind == RS_CHAN_I32 || kind == RS_CHAN_F32 || kind == RS_JOINT;
+    if (kind < RS_PAIR || kind > RS_JOINT || (what != 0 && what != 1) || n < 1 || n > 2048 || guard < 0 || guard > (int64_t(1) << 20) ||
+        prev_classes < 0 || prev_classes > (int64_t(1) << 32) || !L_inout || !nparts || !report || (packed != 0 && packed != 1) ||
+        (lab_packed != 0 && lab_packed != 1) || (lab_packed && !packed) || (sym && packed))
+        return ctx_fail(c, SDPSR_BAD_ARGUMENT, "refine_source: bad arguments");
+    if (pair && (!a_host || !b_host || lab_packed != packed)) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "refine_source: bad pair source");
+    if (proj && (r < 0 || r > 8 || (r > 0 && (!U_host || !coef_host)) || !(atol > 0))) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "refine_source: bad projection");
+    if (chan && (!C_host || T < 1 || T > 8 || ld < n || ld > 2048 || ld % 128)) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "refine_source: bad channels");
+    // the loop refines the packed triangle from full labels into ANOTHER array (LoopLabels::refine_packed: reads L, writes Lp)
+    const bool apart = !pair && packed && !lab_packed;
+    if (apart != (Lnew_inout != nullptr)) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "refine_source: Lnew_inout goes with packed and not lab_packed");
+    hipStream_t s = c->stream;
+    const int64_t np = n * (n + 1) / 2, len = packed ? np : n * n, lablen = lab_packed ? np : n * n;
+    const int64_t rr = proj ? r : 0;
+    const size_t cb = chan ? (size_t)T * ld * ld * 4 : 0;
+    double* ab = pair ? (double*)ctx_buf(c, "prof_rs_ab", (size_t)2 * n * n * 8) : nullptr;
+    double* Ud = proj ? (double*)ctx_buf(c, "prof_rs_u", (size_t)(rr * n * n + rr + 1) * 8) : nullptr;  // + the coefficients
+    void* Cd = chan ? ctx_buf(c, "prof_rs_c", cb) : nullptr;
+    uint32_t* Ld = (uint32_t*)ctx_buf(c, "prof_rs_l", (size_t)(lablen + guard) * 4);
+    uint32_t* Lnew = apart ? (uint32_t*)ctx_buf(c, "prof_rs_lnew", (size_t)(np + guard) * 4) : nullptr;
+    uint64_t* sig = (uint64_t*)ctx_buf(c, "prof_rs_sig", (size_t)len * 8);
+    uint64_t* sig2 = (sig_out && what == 0) ? (uint64_t*)ctx_buf(c, "prof_rs_sig2", (size_t)len * 8) : nullptr;
+    uint32_t* symflag = sym ? (uint32_t*)ctx_buf(c, "prof_rs_symflag", 64) : nullptr;
+    if ((pair && !ab) || (proj && !Ud) || (chan && !Cd) || !Ld || (apart && !Lnew) || !sig || (sig_out && what == 0 && !sig2) || (sym && !symflag))
+        return SDPSR_OUT_OF_MEMORY;
+    double* coef = proj ? Ud + rr * n * n : nullptr;
+    SigSource q;
+    q.sig = sig;
+    if (pair) {
+        q.kind = SIG_PAIR, q.a = ab, q.b = ab + n * n;
+        if (packed) q.n = n, q.packed = 1;
+    } else {
+        if (proj) q.kind = SIG_PROJ, q.U = Ud, q.coef = coef, q.r = (int)rr, q.key = key, q.atol = atol, q.scale = round_scale(c, atol), q.n = n;
+        if (chan) q.kind = kind == RS_JOINT ? SIG_JOINT_I32 : (kind == RS_CHAN_F32 ? SIG_CHAN_F32 : SIG_CHAN_I32), q.n = n, q.ld = ld, q.T = T, q.C = Cd;
+        q.L = Ld, q.packed = packed, q.lab_packed = lab_packed;
+    }
+    // who writes this source's signatures: its functor (insert and materialise kernels), or the stand-alone kernel of its run-time shape
+    const bool standalone = (chan && kind != RS_JOINT) || (kind == RS_PROJ && !packed);
+    if (what == 0 ? !(sig_source_fusable(q) || standalone) : !standalone)
+        return ctx_fail(c, SDPSR_BAD_ARGUMENT, "refine_source: no kernel for this source's shape");
+    if (pair) {
+        HIP_TRY(c, hipMemcpyAsync(ab, a_host, (size_t)n * n * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(ab + n * n, b_host, (size_t)n * n * 8, hipMemcpyHostToDevice, s));
+    }
+    if (rr > 0) {
+        HIP_TRY(c, hipMemcpyAsync(Ud, U_host, (size_t)rr * n * n * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(coef, coef_host, (size_t)rr * 8, hipMemcpyHostToDevice, s));
+    }
+    if (chan) HIP_TRY(c, hipMemcpyAsync(Cd, C_host, cb, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(Ld, L_inout, (size_t)(lablen + guard) * 4, hipMemcpyHostToDevice, s));
+    if (apart) HIP_TRY(c, hipMemcpyAsync(Lnew, Lnew_inout, (size_t)(np + guard) * 4, hipMemcpyHostToDevice, s));
+    uint32_t* labels = apart ? Lnew : Ld;
+    c->table_log2_hint = refine_table_hint(len, (uint64_t)prev_classes);
+    const uint64_t passes0 = c->refine_passes;
+    int64_t d = 0;
+    int symv = -1, st;
+    if (what == 0) {
+        if (sig_out) {
+            if (!launch_sig_materialize(s, len, q, sig2)) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "refine_source: nothing writes this source out");
+            HIP_TRY(c, hipMemcpyAsync(sig_out, sig2, (size_t)len * 8, hipMemcpyDeviceToHost, s));
+        }
+        st = sym ? refine_signatures(c, len, q, labels, &d, n, symflag, &symv) : refine_signatures(c, len, q, labels, &d);
+    } else {
+        if (kind == RS_PROJ) launch_proj_apply(s, len, rr, Ud, Ld, key, nullptr, coef, atol, q.scale, 1, nullptr, sig);
+        else if (kind == RS_CHAN_I32) launch_sig_i32(s, n, ld, T, Ld, (const int32_t*)Cd, sig, packed, lab_packed);
+        else launch_sig_f32(s, n, ld, T, Ld, (const float*)Cd, sig, packed, lab_packed);
+        if (sig_out) HIP_TRY(c, hipMemcpyAsync(sig_out, sig, (size_t)len * 8, hipMemcpyDeviceToHost, s));
+        st = sym ? refine_signatures(c, len, sig, labels, &d, n, symflag, &symv) : refine_signatures(c, len, sig, labels, &d);
+    }
+    if (st) return st;
+    HIP_TRY(c, hipMemcpyAsync(L_inout, Ld, (size_t)(lablen + guard) * 4, hipMemcpyDeviceToHost, s));
+    if (apart) HIP_TRY(c, hipMemcpyAsync(Lnew_inout, Lnew, (size_t)(np + guard) * 4, hipMemcpyDeviceToHost, s));
+    const uint32_t* first = (const uint32_t*)ctx_buf(c, "ref_first", (size_t)refine_first_cap() * 4);
+    if (first_out && first && d > 0)
+        HIP_TRY(c, hipMemcpyAsync(first_out, first, (size_t)std::min<int64_t>(d, refine_first_cap()) * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, hipGetLastError());
+    *nparts = d;
+    report[0] = (int32_t)(c->refine_passes - passes0);
+    report[1] = symv;
+    report[2] = c->first_idx_labels == labels ? 1 : 0;
+    return SDPSR_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------
 // The kernels of the module-compression driver on caller-made inputs (tests/test_gpu_module_kernels.py): host arrays in, the
 // product's own launcher called the way compress.cpp calls it, everything back.  Every output array is in/out: uploaded as the

@@ -134,6 +134,7 @@ struct sdpsr_ctx {
     bool bd_qrm_current = false;
     // hash table capacity hint (log2) for the next refine
     int table_log2_hint = 12;
+    uint64_t refine_passes = 0;  // relabel passes refine_signatures has run on this ctx, repeats included (sdpsr_profile_refine_source)
     hipEvent_t ev[2 * SDPSR_T_COUNT] = {};
     // sdpsr_jordan_reduce_batch: this ctx runs one restart on a fiber of the calling thread; a host wait for one of its
     // streams polls and hands the thread to the other restarts (ctx_sync_stream).  nullptr outside a batch call.
