@@ -873,6 +873,70 @@ int sdpsr_comm_broadcast(sdpsr_ctx* ctx, sdpsr_comm* comm, void* buf, int64_t by
 /* before the ctx it was created on is destroyed */
 int sdpsr_comm_destroy(sdpsr_comm* comm);
 
+/* ---- the reduced PSD blocks as an operator: Z(x), its adjoint, block spectra -------------------------------
+   The reduced PSD constraint is the pencil  Z_k(x) = sum_i x_i blks[i][k],  k = 1 .. nblocks  --
+   sum(blkD.blks[i] .* x[i] for i = 1:dim(P)), docs/src/examples/ErdosRenyiThetaFunction.jl:83, QuadraticAssignmentProblems.jl:136,
+   test/sd_problems.jl:46-52,127-134.  These entries evaluate it, its adjoint  g_i = sum_k <blks[i][k], S_k>  and the spectra of
+   all blocks on the device, from the triplets sdpsr_block_images_sparse writes: what one iteration of a first-order method over
+   the reduced SDP needs, and the certificate (lambda_min of every block) of a solved one.  No SDP is solved here.
+
+   sdpsr_blockop: a device-resident handle, read-only after creation; any ctx of its device may use it; the caller destroys it
+   (before the device is reset; a ctx is not needed for that).
+     nblocks, blk_sizes  host array of the VIRTUAL orders s'_k >= 1 (s_k for real images, 2 s_k for the real embedding of complex
+                  ones), sum s'_k^2 < 2^32;
+     d            the number of classes (x has d elements), 0 <= d < 2^31;
+     classptr blk row col val   exactly what sdpsr_block_images_sparse writes (classptr: d + 1 offsets, 0-based; blk / row / col:
+                  int32, 0-based plus index_base), windows concatenated by the caller included; in `mem`.  Host arrays are
+                  uploaded once; device arrays are read where they lie, never modified, and the handle keeps no pointer into
+                  them.  The entries of a class need not be sorted, duplicates are legal and are summed, a NaN value is legal
+                  and propagates.  classptr may be NULL when nnz == 0;
+     triangle     SDPSR_TRI_FULL: every entry is one position; SDPSR_TRI_UPPER: an entry with row != col stands for (row, col)
+                  and (col, row).  The handle stores the FULL entry list, nnz_full <= 2 nnz entries, < 2^32.
+   A POSITION is the flat index of (k, row, col) in the layout of one class of sdpsr_block_images: blocks side by side, each
+   column-major s'_k x s'_k.  The handle keeps the full list twice, 16 bytes per entry each (32 * nnz_full bytes of device
+   memory in all): sorted by class (input order, a mirror right behind its entry) for the adjoint, and sorted by position with
+   the library's stable radix sort (ties in class-major order) for the forward map.
+   Validation runs on the device in the pass that reads the arrays; its verdict comes back on the ONE host wait a creation makes
+   in front of the allocation (a second wait ends it, the handle is complete on return).  SDPSR_BAD_ARGUMENT with a message that
+   names the lowest offending index: classptr[0] != 0, a non-monotone classptr, classptr[d] != nnz; a block index outside
+   [0, nblocks) after the base; a row or column outside [0, s'_k); row > col under SDPSR_TRI_UPPER.  SDPSR_BAD_ARGUMENT before
+   any kernel: sum s'_k^2 >= 2^32, nnz >= 2^32, nblocks < 1, some s'_k < 1, d < 0, a NULL array with nnz > 0, a bad triangle or
+   index_base (a full entry count >= 2^32 with nnz below it: after the first wait).  nnz == 0 and d == 0 are legal.  After every
+   refusal *op is NULL, nothing is leaked and the ctx stays usable.
+   sdpsr_transfer_bytes of a creation: host arrays (d + 1) * 8 + nnz * 20 bytes up; 56 bytes of verdict words down in either
+   memory space. */
+typedef struct sdpsr_blockop sdpsr_blockop;
+int sdpsr_blockop_create(sdpsr_ctx* ctx, int32_t nblocks, const int32_t* blk_sizes, int64_t d, int64_t nnz, const int64_t* classptr,
+                         const int32_t* blk, const int32_t* row, const int32_t* col, const double* val, int triangle, int index_base,
+                         int mem, sdpsr_blockop** op);
+int sdpsr_blockop_destroy(sdpsr_blockop* op);
+/* every pointer may be NULL; *sum_sq = sum s'_k^2, the length of Z and S */
+int sdpsr_blockop_info(const sdpsr_blockop* op, int64_t* d, int32_t* nblocks, int64_t* sum_sq, int64_t* nnz_full);
+/* The forward map  Z[p] = sum over the full entries e at position p of x[class(e)] * val(e):  x has d elements, Z sum s'_k^2, both
+   in `mem`.  EVERY element of Z is written; a position without an entry gets exactly +0.0; blocks come out as full
+   matrices in the one-class layout of sdpsr_block_images (what sdpsr_blocks_syev reads) -- under SDPSR_TRI_UPPER symmetric up to the
+   rounding of the two sums, which hold the same terms.
+   The adjoint  g[i] = sum over the full entries e of class i of val(e) * S[position(e)]:  for symmetric S this is
+   sum_k <blks[i][k], S_k>; S has sum s'_k^2 elements, g d; an empty class gets +0.0.
+   Both are sums with an order fixed by the inputs alone (the position in the stored arrangement; DESIGN.md "The reduced PSD
+   blocks as an operator"), without floating-point atomics: equal inputs give equal bytes, on any ctx.  An element with one term
+   is exactly x_i * val.  One host wait each (the outputs are complete on return).
+   The complex route needs nothing of its own: its triplets carry the real embedding [Re -Im; Im Re] of order 2 s_k, the operator
+   acts on those virtual blocks, and their spectra are the Hermitian blocks' spectra with every value doubled. */
+int sdpsr_blockop_apply(sdpsr_ctx* ctx, const sdpsr_blockop* op, const double* x, double* Z, int mem);
+int sdpsr_blockop_adjoint(sdpsr_ctx* ctx, const sdpsr_blockop* op, const double* S, double* g, int mem);
+/* The spectra of all blocks in one call.  Z: symmetric blocks in the layout sdpsr_blockop_apply writes (sum s_k^2 elements, in
+   `mem`); only the lower triangle of a block is referenced, as in sdpsr_syev_f64, and Z is not modified.
+     w   sum s_k values: ascending inside a block, the blocks in order;
+     V   NULL (values only: the same w bits), or sum s_k^2 elements in the layout of Z: orthonormal eigenvectors as the columns of
+         block k, column j belonging to the j-th value of the block; the sign is unspecified.
+   The blocks of order <= 64 are solved in ONE launch, one workgroup per block, by the Jacobi solver sdpsr_syev_f64 uses for one
+   matrix of that order (blocks of order 1 are copied); the larger ones go one by one through sdpsr_syev_f64 itself.  Range: as
+   sdpsr_syev_f64 -- a block whose max |a| over the lower triangle lies outside [2^-400, 2^400] is solved on an exact
+   power-of-two multiple and its values are multiplied back.  A block that reaches the Jacobi sweep limit (40): SDPSR_NOT_CONVERGED,
+   every output written as it stands.  nblocks < 1, some s_k < 1, sum s_k^2 >= 2^32, NULL Z or w: SDPSR_BAD_ARGUMENT. */
+int sdpsr_blocks_syev(sdpsr_ctx* ctx, int32_t nblocks, const int32_t* blk_sizes, const double* Z, double* w, double* V, int mem);
+
 #ifdef __cplusplus
 }
 #endif

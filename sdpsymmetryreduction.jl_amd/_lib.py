@@ -192,6 +192,12 @@ def load_library():
         "sdpsr_comm_world": (C.c_int, [vp]),
         "sdpsr_comm_broadcast": (C.c_int, [vp, vp, vp, i64, i32, C.c_int]),
         "sdpsr_comm_destroy": (C.c_int, [vp]),
+        "sdpsr_blockop_create": (C.c_int, [vp, i32, vp, i64, i64, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
+        "sdpsr_blockop_destroy": (C.c_int, [vp]),
+        "sdpsr_blockop_info": (C.c_int, [vp, pi64, pi32, pi64, pi64]),
+        "sdpsr_blockop_apply": (C.c_int, [vp, vp, vp, vp, C.c_int]),
+        "sdpsr_blockop_adjoint": (C.c_int, [vp, vp, vp, vp, C.c_int]),
+        "sdpsr_blocks_syev": (C.c_int, [vp, i32, vp, vp, vp, vp, C.c_int]),
     }
     missing = [s for s in declared_symbols() if not hasattr(lib, s)]
     if missing:

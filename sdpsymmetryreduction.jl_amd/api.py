@@ -1648,3 +1648,212 @@ def eigen_decomposition_batched(P, count, atol=None, values=None, ctx=None, rais
     if rc != 0 and (raise_on_failure or rc not in (2, 9)):
         ctx.check(rc)
     return st, ne, nc
+
+
+# ---------------------------------------------------------------------------
+# the reduced PSD blocks as an operator: Z(x), its adjoint, block spectra
+# ---------------------------------------------------------------------------
+def _flat_blocks(Z, sizes, what):
+    """One flat float64 array (NumPy or torch) in the one-class layout of ``sdpsr_block_images`` -- blocks side by side, each
+    column-major -- from that flat array or from a list of ``s_k x s_k`` matrices."""
+    S = sum(s * s for s in sizes)
+    if _is_torch(Z):
+        import torch
+        flat = Z.reshape(-1).contiguous().to(torch.float64)
+    elif isinstance(Z, np.ndarray) and Z.ndim == 1:
+        flat = np.ascontiguousarray(Z, dtype=np.float64)
+    else:
+        blocks = list(Z)
+        if len(blocks) != len(sizes) or any(tuple(b.shape) != (s, s) for b, s in zip(blocks, sizes)):
+            raise ValueError(f"{what}: one s_k x s_k matrix per block, sizes = {list(sizes)}")
+        if blocks and _is_torch(blocks[0]):
+            import torch
+            flat = torch.cat([b.t().reshape(-1) for b in blocks]).to(torch.float64).contiguous()
+        else:
+            flat = np.concatenate([np.asarray(b, dtype=np.float64).ravel(order="F") for b in blocks])
+    if int(flat.numel() if _is_torch(flat) else flat.size) != S:
+        raise ValueError(f"{what}: {S} elements expected (sum s_k^2), sizes = {list(sizes)}")
+    return flat
+
+
+def _split_blocks(flat, sizes):
+    """The blocks of a flat one-class array as matrices (views)."""
+    out, off = [], 0
+    for s in sizes:
+        b = flat[off:off + s * s]
+        out.append(b.reshape(s, s).t() if _is_torch(b) else b.reshape(s, s, order="F"))
+        off += s * s
+    return out
+
+
+class BlockOperator:
+    """The reduced PSD pencil ``Z_k(x) = sum_i x_i blks[i][k]`` on the device (``sdpsr_blockop_create``):
+    ``sum(blkD.blks[i] .* x[i] for i = 1:dim(P))`` of docs/src/examples/ErdosRenyiThetaFunction.jl:83 and
+    test/sd_problems.jl:46-52 of the reference, its adjoint ``g_i = sum_k <blks[i][k], S_k>`` -- what a first-order method
+    over the reduced SDP evaluates once per iteration.
+
+    ``sp_or_blks``: a ``SparseBlocks`` (``block_images_sparse`` / ``basis_image_sparse``), or dense images -- nested
+    ``blks[i][k]``, a flat array or a torch tensor -- with ``blkSizes``; those go through ``block_images_sparse`` first
+    (upper triangle, ``tol = 0``).  A context manager; ``close()`` frees the device arrays."""
+
+    def __init__(self, sp_or_blks, blkSizes=None, ctx=None):
+        self._h = None
+        self.ctx = _ctx(ctx)
+        sp = sp_or_blks
+        if not isinstance(sp, SparseBlocks):
+            if blkSizes is None:
+                raise ValueError("BlockOperator: dense images need blkSizes")
+            sp = block_images_sparse(sp_or_blks, blkSizes, upper=True, tol=0.0, ctx=self.ctx)
+        on_dev = _is_torch(sp.val)
+        arrays = (sp.classptr, sp.blk, sp.row, sp.col, sp.val)
+        if on_dev:
+            import torch
+            if not all(a.is_cuda for a in arrays):
+                raise TypeError("BlockOperator takes torch tensors on the device (or NumPy arrays)")
+            want = (torch.int64, torch.int32, torch.int32, torch.int32, torch.float64)
+            arrays = tuple(a.contiguous().to(t) for a, t in zip(arrays, want))
+            self.ctx.wait_for(*arrays)
+        else:
+            want = (np.int64, np.int32, np.int32, np.int32, np.float64)
+            arrays = tuple(np.ascontiguousarray(a, dtype=t) for a, t in zip(arrays, want))
+        sz = np.asarray(sp.sizes, dtype=np.int32)
+        nnz = int(sp.nnz)
+        h = C.c_void_p()
+        lib = self.ctx._lib
+        st = lib.sdpsr_blockop_create(self.ctx._h, len(sz), _ptr(sz), sp.nclasses, nnz, _ptr(arrays[0]),
+                                      *[(_ptr(a) if nnz else None) for a in arrays[1:]],
+                                      L.TRI_UPPER if sp.upper else L.TRI_FULL, int(sp.index_base),
+                                      L.MEM_DEVICE if on_dev else L.MEM_HOST, C.byref(h))
+        if st == 5:  # SDPSR_BAD_ARGUMENT: malformed triplets
+            raise ValueError(lib.sdpsr_last_error(self.ctx._h).decode())
+        self.ctx.check(st)
+        self._h = h
+        d, nb, ssq, nf = C.c_int64(0), C.c_int32(0), C.c_int64(0), C.c_int64(0)
+        self.ctx.check(lib.sdpsr_blockop_info(self._h, C.byref(d), C.byref(nb), C.byref(ssq), C.byref(nf)))
+        self.d, self.sum_sq, self.nnz_full = int(d.value), int(ssq.value), int(nf.value)
+        self.sizes = [int(s) for s in sz]
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.ctx._lib.sdpsr_blockop_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def _map(self, fn, v, n_in, n_out, ctx):
+        ctx = self.ctx if ctx is None else ctx
+        if self._h is None:
+            raise ValueError("BlockOperator: the handle is closed")
+        if _is_torch(v):
+            import torch
+            if not v.is_cuda:
+                raise TypeError("BlockOperator takes torch tensors on the device (or NumPy arrays)")
+            out = torch.empty(n_out, dtype=torch.float64, device=v.device)
+            ctx.wait_for(v, out)
+            mem = L.MEM_DEVICE
+        else:
+            out = np.empty(n_out, dtype=np.float64)
+            mem = L.MEM_HOST
+        if int(v.numel() if _is_torch(v) else v.size) != n_in:
+            raise ValueError(f"BlockOperator: {n_in} elements expected")
+        ctx.check(fn(ctx._h, self._h, _ptr(v) if n_in else None, _ptr(out) if n_out else None, mem))
+        return out
+
+    def apply(self, x, flat=False, ctx=None):
+        """``Z(x)``: the list of the symmetric ``Z_k``, or with ``flat=True`` the flat array in the one-class layout of
+        ``sdpsr_block_images``; torch tensors when ``x`` is one."""
+        if _is_torch(x):
+            import torch
+            x = x.reshape(-1).contiguous().to(torch.float64)
+        else:
+            x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+        Z = self._map(self.ctx._lib.sdpsr_blockop_apply, x, self.d, self.sum_sq, ctx)
+        return Z if flat else _split_blocks(Z, self.sizes)
+
+    def adjoint(self, S, ctx=None):
+        """``g_i = sum_k <blks[i][k], S_k>`` for symmetric ``S``, given as the list of blocks or flat."""
+        S = _flat_blocks(S, self.sizes, "BlockOperator.adjoint")
+        return self._map(self.ctx._lib.sdpsr_blockop_adjoint, S, self.sum_sq, self.d, ctx)
+
+
+def block_eigvals(Z, sizes, vectors=False, ctx=None):
+    """The spectra of all blocks in one call (``sdpsr_blocks_syev``): ``Z`` as ``BlockOperator.apply`` returns it (list or
+    flat; only the lower triangles are read).  Returns the list of ascending ``w_k``; with ``vectors=True`` the pair
+    ``(w, V)`` with the orthonormal eigenvectors as the columns of ``V_k``."""
+    ctx = _ctx(ctx)
+    sizes = [int(s) for s in sizes]
+    if not sizes or any(s < 1 for s in sizes):
+        raise ValueError(f"block_eigvals: block sizes must be >= 1, got {sizes}")
+    flat = _flat_blocks(Z, sizes, "block_eigvals")
+    sz = np.asarray(sizes, dtype=np.int32)
+    if _is_torch(flat):
+        import torch
+        if not flat.is_cuda:
+            raise TypeError("block_eigvals takes a torch tensor on the device (or NumPy arrays)")
+        w = torch.empty(int(sz.sum()), dtype=torch.float64, device=flat.device)
+        V = torch.empty_like(flat) if vectors else None
+        ctx.wait_for(flat, w)
+        mem = L.MEM_DEVICE
+    else:
+        w = np.empty(int(sz.sum()), dtype=np.float64)
+        V = np.empty_like(flat) if vectors else None
+        mem = L.MEM_HOST
+    ctx.check(ctx._lib.sdpsr_blocks_syev(ctx._h, len(sizes), _ptr(sz), _ptr(flat), _ptr(w), _ptr(V), mem))
+    ws, off = [], 0
+    for s in sizes:
+        ws.append(w[off:off + s])
+        off += s
+    return (ws, _split_blocks(V, sizes)) if vectors else ws
+
+
+BlockSpectrumCheck = namedtuple("BlockSpectrumCheck", ["full_to_blocks", "blocks_to_full", "lambda_min_full", "lambda_min_blocks",
+                                                       "x", "full_spectrum", "block_spectra"])
+
+
+def _directed_distance(a, b):
+    """max over a of the distance to the nearest element of b (inf for an empty b, 0 for an empty a)."""
+    a, b = np.asarray(a, dtype=np.float64), np.sort(np.asarray(b, dtype=np.float64))
+    if a.size == 0:
+        return 0.0
+    if b.size == 0:
+        return float("inf")
+    j = np.clip(np.searchsorted(b, a), 1, b.size - 1) if b.size > 1 else np.zeros(a.size, dtype=np.int64)
+    lo = np.abs(a - b[np.maximum(j - 1, 0)])
+    return float(np.max(np.minimum(lo, np.abs(a - b[j]))))
+
+
+def block_spectrum_check(P, bd, x=None, ctx=None):
+    """The defining property of ``blockDiagonalize`` end to end: ``x -> (Z_k(x))_k`` is an algebra isomorphism, so the
+    spectrum of ``X(x) = fill(P, x)`` equals, as a set, the union of the spectra of the ``Z_k(x)``.  ``bd``: a
+    ``BlockDiagonalization`` or a pair ``(blks, blkSizes)``.  ``x``: ``dim(P)`` values; drawn through ``randomize`` (the
+    context's seed governs) when None.  The spectrum of ``X`` comes from ``sdpsr_syev_f64``, the block spectra from
+    ``BlockOperator`` and ``block_eigvals``.  Returns the two Hausdorff distances (full -> blocks, blocks -> full),
+    ``lambda_min`` of both sides, ``x`` and the spectra.  Real path only: ``ValueError`` for a non-symmetric ``P``."""
+    ctx = _ctx(ctx)
+    lab = np.asarray(P.matrix.cpu() if _is_torch(P.matrix) else P.matrix)
+    if lab.ndim != 2 or lab.shape[0] != lab.shape[1] or not np.array_equal(lab, lab.T):
+        raise ValueError("block_spectrum_check: P is not symmetric (the real path needs a symmetric partition)")
+    Ph = Partition(P.nparts, lab)
+    blks, sizes = (bd.blks, bd.blkSizes) if hasattr(bd, "blkSizes") else bd
+    if x is None:
+        R = randomize(Ph, ctx=ctx)
+        x = np.zeros(P.nparts, dtype=np.float64)
+        x[lab[lab > 0].astype(np.int64) - 1] = R[lab > 0]
+    x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+    X = fill(Ph, x, ctx=ctx)
+    n = X.shape[0]
+    A = _f(X, np.float64)
+    w_full, vec = np.empty(n, dtype=np.float64), np.empty(n * n, dtype=np.float64)
+    ctx.check(ctx._lib.sdpsr_syev_f64(ctx._h, n, _ptr(A), _ptr(w_full), _ptr(vec), L.MEM_HOST))
+    with BlockOperator(blks, sizes, ctx=ctx) as op:
+        Z = op.apply(x, flat=True)
+        ws = block_eigvals(Z, op.sizes, ctx=ctx)
+    w_blocks = np.concatenate(ws)
+    return BlockSpectrumCheck(_directed_distance(w_full, w_blocks), _directed_distance(w_blocks, w_full), float(w_full.min()),
+                              float(w_blocks.min()), x, w_full, ws)

@@ -478,6 +478,19 @@ void launch_csr_entry_labels(hipStream_t s, int64_t nnz, const uint32_t* col, co
 size_t csr_class_sums_carry_bytes(int64_t nnz);
 void launch_csr_class_sums(hipStream_t s, int64_t nnz, int64_t m, const int64_t* rowptr, const uint32_t* key_sorted,
                            const uint32_t* idx_sorted, const double* val, void* carry, double* out);
+// kernels_blockop.hip: the reduced PSD pencil from triplets (blockop.cpp).  The verdict words of the creation passes, 64 bits
+// each, all ones = nothing found: the lowest offending index of each kind, and the full entry count
+enum { BOV_PTR0 = 0, BOV_MONOTONE = 1, BOV_PTREND = 2, BOV_BLOCK = 3, BOV_RANGE = 4, BOV_TRIANGLE = 5, BOV_TOTAL = 6, BOV_WORDS = 7 };
+int64_t blockop_chunks(int64_t nnz);
+void launch_blockop_check_classptr(hipStream_t s, int64_t d, int64_t nnz, const int64_t* classptr, unsigned long long* verdict);
+void launch_blockop_check(hipStream_t s, int64_t nnz, const int32_t* blk, const int32_t* row, const int32_t* col, int base, int upper, int nb,
+                          const uint32_t* pre, const int32_t* vs, unsigned long long* verdict, uint32_t* cnt, int64_t* off);  // cnt: chunks, off: chunks + 1
+void launch_blockop_expand(hipStream_t s, int64_t nnz, int64_t d, const int64_t* classptr, const int32_t* blk, const int32_t* row,
+                           const int32_t* col, const double* val, int base, int upper, int nb, const uint32_t* pre, const int32_t* vs,
+                           const int64_t* off, void* rec, uint32_t* poskey);
+void launch_blockop_gather(hipStream_t s, int64_t n, const uint32_t* sidx, const void* rec, void* out);
+size_t blockop_carry_bytes(int64_t n);
+void launch_blockop_keyed_sums(hipStream_t s, int64_t n, const void* rec, const double* v, int64_t nv, void* carry, double* out);
 // kernels_rowspace.hip / host_gram_jacobi.cpp: the row space of [newA | b] (rowspace.cpp, sdpsr_compress_constraints)
 double rowspace_scale(double max_abs);
 int rowspace_absmax_blocks(int64_t total);

@@ -12,6 +12,15 @@
 
 namespace sdpsr {
 
+// The range of the symmetric solvers (sdpsr_syev_f64, sdpsr_blocks_syev): their norms are sums of squares, so a matrix whose
+// max |a| (as the bits of a double) lies outside [2^-400, 2^400] is multiplied by 2^-e -- exact -- and its eigenvalues by 2^e.
+__device__ __forceinline__ int syev_scale_exponent(unsigned long long amax_bits) {
+    if (amax_bits == 0 || amax_bits >= 0x7FF0000000000000ull) return 0;  // zero matrix; Inf / NaN
+    const int e = (int)(amax_bits >> 52) - 1023;                        // (subnormal: -1023)
+    if (e >= -400 && e <= 400) return 0;
+    return e < -1000 ? -1000 : (e > 1000 ? 1000 : e);  // 2^1000 brings every subnormal into the normal range; 2^-+e are normal numbers
+}
+
 __device__ __forceinline__ void jacobi_angle(double app, double aqq, double apq, double& c, double& s) {
     // t = tan of the rotation angle (smaller root), c = 1/sqrt(1+t^2), s = t c.  Hardware
     // reciprocal / reciprocal-square-root seeds instead of the IEEE division and sqrt sequences;

@@ -270,11 +270,112 @@ size_t batched_eigdec_lds_bytes(int64_t n) {
     return (size_t)(3 * ldl * m) * 8 + (size_t)n * n * 8 + (size_t)(m - 1) * half * 4 + 64;
 }
 
+// ---------------------------------------------------------------------------
+// sdpsr_blocks_syev: the spectra of many symmetric blocks of order <= 64 in ONE launch, one workgroup per block of order
+// 2 .. 64 on the ping-pong Jacobi core of jacobi64.h (what sdpsr_syev_f64 runs for one such matrix); the blocks of order 1
+// are copied by the threads of the workgroups behind those, one block per thread.  jobs: first the njac blocks of order >= 2,
+// then the n1 of order 1.  Only the lower triangle of a block is read.  Range as sdpsr_syev_f64: a block whose max |a| lies
+// outside [2^-400, 2^400] is multiplied by a power of two in LDS and its values are multiplied back.  V == nullptr: values only.
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(BE_THREADS)
+blocks_syev64_kernel(const BlocksSyevJob* __restrict__ jobs, int njac, int n1, const double* __restrict__ Z, double* __restrict__ wout,
+                     double* __restrict__ V, int* __restrict__ flag) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];  // A, V and their ping-pong twins (m x m, ld ldl)
+    __shared__ double s_red[2 * BE_THREADS / 64];
+    __shared__ unsigned long long s_max[BE_THREADS / 64];
+    __shared__ int s_rank[64];
+    const int tid = threadIdx.x, nthr = blockDim.x;
+    if ((int)blockIdx.x >= njac) {
+        const int64_t t = (int64_t)(blockIdx.x - njac) * nthr + tid;
+        if (t < n1) {
+            const BlocksSyevJob jb = jobs[njac + t];
+            wout[jb.woff] = Z[jb.zoff];
+            if (V) V[jb.zoff] = 1.0;
+        }
+        return;
+    }
+    const BlocksSyevJob jb = jobs[blockIdx.x];
+    const int n = jb.n;
+    const double* __restrict__ Ag = Z + jb.zoff;
+    const int m = (n + 1) & ~1;
+    const int ldl = m | 1;
+    double* sA = smem;
+    double* sV = sA + (size_t)ldl * m;
+    unsigned long long amax = 0;
+    for (int e = tid; e < m * m; e += nthr) {
+        const int j = e / m, i = e - j * m;
+        const int ii = i > j ? i : j, jj = i > j ? j : i;
+        const double a = (ii < n) ? Ag[ii + (int64_t)jj * n] : 0.0;
+        const unsigned long long b = (unsigned long long)__double_as_longlong(a) & 0x7FFFFFFFFFFFFFFFull;
+        amax = b > amax ? b : amax;  // non-negative doubles order like their bit patterns (NaN above Inf)
+        sA[i + j * ldl] = a;
+        sV[i + j * ldl] = (i == j) ? 1.0 : 0.0;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long x = __shfl_down(amax, o, 64);
+        amax = x > amax ? x : amax;
+    }
+    if ((tid & 63) == 0) s_max[tid >> 6] = amax;
+    __syncthreads();
+    amax = 0;
+    for (int k = 0; k < (nthr >> 6); ++k) amax = s_max[k] > amax ? s_max[k] : amax;
+    const int ex = syev_scale_exponent(amax);
+    if (ex != 0) {  // uniform
+        const double f = __longlong_as_double((long long)(1023 - ex) << 52);
+        for (int e = tid; e < m * m; e += nthr) {
+            const int j = e / m, i = e - j * m;
+            sA[i + j * ldl] *= f;
+        }
+        __syncthreads();
+    }
+    const int sweep = jacobi64_sweeps_pp(n, m, ldl, sA, sV, sV + (size_t)ldl * m, sV + 2 * (size_t)ldl * m, s_red);
+    const double back = __longlong_as_double((long long)(1023 + ex) << 52);
+    for (int i = tid; i < n; i += nthr) {
+        const double li = sA[i + i * ldl];
+        int rk = 0;
+        for (int j = 0; j < n; ++j) {
+            const double lj = sA[j + j * ldl];
+            rk += (lj < li) || (lj == li && j < i);
+        }
+        s_rank[i] = rk;
+        wout[jb.woff + rk] = li * back;
+    }
+    __syncthreads();
+    if (V) {
+        double* __restrict__ Vg = V + jb.zoff;
+        for (int e = tid; e < n * n; e += nthr) {
+            const int j = e / n, i = e - j * n;
+            Vg[i + (int64_t)s_rank[j] * n] = sV[i + j * ldl];
+        }
+    }
+    if (tid == 0 && sweep >= 40) atomicOr(flag, 1);  // (an integer flag: order does not matter)
+}
+
 bool batched_set_device_attributes() {
     bool ok = true;
     ok &= hipSuccess == hipFuncSetAttribute(reinterpret_cast<const void*>(&eigdec_batched64_kernel),
                         hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+    ok &= hipSuccess == hipFuncSetAttribute(reinterpret_cast<const void*>(&blocks_syev64_kernel),
+                        hipFuncAttributeMaxDynamicSharedMemorySize, 136 * 1024);
     return ok;
+}
+
+// max_n: the largest order among the njac Jacobi jobs (2 .. 64; ignored when njac == 0); flag: one int, zeroed by the caller
+void launch_blocks_syev64(hipStream_t s, const BlocksSyevJob* jobs, int njac, int n1, int max_n, const double* Z, double* w, double* V,
+                          int* flag) {
+    if (njac + n1 <= 0) return;
+    int threads = 64;
+    size_t lds = 0;
+    if (njac > 0) {
+        const int half = (max_n + 1) / 2, mm = 2 * half;
+        threads = (half * half + 63) / 64 * 64;
+        lds = 4 * (size_t)(mm | 1) * mm * sizeof(double) + 64;
+    } else if (n1 > 64) {
+        threads = 256;
+    }
+    const int grid = njac + (n1 + threads - 1) / threads;
+    blocks_syev64_kernel<<<grid, threads, lds, s>>>(jobs, njac, n1, Z, w, V, flag);
 }
 
 // status/neig/nclasses: device arrays of `count` ints.

@@ -1640,13 +1640,7 @@ __global__ void __launch_bounds__(256) syev_absmax_kernel(int64_t n, const doubl
     if ((threadIdx.x & 63) == 0 && m) atomicMax(slot, m);
 }
 
-__device__ __forceinline__ int syev_scale_exponent(unsigned long long amax_bits) {
-    if (amax_bits == 0 || amax_bits >= 0x7FF0000000000000ull) return 0;  // zero matrix; Inf / NaN
-    const int e = (int)(amax_bits >> 52) - 1023;                        // (subnormal: -1023)
-    if (e >= -400 && e <= 400) return 0;
-    return e < -1000 ? -1000 : (e > 1000 ? 1000 : e);  // 2^1000 brings every subnormal into the normal range; 2^-+e are normal numbers
-}
-
+// (syev_scale_exponent: jacobi64.h, shared with the batched block spectra)
 // dst (ld x ld, column-major; the caller zeroed the padding) <- src (n x n) with the lower triangle times 2^-e
 __global__ void __launch_bounds__(256) syev_scaled_copy_kernel(int64_t n, const double* __restrict__ src, int64_t ld, double* __restrict__ dst,
                                                                unsigned long long* __restrict__ slot) {

@@ -191,6 +191,22 @@ struct sdpsr_sparse {
     int rows_symmetric = 0;           // len = n^2 and every row is a symmetric n x n matrix bit for bit
 };
 
+// sdpsr_blockop_create: the full entry list of the reduced PSD pencil as 16-byte records (uint32 key, uint32 idx, double val),
+// device-resident, shared (read-only) by every apply / adjoint that names it (kernels_blockop.hip)
+struct sdpsr_blockop {
+    int device = 0;
+    int64_t d = 0, sum_sq = 0, nnz_full = 0;
+    std::vector<int32_t> sizes;  // the virtual orders s'_k
+    void* by_class = nullptr;    // nnz_full records sorted by class (key = class, idx = position); hipMalloc'ed, owned
+    void* by_pos = nullptr;      // the same records sorted by position (key = position, idx = class)
+};
+
+// one block of sdpsr_blocks_syev's single launch (kernels_batched.hip): where it starts in Z / V and in w, and its order
+struct BlocksSyevJob {
+    int64_t zoff, woff;
+    int32_t n, pad;
+};
+
 // Host wait for a stream of ctx c (every wait of the library goes through here).  Inside a batch call the wait polls and
 // hands the thread to the other restarts' fibers.  hipStreamQuery records its "not ready" as the thread's last error, and
 // all fibers share that slot: exactly that value is dropped on every way out (a fiber whose first query succeeds must not
@@ -653,6 +669,8 @@ bool launch_basis_image_commutative(hipStream_t s, int64_t n, int64_t d, uint32_
                                     double atol, double tol, double* ws, double* out, uint32_t* flag, bool plain = false);
 void launch_transpose_to_rowmajor(hipStream_t s, int64_t n, int64_t S1, const double* Qcm,
                                   double* Qrm);
+void launch_blocks_syev64(hipStream_t s, const BlocksSyevJob* jobs, int njac, int n1, int max_n, const double* Z, double* w, double* V,
+                          int* flag);
 // Stable LSD radix sort of the pairs (keys[e], e), e < len < 2^32, by the low `bits` bits of the key (4 bits per pass; the
 // keys must not exceed them).  kA / kB / vA / vB: len words each, hist: radix_sort_hist_words(len).  The sorted keys and
 // indices end in (kB, vB).  No atomics on the way: the order is a function of the keys alone.  (first, cnt): the first pass

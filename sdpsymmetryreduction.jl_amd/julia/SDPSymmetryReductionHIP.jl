@@ -435,6 +435,77 @@ function block_images_sparse(blks::AbstractVector{<:AbstractVector{<:AbstractMat
     return (classptr=classptr, blk=blk, row=row, col=col, val=val, sizes=(T === ComplexF64 ? 2 .* sizes : sizes))
 end
 
+# ---- the reduced PSD blocks as an operator (sdpsr_blockop_*, sdpsr_blocks_syev): Z_k(x) = sum(blks[i][k] .* x[i] for i = 1:dim(P)),
+# ErdosRenyiThetaFunction.jl:83, test/sd_problems.jl:46-52 -- its adjoint and the spectra of all blocks, on the device ----
+# sp: what block_images_sparse returns (1-based indices).  The handle is device-resident; close(op) frees it.
+mutable struct BlockOperator
+    handle::Ptr{Cvoid}
+    d::Int64
+    sizes::Vector{Int32}
+    sum_sq::Int64
+    nnz_full::Int64
+end
+function BlockOperator(sp; upper::Bool=true)
+    cx = ctx()
+    sizes = Vector{Int32}(sp.sizes); d = Int64(length(sp.classptr) - 1); m = Int64(length(sp.val))
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(cx, ccall((:sdpsr_blockop_create, libsdpsr), Cint,
+                    (Ptr{Cvoid}, Int32, Ptr{Int32}, Int64, Int64, Ptr{Int64}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Cint, Cint,
+                     Cint, Ref{Ptr{Cvoid}}),
+                    cx.handle, length(sizes), sizes, d, m, sp.classptr, sp.blk, sp.row, sp.col, sp.val, upper ? Cint(0) : Cint(1), Cint(1),
+                    MEM_HOST, h))
+    dd = Ref{Int64}(0); nb = Ref{Int32}(0); ssq = Ref{Int64}(0); nf = Ref{Int64}(0)
+    ccall((:sdpsr_blockop_info, libsdpsr), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int32}, Ref{Int64}, Ref{Int64}), h[], dd, nb, ssq, nf)
+    op = BlockOperator(h[], dd[], sizes, ssq[], nf[])
+    finalizer(close, op)
+    return op
+end
+function Base.close(op::BlockOperator)
+    op.handle == C_NULL || ccall((:sdpsr_blockop_destroy, libsdpsr), Cint, (Ptr{Cvoid},), op.handle)
+    op.handle = C_NULL
+    return nothing
+end
+function _split_blocks(flat::Vector{Float64}, sizes)
+    out = Matrix{Float64}[]; off = 0
+    for s in sizes
+        push!(out, reshape(flat[off+1:off+s*s], Int(s), Int(s))); off += s * s
+    end
+    return out
+end
+# Z(x): the symmetric Z_k as full matrices
+function apply(op::BlockOperator, x::AbstractVector{<:Real})
+    cx = ctx(); xv = Vector{Float64}(x); Z = Vector{Float64}(undef, op.sum_sq)
+    check(cx, ccall((:sdpsr_blockop_apply, libsdpsr), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cint),
+                    cx.handle, op.handle, xv, Z, MEM_HOST))
+    return _split_blocks(Z, op.sizes)
+end
+# g_i = sum_k <blks[i][k], S_k> for symmetric S_k
+function adjoint(op::BlockOperator, S::AbstractVector{<:AbstractMatrix{<:Real}})
+    cx = ctx(); flat = Float64[]
+    for b in S
+        append!(flat, vec(Matrix{Float64}(b)))
+    end
+    g = Vector{Float64}(undef, op.d)
+    check(cx, ccall((:sdpsr_blockop_adjoint, libsdpsr), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cint),
+                    cx.handle, op.handle, flat, g, MEM_HOST))
+    return g
+end
+# the spectra of all blocks in one call: (w, V) with w[k] ascending and the eigenvectors as the columns of V[k]
+function block_eigen(Z::AbstractVector{<:AbstractMatrix{<:Real}})
+    cx = ctx(); sizes = Int32[size(b, 1) for b in Z]; flat = Float64[]
+    for b in Z
+        append!(flat, vec(Matrix{Float64}(b)))
+    end
+    w = Vector{Float64}(undef, sum(sizes)); V = Vector{Float64}(undef, length(flat))
+    check(cx, ccall((:sdpsr_blocks_syev, libsdpsr), Cint, (Ptr{Cvoid}, Int32, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cint),
+                    cx.handle, length(sizes), sizes, flat, w, V, MEM_HOST))
+    ws = Vector{Float64}[]; off = 0
+    for s in sizes
+        push!(ws, w[off+1:off+s]); off += s
+    end
+    return ws, _split_blocks(V, sizes)
+end
+
 # ---- blockDiagonalize(ComplexF64, P) (compat.jl:26-32,54-57; n <= 3072 in this library version) ---
 function SR.blockDiagonalize(::Type{ComplexF64}, P::HIPPartition, verbose=true;
                              epsilon=Base.rtoldefault(Float64))
