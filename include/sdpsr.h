@@ -164,7 +164,15 @@ enum {
        check X_t^2 against its class constants with a random vector (v'X_t^2 v = v'C_t v, exact integers, one pass over the
        labels, no product; a difference is missed w.p. <= 2^-15 per channel) and form the square only when the check of a
        verdict read inside the loop says "violated".  Same results. */
-    SDPSR_FLAG_SQUARE_EVERY_VERDICT = 1u << 18
+    SDPSR_FLAG_SQUARE_EVERY_VERDICT = 1u << 18,
+    /* A/B: the guessed-closed path of sdpsr_jordan_reduce launches every check whose only product is a verdict word inside the
+       loop, in front of blockDiagonalize: the compare of the guessed initial partition, the projection's dot products and
+       compare, and the square check's verdict kernels.  By default (no phase timers) they are registered on the ctx and
+       enqueued inside blockDiagonalize, behind the two products of the module growth whose read-backs the host waits for, so
+       that they run while the host selects directions and solves the compressed problem; every other route enqueues them
+       before its own first launch.  Same kernels, keys, stream and order among themselves; same results bit for bit, same
+       host waits. */
+    SDPSR_FLAG_CHECKS_IN_LOOP = 1u << 19
 };
 
 typedef struct sdpsr_opts {

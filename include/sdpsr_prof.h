@@ -132,6 +132,16 @@ int sdpsr_profile_refine_source(sdpsr_ctx* ctx, int kind, int what, int64_t n, i
 /* Guessed-closed first iterations of ctx (restart 0) or of batch restart `restart` whose two rounds were judged by the square check instead of
    two int8 squares (out[0]), and those of them that formed a real square behind a "violated" verdict read inside the loop (out[1]). */
 int sdpsr_profile_square_checks(sdpsr_ctx* ctx, int32_t restart, uint64_t* out);
+/* The check segments of the guessed-closed path (include/sdpsr.h: SDPSR_FLAG_CHECKS_IN_LOOP) on ctx (restart 0) or on batch restart
+   `restart`, since the ctx was created: out[0] = segments registered instead of launched in the loop, out[1] = of those, enqueued inside
+   a ride (behind a product of the module growth, in front of the host's wait for it), out[2] = enqueued anywhere else.  And the two
+   host windows the rides fill, measured on every reduction that takes the module-compression route, whatever it defers: the
+   steady-clock time from the return of the wait for a growth step's product to the next thing the host enqueues -- out[3] nanoseconds
+   and out[4] windows behind the class-sum step, out[5] and out[6] behind the growth rounds (the last of them holds the compressed
+   eigenproblem).  out[7..9] = the three deferred verdict words as the last voided reduction read them behind its last wait (the
+   first round's, the speculative round's, the initial partition's; 0 = not violated or not deferred, 1 = stored by a kernel that
+   ran, 0xDEFE44ED = its segment was never enqueued).  out: 10 words. */
+int sdpsr_profile_deferred_checks(sdpsr_ctx* ctx, int32_t restart, uint64_t* out);
 /* The square check (csrc/kernels_square_check.hip) on caller-made inputs: "does X_t^2 take its class representative's value on every entry,
    0 on label 0?" for G (1 or 2) rounds with keys[g], T (2 or 4) channels each, on the packed labels Lp_host (<= d <= 255, width 8 or 32 as
    above) of order n <= 8192 with the representatives first_idx_host.  layout[0..6] = byte offsets of c (int32 [G T][d]), part_x (int32

@@ -55,6 +55,7 @@ struct Module {
     bool spec_b2 = false;               // the second compressed element was formed behind the final round's product
     bool sym_pre = false, sym_trusted = false, sym_checked = false;  // the symmetric check's verdict: who made it, whether it was looked at
     bool forked = false;                // device tail: the fork point of the next prefetch is marked
+    int window = 0;                     // which of the two host windows the step at hand opens (sdpsr_internal.h: 0 class sums, 1 growth rounds)
     // Scratch discipline (DESIGN.md "module scratch").  lean: the growth is on the small-module route -- small_on_host(), every
     // product the fused label product, the skinny Gram kernel or the row-owning tall product -- whose kernels read exact shapes:
     // only the padding rows n .. ld-1 of W are kept zero (seed_basis), nothing is filled per round and Q1 is not used.  The first
@@ -146,6 +147,7 @@ int Module::seed_basis() {
 // Y <- A W for a fresh generic element A: fused label product when the shape allows it,
 // gather + split-K MFMA GEMM otherwise.  Columns >= wcols of dst keep their old content.
 int Module::apply_generic(int wcols, double* dst) {
+    deferred_window_close(c);
     const uint64_t key = next_key(c);
     if (fused_product(wcols)) {
         double* part = (double*)ctx_buf(c, "cm_part", label_spmm_pair_partial_doubles(n) * 8);
@@ -169,6 +171,7 @@ int Module::apply_generic(int wcols, double* dst) {
 // enqueued between the product and its host wait and comes back with that wait.
 int Module::ortho_step(int mc, double tol, bool take_ref, const Rider* rider, Selection& sel) {
     const int64_t ap = round_up(w + mc, 128), mp = round_up(mc, 128);
+    deferred_window_close(c);
     // the exact-shape Gram kernel stores the product into pinned host memory as well: no copy launch before the read-back
     double* hpin = (double*)ctx_pinned(c, (size_t)ap * mp * 8);
     bool host_filled = false;
@@ -178,7 +181,9 @@ int Module::ortho_step(int mc, double tol, bool take_ref, const Rider* rider, Se
     // compressed problem (invariance round); what the host enqueues next follows them in stream order.  The segments' buffers belong to
     // the loop (flush_deferred_tail names them); the growth works on "cm_*", "gram_partials", the labels and the pinned buffers only and
     // runs no refinement, so "ref_first" stays what the verify passes expect.  Any other step waits for the stream, or may request
-    // buffers: everything pending is enqueued before its product.
+    // buffers: everything pending is enqueued before its product.  (ctx_buf itself enqueues what is pending before it frees ANY buffer, the
+    // growth's own "cm_*" / "gram_partials" included: on a ctx whose buffers still grow a segment that would have ridden is then
+    // counted as enqueued outside a ride -- the first reductions of an order, never the steady state.)
     const bool ride = take_ref && hpin && deferred_tail_pending(c) && small_on_host() && gram_tn_is_skinny(w + mc, mc);
     // (Trade-off, off the benchmark's path: a step that does not ride -- the second orthogonalisation step of a non-commutative round --
     // puts the pending segment in front of its product, so its stream wait is ~100 us longer than the product alone; and an upload behind
@@ -201,11 +206,13 @@ int Module::ortho_step(int mc, double tol, bool take_ref, const Rider* rider, Se
         const uint32_t seq = ++c->report_seq ? c->report_seq : ++c->report_seq;
         *(volatile uint32_t*)stamp = 0;
         launch_report_stamp(c->stream, stamp, seq);  // (a kernel of its own: a ticket inside gram_reduce_kernel, last workgroup stamps, measured 3 % slower, profiles/r15)
-        flush_deferred_tail(c, 1);
+        flush_deferred_tail(c, 1, /*in_ride=*/true);
         if (ctx_wait_word(c, c->stream, stamp, seq) != hipSuccess) return ctx_fail(c, SDPSR_HIP_ERROR, "report wait (module growth)");
+        deferred_window_open(c, window);
         memcpy(hG.data(), hpin, (size_t)ap * mc * 8);
     } else if (host_filled) {
         if (ctx_sync_stream(c, c->stream) != hipSuccess) return ctx_fail(c, SDPSR_HIP_ERROR, "hipStreamSynchronize (module growth)");
+        if (take_ref) deferred_window_open(c, window);  // (the step a segment would ride with: the window is measured either way)
         memcpy(hG.data(), hpin, (size_t)ap * mc * 8);
     } else {
         st = d2h_sync(c, hG.data(), Cc, (size_t)ap * mc * 8);  // the mc columns the host looks at
@@ -285,6 +292,7 @@ int Module::class_sum_round() {
         return SDPSR_OK;
     }
     launch_class_sums(c->stream, n, d, L, W, W + (size_t)w * ld, ld);  // W[:, w + i] = P_{i+1} x
+    window = 0;
     int got;
     live = (int)d;
     return absorb((int)d, nullptr, got);
@@ -302,6 +310,8 @@ int Module::growth_round(int& got) {
     const int m = G * w;
     double* Y = W + (size_t)w * ld;
     live = 0;
+    window = 1;
+    deferred_window_close(c);
     if (lean && !(fused && small_on_host())) {  // the module has outgrown the small-module route
         const int e0 = restore_fills();
         if (e0) return e0;
@@ -513,6 +523,7 @@ int Module::device_tail(PhaseTimer& tm, double atol, EigInfo& info, std::vector<
 // does not move here and stream order suffices
 int Module::lift(PhaseTimer& tm, const double* Qs_host, int64_t S1, double atol) {
     PhaseScope phase{tm, SDPSR_T_IRRED, false};
+    deferred_window_close(c);
     double* qs = (double*)ctx_buf(c, "cm_qsmall", (size_t)w * S1 * 8);
     double* Qhat = (double*)ctx_buf(c, "bd_qhat", (size_t)n * S1 * 8);
     if (!qs || !Qhat) return SDPSR_OUT_OF_MEMORY;

@@ -33,6 +33,9 @@ void* ctx_buf(sdpsr_ctx* c, const char* name, size_t bytes) {
     if (nm == "adm_symflag") c->symflag_zero = false;
     if (nm == "bd_qhat" || nm == "bd_qrm") c->bd_qrm_current = false;
     if (b.p) {
+        // The one place where the allocator knows about the loop: a pending segment of its deferred tail (loop.cpp) may read this
+        // buffer, so it is enqueued before the buffer goes -- whichever buffer it is; no caller has to remember the operands' names.
+        flush_deferred_tail(c);
         ctx_sync_stream(c, c->stream);
         hipFree(b.p);
         b.p = nullptr;
@@ -55,6 +58,9 @@ void* ctx_buf(sdpsr_ctx* c, const char* name, size_t bytes) {
 
 
 namespace sdpsr {
+uint64_t steady_ns() {
+    return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
 // Small host<->device transfers go through a growable pinned staging area: a hipMemcpyAsync
 // to or from pageable memory costs milliseconds of host time on this stack.
 void* ctx_pinned(sdpsr_ctx* c, size_t bytes) {  // shared with eigen.cpp
@@ -113,6 +119,7 @@ int d2h_sync(sdpsr_ctx* c, void* host, const void* dev, size_t bytes) {
 constexpr size_t H2D_SLOT = 32 * 1024;
 constexpr int H2D_SLOTS = 32;
 int h2d_sync(sdpsr_ctx* c, void* dev, const void* host, size_t bytes) {
+    deferred_window_close(c);
     c->h2d_bytes += bytes;
     if (bytes <= H2D_SLOT) {
         if (!c->h2d_ring && hipHostMalloc(&c->h2d_ring, H2D_SLOT * H2D_SLOTS, hipHostMallocDefault) != hipSuccess) {

@@ -191,12 +191,22 @@ struct Loop {
                square_check_supports(n, current, 2, T) && !(c->opts.flags & SDPSR_FLAG_SQUARE_EVERY_VERDICT) &&
                (proj_dead || r == 0 || current <= (int64_t)verify_lds_cap());
     }
+    // The launches whose only product is a verdict word read in reduce.cpp -- the pair check of a guessed initial partition, the
+    // projection's dot products and compare, the square check's verdict kernels -- go to the ctx's deferred tail as check segments
+    // (sdpsr_internal.h) under the conditions that let check_round leave its verdicts unread, with the phase timers off (as in
+    // tail_applies).  SDPSR_FLAG_CHECKS_IN_LOOP: everything is launched here.
+    bool checks_deferrable() const {
+        return c->allow_deferred_verdict && c->pinned_small != nullptr && !tm.enabled && !(c->opts.flags & SDPSR_FLAG_CHECKS_IN_LOOP);
+    }
     // The checked rounds: key2 is the joint round's key, the confirm round's is drawn here, where verify_round draws it.  Stream order:
     // class constants, the pass (which writes the full labels: expected to be the call's last label pass), the projection compare into
-    // the first verdict word, the verdicts.  Nothing is deferred to the ctx's tail: the label write cannot wait, and nothing long is left.
+    // the first verdict word, the verdicts.  The label write cannot wait.  tail (joint_iteration decides, and has then left the
+    // projection's dot products to this round too): what follows the pass is registered as the round's check segment instead of
+    // launched -- dot products, projection compare, verdict kernels, with the arguments they have here -- and both words read
+    // "violated" until the segment is enqueued.
     // Both rounds count as squares examined.  A "violated" first verdict read here forms the real square of key2 for the refinement
     // that follows (not counted again).
-    int check_round(const SigSource& qj, uint64_t key2, Verdict* v) {
+    int check_round(const SigSource& qj, uint64_t key2, bool tail, Verdict* v) {
         SquareCheck q;
         q.n = n, q.d = current, q.G = 2, q.T = T;
         void* ws = ctx_buf(c, "adm_sqcheck", square_check_ws_bytes(n, current, 2, T));
@@ -210,11 +220,30 @@ struct Loop {
         q.key[0] = key2, q.key[1] = next_key(c);
         q.Lp = lab.Lp, q.Lp8 = lab.shadow(), q.first_idx = first, q.Lfull = lab.full_from_gather();
         q.flag[0] = hv, q.flag[1] = hv2;
-        *(volatile uint32_t*)hv = 0u;  // (the kernels only ever store 1; the last verdicts on these words have been read)
-        *(volatile uint32_t*)hv2 = 0u;
-        launch_square_check_ref_and_pass(s, q);
-        if (qj.kind == SIG_JOINT_I32 && r >= 1) launch_verify_projection(s, qj, current, first, hv);
-        launch_square_check_verdict(s, q);
+        const bool proj_verify = qj.kind == SIG_JOINT_I32 && r >= 1;
+        // (joint_iteration has left the dot products to the segment: a round that cannot register one would compare against stale "proj_coef")
+        if (tail && !defer) return ctx_fail(c, SDPSR_BAD_STATE, "admissible_subspace: check segment asked for where the verdicts are read in the loop");
+        if (tail) {
+            *(volatile uint32_t*)hv = DEFERRED_NEVER_RAN;  // (flush_deferred_tail clears both words from the host in front of the segment)
+            *(volatile uint32_t*)hv2 = DEFERRED_NEVER_RAN;
+            launch_square_check_ref_and_pass(s, q);
+            DeferredTail& t = c->deferred_tail;
+            if (t.next == t.count) t.next = t.count = 0;
+            if (t.count >= DEFERRED_SEGMENTS) return ctx_fail(c, SDPSR_BAD_STATE, "admissible_subspace: no room for the round's check segment");
+            DeferredSegment& g = t.seg[t.count++] = DeferredSegment{};
+            g.kind = DEFERRED_CHECK, g.q = qj, g.n = n, g.d = current, g.first = first, g.flag = hv;
+            g.Lp = lab.Lp, g.Lp8 = lab.shadow();
+            g.proj_coef = !proj_dead, g.partial = partial, g.coef = coef, g.nblk = nblk;
+            g.proj_verify = proj_verify;
+            g.verdict = true, g.sq = q;
+            ++c->check_stats.registered;
+        } else {
+            *(volatile uint32_t*)hv = 0u;  // (the kernels only ever store 1; the last verdicts on these words have been read)
+            *(volatile uint32_t*)hv2 = 0u;
+            launch_square_check_ref_and_pass(s, q);
+            if (proj_verify) launch_verify_projection(s, qj, current, first, hv);
+            launch_square_check_verdict(s, q);
+        }
         c->squares_launched += 2, ++c->squares_speculative, ++c->square_checks;
         if (defer) {
             c->deferred_verdict = true;  // both words are read in reduce.cpp
@@ -261,6 +290,7 @@ struct Loop {
             launch_square(true, next_key(c), Xs, Cs, current, /*write_full=*/true, /*gather_only=*/true);
             DeferredTail& t = c->deferred_tail;
             t.ld = ld, t.d = current, t.T = T, t.zero_flag = zero_flag, t.first = first;
+            t.seg[0] = t.seg[1] = DeferredSegment{};  // (kind DEFERRED_SQUARE; nothing is pending here: joint_iteration)
             t.seg[0].X = (const int8_t*)Xp, t.seg[0].C = (int32_t*)Cp, t.seg[0].q = qv, t.seg[0].vref = vref, t.seg[0].flag = hv, t.seg[0].speculative = false;
             t.seg[1].X = Xs, t.seg[1].C = Cs, t.seg[1].q = qj, t.seg[1].vref = vref2, t.seg[1].flag = hv2, t.seg[1].speculative = true;
             t.seg[1].q.kind = SIG_CHAN_I32, t.seg[1].q.C = Cs;
@@ -313,6 +343,11 @@ struct Loop {
         int st = SDPSR_OK;
         const bool jl = lab.packed();
         if (!jl) lab.need_full();
+        // The guessed-closed first round as check segments (checks_deferrable, check_round): decided here, in front of the iteration's
+        // first launch, because the dot products -- read only by that round's projection compare when nothing refines -- go with them.
+        // Every other iteration first enqueues what is pending (the pair check of a guessed initial partition): in stream order again.
+        const bool defer_checks = checks_deferrable() && check_applies(false, jl);
+        if (!defer_checks) flush_deferred_tail(c);
         // (at most three attempts: a basis that is never class-constant must not pay the check in every iteration)
         if (!proj_dead && it >= 2 && it <= 4 && r >= 1 && jl && c->first_idx_labels == lab.Lp && current >= 1 &&
             current <= (int64_t)refine_first_cap() && !(c->opts.flags & SDPSR_FLAG_ALWAYS_PROJECT)) {
@@ -322,24 +357,28 @@ struct Loop {
         // (Round 3 measured this dot-product pass on the side stream BESIDE the channel gather and the int8 square -- two independent readers of the
         // same labels: theta_c32xk128 477 against 480 reductions/s in sequence, closed_scheme 1016 against 1028.  The square slows by what the
         // overlapped pass takes from it; kept in sequence.)
-        if (!proj_dead) launch_proj_coef_lower(s, n, r, dU, lab.current(jl), jl ? 1 : 0, key, partial, nblk, coef, lab.shadow(jl));
+        if (!proj_dead && !defer_checks) launch_proj_coef_lower(s, n, r, dU, lab.current(jl), jl ? 1 : 0, key, partial, nblk, coef, lab.shadow(jl));
         tm.end();
         int64_t dj = current;
         bool confirming = false;  // this round repeats the square after a round that did not refine
         for (;;) {
-            flush_deferred_tail(c);  // (never pending here: the round that registers the tail is the loop's last, tail_applies)
+            // the loop goes into another round: its gathers and a refinement behind it touch the pending segments' operands.  (A square
+            // tail is never pending here: the round that registers one is the loop's last, tail_applies)
+            if (confirming) flush_deferred_tail(c);
             tm.begin(SDPSR_T_SQUARE);
             const uint64_t key2 = next_key(c);
             const bool jl2 = lab.packed();
             // a confirm round that the verify pass will judge is expected to leave the labels as they are: its gather writes the full matrix
             const SigSource qj = joint_source(jl2);
             const bool check = check_applies(confirming, jl2);             // this round and the speculative one are checked, not squared
+            if (defer_checks && !confirming && !check)  // (the same predicate on the same state; the dot products were left to this round's segment)
+                return ctx_fail(c, SDPSR_BAD_STATE, "admissible_subspace: the round that was to carry the dot products is not a checked round");
             const bool tail = !check && tail_applies(qj, confirming, jl2);  // this square and the speculative one go to the ctx's deferred tail
             if (!check) launch_square(jl2, key2, Xp, Cp, current, /*write_full=*/confirming && verify_applies(confirming, jl2), /*gather_only=*/tail);
             tm.end();
             tm.begin(SDPSR_T_REFINE);
             Verdict v;
-            st = check ? check_round(qj, key2, &v) : verify_round(qj, confirming, jl2, tail, &v);
+            st = check ? check_round(qj, key2, defer_checks && !confirming, &v) : verify_round(qj, confirming, jl2, tail, &v);
             if (st) return st;
             if (v.unchanged) dj = current;  // labels (packed, and full where a gather has written them), class representatives and table hints stay as they are
             else if (!(st = initial_guess_settled())) st = lab.refine_packed(qj, &dj);  // (never a refinement of labels that were only guessed)
@@ -407,6 +446,7 @@ struct Loop {
     int separate_iteration(int64_t* d_out) {
         int st = SDPSR_OK;
         double* probe_host = nullptr;  // set: the dot products carry the symmetry probe of the basis, copied towards here
+        flush_deferred_tail(c);  // (a guessed initial partition's pair check: this iteration refines)
         const bool plab = packed_proj && lab.packed();  // the projection reads the packed labels
         if (!plab) lab.need_full();
         if (packed_proj) {
@@ -484,7 +524,24 @@ struct Loop {
                 ++c->label_narrowings;
             }
         }
-        if (guess && launch_verify_pair(s, n, dCL, dX0, lab.Lp, guess->d0, guess->first, c->pinned_small + PINNED_SMALL_DEFERRED_INITIAL.first, Lp8)) {
+        // The pair check's only product is its word: where the round's checks can be deferred (checks_deferrable; not beside a square
+        // tail, which fills the ctx's two segments itself) it is registered as the first check segment instead of launched -- dCL / dX0
+        // are the caller's device arrays or their staging copies "adm_cl" / "adm_x0", both outlive the reduction -- and the word
+        // reads "violated" until the segment is enqueued.  The shadow's narrowing launch above stays: the loop's passes stream it.
+        bool pair_registered = false;
+        if (guess && checks_deferrable() && !(c->opts.flags & SDPSR_FLAG_SQUARE_EVERY_VERDICT) && n < (int64_t(1) << 31) && guess->d0 >= 1 &&
+            guess->d0 <= (int64_t)verify_lds_cap()) {  // (the shapes launch_verify_pair takes)
+            flush_deferred_tail(c);  // (nothing is pending at the start of a loop call)
+            DeferredTail& t = c->deferred_tail;
+            DeferredSegment& g = t.seg[0] = DeferredSegment{};
+            g.kind = DEFERRED_CHECK, g.pair = true, g.n = n, g.a = dCL, g.b = dX0, g.Lp = lab.Lp, g.Lp8 = Lp8, g.d = guess->d0, g.first = guess->first;
+            g.flag = c->pinned_small + PINNED_SMALL_DEFERRED_INITIAL.first;
+            *(volatile uint32_t*)g.flag = DEFERRED_NEVER_RAN;
+            t.next = 0, t.count = 1;
+            ++c->check_stats.registered;
+            pair_registered = true;
+        }
+        if (guess && (pair_registered || launch_verify_pair(s, n, dCL, dX0, lab.Lp, guess->d0, guess->first, c->pinned_small + PINNED_SMALL_DEFERRED_INITIAL.first, Lp8))) {
             c->initial_guess_pending = true;
             ++c->initial_guesses;
             HIP_TRY(c, hipGetLastError());
@@ -501,6 +558,7 @@ struct Loop {
     // STATUS_REPEAT_REDUCTION (the word stays pending: reduce.cpp reads it again and repeats the reduction).
     int initial_guess_settled() {
         if (!c->initial_guess_pending) return SDPSR_OK;
+        flush_deferred_tail(c);  // (the word is read: its pair check must have been enqueued; and what follows refines)
         HIP_TRY(c, ctx_sync_stream(c, s));
         HIP_TRY(c, hipGetLastError());
         if (initial_guess_violated(c) != 0) return STATUS_REPEAT_REDUCTION;
@@ -529,12 +587,31 @@ namespace sdpsr {
 // The deferred tail's segments, in order, on the ctx's stream; squares are counted here, where they are enqueued.  A segment reads
 // "adm_xi8" / "adm_xi8_spec" (its gathered element), "adm_lpacked" or its shadow "adm_lpacked8" and "ref_first" (labels and class representatives), "proj_coef" and
 // the caller's U (joint verify), "adm_symflag" (the constant zero); it writes "adm_ci32" / "adm_ci32_spec", "adm_vref" / "adm_vref2"
-// and its verdict word.  Whoever enqueues work of its own while segments are pending must touch none of these -- in particular run no
-// refinement (refine_signatures rewrites "ref_first") and request none of these buffers with another size (ctx_buf would free them).
-void flush_deferred_tail(sdpsr_ctx* c, int max_segments) {
+// and its verdict word.  A check segment (DEFERRED_CHECK) reads "adm_lpacked" or "adm_lpacked8" and "ref_first" as well; the pair check reads the
+// caller's C_L / X0_L (or "adm_cl" / "adm_x0"); the round's segment reads the caller's U (or "adm_u") and the square check's partial sums in
+// "adm_sqcheck" (written by the pass, which ran in the loop), and writes "proj_partial", "proj_coef", the rest of "adm_sqcheck" and its two
+// verdict words, which the host clears here, in front of the segment's first launch (the kernels only ever store 1).
+// Whoever enqueues work of its own while segments are pending must touch none of these -- in particular run no refinement
+// (refine_signatures rewrites "ref_first") and request none of these buffers with another size (ctx_buf enqueues what is pending before
+// it frees any buffer).  Whoever waits for the stream in order to read a deferred word enqueues what is pending first.
+void flush_deferred_tail(sdpsr_ctx* c, int max_segments, bool in_ride) {
     DeferredTail& t = c->deferred_tail;
+    if (!in_ride && t.next < t.count) deferred_window_close(c);
     for (; max_segments > 0 && t.next < t.count; --max_segments, ++t.next) {
         const DeferredSegment& g = t.seg[t.next];
+        if (g.kind == DEFERRED_CHECK) {
+            if (g.pair) {
+                launch_verify_pair(c->stream, g.n, g.a, g.b, g.Lp, g.d, g.first, g.flag, g.Lp8);  // (clears the word from the host)
+            } else {
+                *(volatile uint32_t*)g.sq.flag[0] = 0u;
+                *(volatile uint32_t*)g.sq.flag[1] = 0u;
+                if (g.proj_coef) launch_proj_coef_lower(c->stream, g.n, g.q.r, g.q.U, g.Lp, 1, g.q.key, g.partial, g.nblk, g.coef, g.Lp8);
+                if (g.proj_verify) launch_verify_projection(c->stream, g.q, g.d, g.first, g.flag);
+                if (g.verdict) launch_square_check_verdict(c->stream, g.sq);
+            }
+            ++(in_ride ? c->check_stats.in_ride : c->check_stats.outside_ride);
+            continue;
+        }
         launch_gemm_tn_i8_sym(c->stream, t.ld, t.ld, g.X, t.ld, g.C, t.ld, t.T, t.ld * t.ld, t.ld * t.ld, t.zero_flag, c->num_cus, c->opts.square_kernel);
         ++c->squares_launched;
         if (g.speculative) ++c->squares_speculative;

@@ -394,6 +394,16 @@ extern "C" int sdpsr_profile_square_checks(sdpsr_ctx* c, int32_t restart, uint64
     return SDPSR_OK;
 }
 
+extern "C" int sdpsr_profile_deferred_checks(sdpsr_ctx* c, int32_t restart, uint64_t* out) {
+    CHECK_CTX(c);
+    if (!out || restart < 0 || restart > (int32_t)c->batch_children.size()) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "bad arguments");
+    const DeferredCheckStats& t = (restart == 0 ? c : c->batch_children[restart - 1])->check_stats;
+    out[0] = t.registered, out[1] = t.in_ride, out[2] = t.outside_ride;
+    out[3] = t.window_ns[0], out[4] = t.window_count[0], out[5] = t.window_ns[1], out[6] = t.window_count[1];
+    out[7] = t.voided[0], out[8] = t.voided[1], out[9] = t.voided[2];
+    return SDPSR_OK;
+}
+
 // The square check on caller-made inputs (tests/test_gpu_square_check.py).  ws_inout == nullptr: only layout[] is filled.
 extern "C" int sdpsr_profile_square_check(sdpsr_ctx* c, int64_t n, int64_t d, int G, int T, const uint64_t* keys, int width, int write_full,
                                           const uint32_t* Lp_host, const uint32_t* first_idx_host, uint8_t* ws_inout, uint64_t* layout,

@@ -47,14 +47,19 @@ int jordan_reduce_impl(sdpsr_ctx* c, int64_t n, const double* CL, const double* 
     // error return drops what is left of it, so that no later call on the ctx enqueues segments that point into this call's arguments
     struct DropTail {
         sdpsr_ctx* c;
-        ~DropTail() { c->deferred_tail.count = c->deferred_tail.next = 0; }
+        ~DropTail() {
+            c->deferred_tail.count = c->deferred_tail.next = 0;
+            c->check_stats.window_open = -1;  // (an error return may leave a window open: the next reduction's first upload must not close it)
+        }
     } drop_tail{c};
+    c->check_stats.window_open = -1;
     // A wrong guess of the loop (its input closed, its initial partition the recorded one) voids the run: the reduction is done again from the
     // caller's seed position with the caller's hint, and this time nothing is guessed (predict_closed is off, the record is gone).
     auto repeat_without_guesses = [&](uint32_t dv, uint32_t dv_spec, uint32_t dv_init) -> int {
         c->predict_closed = false;
         c->initial_record = InitialRecord{};
         if (dv_init != 0) ++c->initial_guesses_violated;
+        c->check_stats.voided[0] = dv, c->check_stats.voided[1] = dv_spec, c->check_stats.voided[2] = dv_init;
         if (dbg_on())
             fprintf(stderr, "[sdpsr] jordan_reduce: %s%s%s (deferred verdicts: verify %u, speculative %u, initial partition %u): reduction repeated\n",
                     dv_init != 0 ? "the initial partition was not the recorded one" : "", dv_init != 0 && (dv != 0 || dv_spec != 0) ? "; " : "",

@@ -48,18 +48,65 @@ struct SigSource {
     const uint8_t* L8 = nullptr;                                  // (with lab_packed) a byte copy of L, every label <= 255: the verify passes read it instead (the label width of the source: 8 when set)
 };
 
-// The tail of the loop's guessed-closed path that sdpsr_jordan_reduce defers (loop.cpp, verify_round): two segments, each the
-// int8 square of a gathered element and the verify pass over its product, registered on the ctx instead of launched.  Nothing in
-// blockDiagonalize reads what they write, so they are enqueued -- same stream, same kernels, same arguments -- where the host
-// would otherwise leave the stream idle: behind the products of the module growth whose read-backs the host waits for
-// (compress.cpp, Module::ortho_step).  Every other route enqueues them before it enqueues anything of its own.
+// kernels_square_check.hip: "is X_t^2 constant on the classes (0 on label 0)?" for G rounds of T channels without forming X_t^2, from the
+// packed labels (Lp8: their byte copy, or null) and the representatives.  Stream order: ref_and_pass (class constants c, then the ONE pass
+// over the labels, which writes the full n x n label matrix to Lfull unless that is null), then verdict (y, w, the (round, channel)
+// equality bits, and a 1 into flag[g][0] -- pinned host words the caller has cleared -- for every round with a channel that differs).
+constexpr int SQUARE_CHECK_MAX_CLASSES = 255;
+constexpr int64_t SQUARE_CHECK_MAX_ORDER = 1 << 15;
+struct SquareCheck {
+    int64_t n = 0, d = 0;
+    int G = 0, T = 0;
+    uint64_t key[2] = {0, 0};
+    const uint32_t* Lp = nullptr;
+    const uint8_t* Lp8 = nullptr;
+    const uint32_t* first_idx = nullptr;
+    uint32_t* Lfull = nullptr;
+    uint32_t* flag[2] = {nullptr, nullptr};
+    // workspace (square_check_ws_carve): c [G T][d]; part_x, part_c [G T][nb][64 nb], nb = ceil(n / 64); y, w [G T][64 nb];
+    // esum [G T][nb][2]; bits [G T]
+    int32_t *c = nullptr, *part_x = nullptr;
+    int64_t *part_c = nullptr, *y = nullptr, *w = nullptr;
+    uint64_t* esum = nullptr;
+    uint32_t* bits = nullptr;
+};
+
+// The tail of the loop's guessed-closed path that sdpsr_jordan_reduce defers: up to two segments registered on the ctx instead of
+// launched.  Nothing in blockDiagonalize reads what they write, so they are enqueued -- same stream, same kernels, same arguments --
+// where the host would otherwise leave the stream idle: behind the products of the module growth whose read-backs the host waits for
+// (compress.cpp, Module::ortho_step).  Every other route enqueues them before it enqueues anything of its own.  Two kinds:
+//   DEFERRED_SQUARE  (loop.cpp, verify_round; SDPSR_FLAG_SQUARE_EVERY_VERDICT): the int8 square of a gathered element and the verify
+//                    pass over its product, one segment per round
+//   DEFERRED_CHECK   (loop.cpp, initial_partition and check_round): launches whose only product is a verdict word.  Segment "pair":
+//                    the compare of the guessed initial partition (launch_verify_pair).  Segment "round": the dot products of the
+//                    projection (launch_proj_coef_lower), the projection compare (launch_verify_projection) and the square check's
+//                    verdict kernels (launch_square_check_verdict), in the loop's order.  The square check's class constants and its
+//                    pass stay in the loop: the pass writes the full labels blockDiagonalize reads.
+// A segment carries its keys: every key is drawn in the loop, where it always was.
+enum { DEFERRED_SQUARE = 0, DEFERRED_CHECK = 1 };
 struct DeferredSegment {
+    int kind = DEFERRED_SQUARE;
+    // --- DEFERRED_SQUARE ---
     const int8_t* X = nullptr;  // the gathered channels (the gather itself ran in the loop)
     int32_t* C = nullptr;       // their squares
-    SigSource q;                // the verify pass's source (q.C == C)
+    SigSource q;                // the verify pass's source (q.C == C); DEFERRED_CHECK: the projection compare's source
     void* vref = nullptr;
-    uint32_t* flag = nullptr;   // the verdict's word of c->pinned_small
+    uint32_t* flag = nullptr;   // the verdict's word of c->pinned_small (DEFERRED_CHECK: the pair check's, or the round's first)
     bool speculative = false;   // counts as a speculative square
+    // --- DEFERRED_CHECK ---
+    bool pair = false;          // launch_verify_pair(n, a, b, Lp, d, first, flag, Lp8)
+    const double *a = nullptr, *b = nullptr;
+    const uint32_t* Lp = nullptr;
+    const uint8_t* Lp8 = nullptr;
+    int64_t n = 0, d = 0;
+    const uint32_t* first = nullptr;
+    bool proj_coef = false;     // launch_proj_coef_lower(n, q.r, q.U, Lp, 1, q.key, partial, nblk, coef, Lp8); coef == q.coef
+    double* partial = nullptr;
+    double* coef = nullptr;
+    int nblk = 0;
+    bool proj_verify = false;   // launch_verify_projection(q, d, first, flag)
+    bool verdict = false;       // launch_square_check_verdict(sq): sq.flag[0] == flag, sq.flag[1] the second word
+    SquareCheck sq;
 };
 constexpr int DEFERRED_SEGMENTS = 2;
 struct DeferredTail {
@@ -69,6 +116,14 @@ struct DeferredTail {
     int T = 0;
     const uint32_t* zero_flag = nullptr;
     const uint32_t* first = nullptr;  // "ref_first" of the packed labels
+};
+// what the check segments did on a ctx, and the host time of the two windows they ride in (sdpsr_profile_deferred_checks)
+struct DeferredCheckStats {
+    uint64_t registered = 0, in_ride = 0, outside_ride = 0;
+    uint64_t window_ns[2] = {0, 0}, window_count[2] = {0, 0};  // [0] class-sum step, [1] growth rounds: wait returned -> next enqueue
+    int window_open = -1;
+    uint64_t window_t0 = 0;
+    uint32_t voided[3] = {0, 0, 0};  // the words as the last voided reduction read them (reduce.cpp): verify, speculative, initial partition
 };
 constexpr uint32_t DEFERRED_NEVER_RAN = 0xDEFE44EDu;  // what a verdict word holds until its segment is enqueued: reads as "violated"
 // "adm_lpacked" (Lp) and "ref_first" (first) describe the initial partition of the last loop call: order n, d0 classes, labels symmetric
@@ -161,7 +216,8 @@ struct sdpsr_ctx {
     // discard everything and the reduction is repeated without the guess.
     bool allow_deferred_verdict = false;
     bool deferred_verdict = false;  // both wait in c->pinned_small (host_internal.h: PINNED_SMALL_DEFERRED_*) and must be 0
-    sdpsr::DeferredTail deferred_tail;  // ... and the squares and verify passes that produce them, while they are not enqueued yet
+    sdpsr::DeferredTail deferred_tail;  // ... and the launches that produce them (and the initial guess's word), while they are not enqueued yet
+    sdpsr::DeferredCheckStats check_stats;
     // The loop's second guess (loop.cpp, initial_partition): the last loop call on this ctx found its input closed, so "adm_lpacked" /
     // "ref_first" still hold its INITIAL partition -- the next call of sdpsr_jordan_reduce checks that partition against its inputs
     // (launch_verify_pair) instead of rebuilding it, and the verdict rides with the two above.  Dropped by every refinement, by a
@@ -394,28 +450,7 @@ bool launch_verify_pair(hipStream_t s, int64_t n, const double* a, const double*
 // the projection half of the joint verdict alone (q: SIG_JOINT_I32 with 1 <= q.r <= 4, packed labels, d <= verify_lds_cap()): the rounded
 // projected value of every entry against its class representative's; flag as above.  false: no instance, nothing enqueued
 bool launch_verify_projection(hipStream_t s, const SigSource& q, int64_t d, const uint32_t* first_idx, uint32_t* flag);
-// kernels_square_check.hip: "is X_t^2 constant on the classes (0 on label 0)?" for G rounds of T channels without forming X_t^2, from the
-// packed labels (Lp8: their byte copy, or null) and the representatives.  Stream order: ref_and_pass (class constants c, then the ONE pass
-// over the labels, which writes the full n x n label matrix to Lfull unless that is null), then verdict (y, w, the (round, channel)
-// equality bits, and a 1 into flag[g][0] -- pinned host words the caller has cleared -- for every round with a channel that differs).
-constexpr int SQUARE_CHECK_MAX_CLASSES = 255;
-constexpr int64_t SQUARE_CHECK_MAX_ORDER = 1 << 15;
-struct SquareCheck {
-    int64_t n = 0, d = 0;
-    int G = 0, T = 0;
-    uint64_t key[2] = {0, 0};
-    const uint32_t* Lp = nullptr;
-    const uint8_t* Lp8 = nullptr;
-    const uint32_t* first_idx = nullptr;
-    uint32_t* Lfull = nullptr;
-    uint32_t* flag[2] = {nullptr, nullptr};
-    // workspace (square_check_ws_carve): c [G T][d]; part_x, part_c [G T][nb][64 nb], nb = ceil(n / 64); y, w [G T][64 nb];
-    // esum [G T][nb][2]; bits [G T]
-    int32_t *c = nullptr, *part_x = nullptr;
-    int64_t *part_c = nullptr, *y = nullptr, *w = nullptr;
-    uint64_t* esum = nullptr;
-    uint32_t* bits = nullptr;
-};
+// kernels_square_check.hip (SquareCheck: above, with the deferred tail that carries one)
 bool square_check_supports(int64_t n, int64_t d, int G, int T);
 size_t square_check_ws_bytes(int64_t n, int64_t d, int G, int T);
 // sets the workspace pointers (n, d, G, T set); returns the bytes.  gap (a multiple of 16): bytes left untouched in front of every array and
@@ -423,9 +458,21 @@ size_t square_check_ws_bytes(int64_t n, int64_t d, int G, int T);
 size_t square_check_ws_carve(SquareCheck& q, void* ws, size_t gap = 0);
 void launch_square_check_ref_and_pass(hipStream_t s, const SquareCheck& q);
 void launch_square_check_verdict(hipStream_t s, const SquareCheck& q);
-// loop.cpp: enqueue the next max_segments segments of the ctx's deferred tail on c->stream (none pending: nothing happens)
-void flush_deferred_tail(sdpsr_ctx* c, int max_segments = DEFERRED_SEGMENTS);
+// loop.cpp: enqueue the next max_segments segments of the ctx's deferred tail on c->stream (none pending: nothing happens).
+// in_ride: the caller is the module growth's ride (compress.cpp, Module::ortho_step) -- only counted (DeferredCheckStats)
+void flush_deferred_tail(sdpsr_ctx* c, int max_segments = DEFERRED_SEGMENTS, bool in_ride = false);
 inline bool deferred_tail_pending(const sdpsr_ctx* c) { return c->deferred_tail.next < c->deferred_tail.count; }
+// The two windows of blockDiagonalize in which the host works while the stream has nothing of blockDiagonalize's own (compress.cpp):
+// opened when the wait for a growth step's product returns, closed by whatever the host enqueues next (an upload, a label product,
+// the lift).  Steady-clock time, accumulated per ctx; read through sdpsr_profile_deferred_checks.
+uint64_t steady_ns();
+inline void deferred_window_open(sdpsr_ctx* c, int which) { c->check_stats.window_open = which, c->check_stats.window_t0 = steady_ns(); }
+inline void deferred_window_close(sdpsr_ctx* c) {
+    DeferredCheckStats& t = c->check_stats;
+    if (t.window_open < 0) return;
+    t.window_ns[t.window_open] += steady_ns() - t.window_t0, ++t.window_count[t.window_open];
+    t.window_open = -1;
+}
 // kernels_module.hip: one thread stores `seq` into a word of coherent pinned host memory, behind a system-scope fence: what the
 // kernels before it in the stream stored into pinned memory is complete when the host sees the stamp (ctx_wait_word)
 void launch_report_stamp(hipStream_t s, uint32_t* host_word, uint32_t seq);

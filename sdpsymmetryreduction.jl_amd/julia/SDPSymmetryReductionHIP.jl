@@ -37,6 +37,8 @@ struct Opts
     square_kernel::Int32     # 0 = by size, 1 = 128 x 128 tiles, 64 = persistent 256 x 256 launch forced
     reserved::NTuple{3,Int32}
 end
+# SDPSR_FLAG_* (A/B switch, same results either way; the full list is in include/sdpsr.h)
+const FLAG_CHECKS_IN_LOOP = UInt32(1) << 19   # the guessed-closed path's verdict-only checks run in the loop, not in blockDiagonalize's waits
 Opts(; flags=0, round_mode=0, label_bits=0, square_mode=0, channels=0) =
     Opts(UInt32(64), square_mode, channels, 0, 0, 0, UInt32(flags), round_mode, 0, 0, label_bits, 0, 0, (Int32(0), Int32(0), Int32(0)))
 
