@@ -172,7 +172,15 @@ enum {
        that they run while the host selects directions and solves the compressed problem; every other route enqueues them
        before its own first launch.  Same kernels, keys, stream and order among themselves; same results bit for bit, same
        host waits. */
-    SDPSR_FLAG_CHECKS_IN_LOOP = 1u << 19
+    SDPSR_FLAG_CHECKS_IN_LOOP = 1u << 19,
+    /* A/B: a guessed reduction of sdpsr_jordan_reduce writes the caller's full labels in the loop, in front of blockDiagonalize,
+       which reads them there.  By default (device P_out at label width 32, no phase timers, none of SDPSR_FLAG_CHECKS_IN_LOOP /
+       _SQUARE_EVERY_VERDICT / _WAIT_FOR_EVERY_VERDICT) the ctx keeps a full copy of the recorded initial partition's labels
+       (n^2 * 4 bytes, made once by the unguessed call that makes the record); blockDiagonalize of a guessed reduction, which
+       refines nothing, reads that copy, and the square check's class constants and its pass -- the launches that write P_out --
+       are enqueued with the other checks inside blockDiagonalize.  With this flag no copy is made.  Same kernels, keys and
+       stream; same results bit for bit, same host waits. */
+    SDPSR_FLAG_LABELS_BEFORE_BLOCKDIAG = 1u << 20
 };
 
 typedef struct sdpsr_opts {
@@ -604,7 +612,11 @@ int sdpsr_basis_image(sdpsr_ctx* ctx, int64_t n, const uint32_t* P, int64_t d, i
      blks            d * sum_sq doubles if that is <= blks_capacity (in doubles), else untouched: the caller reads
                      *dim_out * *sum_sq, allocates and calls sdpsr_block_images; blks_capacity = 0: sizes only;
      Q_hat           n * sum_s doubles under the same rule with qhat_capacity; may be NULL.
-   With device-resident P_out the partition is formed and read in the caller's buffer (no copy); once this call has
+   With device-resident P_out the partition is formed in the caller's buffer (no copy).  A reduction that guesses its input
+   closed may write P_out late, inside blockDiagonalize, which then reads the ctx's own copy of the same labels
+   (SDPSR_FLAG_LABELS_BEFORE_BLOCKDIAG); whenever the call returns -- successfully, with an error, or after a voided guess
+   and its repeat -- everything it registered has been enqueued and waited for, and P_out holds the complete labels of the
+   partition the call reports.  Once this call has
    delivered the images itself, a further sdpsr_block_images needs a new sdpsr_block_diagonalize (sizes and Q_hat stay
    available through sdpsr_block_sizes / sdpsr_q_hat).
    Status: that of the first stage that fails.  After SDPSR_NUMERICAL_INCONSISTENCY / SDPSR_DIMENSION_MISMATCH

@@ -142,6 +142,11 @@ int sdpsr_profile_square_checks(sdpsr_ctx* ctx, int32_t restart, uint64_t* out);
    first round's, the speculative round's, the initial partition's; 0 = not violated or not deferred, 1 = stored by a kernel that
    ran, 0xDEFE44ED = its segment was never enqueued).  out: 10 words. */
 int sdpsr_profile_deferred_checks(sdpsr_ctx* ctx, int32_t restart, uint64_t* out);
+/* The same ten words with one appended: out[10] = reductions of sdpsr_jordan_reduce on that ctx whose blockDiagonalize read the
+   ctx's copy of the recorded labels while the pass that writes P_out waited among the check segments (include/sdpsr.h:
+   SDPSR_FLAG_LABELS_BEFORE_BLOCKDIAG); a voided reduction counts, its repeat does not.  out: 11 words.  (An entry of its own:
+   callers of sdpsr_profile_deferred_checks hand in 10 words.) */
+int sdpsr_profile_recorded_labels(sdpsr_ctx* ctx, int32_t restart, uint64_t* out);
 /* The square check (csrc/kernels_square_check.hip) on caller-made inputs: "does X_t^2 take its class representative's value on every entry,
    0 on label 0?" for G (1 or 2) rounds with keys[g], T (2 or 4) channels each, on the packed labels Lp_host (<= d <= 255, width 8 or 32 as
    above) of order n <= 8192 with the representatives first_idx_host.  layout[0..6] = byte offsets of c (int32 [G T][d]), part_x (int32

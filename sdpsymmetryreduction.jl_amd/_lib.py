@@ -41,6 +41,7 @@ FLAG_WIDE_LOOP_LABELS = 1 << 16
 FLAG_MODULE_SCRATCH_FILLS = 1 << 17
 FLAG_SQUARE_EVERY_VERDICT = 1 << 18
 FLAG_CHECKS_IN_LOOP = 1 << 19
+FLAG_LABELS_BEFORE_BLOCKDIAG = 1 << 20
 BASIS_IMAGE_KERNELS = {"auto": 0, "two_stage": 1, "outer": 2, "chunk": 3}
 # sdpsr_basis_image: *route
 BI_ROUTE_COMMUTATIVE, BI_ROUTE_BLOCKS, BI_ROUTE_TWO_STAGE, BI_ROUTE_OUTER, BI_ROUTE_CHUNK = 1, 2, 3, 4, 5
@@ -263,6 +264,8 @@ def load_prof_library():
     lib.sdpsr_profile_square_checks.argtypes = [vp, C.c_int32, C.POINTER(C.c_uint64)]
     lib.sdpsr_profile_deferred_checks.restype = C.c_int
     lib.sdpsr_profile_deferred_checks.argtypes = [vp, C.c_int32, C.POINTER(C.c_uint64)]
+    lib.sdpsr_profile_recorded_labels.restype = C.c_int
+    lib.sdpsr_profile_recorded_labels.argtypes = [vp, C.c_int32, C.POINTER(C.c_uint64)]
     lib.sdpsr_profile_square_check.restype = C.c_int
     lib.sdpsr_profile_square_check.argtypes = [vp, i64, i64, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, i64]
     lib.sdpsr_profile_proj_coef_lower.restype = C.c_int

@@ -29,7 +29,7 @@ void* ctx_buf(sdpsr_ctx* c, const char* name, size_t bytes) {
     DevBuf& b = it != c->bufs.end() ? it->second : c->bufs[std::string(name)];
     // what the ctx remembers ABOUT a buffer's contents goes with the buffer (the new one may come back at the old address)
     const std::string_view nm(name);
-    if (nm == "adm_lpacked" || nm == "adm_lpacked8" || nm == "ref_first") c->initial_record = InitialRecord{};
+    if (nm == "adm_lpacked" || nm == "adm_lpacked8" || nm == "ref_first" || nm == "adm_lfull_rec") c->initial_record = InitialRecord{};
     if (nm == "adm_symflag") c->symflag_zero = false;
     if (nm == "bd_qhat" || nm == "bd_qrm") c->bd_qrm_current = false;
     if (b.p) {

@@ -5,7 +5,7 @@
 // and D = X_t^2 - C_t = 0 is tested with a random vector v in {0 .. 2^16 - 1}^n:  v'Dv = |X_t v|^2 - v'(C_t v) is a polynomial of degree 2
 // in v that is not the zero polynomial when D != 0, so it vanishes with probability <= 2 / 2^16 (Schwartz-Zippel); "violated" is never
 // false.  Everything is exact integer arithmetic, O(n^2) operations on the packed labels, no int8 matrix and no int32 product:
-//   square_check_ref_kernel      c[g][t][k]: one workgroup per (class, round), the 2 n label reads of row i and column j of the representative
+//   square_check_ref_kernel      c[g][t][k]: one workgroup per class, the 2 n label reads of row i and column j of the representative for both rounds
 //   square_check_pass_kernel     ONE pass over the packed labels, the tile-pair walk of gather_i8_sym_packed_kernel: writes the full label
 //                                matrix (WRITE_L) and, per 64 x 64 tile, the tile's share of X_t v and C_t v (rows, and columns for the
 //                                mirrored tile) into part[column block][row]: every slot has one owner, no atomics, no fills
@@ -39,38 +39,61 @@ __device__ __forceinline__ uint32_t check_label(const LT* __restrict__ Lp, int n
     return (uint32_t)Lp[(int64_t)lo * n - (int64_t)lo * (lo - 1) / 2 + (hi - lo)];
 }
 
+// One workgroup of REF_THREADS per class serves both rounds from the same label reads (the labels of row i above the diagonal are n
+// bytes apart: every lane its own cache line), REF_UNROLL entries of the row and of the column in flight per thread.  int32 sums:
+// any order gives the same bits.
+constexpr int REF_THREADS = 1024, REF_UNROLL = 4;
 template <int T, typename LT>
-__global__ void __launch_bounds__(256)
-square_check_ref_kernel(int n, int d, const LT* __restrict__ Lp, const uint32_t* __restrict__ first_idx, uint64_t key0, uint64_t key1,
+__global__ void __launch_bounds__(REF_THREADS)
+square_check_ref_kernel(int n, int d, int G, const LT* __restrict__ Lp, const uint32_t* __restrict__ first_idx, uint64_t key0, uint64_t key1,
                         int32_t* __restrict__ c) {
-    __shared__ uint32_t xt[SQUARE_CHECK_MAX_CLASSES + 1];
-    __shared__ int32_t red[4][T];
-    const int k = blockIdx.x, g = blockIdx.y;
-    const uint64_t key = g ? key1 : key0;
-    for (int l = threadIdx.x; l <= SQUARE_CHECK_MAX_CLASSES; l += blockDim.x) xt[l] = (l && l <= d) ? (uint32_t)sdpsr_class_bits(key, (uint32_t)l) : 0u;
+    __shared__ uint32_t xt[2][SQUARE_CHECK_MAX_CLASSES + 1];
+    __shared__ int32_t red[REF_THREADS / 64][2 * T];
+    const int k = blockIdx.x;
+    for (int l = threadIdx.x; l < 2 * (SQUARE_CHECK_MAX_CLASSES + 1); l += blockDim.x) {
+        const int g = l / (SQUARE_CHECK_MAX_CLASSES + 1), cl = l % (SQUARE_CHECK_MAX_CLASSES + 1);
+        xt[g][cl] = (cl && cl <= d && g < G) ? (uint32_t)sdpsr_class_bits(g ? key1 : key0, (uint32_t)cl) : 0u;
+    }
     __syncthreads();
-    int32_t acc[T];
+    int32_t acc[2 * T];
 #pragma unroll
-    for (int t = 0; t < T; ++t) acc[t] = 0;
+    for (int a = 0; a < 2 * T; ++a) acc[a] = 0;
     const int64_t e = (int64_t)first_idx[k];
     if (e < (int64_t)n * (n + 1) / 2) {  // (a representative outside the triangle: the class constants stay 0)
         int i, j;
         check_packed_ij(n, e, i, j);
-        for (int m = threadIdx.x; m < n; m += blockDim.x) {
-            const uint32_t la = check_label(Lp, n, i, m), lb = check_label(Lp, n, m, j);
-            const uint32_t xa = la <= (uint32_t)d ? xt[la] : 0u, xb = lb <= (uint32_t)d ? xt[lb] : 0u;
+        for (int m0 = threadIdx.x; m0 < n; m0 += REF_UNROLL * (int)blockDim.x) {
+            uint32_t la[REF_UNROLL], lb[REF_UNROLL];
 #pragma unroll
-            for (int t = 0; t < T; ++t) acc[t] += __mul24(sdpsr_class_i8(xa, t), sdpsr_class_i8(xb, t));
+            for (int u = 0; u < REF_UNROLL; ++u) {
+                const int m = m0 + u * (int)blockDim.x;
+                la[u] = m < n ? check_label(Lp, n, i, m) : 0u;  // (label 0: the channel bytes are 0, nothing is added)
+                lb[u] = m < n ? check_label(Lp, n, m, j) : 0u;
+            }
+#pragma unroll
+            for (int u = 0; u < REF_UNROLL; ++u) {
+                const uint32_t a = la[u] <= (uint32_t)d ? la[u] : 0u, b = lb[u] <= (uint32_t)d ? lb[u] : 0u;
+#pragma unroll
+                for (int g = 0; g < 2; ++g) {
+                    const uint32_t xa = xt[g][a], xb = xt[g][b];
+#pragma unroll
+                    for (int t = 0; t < T; ++t) acc[g * T + t] += __mul24(sdpsr_class_i8(xa, t), sdpsr_class_i8(xb, t));
+                }
+            }
         }
     }
 #pragma unroll
-    for (int t = 0; t < T; ++t) {
-        int v = acc[t];
+    for (int a = 0; a < 2 * T; ++a) {
+        int v = acc[a];
         for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][t] = v;
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][a] = v;
     }
     __syncthreads();
-    if (threadIdx.x < T) c[(int64_t)(g * T + threadIdx.x) * d + k] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+    if ((int)threadIdx.x < G * T) {  // (g, t) = threadIdx.x / T, threadIdx.x % T: row g T + t of c, as before
+        int32_t v = 0;
+        for (int w = 0; w < (int)blockDim.x / 64; ++w) v += red[w][threadIdx.x];
+        c[(int64_t)threadIdx.x * d + k] = v;
+    }
 }
 
 // what the pass looks up per (round, label): the channel bytes of the class and its T class constants
@@ -182,12 +205,20 @@ square_check_pass_kernel(int n, int d, const LT* __restrict__ Lp, uint64_t key0,
     if (bi != bj) check_tile_sums<G, T, false>(tile, cls, vrow, d, part_x, part_c, (int64_t)bi * npad + j0, gt_stride);
 }
 
+// 128-bit sum over the lanes of a wave (mod 2^128: any order gives the same bits); lane 0 holds it
+__device__ __forceinline__ unsigned __int128 check_wave_sum128(unsigned __int128 e) {
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint64_t lo = (uint64_t)__shfl_down((unsigned long long)(uint64_t)e, o), hi = (uint64_t)__shfl_down((unsigned long long)(uint64_t)(e >> 64), o);
+        e += ((unsigned __int128)hi << 64) | (unsigned __int128)lo;
+    }
+    return e;
+}
+
 // grid (nb, G T), 256 threads = 64 rows x 4 slices of the column blocks.  esum: [G T][nb] 128-bit sums as (low, high) words.
 __global__ void __launch_bounds__(256)
 square_check_rows_kernel(int n, int nb, int T, uint64_t key0, uint64_t key1, const int32_t* __restrict__ part_x, const int64_t* __restrict__ part_c,
                          int64_t* __restrict__ y, int64_t* __restrict__ w, uint64_t* __restrict__ esum) {
     __shared__ int64_t sy[4][CHECK_TILE], sw[4][CHECK_TILE];
-    __shared__ uint64_t se[CHECK_TILE][2];
     const int r = threadIdx.x & 63, sl = threadIdx.x >> 6, gt = blockIdx.y;
     const int64_t npad = (int64_t)nb * CHECK_TILE, i = (int64_t)blockIdx.x * CHECK_TILE + r;
     int64_t ys = 0, ws = 0;
@@ -205,25 +236,25 @@ square_check_rows_kernel(int n, int nb, int T, uint64_t key0, uint64_t key1, con
         const uint64_t key = (gt / T) ? key1 : key0;
         const int64_t v = i < n ? (int64_t)sdpsr_check_vector(sdpsr_check_vector_key(key), (uint32_t)i) : 0;
         const __int128 e = (__int128)ys * (__int128)ys - (__int128)v * (__int128)ws;  // |y| < 2^38, |v w| < 2^76
-        se[r][0] = (uint64_t)(unsigned __int128)e, se[r][1] = (uint64_t)((unsigned __int128)e >> 64);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned __int128 tot = 0;
-        for (int k = 0; k < CHECK_TILE; ++k) tot += ((unsigned __int128)se[k][1] << 64) | (unsigned __int128)se[k][0];
-        esum[((int64_t)gt * nb + blockIdx.x) * 2] = (uint64_t)tot;
-        esum[((int64_t)gt * nb + blockIdx.x) * 2 + 1] = (uint64_t)(tot >> 64);
+        const unsigned __int128 tot = check_wave_sum128((unsigned __int128)e);  // (sl == 0 is exactly the first wave)
+        if (r == 0) {
+            esum[((int64_t)gt * nb + blockIdx.x) * 2] = (uint64_t)tot;
+            esum[((int64_t)gt * nb + blockIdx.x) * 2 + 1] = (uint64_t)(tot >> 64);
+        }
     }
 }
 
-// one workgroup; thread gt < G T adds the nb sums of its (round, channel): |X_t v|^2 == v'C_t v exactly when the total is 0
-__global__ void __launch_bounds__(64)
+// one workgroup of G T waves; wave gt adds the nb sums of its (round, channel), a lane every 64th: |X_t v|^2 == v'C_t v exactly when
+// the total is 0
+__global__ void __launch_bounds__(512)
 square_check_verdict_kernel(int nb, int GT, int T, const uint64_t* __restrict__ esum, uint32_t* __restrict__ bits, uint32_t* __restrict__ flag0,
                             uint32_t* __restrict__ flag1) {
-    const int gt = threadIdx.x;
+    const int gt = threadIdx.x >> 6, lane = threadIdx.x & 63;
     if (gt >= GT) return;
     unsigned __int128 tot = 0;
-    for (int b = 0; b < nb; ++b) tot += ((unsigned __int128)esum[((int64_t)gt * nb + b) * 2 + 1] << 64) | (unsigned __int128)esum[((int64_t)gt * nb + b) * 2];
+    for (int b = lane; b < nb; b += 64) tot += ((unsigned __int128)esum[((int64_t)gt * nb + b) * 2 + 1] << 64) | (unsigned __int128)esum[((int64_t)gt * nb + b) * 2];
+    tot = check_wave_sum128(tot);
+    if (lane != 0) return;
     const bool differs = tot != 0;
     bits[gt] = differs ? 0u : 1u;
     if (differs) (gt / T ? flag1 : flag0)[0] = 1u;
@@ -233,9 +264,9 @@ template <typename LT>
 void square_check_front(hipStream_t s, const SquareCheck& q, const LT* Lp) {
     const int n = (int)q.n, d = (int)q.d, nb = (int)((q.n + CHECK_TILE - 1) / CHECK_TILE);
     const uint64_t k0 = q.key[0], k1 = q.G > 1 ? q.key[1] : 0;
-    const dim3 gr((unsigned)d, (unsigned)q.G), gp((unsigned)nb, (unsigned)nb);
-    if (q.T == 2) square_check_ref_kernel<2, LT><<<gr, 256, 0, s>>>(n, d, Lp, q.first_idx, k0, k1, q.c);
-    else square_check_ref_kernel<4, LT><<<gr, 256, 0, s>>>(n, d, Lp, q.first_idx, k0, k1, q.c);
+    const dim3 gr((unsigned)d), gp((unsigned)nb, (unsigned)nb);
+    if (q.T == 2) square_check_ref_kernel<2, LT><<<gr, REF_THREADS, 0, s>>>(n, d, q.G, Lp, q.first_idx, k0, k1, q.c);
+    else square_check_ref_kernel<4, LT><<<gr, REF_THREADS, 0, s>>>(n, d, q.G, Lp, q.first_idx, k0, k1, q.c);
 #define SDPSR_CHECK_PASS_CASE(GG, TT)                                                                                                          \
     if (q.G == GG && q.T == TT) {                                                                                                              \
         if (q.Lfull) square_check_pass_kernel<GG, TT, true, LT><<<gp, 256, 0, s>>>(n, d, Lp, k0, k1, q.c, q.Lfull, q.part_x, q.part_c);        \
@@ -285,7 +316,7 @@ void launch_square_check_verdict(hipStream_t s, const SquareCheck& q) {
     const int nb = (int)((q.n + CHECK_TILE - 1) / CHECK_TILE), GT = q.G * q.T;
     const uint64_t k0 = q.key[0], k1 = q.G > 1 ? q.key[1] : 0;
     square_check_rows_kernel<<<dim3((unsigned)nb, (unsigned)GT), 256, 0, s>>>((int)q.n, nb, q.T, k0, k1, q.part_x, q.part_c, q.y, q.w, q.esum);
-    square_check_verdict_kernel<<<1, 64, 0, s>>>(nb, GT, q.T, q.esum, q.bits, q.flag[0], q.G > 1 ? q.flag[1] : q.flag[0]);
+    square_check_verdict_kernel<<<1, 64 * GT, 0, s>>>(nb, GT, q.T, q.esum, q.bits, q.flag[0], q.G > 1 ? q.flag[1] : q.flag[0]);
 }
 
 }  // namespace sdpsr

@@ -200,7 +200,8 @@ struct Loop {
     }
     // The checked rounds: key2 is the joint round's key, the confirm round's is drawn here, where verify_round draws it.  Stream order:
     // class constants, the pass (which writes the full labels: expected to be the call's last label pass), the projection compare into
-    // the first verdict word, the verdicts.  The label write cannot wait.  tail (joint_iteration decides, and has then left the
+    // the first verdict word, the verdicts.  The label write cannot wait unless blockDiagonalize reads the record's copy of the labels
+    // (on_record below: then the class constants and the pass are a segment too).  tail (joint_iteration decides, and has then left the
     // projection's dot products to this round too): what follows the pass is registered as the round's check segment instead of
     // launched -- dot products, projection compare, verdict kernels, with the arguments they have here -- and both words read
     // "violated" until the segment is enqueued.
@@ -226,7 +227,11 @@ struct Loop {
         if (tail) {
             *(volatile uint32_t*)hv = DEFERRED_NEVER_RAN;  // (flush_deferred_tail clears both words from the host in front of the segment)
             *(volatile uint32_t*)hv2 = DEFERRED_NEVER_RAN;
-            launch_square_check_ref_and_pass(s, q);
+            // The guessed initial partition is the record's, and the record holds its full labels (rec_full): nothing refines in this
+            // call unless a verdict is violated, so blockDiagonalize starts on that copy (reduce.cpp) and the class constants and the
+            // pass, whose label write was all that kept them here, go in front of everything else that is pending.
+            const bool on_record = rec_full != nullptr && c->initial_guess_pending && q.Lfull == lab.L;
+            if (!on_record) launch_square_check_ref_and_pass(s, q);
             DeferredTail& t = c->deferred_tail;
             if (t.next == t.count) t.next = t.count = 0;
             if (t.count >= DEFERRED_SEGMENTS) return ctx_fail(c, SDPSR_BAD_STATE, "admissible_subspace: no room for the round's check segment");
@@ -237,6 +242,20 @@ struct Loop {
             g.proj_verify = proj_verify;
             g.verdict = true, g.sq = q;
             ++c->check_stats.registered;
+            if (on_record) {
+                // Two segments as before.  The pending pair segment becomes {class constants, pass} and its compare moves into the
+                // round's segment (same labels, same representatives): 51 us behind the class sums' product and 86 us behind the
+                // growth round's at N = 4096.  The host's own work there is 14 and 58 us, so both overflow under any split and
+                // the order is what matters: the pass before the block sums (profiles/r28_recorded_labels.txt).  No pair segment
+                // pending: the round's own segment starts with the pass.
+                DeferredSegment& g0 = t.seg[t.next];
+                if (&g0 != &g && g0.pair && g0.n == g.n && g0.Lp == g.Lp && g0.Lp8 == g.Lp8 && g0.first == g.first) {
+                    g.pair = true, g.a = g0.a, g.b = g0.b, g.pair_d = g0.pair_d, g.pair_flag = g0.pair_flag;
+                    g0.pair = false;
+                }
+                g0.sq_pass = true, g0.sq = q;
+                c->labels_on_record = rec_full;
+            }
         } else {
             *(volatile uint32_t*)hv = 0u;  // (the kernels only ever store 1; the last verdicts on these words have been read)
             *(volatile uint32_t*)hv2 = 0u;
@@ -534,9 +553,9 @@ struct Loop {
             flush_deferred_tail(c);  // (nothing is pending at the start of a loop call)
             DeferredTail& t = c->deferred_tail;
             DeferredSegment& g = t.seg[0] = DeferredSegment{};
-            g.kind = DEFERRED_CHECK, g.pair = true, g.n = n, g.a = dCL, g.b = dX0, g.Lp = lab.Lp, g.Lp8 = Lp8, g.d = guess->d0, g.first = guess->first;
-            g.flag = c->pinned_small + PINNED_SMALL_DEFERRED_INITIAL.first;
-            *(volatile uint32_t*)g.flag = DEFERRED_NEVER_RAN;
+            g.kind = DEFERRED_CHECK, g.pair = true, g.n = n, g.a = dCL, g.b = dX0, g.Lp = lab.Lp, g.Lp8 = Lp8, g.pair_d = guess->d0, g.first = guess->first;
+            g.pair_flag = c->pinned_small + PINNED_SMALL_DEFERRED_INITIAL.first;
+            *(volatile uint32_t*)g.pair_flag = DEFERRED_NEVER_RAN;
             t.next = 0, t.count = 1;
             ++c->check_stats.registered;
             pair_registered = true;
@@ -566,6 +585,7 @@ struct Loop {
         return SDPSR_OK;
     }
     bool initial_packed = false;  // the initial partition was formed (or guessed) on the packed lower triangle
+    const uint32_t* rec_full = nullptr;  // the guessed record's full labels, where this call may leave blockDiagonalize to them (check_round)
     // The square mode's buffers (same names and sizes for every call of a mode; T = 1 in the fp64 mode)
     int square_buffers() {
         static const struct { const char *x, *c; size_t xb, cb; } B[] = {{"adm_xi8", "adm_ci32", 1, 4}, {"adm_xf32", "adm_cf32", 4, 4}, {"adm_xf64", "adm_cf64", 8, 8}};
@@ -591,6 +611,9 @@ namespace sdpsr {
 // caller's C_L / X0_L (or "adm_cl" / "adm_x0"); the round's segment reads the caller's U (or "adm_u") and the square check's partial sums in
 // "adm_sqcheck" (written by the pass, which ran in the loop), and writes "proj_partial", "proj_coef", the rest of "adm_sqcheck" and its two
 // verdict words, which the host clears here, in front of the segment's first launch (the kernels only ever store 1).
+// Where blockDiagonalize reads the record's labels "adm_lfull_rec" (check_round), the pass is a segment too: it reads "adm_lpacked" or
+// "adm_lpacked8" and "ref_first", writes all of "adm_sqcheck" and the caller's label matrix, which nothing reads before the call's last
+// flush; "adm_lfull_rec" itself is read by blockDiagonalize's kernels between the segments and written by nobody while a record lives.
 // Whoever enqueues work of its own while segments are pending must touch none of these -- in particular run no refinement
 // (refine_signatures rewrites "ref_first") and request none of these buffers with another size (ctx_buf enqueues what is pending before
 // it frees any buffer).  Whoever waits for the stream in order to read a deferred word enqueues what is pending first.
@@ -600,14 +623,14 @@ void flush_deferred_tail(sdpsr_ctx* c, int max_segments, bool in_ride) {
     for (; max_segments > 0 && t.next < t.count; --max_segments, ++t.next) {
         const DeferredSegment& g = t.seg[t.next];
         if (g.kind == DEFERRED_CHECK) {
-            if (g.pair) {
-                launch_verify_pair(c->stream, g.n, g.a, g.b, g.Lp, g.d, g.first, g.flag, g.Lp8);  // (clears the word from the host)
-            } else {
+            if (g.sq_pass) launch_square_check_ref_and_pass(c->stream, g.sq);
+            if (g.pair) launch_verify_pair(c->stream, g.n, g.a, g.b, g.Lp, g.pair_d, g.first, g.pair_flag, g.Lp8);  // (clears the word from the host)
+            if (g.verdict) {
                 *(volatile uint32_t*)g.sq.flag[0] = 0u;
                 *(volatile uint32_t*)g.sq.flag[1] = 0u;
                 if (g.proj_coef) launch_proj_coef_lower(c->stream, g.n, g.q.r, g.q.U, g.Lp, 1, g.q.key, g.partial, g.nblk, g.coef, g.Lp8);
                 if (g.proj_verify) launch_verify_projection(c->stream, g.q, g.d, g.first, g.flag);
-                if (g.verdict) launch_square_check_verdict(c->stream, g.sq);
+                launch_square_check_verdict(c->stream, g.sq);
             }
             ++(in_ride ? c->check_stats.in_ride : c->check_stats.outside_ride);
             continue;
@@ -686,6 +709,12 @@ int admissible_subspace_impl(sdpsr_ctx* c, int64_t n, const double* CL, const do
     // labels; SDPSR_FLAG_WIDE_LOOP_LABELS: never).  No buffer: the wide labels.
     if (guess_initial && rec.d0 <= 255 && !(c->opts.flags & SDPSR_FLAG_WIDE_LOOP_LABELS))
         lp.lab.Lp8 = (uint8_t*)ctx_buf(c, "adm_lpacked8", (size_t)(n * (n + 1) / 2));
+    // The record's full labels ("adm_lfull_rec", InitialRecord::Lfull) serve a guessed call of sdpsr_jordan_reduce whose first round is the
+    // checked one with its segments (check_applies, checks_deferrable: the conditions known here; check_round looks at the rest), and
+    // are made for the next call, under the same conditions, by a call that ends with a record and finds no copy (below).
+    const bool record_labels = c->record_labels_allowed && c->allow_deferred_verdict && c->pinned_small && !tm.enabled && first_joint && (hint & 2) &&
+                               lp.mode == SDPSR_SQUARE_I8 && !(c->opts.flags & (SDPSR_FLAG_CHECKS_IN_LOOP | SDPSR_FLAG_SQUARE_EVERY_VERDICT));
+    if (guess_initial && record_labels && rec.Lfull && rec.Lfull == (const uint32_t*)ctx_buf(c, "adm_lfull_rec", (size_t)len * 4)) lp.rec_full = rec.Lfull;
     int64_t d = 0;
     tm.begin(SDPSR_T_REFINE);
     st = lp.initial_partition(dCL, dX0, hint, guess_initial ? &rec : nullptr, &d);
@@ -728,11 +757,24 @@ int admissible_subspace_impl(sdpsr_ctx* c, int64_t n, const double* CL, const do
     // a call that refined nothing after its initial partition leaves that partition, and its representatives, where the next call looks for them
     if (converged && lp.initial_packed && c->first_idx_labels == lp.lab.Lp && c->adm_dims[0] >= 1 && c->adm_dims[0] <= (int64_t)verify_lds_cap() &&
         std::all_of(c->adm_dims.begin(), c->adm_dims.end(), [&](int64_t x) { return x == c->adm_dims[0]; })) {
+        // The full labels that belong to it: a guessed call leaves the record's copy as it found it.  A call that finds none -- an
+        // unguessed one, or one that guessed on a record made where no copy was wanted (a timed call, a flag since cleared) and so
+        // wrote its labels in the loop -- copies its output (complete in stream order: need_full above) where the next call could
+        // start blockDiagonalize on the copy.  A wrong guess drops the record, and the copy with it, before anybody reads either.
+        const uint32_t* lfull = guess_initial ? rec.Lfull : nullptr;
+        if (!lfull && record_labels && lp.lab.sym && square_check_supports(n, c->adm_dims[0], 2, lp.T)) {
+            uint32_t* copy = (uint32_t*)ctx_buf(c, "adm_lfull_rec", (size_t)len * 4);
+            if (copy && hipMemcpyAsync(copy, lp.lab.L, (size_t)len * 4, hipMemcpyDeviceToDevice, s) == hipSuccess) lfull = copy;
+            else (void)hipGetLastError();  // (no copy: the next call keeps the old order)
+        }
         InitialRecord& ir = c->initial_record;
         ir.first = (const uint32_t*)ctx_buf(c, "ref_first", (size_t)refine_first_cap() * 4);  // (before `valid`: ctx_buf drops the record of a buffer it replaces)
+        ir.Lfull = lfull;
         ir.n = n, ir.d0 = c->adm_dims[0], ir.Lp = lp.lab.Lp, ir.sym = lp.lab.sym;
         ir.narrow = lp.lab.narrow(), ir.Lp8 = ir.narrow ? lp.lab.Lp8 : nullptr;  // (the shadow, where the call ends with a current one)
         ir.valid = ir.first != nullptr;
+    } else {
+        c->labels_on_record = nullptr;  // (something refined behind a settled guess: the call's labels are its own, formed by need_full above)
     }
     *dim_out = lp.current;
     if (iters_out) *iters_out = lp.it;

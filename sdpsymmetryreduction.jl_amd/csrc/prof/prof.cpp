@@ -403,6 +403,12 @@ extern "C" int sdpsr_profile_deferred_checks(sdpsr_ctx* c, int32_t restart, uint
     out[7] = t.voided[0], out[8] = t.voided[1], out[9] = t.voided[2];
     return SDPSR_OK;
 }
+extern "C" int sdpsr_profile_recorded_labels(sdpsr_ctx* c, int32_t restart, uint64_t* out) {
+    const int st = sdpsr_profile_deferred_checks(c, restart, out);
+    if (st) return st;
+    out[10] = (restart == 0 ? c : c->batch_children[restart - 1])->check_stats.on_record;
+    return SDPSR_OK;
+}
 
 // The square check on caller-made inputs (tests/test_gpu_square_check.py).  ws_inout == nullptr: only layout[] is filled.
 extern "C" int sdpsr_profile_square_check(sdpsr_ctx* c, int64_t n, int64_t d, int G, int T, const uint64_t* keys, int width, int write_full,

@@ -91,9 +91,21 @@ int jordan_reduce_impl(sdpsr_ctx* c, int64_t n, const double* CL, const double* 
         return st_err == STATUS_REPEAT_REDUCTION ? ctx_fail(c, SDPSR_BAD_STATE, "jordan_reduce: a repeat was asked for without a violated verdict") : st_err;
     };
     c->allow_deferred_verdict = !(c->opts.flags & SDPSR_FLAG_WAIT_FOR_EVERY_VERDICT);  // (the loop's last verdicts may ride on this reduction's later host waits, see sdpsr_internal.h)
+    // A guessed reduction refines nothing, so its labels are the record's: where the partition is formed in the caller's buffer, the loop
+    // may leave the pass that writes it to the deferred tail and name the ctx's copy of the same labels for blockDiagonalize
+    // (c->labels_on_record; loop.cpp, check_round).  Host outputs and narrow labels deliver P_out in front of blockDiagonalize, a
+    // timed call launches everything in the loop: both keep the old order, like SDPSR_FLAG_LABELS_BEFORE_BLOCKDIAG.
+    c->record_labels_allowed = in_place && !phase_ms && !(c->opts.flags & SDPSR_FLAG_LABELS_BEFORE_BLOCKDIAG);
+    c->labels_on_record = nullptr;
     st = admissible_subspace_impl(c, n, CL, X0L, U, r, atol, L, dim_out, iters_out, phase_ms ? pm_a : nullptr, mem_in, SDPSR_MEM_DEVICE,
                                   /*final_sync=*/false, &labels_sym);
     c->allow_deferred_verdict = false;
+    c->record_labels_allowed = false;
+    // blockDiagonalize's labels: L, or the record's copy of them while the pass that writes L waits in the tail.  Everything that
+    // remembers the pointer (bd_labels_ext, bd_trusted_symmetric) then remembers the ctx's copy, which holds the same labels; P_out
+    // itself is complete behind the flush below, in front of the images and of the copy into "bd_labels".
+    const uint32_t* Lbd = c->labels_on_record ? c->labels_on_record : L;
+    c->labels_on_record = nullptr;
     const int st_loop = st;
     if (st && st != SDPSR_NOT_CONVERGED) return leave(st);
     // more classes than the ctx's label width holds (the reference's InexactError of Partition{T}): the reduction stops behind the loop,
@@ -106,8 +118,9 @@ int jordan_reduce_impl(sdpsr_ctx* c, int64_t n, const double* CL, const double* 
     const int64_t d = *dim_out;
     int32_t nb = 0;
     int64_t S = 0, S1 = 0;
+    if (!overflow && Lbd != L) ++c->check_stats.on_record;
     st = overflow ? SDPSR_OK
-                  : block_diagonalize_impl(c, n, L, d, epsilon, &nb, &S, &S1, phase_ms ? pm_b : nullptr, SDPSR_MEM_DEVICE, labels_sym != 0,
+                  : block_diagonalize_impl(c, n, Lbd, d, epsilon, &nb, &S, &S1, phase_ms ? pm_b : nullptr, SDPSR_MEM_DEVICE, labels_sym != 0,
                                            /*final_sync=*/false, in_place);
     // whatever blockDiagonalize did (a failure included): the rest of the deferred tail goes in front of the images' kernels and of the
     // wait behind which the verdicts are read

@@ -81,7 +81,9 @@ struct SquareCheck {
 //                    the compare of the guessed initial partition (launch_verify_pair).  Segment "round": the dot products of the
 //                    projection (launch_proj_coef_lower), the projection compare (launch_verify_projection) and the square check's
 //                    verdict kernels (launch_square_check_verdict), in the loop's order.  The square check's class constants and its
-//                    pass stay in the loop: the pass writes the full labels blockDiagonalize reads.
+//                    pass (launch_square_check_ref_and_pass) stay in the loop -- the pass writes the full labels blockDiagonalize
+//                    reads -- unless blockDiagonalize reads the record's copy of them (InitialRecord::Lfull; loop.cpp, check_round):
+//                    then they are segment "pass", the first of the two, and the pair check moves into segment "round" behind it.
 // A segment carries its keys: every key is drawn in the loop, where it always was.
 enum { DEFERRED_SQUARE = 0, DEFERRED_CHECK = 1 };
 struct DeferredSegment {
@@ -93,8 +95,11 @@ struct DeferredSegment {
     void* vref = nullptr;
     uint32_t* flag = nullptr;   // the verdict's word of c->pinned_small (DEFERRED_CHECK: the pair check's, or the round's first)
     bool speculative = false;   // counts as a speculative square
-    // --- DEFERRED_CHECK ---
-    bool pair = false;          // launch_verify_pair(n, a, b, Lp, d, first, flag, Lp8)
+    // --- DEFERRED_CHECK --- (what is set is launched in the order of the fields)
+    bool sq_pass = false;       // launch_square_check_ref_and_pass(sq): writes sq.Lfull, the caller's labels
+    bool pair = false;          // launch_verify_pair(n, a, b, Lp, pair_d, first, pair_flag, Lp8)
+    int64_t pair_d = 0;
+    uint32_t* pair_flag = nullptr;
     const double *a = nullptr, *b = nullptr;
     const uint32_t* Lp = nullptr;
     const uint8_t* Lp8 = nullptr;
@@ -124,10 +129,13 @@ struct DeferredCheckStats {
     int window_open = -1;
     uint64_t window_t0 = 0;
     uint32_t voided[3] = {0, 0, 0};  // the words as the last voided reduction read them (reduce.cpp): verify, speculative, initial partition
+    uint64_t on_record = 0;  // reductions whose blockDiagonalize read the record's copy of the labels (sdpsr_profile_recorded_labels)
 };
 constexpr uint32_t DEFERRED_NEVER_RAN = 0xDEFE44EDu;  // what a verdict word holds until its segment is enqueued: reads as "violated"
 // "adm_lpacked" (Lp) and "ref_first" (first) describe the initial partition of the last loop call: order n, d0 classes, labels symmetric
 // narrow: "adm_lpacked8" (Lp8) is a byte copy of Lp (d0 <= 255) -- the 8-bit shadow the guessed-closed path streams instead of Lp
+// Lfull: "adm_lfull_rec" holds the full symmetric n x n labels that belong to Lp (copied from the output of the unguessed call that
+// made the record): blockDiagonalize of a guessed reduction starts on them while the pass that writes the caller's copy is deferred
 struct InitialRecord {
     bool valid = false;
     int64_t n = 0, d0 = 0;
@@ -135,6 +143,7 @@ struct InitialRecord {
     int sym = 0;
     bool narrow = false;
     const uint8_t* Lp8 = nullptr;
+    const uint32_t* Lfull = nullptr;
 };
 // the loop's outcome "the initial partition was not the recorded one: repeat the reduction" -- never leaves jordan_reduce_impl
 constexpr int STATUS_REPEAT_REDUCTION = -0x5250;
@@ -224,6 +233,10 @@ struct sdpsr_ctx {
     // violated verdict, and by ctx_buf when it frees either buffer (or "adm_lpacked8", the labels' 8-bit shadow).
     sdpsr::InitialRecord initial_record;
     bool initial_guess_pending = false;  // this reduction took the guess; its word (PINNED_SMALL_DEFERRED_INITIAL) has not been read
+    // sdpsr_jordan_reduce forms the partition in the caller's device buffer, untimed, without SDPSR_FLAG_LABELS_BEFORE_BLOCKDIAG: the
+    // loop may keep the record's full labels and defer the pass that writes the caller's (set around the loop call only) ...
+    bool record_labels_allowed = false;
+    const uint32_t* labels_on_record = nullptr;  // ... and has done so: blockDiagonalize reads these; the caller's are written by segment "pass"
     uint64_t initial_guesses = 0, initial_guesses_violated = 0;  // sdpsr_profile_initial_guess
     uint64_t label_narrowings = 0;  // launches that made the 8-bit shadow of the packed labels (loop.cpp, initial_partition); sdpsr_profile_narrow_labels
     bool symflag_zero = false;  // every word of "adm_symflag" is 0 (the loop's last call wrote none of them)
