@@ -345,6 +345,37 @@ int sdpsr_profile_backtransform(sdpsr_ctx* ctx, int64_t n, int64_t ld, const dou
 int sdpsr_profile_stedc(sdpsr_ctx* ctx, int64_t n, int64_t ld, const double* d_host, const double* e_host, double* w_inout, double* Z_inout,
                         int64_t guard);
 
+/* ---- The row-space kernels of sdpsr_compress_constraints on caller-made inputs (tests/test_gpu_rowspace_kernels.py). ----
+   Conventions of the module-kernel entries above.  M, W and out are m x ncols, column-major with leading dimension m.
+   SDPSR_BAD_ARGUMENT, before anything is uploaded, for: a null pointer (where none is allowed), m < 1 or m > 1024, ncols < 1,
+   m * ncols > 2^26, guard outside [0, 2^20], r outside [0, m], a perm entry outside [0, m), a droptol that is not >= 0. */
+
+/* launch_rowspace_scale on M = [A | b] (A_host: m x d, b_host: m or NULL; ncols = d + (b_host != NULL)), after zeroing the flag word
+   as the driver does.  W_inout (m * ncols + guard) = M * 2^-e, e the exponent of max |M| (the scale is capped at 2^1000, and 1 for
+   max |M| = 0); info_out[0] = max |M| over the finite entries, info_out[1] = 1.0 when an entry is Inf or NaN -- and then no element
+   of W_inout is written. */
+int sdpsr_profile_rowspace_scale(sdpsr_ctx* ctx, int64_t m, int64_t d, const double* A_host, const double* b_host, double* W_inout,
+                                 double* info_out, int64_t guard);
+/* G = W W' through launch_rowspace_gram: both triangles of the m x m G_inout (m * m + guard) are written, G[p, q] and G[q, p] with
+   one value.  The partial sums are filled with NaN bytes before the launch, so one the Gram kernel left out shows.  report = {npairs,
+   Z, cps} from rowspace_gram_shape, which the launcher asks: block pairs of 64 x 64, K splits, columns per split.  Order of summation:
+   within a split four columns per matrix-core step, ascending; the splits' partial sums are added in ascending order from +0.0. */
+int sdpsr_profile_rowspace_gram(sdpsr_ctx* ctx, int64_t m, int64_t ncols, const double* W_host, double* G_inout, int64_t guard,
+                                int32_t* report);
+/* W <- J W in place through launch_rowspace_rotate; J_host: m x m, column-major (J[i + k m]); W_inout: m * ncols + guard.  Each entry
+   is the sum over k ascending from +0.0, a multiply and an add (or one FMA) per term.  report = {cc, j_lds} from rowspace_chunk, which
+   the launcher asks: columns per workgroup, and 1 when J is staged in LDS beside them. */
+int sdpsr_profile_rowspace_rotate(sdpsr_ctx* ctx, int64_t m, int64_t ncols, const double* J_host, double* W_inout, int64_t guard,
+                                  int32_t* report);
+/* launch_rowspace_finish.  perm_host, sigma_host: m entries, the first r used.  sig[k] = sigma[k] with the sign of the first entry of
+   largest magnitude of row perm[k] of W, k < r (sig_inout: m + guard; entries >= r are not written).  out[k, c] = W[perm[k], c] / sig[k],
+   values of magnitude <= droptol and the rows >= r as +0.0; *nnz_out = the non-zeros written.  in_place != 0: out is W, as in the driver
+   (out_inout unused, may be NULL; the result comes back in W_inout); otherwise out_inout (m * ncols + guard) receives it and W_inout
+   (m * ncols + guard) comes back as it went in. */
+int sdpsr_profile_rowspace_finish(sdpsr_ctx* ctx, int64_t m, int64_t ncols, int64_t r, const int32_t* perm_host, const double* sigma_host,
+                                  double droptol, int in_place, double* W_inout, double* out_inout, double* sig_inout, int64_t* nnz_out,
+                                  int64_t guard);
+
 #ifdef __cplusplus
 }
 #endif

@@ -336,5 +336,14 @@ def load_prof_library():
     lib.sdpsr_profile_backtransform.argtypes = [vp, i64, i64, vp, vp, vp, i64]
     lib.sdpsr_profile_stedc.restype = C.c_int
     lib.sdpsr_profile_stedc.argtypes = [vp, i64, i64, vp, vp, vp, vp, i64]
+    # the row-space kernels of compress_constraints on caller-made inputs (tests)
+    lib.sdpsr_profile_rowspace_scale.restype = C.c_int
+    lib.sdpsr_profile_rowspace_scale.argtypes = [vp, i64, i64, vp, vp, vp, vp, i64]
+    lib.sdpsr_profile_rowspace_gram.restype = C.c_int
+    lib.sdpsr_profile_rowspace_gram.argtypes = [vp, i64, i64, vp, vp, i64, rep]
+    lib.sdpsr_profile_rowspace_rotate.restype = C.c_int
+    lib.sdpsr_profile_rowspace_rotate.argtypes = [vp, i64, i64, vp, vp, i64, rep]
+    lib.sdpsr_profile_rowspace_finish.restype = C.c_int
+    lib.sdpsr_profile_rowspace_finish.argtypes = [vp, i64, i64, i64, vp, vp, f64, C.c_int, vp, vp, vp, C.POINTER(i64), i64]
     _prof = lib
     return lib

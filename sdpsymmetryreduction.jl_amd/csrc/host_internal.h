@@ -495,6 +495,8 @@ void launch_blockop_keyed_sums(hipStream_t s, int64_t n, const void* rec, const 
 double rowspace_scale(double max_abs);
 int rowspace_absmax_blocks(int64_t total);
 size_t rowspace_gram_partial_doubles(int64_t m, int64_t ncols);
+void rowspace_gram_shape(int64_t m, int64_t ncols, int* npairs, int* Z, int64_t* cps);
+int rowspace_chunk(int64_t m, bool* j_lds);  // columns per workgroup of the rotation (j_lds given) resp. the write-out (nullptr)
 void launch_rowspace_scale(hipStream_t s, int64_t total, int64_t md, const double* A, const double* b, double* pmax, uint32_t* flag,
                            double* W, double* info);
 void launch_rowspace_gram(hipStream_t s, int64_t m, int64_t ncols, const double* W, double* P, double* G);

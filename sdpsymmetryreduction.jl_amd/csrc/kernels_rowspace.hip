@@ -310,7 +310,7 @@ void launch_rowspace_gram(hipStream_t s, int64_t m, int64_t ncols, const double*
 }
 
 // columns per workgroup of the two kernels that stage columns in LDS (64 KiB, no attribute), and whether J fits beside them
-static int rowspace_chunk(int64_t m, bool* j_lds) {
+int rowspace_chunk(int64_t m, bool* j_lds) {
     const int64_t lds = 8000;  // doubles: 64 KiB less the kernels' static words
     const bool fits = m * m + m <= lds / 2;
     if (j_lds) *j_lds = fits;

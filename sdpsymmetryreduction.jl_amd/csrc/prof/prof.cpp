@@ -1406,6 +1406,129 @@ extern "C" int sdpsr_profile_stedc(sdpsr_ctx* c, int64_t n, int64_t ld, const do
     return hinfo[0] ? ctx_fail(c, SDPSR_SOLVER_ERROR, "stedc: the checks raised info = " + std::to_string(hinfo[0])) : SDPSR_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// The row-space kernels of sdpsr_compress_constraints (kernels_rowspace.hip) on caller-made inputs (tests/test_gpu_rowspace_kernels.py),
+// by the conventions of the module-kernel entries: each calls the launcher rowspace.cpp calls, the way it calls it.  M and W are
+// m x ncols, column-major with leading dimension m, 1 <= m <= 1024, 1 <= ncols, m * ncols <= 2^26.
+// ---------------------------------------------------------------------------------------------------------------------------
+namespace {
+constexpr int64_t RS_MAX_M = 1024, RS_MAX_TOTAL = int64_t(1) << 26;
+bool rs_shape_ok(int64_t m, int64_t ncols, int64_t guard) {
+    return m >= 1 && m <= RS_MAX_M && ncols >= 1 && ncols <= RS_MAX_TOTAL && m * ncols <= RS_MAX_TOTAL && ds_guard_ok(guard);
+}
+}  // namespace
+
+extern "C" int sdpsr_profile_rowspace_scale(sdpsr_ctx* c, int64_t m, int64_t d, const double* A_host, const double* b_host, double* W_inout,
+                                            double* info_out, int64_t guard) {
+    CHECK_CTX(c);
+    if (d < 0 || d > RS_MAX_TOTAL) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "rowspace_scale: bad arguments");
+    const int64_t ncols = d + (b_host ? 1 : 0);
+    if ((d > 0 && !A_host) || !W_inout || !info_out || !rs_shape_ok(m, ncols, guard)) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "rowspace_scale: bad arguments");
+    const int64_t md = m * d, total = m * ncols;
+    const size_t wn = (size_t)total + (size_t)guard;
+    hipStream_t s = c->stream;
+    double* A = md ? (double*)ctx_buf(c, "prof_rs_a", (size_t)md * 8) : nullptr;
+    double* b = b_host ? (double*)ctx_buf(c, "prof_rs_b", (size_t)m * 8) : nullptr;
+    double* W = (double*)ctx_buf(c, "prof_rs_w", wn * 8);
+    double* pmax = (double*)ctx_buf(c, "cc_pmax", (size_t)rowspace_absmax_blocks(total) * 8);
+    double* info = (double*)ctx_buf(c, "prof_rs_info", 64);
+    uint32_t* flag = (uint32_t*)ctx_buf(c, "prim_flag", 64);
+    if ((md && !A) || (b_host && !b) || !W || !pmax || !info || !flag) return SDPSR_OUT_OF_MEMORY;
+    int st = md ? ds_up(c, A, A_host, (size_t)md) : SDPSR_OK;
+    if (!st && b) st = ds_up(c, b, b_host, (size_t)m);
+    if (!st) st = ds_up(c, W, W_inout, wn);
+    if (st) return st;
+    HIP_TRY(c, hipMemsetAsync(flag, 0, 4, s));
+    launch_rowspace_scale(s, total, md, A, b, pmax, flag, W, info);
+    st = ds_down(c, W_inout, W, wn);
+    if (!st) st = ds_down(c, info_out, info, 2);
+    return st ? st : ds_finish(c);
+}
+
+// (the partial sums are filled with NaN bytes first: a partial the Gram kernel did not write shows in G)
+extern "C" int sdpsr_profile_rowspace_gram(sdpsr_ctx* c, int64_t m, int64_t ncols, const double* W_host, double* G_inout, int64_t guard,
+                                           int32_t* report) {
+    CHECK_CTX(c);
+    if (!W_host || !G_inout || !report || !rs_shape_ok(m, ncols, guard)) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "rowspace_gram: bad arguments");
+    const size_t wn = (size_t)(m * ncols), gn = (size_t)(m * m) + (size_t)guard, pn = rowspace_gram_partial_doubles(m, ncols);
+    hipStream_t s = c->stream;
+    double* W = (double*)ctx_buf(c, "prof_rs_w", wn * 8);
+    double* G = (double*)ctx_buf(c, "prof_rs_g", gn * 8);
+    double* P = (double*)ctx_buf(c, "cc_partials", pn * 8);
+    if (!W || !G || !P) return SDPSR_OUT_OF_MEMORY;
+    int st = ds_up(c, W, W_host, wn);
+    if (!st) st = ds_up(c, G, G_inout, gn);
+    if (st) return st;
+    HIP_TRY(c, hipMemsetAsync(P, 0xFF, pn * 8, s));
+    launch_rowspace_gram(s, m, ncols, W, P, G);
+    st = ds_down(c, G_inout, G, gn);
+    if (!st) st = ds_finish(c);
+    if (st) return st;
+    int npairs, Z;
+    int64_t cps;
+    rowspace_gram_shape(m, ncols, &npairs, &Z, &cps);
+    report[0] = npairs, report[1] = Z, report[2] = (int32_t)cps;
+    return SDPSR_OK;
+}
+
+extern "C" int sdpsr_profile_rowspace_rotate(sdpsr_ctx* c, int64_t m, int64_t ncols, const double* J_host, double* W_inout, int64_t guard,
+                                             int32_t* report) {
+    CHECK_CTX(c);
+    if (!J_host || !W_inout || !report || !rs_shape_ok(m, ncols, guard)) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "rowspace_rotate: bad arguments");
+    const size_t wn = (size_t)(m * ncols) + (size_t)guard;
+    double* J = (double*)ctx_buf(c, "cc_j", (size_t)(m * m) * 8);
+    double* W = (double*)ctx_buf(c, "prof_rs_w", wn * 8);
+    if (!J || !W) return SDPSR_OUT_OF_MEMORY;
+    int st = ds_up(c, J, J_host, (size_t)(m * m));
+    if (!st) st = ds_up(c, W, W_inout, wn);
+    if (st) return st;
+    launch_rowspace_rotate(c->stream, m, ncols, J, W);
+    st = ds_down(c, W_inout, W, wn);
+    if (!st) st = ds_finish(c);
+    if (st) return st;
+    bool j_lds;
+    report[0] = rowspace_chunk(m, &j_lds);
+    report[1] = j_lds ? 1 : 0;
+    return SDPSR_OK;
+}
+
+extern "C" int sdpsr_profile_rowspace_finish(sdpsr_ctx* c, int64_t m, int64_t ncols, int64_t r, const int32_t* perm_host, const double* sigma_host,
+                                             double droptol, int in_place, double* W_inout, double* out_inout, double* sig_inout, int64_t* nnz_out,
+                                             int64_t guard) {
+    CHECK_CTX(c);
+    if (!perm_host || !sigma_host || !W_inout || (!in_place && !out_inout) || !sig_inout || !nnz_out || !rs_shape_ok(m, ncols, guard) || r < 0 || r > m ||
+        !(droptol >= 0))
+        return ctx_fail(c, SDPSR_BAD_ARGUMENT, "rowspace_finish: bad arguments");
+    for (int64_t k = 0; k < m; ++k)
+        if (perm_host[k] < 0 || perm_host[k] >= m) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "rowspace_finish: a perm entry outside [0, m)");
+    const size_t wn = (size_t)(m * ncols) + (size_t)guard, sn = (size_t)m + (size_t)guard;
+    hipStream_t s = c->stream;
+    double* W = (double*)ctx_buf(c, "prof_rs_w", wn * 8);
+    double* out = in_place ? W : (double*)ctx_buf(c, "prof_rs_out", wn * 8);
+    double* sigma = (double*)ctx_buf(c, "prof_rs_sigma", (size_t)m * 8);
+    double* sig = (double*)ctx_buf(c, "prof_rs_sig", sn * 8);
+    int32_t* perm = (int32_t*)ctx_buf(c, "prof_rs_perm", (size_t)m * 4);
+    unsigned long long* nnz = (unsigned long long*)ctx_buf(c, "prof_rs_nnz", 64);
+    if (!W || !out || !sigma || !sig || !perm || !nnz) return SDPSR_OUT_OF_MEMORY;
+    int st = ds_up(c, W, W_inout, wn);
+    if (!st && !in_place) st = ds_up(c, out, out_inout, wn);
+    if (!st) st = ds_up(c, sigma, sigma_host, (size_t)m);
+    if (!st) st = ds_up(c, sig, sig_inout, sn);
+    if (st) return st;
+    HIP_TRY(c, hipMemcpyAsync(perm, perm_host, (size_t)m * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemsetAsync(nnz, 0, 8, s));
+    launch_rowspace_finish(s, m, ncols, r, W, perm, sigma, sig, droptol, out, nnz);
+    unsigned long long hn = 0;
+    HIP_TRY(c, hipMemcpyAsync(&hn, nnz, 8, hipMemcpyDeviceToHost, s));
+    st = ds_down(c, W_inout, W, wn);
+    if (!st && !in_place) st = ds_down(c, out_inout, out, wn);
+    if (!st) st = ds_down(c, sig_inout, sig, sn);
+    if (!st) st = ds_finish(c);
+    if (st) return st;
+    *nnz_out = (int64_t)hn;
+    return SDPSR_OK;
+}
+
 extern "C" int sdpsr_profile_kernel(sdpsr_ctx* c, int kind, int64_t n, int64_t aux, int reps,
                                     double* ms_per_launch) {
     CHECK_CTX(c);
