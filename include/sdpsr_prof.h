@@ -104,6 +104,18 @@ int sdpsr_profile_verify_pair_w(sdpsr_ctx* ctx, int64_t n, int64_t d, int width,
                                 const double* a_host, const double* b_host, uint32_t* out);
 int sdpsr_profile_proj_coef_lower(sdpsr_ctx* ctx, int64_t n, int64_t r, uint64_t key, int width, const uint32_t* Lp_host, const double* U_host,
                                   double* partial_out, double* coef_out);
+/* The full-matrix channel gathers of the square step on caller-made labels (tests/test_gpu_primitives.py).  kind 0: launch_gather_i8
+   (T = 1 .. 8 int8 channels; dmax as the loop passes it: 0 = unknown, 1 .. 2048 = the LDS table of class bits, beyond = hashed per entry),
+   kind 1: launch_gather_f32 (T float channels in [-vmax, vmax]), kind 2: launch_gather_f64_padded (T = 1).  L_host: any n x n labels
+   (with dmax > 0: none above it); X_inout: T * ld * ld + guard elements of the kind's type, ld = n rounded up to 128, uploaded as they are
+   and downloaded after the kernel.  out[0] = the kernel's work items, out[1] = the threads of its launch. */
+int sdpsr_profile_gather_full(sdpsr_ctx* ctx, int kind, int64_t n, int T, int vmax, int64_t dmax, uint64_t key, const uint32_t* L_host,
+                              void* X_inout, int64_t guard, uint64_t* out);
+/* The dot products <U_k, x> of the projection, x drawn from the labels and key, in 2048 workgroups as the library launches them.  form 0:
+   launch_proj_coef, coef_out[0 .. r); form 1: launch_proj_coef_probe (len == n * n), coef_out[0 .. 2r): the dot products, then the symmetry
+   probes <U_k, W - W'>.  U_host: r * len, 1 <= r <= 4. */
+int sdpsr_profile_proj_coef(sdpsr_ctx* ctx, int form, int64_t len, int64_t n, int64_t r, uint64_t key, const uint32_t* L_host,
+                            const double* U_host, double* coef_out);
 /* One refinement over a COMPUTED signature source on caller-made inputs (tests/test_gpu_refine_sources.py): the source is put together as the
    loop does it and handed to the product's own refine_signatures, which refines through it in the form the ctx's flags and refine_path
    choose (insert kernel of the source's functor, materialised array, sort, bucket, the mid kernel).  Conventions of the module-kernel entries

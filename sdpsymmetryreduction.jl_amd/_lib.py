@@ -270,6 +270,11 @@ def load_prof_library():
     lib.sdpsr_profile_square_check.argtypes = [vp, i64, i64, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, i64]
     lib.sdpsr_profile_proj_coef_lower.restype = C.c_int
     lib.sdpsr_profile_proj_coef_lower.argtypes = [vp, i64, i64, C.c_uint64, C.c_int, vp, vp, vp, vp]
+    # the full-matrix channel gathers and the projection's dot products on labels, on caller-made inputs (tests)
+    lib.sdpsr_profile_gather_full.restype = C.c_int
+    lib.sdpsr_profile_gather_full.argtypes = [vp, C.c_int, i64, C.c_int, C.c_int, i64, C.c_uint64, vp, vp, i64, C.POINTER(C.c_uint64)]
+    lib.sdpsr_profile_proj_coef.restype = C.c_int
+    lib.sdpsr_profile_proj_coef.argtypes = [vp, C.c_int, i64, i64, i64, C.c_uint64, vp, vp, vp]
     # one refinement over a computed signature source on caller-made inputs (tests)
     lib.sdpsr_profile_refine_source.restype = C.c_int
     lib.sdpsr_profile_refine_source.argtypes = [vp, C.c_int, C.c_int, i64, i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_double,

@@ -272,18 +272,20 @@ __global__ void gather_f32_kernel(int64_t n, int64_t ld, int T, int vmax,
         const int64_t j = c / chunks_per_col;
         const int64_t i0 = (c - j * chunks_per_col) * 4;
         uint64_t bits[4];
+        bool nz[4];  // "non-zero class", kept apart from the 64 bits: channel t draws from byte t of ALL of them, t = 7 included
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int64_t i = i0 + q;
             uint32_t l = (i < n && j < n) ? L[i + j * n] : 0u;
-            bits[q] = l ? (sdpsr_class_bits(key, l) | (1ull << 63)) : 0ull;  // bit 63: nonzero class
+            nz[q] = l != 0u;
+            bits[q] = l ? sdpsr_class_bits(key, l) : 0ull;
         }
         for (int t = 0; t < T; ++t) {
             float4 v;
-            v.x = bits[0] ? (float)sdpsr_class_small(bits[0], t, vmax) : 0.f;
-            v.y = bits[1] ? (float)sdpsr_class_small(bits[1], t, vmax) : 0.f;
-            v.z = bits[2] ? (float)sdpsr_class_small(bits[2], t, vmax) : 0.f;
-            v.w = bits[3] ? (float)sdpsr_class_small(bits[3], t, vmax) : 0.f;
+            v.x = nz[0] ? (float)sdpsr_class_small(bits[0], t, vmax) : 0.f;
+            v.y = nz[1] ? (float)sdpsr_class_small(bits[1], t, vmax) : 0.f;
+            v.z = nz[2] ? (float)sdpsr_class_small(bits[2], t, vmax) : 0.f;
+            v.w = nz[3] ? (float)sdpsr_class_small(bits[3], t, vmax) : 0.f;
             *reinterpret_cast<float4*>(X + (int64_t)t * ld * ld + i0 + j * ld) = v;
         }
     }

@@ -15,6 +15,7 @@
 #include <rocsolver/rocsolver.h>
 
 #include "../host_internal.h"
+#include "../kernel_util.h"
 #include "../../../include/sdpsr_prof.h"
 
 using namespace sdpsr;
@@ -475,6 +476,68 @@ extern "C" int sdpsr_profile_proj_coef_lower(sdpsr_ctx* c, int64_t n, int64_t r,
     launch_proj_coef_lower(s, n, r, Ud, Lp, 1, key, partial, nblk, coef, Lp8);
     HIP_TRY(c, hipMemcpyAsync(partial_out, partial, (size_t)r * nblk * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipMemcpyAsync(coef_out, coef, (size_t)r * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, hipGetLastError());
+    return SDPSR_OK;
+}
+
+// The full-matrix channel gathers of the square step on caller-made labels (tests/test_gpu_primitives.py).  kind 0 / 1 / 2: launch_gather_i8
+// / launch_gather_f32 / launch_gather_f64_padded (one channel).  L_host: ANY n x n labels; X_inout: T * ld * ld + guard elements of the kind's
+// type (ld = n rounded up to 128), uploaded as they are (the test's fill) and downloaded after the kernel.  out[0] = the kernel's work items
+// (one per 16 / 4 / 2 rows of a column), out[1] = the threads of its launch.
+extern "C" int sdpsr_profile_gather_full(sdpsr_ctx* c, int kind, int64_t n, int T, int vmax, int64_t dmax, uint64_t key, const uint32_t* L_host,
+                                         void* X_inout, int64_t guard, uint64_t* out) {
+    CHECK_CTX(c);
+    if (!L_host || !X_inout || !out || kind < 0 || kind > 2 || n < 1 || n > 8192 || T < 1 || T > 8 || (kind == 2 && T != 1) || dmax < 0 ||
+        guard < 0 || guard > (int64_t(1) << 20) || (kind == 1 && (vmax < 1 || vmax > 127)))
+        return ctx_fail(c, SDPSR_BAD_ARGUMENT, "bad arguments");
+    if (dmax > 0)  // (the int8 form indexes its LDS table with the labels)
+        for (int64_t e = 0; e < n * n; ++e)
+            if ((int64_t)L_host[e] > dmax) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "a label above dmax");
+    hipStream_t s = c->stream;
+    const int64_t ld = round_up(n, 128);
+    const int elem = kind == 0 ? 1 : (kind == 1 ? 4 : 8), per_thread = kind == 0 ? 16 : (kind == 1 ? 4 : 2);
+    const size_t xb = ((size_t)T * ld * ld + (size_t)guard) * elem;
+    uint32_t* L = (uint32_t*)ctx_buf(c, "prof_lfull", (size_t)n * n * 4);
+    void* X = ctx_buf(c, "prof_gx", xb);
+    if (!L || !X) return SDPSR_OUT_OF_MEMORY;
+    HIP_TRY(c, hipMemcpyAsync(L, L_host, (size_t)n * n * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(X, X_inout, xb, hipMemcpyHostToDevice, s));
+    if (kind == 0) launch_gather_i8(s, n, ld, T, L, key, (int8_t*)X, dmax);
+    else if (kind == 1) launch_gather_f32(s, n, ld, T, vmax, L, key, (float*)X);
+    else launch_gather_f64_padded(s, n, ld, L, key, (double*)X);
+    HIP_TRY(c, hipMemcpyAsync(X_inout, X, xb, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, hipGetLastError());
+    const int64_t work = ld / per_thread * ld;
+    out[0] = (uint64_t)work;
+    out[1] = (uint64_t)grid_for(work, 256) * 256u;
+    return SDPSR_OK;
+}
+
+// The dot products of the projection on labels (tests/test_gpu_primitives.py): form 0 = launch_proj_coef with x drawn from L_host and key,
+// coef_out[0 .. r); form 1 = launch_proj_coef_probe (len == n * n), coef_out[0 .. 2r): the dot products, then the symmetry probes.
+// U_host: r * len, 1 <= r <= 4; 2048 workgroups as in primitives.cpp and loop.cpp.
+extern "C" int sdpsr_profile_proj_coef(sdpsr_ctx* c, int form, int64_t len, int64_t n, int64_t r, uint64_t key, const uint32_t* L_host,
+                                       const double* U_host, double* coef_out) {
+    CHECK_CTX(c);
+    if (!L_host || !U_host || !coef_out || (form != 0 && form != 1) || len < 1 || len > (int64_t(1) << 26) || r < 1 || r > 4 ||
+        (form == 1 && (n < 1 || n > 8192 || n * n != len)))
+        return ctx_fail(c, SDPSR_BAD_ARGUMENT, "bad arguments");
+    constexpr int nblk = 2048;
+    hipStream_t s = c->stream;
+    const int64_t rows = form == 1 ? 2 * r : r;
+    uint32_t* L = (uint32_t*)ctx_buf(c, "prof_lfull", (size_t)len * 4);
+    double* Ud = (double*)ctx_buf(c, "prof_vu", (size_t)r * len * 8);
+    double* partial = (double*)ctx_buf(c, "prof_partial", (size_t)(rows * nblk + rows) * 8);
+    if (!L || !Ud || !partial) return SDPSR_OUT_OF_MEMORY;
+    double* coef = partial + rows * nblk;
+    HIP_TRY(c, hipMemcpyAsync(L, L_host, (size_t)len * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(Ud, U_host, (size_t)r * len * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemsetAsync(partial, 0xFF, (size_t)(rows * nblk + rows) * 8, s));
+    if (form == 0) launch_proj_coef(s, len, r, Ud, L, key, nullptr, partial, nblk, coef);
+    else launch_proj_coef_probe(s, len, n, r, Ud, L, key, partial, nblk, coef);
+    HIP_TRY(c, hipMemcpyAsync(coef_out, coef, (size_t)rows * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
     HIP_TRY(c, hipGetLastError());
     return SDPSR_OK;

@@ -9,6 +9,7 @@ import pytest
 import scipy.sparse as sp
 
 from conftest import ROOT
+from csr_setup_helpers import _compare_with_host_setup
 
 pytestmark = pytest.mark.gpu
 
@@ -40,45 +41,6 @@ def _setup_ctypes(pkg, ctx, n, m, rowptr, colind, val, base, b, c, mem_out=0):
     st = ctx._lib.sdpsr_admissible_setup_csr(ctx._h, n, m, p(rowptr), p(colind), p(val), base, p(b), p(c), ATOL, p(CL), p(X0), p(U),
                                              C.byref(r), C.byref(hint), C.byref(info), mem_out)
     return st, CL, X0, U[:, :max(r.value, 0)], hint.value, info.value
-
-
-def _host_partition(v):
-    """Canonical labels of equal values, first occurrence in column-major order, 0.0 -> 0 (src/partitions.jl:24-35)."""
-    v = np.asarray(v).reshape(-1)
-    _, first, inv = np.unique(v, return_index=True, return_inverse=True)
-    rank = np.empty(first.size, dtype=np.int64)
-    nz = v[first] != 0
-    order = np.argsort(first[nz], kind="stable")
-    ids = np.flatnonzero(nz)[order]
-    rank[:] = 0
-    rank[ids] = np.arange(1, ids.size + 1)
-    return rank[inv]
-
-
-def _within_one_rounding_unit(a, b):
-    big = np.maximum(np.abs(a), np.abs(b))
-    _, e = np.frexp(big)
-    return np.all(np.abs(a - b) <= np.ldexp(1.0000001e-7, e))
-
-
-def _compare_with_host_setup(pkg, Sd, Sh, seed=0):
-    n, CLd, X0d, Ud = Sd
-    _, CLh, X0h, Uh = Sh
-    Ud = Ud.cpu().numpy() if hasattr(Ud, "cpu") else Ud
-    CLd = CLd.cpu().numpy() if hasattr(CLd, "cpu") else CLd
-    X0d = X0d.cpu().numpy() if hasattr(X0d, "cpu") else X0d
-    assert Ud.shape[1] == Uh.shape[1]
-    r = Ud.shape[1]
-    if r:
-        assert np.abs(Ud.T @ Ud - np.eye(r)).max() <= 1e-13
-        rng = np.random.default_rng(seed)
-        for _ in range(3):
-            x = rng.standard_normal(n * n)
-            pd, ph = Ud @ (Ud.T @ x), Uh @ (Uh.T @ x)
-            assert np.linalg.norm(pd - ph) <= 1e-12 * np.linalg.norm(x)
-    assert np.array_equal(_host_partition(CLd), _host_partition(CLh))
-    assert np.array_equal(_host_partition(X0d), _host_partition(X0h))
-    assert _within_one_rounding_unit(CLd, CLh) and _within_one_rounding_unit(X0d, X0h)
 
 
 # ------------------------------------------------------------------ results
