@@ -898,7 +898,8 @@ int sdpsr_comm_destroy(sdpsr_comm* comm);
    sum(blkD.blks[i] .* x[i] for i = 1:dim(P)), docs/src/examples/ErdosRenyiThetaFunction.jl:83, QuadraticAssignmentProblems.jl:136,
    test/sd_problems.jl:46-52,127-134.  These entries evaluate it, its adjoint  g_i = sum_k <blks[i][k], S_k>  and the spectra of
    all blocks on the device, from the triplets sdpsr_block_images_sparse writes: what one iteration of a first-order method over
-   the reduced SDP needs, and the certificate (lambda_min of every block) of a solved one.  No SDP is solved here.
+   the reduced SDP needs, and the certificate (lambda_min of every block) of a solved one.  No SDP is solved here
+   (sdpsr_sdp_solve, below, is the solver built on these entries).
 
    sdpsr_blockop: a device-resident handle, read-only after creation; any ctx of its device may use it; the caller destroys it
    (before the device is reset; a ctx is not needed for that).
@@ -956,6 +957,74 @@ int sdpsr_blockop_adjoint(sdpsr_ctx* ctx, const sdpsr_blockop* op, const double*
    power-of-two multiple and its values are multiplied back.  A block that reaches the Jacobi sweep limit (40): SDPSR_NOT_CONVERGED,
    every output written as it stands.  nblocks < 1, some s_k < 1, sum s_k^2 >= 2^32, NULL Z or w: SDPSR_BAD_ARGUMENT. */
 int sdpsr_blocks_syev(sdpsr_ctx* ctx, int32_t nblocks, const int32_t* blk_sizes, const double* Z, double* w, double* V, int mem);
+
+/* ---- Solving the reduced SDP: PSD projection and a first-order (ADMM) driver ---------------------------------
+   The last step of the reference's work flow, reduceAndSolve (docs/src/examples/ReduceAndSolveJuMP.jl:40-91; the models of
+   test/sd_problems.jl:29-55,107-137; the pinned optima of test/lovasz.jl:16,32,48 and test/qap.jl:31):
+       max / min  c'x   s.t.   A x = b,   x >= 0,   Z_k(x) = sum_i x_i blks[i][k] in PSDCone() for all k.
+   The reference hands this model to CSDP (an interior-point method) through JuMP.  The library solves it on the device with a
+   first-order method over the operator handle above.  It is NOT an interior-point replacement: the theta' pins of the
+   reference are reached to their printed 8 digits, a degenerate instance (esc16j) to about 1e-4 relative in 20 000 iterations
+   (DESIGN.md "Deviations", README "Solving the reduced SDP").
+
+   sdpsr_psd_project: P_k = V max(w, 0) V' for every block, the projection onto the PSD cone in the Frobenius norm.  Z and P: the
+   one-class layout sdpsr_blockop_apply writes (sum s_k^2 elements, in `mem`); only the lower triangle of a block is referenced,
+   as in sdpsr_blocks_syev; P is written as a full matrix that is symmetric bit for bit (one triangle is computed and mirrored)
+   and may alias Z.  lambda_min: NULL, or nblocks values: the smallest eigenvalue of each block.  A block of order 1 is a clamp;
+   a block without a positive eigenvalue (an all-zero or negative semidefinite one) gives +0.0 everywhere.  ONE launch for all
+   blocks, one workgroup per block on the Jacobi solver of sdpsr_blocks_syev (one wave per block while every order is <= 16);
+   the sum runs over the eigenvalues w > 0, or over those < 0 subtracted from Z when these are fewer.  Range: the rule of
+   sdpsr_syev_f64 -- a block whose max |a| lies outside [2^-400, 2^400] is projected as an exact power-of-two multiple and
+   multiplied back: the result scales exactly.  A NaN or Inf in a block's lower triangle: that block's outputs are NaN, the
+   others are intact, SDPSR_SOLVER_ERROR.  The Jacobi sweep limit (40): SDPSR_NOT_CONVERGED, outputs written as they stand.
+   An order above 64: SDPSR_BAD_ARGUMENT with a message that says so (not supported by this version); also nblocks < 1, some
+   s_k < 1, sum s_k^2 >= 2^32, NULL Z or P.  One host wait.  Equal inputs give equal bytes, on any ctx.
+
+   sdpsr_sdp_solve.  B: R^d -> (+)_k Sym(s'_k) is sdpsr_blockop_apply, B' sdpsr_blockop_adjoint (both on full entries, so
+   <Bx, S> = x'B'S as stored).  A: r x d, column-major, with INDEPENDENT rows (the output of sdpsr_compress_constraints), b: r,
+   c: d, all in `mem`.  Split x = u (u >= 0) and Bx = S (S PSD) with scaled duals lam, Lam; chat = -+c / |c|_2 (minus for max);
+       M = I + B'B (d x d),   G = A M^-1 A',   Kt = M^-1 - M^-1 A' G^-1 A M^-1,   x0 = M^-1 A' G^-1 b
+   are built once and do not depend on rho.  One iteration:
+       g    = (u - lam) + B'(S - Lam) - chat / rho
+       x    = Kt g + x0                                   (A x = b up to the rounding of one d-length sum)
+       u+   = max(0, x + lam)            S+   = proj_PSD(Bx + Lam)      (sdpsr_psd_project's kernel, fused with the next line)
+       lam+ = (x + lam) - u+             Lam+ = (Bx + Lam) - S+
+       r_p^2 = |x - u+|^2 + |Bx - S+|^2,   r_d^2 = rho^2 (|u+ - u|^2 + |S+ - S|^2)
+   from u = lam = 0, S = Lam = 0.  Every check_every iterations (and at the last one) the host reads r_p^2, r_d^2 and a
+   non-finite flag from pinned memory and stops when r_p <= eps and r_d <= eps.  adapt_rho (residual balancing, at a check that
+   does not stop): r_p > 10 r_d doubles rho, r_d > 10 r_p halves it, lam and Lam are multiplied by rho_old / rho_new; Kt and x0
+   stay.  It is an option, not the default: on ER(7) it changed rho 105 times and was slower than rho = 1.
+     opts   NULL or a zeroed struct: rho = 1, eps = 1e-9, max_iters = 20000, check_every = 50, no adaptation, sense = +1 (max),
+            x >= 0 enforced.  A zero field selects its default; nonneg = -1 drops x >= 0 (u+ = x + lam); reserved stays 0;
+     x      d values: the last iterate of the affine step;   S: NULL or sum s'_k^2 values, the PSD split variable;
+     Y      NULL or sum s'_k^2 values: rho Lam, the multiplier of Bx = S;
+     info   NULL or the report, computed on the host from the returned x itself: objective = c'x (the unscaled c), eq_residual =
+            |A x - b|_inf, min_x, lambda_min = min_k lambda_min(Z_k(x)) through the projection kernel; r_primal, r_dual and rho
+            as of the last check, iters, rho_changes.
+   Setup (not the hot path): M by a Gram kernel over the handle's entries sorted by (class, position) -- entries sharing a
+   position contribute val_i val_j to M_ij, positions ascending, one thread per element, no floating-point atomics; M^-1 through
+   sdpsr_syev_f64; G goes to the host (Cholesky).  The loop is six kernels and two fills per iteration and makes no host wait
+   between two checks: host waits of a call = ceil(iters / check_every) + a constant that depends on the setup path (d, r, mem),
+   not on the iteration count -- 5 for host arrays with d <= 64 and r > 0 (tests/test_gpu_sdp_solve.py holds the count).
+   Every sum has an order fixed by the inputs alone: equal inputs give equal bytes, on any ctx.
+   SDPSR_BAD_ARGUMENT, nothing written: d < 1 or d > 4096 (Kt is 134 MB at the cap; checked before any allocation); a virtual
+   block order above 64; r outside [0, min(d, 1024)]; a non-finite value in A, b or c; bad options; G numerically singular
+   ("rows of A are dependent: compress_constraints first").  r = 0 is legal.  The iteration limit: SDPSR_NOT_CONVERGED with every
+   output and the report written as they stand.  A non-finite value met on the way (a NaN in the operator): SDPSR_SOLVER_ERROR.
+   The ctx and the handle stay usable after every refusal.  The complex route needs nothing of its own (real embedding). */
+int sdpsr_psd_project(sdpsr_ctx* ctx, int32_t nblocks, const int32_t* blk_sizes, const double* Z, double* P, double* lambda_min,
+                      int mem);
+typedef struct {
+    double rho, eps;
+    int32_t max_iters, check_every, adapt_rho, sense /* +1 max, -1 min */, nonneg /* 0, 1: x >= 0; -1: free */;
+    int32_t reserved[5];
+} sdpsr_sdp_opts;
+typedef struct {
+    double objective, r_primal, r_dual, rho, eq_residual, min_x, lambda_min;
+    int32_t iters, rho_changes;
+} sdpsr_sdp_info;
+int sdpsr_sdp_solve(sdpsr_ctx* ctx, const sdpsr_blockop* op, int64_t r, const double* A, const double* b, const double* c,
+                    const sdpsr_sdp_opts* opts, double* x, double* S, double* Y, sdpsr_sdp_info* info, int mem);
 
 #ifdef __cplusplus
 }

@@ -14,6 +14,6 @@ from .api import (BlockDiagonalization, Context, DimensionMismatch, InvalidDecom
                   diagonalize, dim, eigen_decomposition, jordan_reduce_batch, Problem, eigen_decomposition_batched, fill, labels_convert, partition_checksum, randomize, reduce_constraints,
                   reduce_constraints_csr, SparseConstraints, compress_constraints, reduced_sdp,
                   refine, relabel_keys, SparseBlocks, basis_image_sparse, block_images_sparse,
-                  BlockOperator, block_eigvals, block_spectrum_check)
+                  BlockOperator, block_eigvals, block_spectrum_check, psd_project, reduce_and_solve, SolveResult)
 from . import agree  # noqa: F401
 from .agree import Comm, agree_block_diagonalization, agree_partitions, meet_keys  # noqa: F401

@@ -87,6 +87,35 @@ class Opts(C.Structure):
     ]
 
 
+class SdpOpts(C.Structure):
+    """sdpsr_sdp_opts: a zero field selects its default (rho 1, eps 1e-9, max_iters 20000, check_every 50, max, x >= 0)."""
+    _fields_ = [
+        ("rho", C.c_double),
+        ("eps", C.c_double),
+        ("max_iters", C.c_int32),
+        ("check_every", C.c_int32),
+        ("adapt_rho", C.c_int32),
+        ("sense", C.c_int32),
+        ("nonneg", C.c_int32),
+        ("reserved", C.c_int32 * 5),
+    ]
+
+
+class SdpInfo(C.Structure):
+    """sdpsr_sdp_info: the report of sdpsr_sdp_solve, computed from the returned x."""
+    _fields_ = [
+        ("objective", C.c_double),
+        ("r_primal", C.c_double),
+        ("r_dual", C.c_double),
+        ("rho", C.c_double),
+        ("eq_residual", C.c_double),
+        ("min_x", C.c_double),
+        ("lambda_min", C.c_double),
+        ("iters", C.c_int32),
+        ("rho_changes", C.c_int32),
+    ]
+
+
 def declared_symbols(header_path=HEADER_PATH):
     """Every function the header declares (used by the symbol-export test)."""
     txt = open(header_path).read()
@@ -200,6 +229,8 @@ def load_library():
         "sdpsr_blockop_apply": (C.c_int, [vp, vp, vp, vp, C.c_int]),
         "sdpsr_blockop_adjoint": (C.c_int, [vp, vp, vp, vp, C.c_int]),
         "sdpsr_blocks_syev": (C.c_int, [vp, i32, vp, vp, vp, vp, C.c_int]),
+        "sdpsr_psd_project": (C.c_int, [vp, i32, vp, vp, vp, vp, C.c_int]),
+        "sdpsr_sdp_solve": (C.c_int, [vp, vp, i64, vp, vp, vp, C.POINTER(SdpOpts), vp, vp, vp, C.POINTER(SdpInfo), C.c_int]),
     }
     missing = [s for s in declared_symbols() if not hasattr(lib, s)]
     if missing:

@@ -1782,6 +1782,130 @@ class BlockOperator:
         return self._map(self.ctx._lib.sdpsr_blockop_adjoint, S, self.sum_sq, self.d, ctx)
 
 
+    def solve(self, newA, newB, newC, sense="max", rho=1.0, eps=1e-9, max_iters=20000, check_every=50, adapt_rho=False,
+              nonneg=True, return_S=False, return_Y=False, raise_on_limit=False, ctx=None):
+        """The reduced SDP ``max / min newC x  s.t.  newA x = newB, x >= 0, Z_k(x) PSD`` over this operator by the
+        library's first-order solver (``sdpsr_sdp_solve``; the model of docs/src/examples/ReduceAndSolveJuMP.jl:40-84).
+        ``newA``: r x d with independent rows (``reduced_sdp`` / ``compress_constraints``; r = 0 or ``None`` is legal),
+        ``newB``: r, ``newC``: d -- NumPy arrays or torch tensors (read on the host).  Returns a ``SolveResult``: ``x``,
+        ``objective``, ``status`` (``"converged"`` or ``"iteration_limit"``), the fields of ``sdpsr_sdp_info``, and on
+        request ``S`` (the PSD split variable, a list of blocks) and ``Y = rho * Lambda`` (its multiplier).  Dependent rows,
+        non-finite inputs, d > 4096 or a block of order > 64: ``ValueError``.  ``raise_on_limit``: ``NotConverged`` instead
+        of the ``"iteration_limit"`` status.  This is ADMM, not an interior-point method: see the README for what accuracy
+        to expect."""
+        ctx = self.ctx if ctx is None else ctx
+        if self._h is None:
+            raise ValueError("BlockOperator: the handle is closed")
+        if sense not in ("max", "min"):
+            raise ValueError("sense is 'max' or 'min'")
+
+        def host(a):
+            return np.asarray(a.detach().cpu().numpy() if _is_torch(a) else _dense(a), dtype=np.float64)
+
+        c = np.ascontiguousarray(host(newC).reshape(-1))
+        if c.size != self.d:
+            raise ValueError(f"newC has {c.size} entries, the operator {self.d} classes")
+        if newA is None:
+            A, b = np.zeros((0, self.d), order="F"), np.zeros(0)
+        else:
+            A = np.asfortranarray(host(newA).reshape(-1, self.d))
+            b = np.ascontiguousarray(host(newB).reshape(-1))
+        r = A.shape[0]
+        if b.size != r:
+            raise ValueError(f"newB has {b.size} entries, newA {r} rows")
+        o = L.SdpOpts(float(rho), float(eps), int(max_iters), int(check_every), 1 if adapt_rho else 0, 1 if sense == "max" else -1,
+                      1 if nonneg else -1)
+        info = L.SdpInfo()
+        x = np.zeros(self.d)
+        S = np.zeros(self.sum_sq) if return_S else None
+        Y = np.zeros(self.sum_sq) if return_Y else None
+        lib = ctx._lib
+        st = lib.sdpsr_sdp_solve(ctx._h, self._h, r, _ptr(A) if r else None, _ptr(b) if r else None, _ptr(c), C.byref(o), _ptr(x),
+                                 _ptr(S), _ptr(Y), C.byref(info), L.MEM_HOST)
+        if st == 5:  # SDPSR_BAD_ARGUMENT
+            raise ValueError(lib.sdpsr_last_error(ctx._h).decode())
+        if st == 9 and not raise_on_limit:  # SDPSR_NOT_CONVERGED: every output is written as it stands
+            st = 0
+            status = "iteration_limit"
+        else:
+            status = "converged"
+        ctx.check(st)
+        return SolveResult(x, float(info.objective), status, int(info.iters), float(info.r_primal), float(info.r_dual), float(info.rho),
+                           int(info.rho_changes), float(info.eq_residual), float(info.min_x), float(info.lambda_min),
+                           _split_blocks(S, self.sizes) if return_S else None, _split_blocks(Y, self.sizes) if return_Y else None)
+
+
+SolveResult = namedtuple("SolveResult", ["x", "objective", "status", "iters", "r_primal", "r_dual", "rho", "rho_changes", "eq_residual",
+                                         "min_x", "lambda_min", "S", "Y"])
+
+
+def psd_project(Z, sizes, return_lambda_min=False, ctx=None):
+    """The projection of every block onto the PSD cone, ``P_k = V max(w, 0) V'`` (``sdpsr_psd_project``): ``Z`` as
+    ``BlockOperator.apply`` returns it (a list of blocks or the flat array; NumPy, or torch on the device; only the lower
+    triangles are read).  Returns the blocks in the form they came in (list or flat), exactly symmetric; with
+    ``return_lambda_min=True`` the pair ``(P, lambda_min)`` with the smallest eigenvalue of each block.  Orders above 64:
+    ``ValueError``."""
+    ctx = _ctx(ctx)
+    sizes = [int(s) for s in sizes]
+    if not sizes or any(s < 1 for s in sizes):
+        raise ValueError(f"psd_project: block sizes must be >= 1, got {sizes}")
+    was_flat = _is_torch(Z) or (isinstance(Z, np.ndarray) and Z.ndim == 1)
+    flat = _flat_blocks(Z, sizes, "psd_project")
+    sz = np.asarray(sizes, dtype=np.int32)
+    if _is_torch(flat):
+        import torch
+        if not flat.is_cuda:
+            raise TypeError("psd_project takes a torch tensor on the device (or NumPy arrays)")
+        P = torch.empty_like(flat)
+        lm = torch.empty(len(sizes), dtype=torch.float64, device=flat.device) if return_lambda_min else None
+        ctx.wait_for(flat, P)
+        mem = L.MEM_DEVICE
+    else:
+        P = np.empty_like(flat)
+        lm = np.empty(len(sizes), dtype=np.float64) if return_lambda_min else None
+        mem = L.MEM_HOST
+    st = ctx._lib.sdpsr_psd_project(ctx._h, len(sizes), _ptr(sz), _ptr(flat), _ptr(P), _ptr(lm), mem)
+    if st == 5:  # SDPSR_BAD_ARGUMENT
+        raise ValueError(ctx._lib.sdpsr_last_error(ctx._h).decode())
+    ctx.check(st)
+    out = P if was_flat else _split_blocks(P, sizes)
+    return (out, lm) if return_lambda_min else out
+
+
+ReduceAndSolveResult = namedtuple("ReduceAndSolveResult", ["jTime", "blkTime", "solveTime", "optVal", "blkSize", "originalSize", "newSize",
+                                                           "solution"])
+
+
+def reduce_and_solve(C_, A, b, sense="max", complex=False, limit_size=3000, ctx=None, verbose=False, retries=2, **solver):
+    """``reduceAndSolve(C, A, b; objSense, verbose, complex, limitSize)`` of docs/src/examples/ReduceAndSolveJuMP.jl:10-113
+    with the library's own solver in CSDP's place: ``admissible_subspace`` -> ``blockDiagonalize`` -> ``reduced_sdp`` ->
+    ``basis_image_sparse`` -> ``BlockOperator`` -> ``solve``.  Returns the reference's named tuple -- ``jTime``,
+    ``blkTime``, ``solveTime`` (seconds), ``optVal``, ``blkSize``, ``originalSize``, ``newSize`` -- plus ``solution``, the
+    ``SolveResult``; above ``limit_size`` the zero-filled tuple the reference returns; ``None`` when ``blockDiagonalize``
+    fails (``retries`` fresh generic elements first).  ``solver``: keyword arguments of ``BlockOperator.solve``."""
+    import time
+    ctx = _ctx(ctx)
+    t0 = time.perf_counter()
+    P = admissible_subspace(C_, A, b, ctx=ctx, verbose=verbose)
+    j_time = time.perf_counter() - t0
+    n = int(P.shape[0])
+    if dim(P) > limit_size:
+        return ReduceAndSolveResult(j_time, 0, 0, 0, 0, n, dim(P), None)
+    t0 = time.perf_counter()
+    try:
+        bd = blockDiagonalize(P, verbose, complex=complex, ctx=ctx, retries=retries)
+    except (NumericalInconsistency, DimensionMismatch, InvalidDecompositionField):
+        return None  # either random / rounding error, or complex numbers needed
+    blk_time = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    newA, newB, newC = reduced_sdp(P, A, b, C_, ctx=ctx)
+    sp = basis_image_sparse(bd.Q_hat, P, ctx=ctx)
+    with BlockOperator(sp, ctx=ctx) as op:
+        sol = op.solve(newA, newB, newC, sense=sense, **solver)
+    solve_time = time.perf_counter() - t0
+    return ReduceAndSolveResult(j_time, blk_time, solve_time, sol.objective, list(bd.blkSizes), n, dim(P), sol)
+
+
 def block_eigvals(Z, sizes, vectors=False, ctx=None):
     """The spectra of all blocks in one call (``sdpsr_blocks_syev``): ``Z`` as ``BlockOperator.apply`` returns it (list or
     flat; only the lower triangles are read).  Returns the list of ascending ``w_k``; with ``vectors=True`` the pair

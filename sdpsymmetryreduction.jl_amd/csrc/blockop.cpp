@@ -9,6 +9,19 @@
 
 using namespace sdpsr;
 
+namespace sdpsr {
+
+// out[0 .. nout) = the keyed sums of one arrangement of the handle's records with dv: stream-ordered, no host wait
+int blockop_map_enqueue(sdpsr_ctx* c, const sdpsr_blockop* op, bool adjoint, const double* dv, void* carry, double* dout) {
+    const int64_t nv = adjoint ? op->sum_sq : op->d, nout = adjoint ? op->d : op->sum_sq;
+    if (nout == 0) return SDPSR_OK;
+    HIP_TRY(c, hipMemsetAsync(dout, 0, (size_t)nout * 8, c->stream));  // a key without an entry: +0.0
+    launch_blockop_keyed_sums(c->stream, op->nnz_full, adjoint ? op->by_class : op->by_pos, dv, nv, carry, dout);
+    return SDPSR_OK;
+}
+
+}  // namespace sdpsr
+
 namespace {
 
 // the block table: virtual orders, the prefix of their squares; false with a message left in the ctx
@@ -120,8 +133,8 @@ int check_op(sdpsr_ctx* c, const sdpsr_blockop* op, const char* who) {
     return SDPSR_OK;
 }
 
-// out[0 .. nout) = keyed sums of rec with v[0 .. nv); every element of out is written
-int keyed_map(sdpsr_ctx* c, const sdpsr_blockop* op, const void* rec, const double* v, int64_t nv, double* out, int64_t nout, int mem,
+// the public form of blockop_map_enqueue: v (nv elements) and out (nout) in `mem`; every element of out is written
+int keyed_map(sdpsr_ctx* c, const sdpsr_blockop* op, bool adjoint, const double* v, int64_t nv, double* out, int64_t nout, int mem,
               const char* in_name, const char* out_name) {
     if ((nv > 0 && !v) || (nout > 0 && !out)) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "blockop: a NULL vector");
     if (nout == 0) return SDPSR_OK;
@@ -134,8 +147,8 @@ int keyed_map(sdpsr_ctx* c, const sdpsr_blockop* op, const void* rec, const doub
         (void)ctx_sync_stream(c, s);
         return st ? st : SDPSR_OUT_OF_MEMORY;
     }
-    HIP_TRY(c, hipMemsetAsync(dout, 0, (size_t)nout * 8, s));  // a key without an entry: +0.0
-    launch_blockop_keyed_sums(s, op->nnz_full, rec, dv, nv, carry, dout);
+    st = blockop_map_enqueue(c, op, adjoint, dv, carry, dout);
+    if (st) return st;
     HIP_TRY(c, hipGetLastError());
     return out_finish(c, out, dout, (size_t)nout, mem);
 }
@@ -196,14 +209,14 @@ int sdpsr_blockop_apply(sdpsr_ctx* c, const sdpsr_blockop* op, const double* x, 
     CHECK_CTX(c);
     const int st = check_op(c, op, "blockop_apply");
     if (st) return st;
-    return keyed_map(c, op, op->by_pos, x, op->d, Z, op->sum_sq, mem, "bop_x", "bop_z");
+    return keyed_map(c, op, false, x, op->d, Z, op->sum_sq, mem, "bop_x", "bop_z");
 }
 
 int sdpsr_blockop_adjoint(sdpsr_ctx* c, const sdpsr_blockop* op, const double* S, double* g, int mem) {
     CHECK_CTX(c);
     const int st = check_op(c, op, "blockop_adjoint");
     if (st) return st;
-    return keyed_map(c, op, op->by_class, S, op->sum_sq, g, op->d, mem, "bop_s", "bop_g");
+    return keyed_map(c, op, true, S, op->sum_sq, g, op->d, mem, "bop_s", "bop_g");
 }
 
 int sdpsr_blocks_syev(sdpsr_ctx* c, int32_t nblocks, const int32_t* blk_sizes, const double* Z, double* w, double* V, int mem) {

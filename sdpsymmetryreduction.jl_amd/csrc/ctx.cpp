@@ -252,6 +252,7 @@ int sdpsr_create(int device_id, uint64_t seed, const sdpsr_opts* opts, sdpsr_ctx
     attrs_ok &= small_syev_set_device_attributes();
     attrs_ok &= stedc_set_device_attributes();
     attrs_ok &= batched_set_device_attributes();
+    attrs_ok &= psd_set_device_attributes();
     attrs_ok &= backtransform_set_device_attributes();
     attrs_ok &= complex_set_device_attributes();
     if (hipGetLastError() != hipSuccess || !attrs_ok) {  // a failed LDS opt-in would surface later as an opaque launch error

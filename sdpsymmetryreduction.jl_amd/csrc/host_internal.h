@@ -491,6 +491,10 @@ void launch_blockop_expand(hipStream_t s, int64_t nnz, int64_t d, const int64_t*
 void launch_blockop_gather(hipStream_t s, int64_t n, const uint32_t* sidx, const void* rec, void* out);
 size_t blockop_carry_bytes(int64_t n);
 void launch_blockop_keyed_sums(hipStream_t s, int64_t n, const void* rec, const double* v, int64_t nv, void* carry, double* out);
+// blockop.cpp: the enqueue-only form of sdpsr_blockop_apply (adjoint = false: dv has d elements, dout sum s'_k^2) and
+// sdpsr_blockop_adjoint (true: the other way round) on device arrays; carry: blockop_carry_bytes(op->nnz_full) of device scratch.
+// Stream-ordered, no host wait; the public entries call it between their copies (sdp_solve.cpp: once each per iteration).
+int blockop_map_enqueue(sdpsr_ctx* c, const sdpsr_blockop* op, bool adjoint, const double* dv, void* carry, double* dout);
 // kernels_rowspace.hip / host_gram_jacobi.cpp: the row space of [newA | b] (rowspace.cpp, sdpsr_compress_constraints)
 double rowspace_scale(double max_abs);
 int rowspace_absmax_blocks(int64_t total);

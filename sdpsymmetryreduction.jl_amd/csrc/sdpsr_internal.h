@@ -276,6 +276,12 @@ struct BlocksSyevJob {
     int32_t n, pad;
 };
 
+// one block of sdpsr_psd_project's single launch (kernels_psd.hip): where it starts in Z / P, its order and its index
+struct PsdJob {
+    int64_t zoff;
+    int32_t n, blk;
+};
+
 // Host wait for a stream of ctx c (every wait of the library goes through here).  Inside a batch call the wait polls and
 // hands the thread to the other restarts' fibers.  hipStreamQuery records its "not ready" as the thread's last error, and
 // all fibers share that slot: exactly that value is dropped on every way out (a fiber whose first query succeeds must not
@@ -567,6 +573,7 @@ bool sytrd_set_device_attributes();
 bool small_syev_set_device_attributes();
 bool stedc_set_device_attributes();
 bool batched_set_device_attributes();
+bool psd_set_device_attributes();
 bool backtransform_set_device_attributes();
 bool complex_set_device_attributes();
 // kernels_complex.hip (complex path of blockDiagonalize, n <= 64; planes re / im, ld = n)
@@ -731,6 +738,24 @@ void launch_transpose_to_rowmajor(hipStream_t s, int64_t n, int64_t S1, const do
                                   double* Qrm);
 void launch_blocks_syev64(hipStream_t s, const BlocksSyevJob* jobs, int njac, int n1, int max_n, const double* Z, double* w, double* V,
                           int* flag);
+// kernels_psd.hip: P_k = V max(w, 0) V' of the blocks of order <= 64 in one launch (jobs: the njac of order >= 2, then the n1 of
+// order 1; max_n: the largest order; flag: one zeroed int -- bit 1 sweep limit, bit 2 a NaN / Inf).  Lam == nullptr: the plain
+// form Z -> P, lam_min (one per block) optional.  Otherwise the solver's fused form: Z = Bx, P = S (previous iterate in, new one
+// out), Lam <- (Bx + Lam) - S+, D = S+ - Lam+, slots[2 blk], [2 blk + 1] = the block's |Bx - S+|^2, |S+ - S|^2.
+void launch_psd_project(hipStream_t s, const PsdJob* jobs, int njac, int n1, int max_n, const double* Z, double* P, double* lam_min,
+                        double* Lam, double* D, double* slots, int* flag);
+// kernels_sdp.hip: the setup and the affine step of sdpsr_sdp_solve (sdp_solve.cpp); stream-ordered, no host wait
+void launch_sdp_record_class(hipStream_t s, int64_t n, const void* rec, uint32_t* cls);
+void launch_sdp_gram(hipStream_t s, int64_t d, int64_t n, const void* rec_by_class_pos, int64_t* cptr, double* M);  // cptr: d + 1
+void launch_sdp_scale_columns(hipStream_t s, int64_t d, const double* w, double* V);
+void launch_sdp_gemm(hipStream_t s, int64_t m, int64_t n, int64_t k, const double* A, int64_t ar, int64_t ac, const double* B, int64_t br,
+                     int64_t bc, double alpha, double beta, double* C, int64_t ldc);
+void launch_sdp_affine_step(hipStream_t s, int64_t d, int nonneg, double rho, const double* Kt, const double* x0, const double* adj,
+                            const double* chat, const double* uml_in, double* x, double* u, double* lam, double* uml_out, double* vs);
+void launch_sdp_verdict(hipStream_t s, int64_t d, const double* vs, int64_t nblocks, const double* bs, double* pinned_out);
+void launch_sdp_rescale(hipStream_t s, int64_t d, int64_t n, double f, const double* u, double* lam, double* uml, const double* S, double* Lam,
+                        double* D);
+void launch_sdp_scaled_copy(hipStream_t s, int64_t n, double f, const double* in, double* out);
 // Stable LSD radix sort of the pairs (keys[e], e), e < len < 2^32, by the low `bits` bits of the key (4 bits per pass; the
 // keys must not exceed them).  kA / kB / vA / vB: len words each, hist: radix_sort_hist_words(len).  The sorted keys and
 // indices end in (kB, vB).  No atomics on the way: the order is a function of the keys alone.  (first, cnt): the first pass

@@ -508,6 +508,44 @@ function block_eigen(Z::AbstractVector{<:AbstractMatrix{<:Real}})
     return ws, _split_blocks(V, sizes)
 end
 
+# ---- solving the reduced SDP (sdpsr_psd_project, sdpsr_sdp_solve): the model of docs/src/examples/ReduceAndSolveJuMP.jl:40-84 by the
+# library's first-order (ADMM) solver in CSDP's place -- not an interior-point replacement, see the README ----
+# P_k = V max(w, 0) V' of every block (orders <= 64) and the blocks' smallest eigenvalues
+function psd_project(Z::AbstractVector{<:AbstractMatrix{<:Real}})
+    cx = ctx(); sizes = Int32[size(b, 1) for b in Z]; flat = Float64[]
+    for b in Z
+        append!(flat, vec(Matrix{Float64}(b)))
+    end
+    P = Vector{Float64}(undef, length(flat)); lmin = Vector{Float64}(undef, length(sizes))
+    check(cx, ccall((:sdpsr_psd_project, libsdpsr), Cint, (Ptr{Cvoid}, Int32, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cint),
+                    cx.handle, length(sizes), sizes, flat, P, lmin, MEM_HOST))
+    return _split_blocks(P, sizes), lmin
+end
+struct SdpOpts  # sdpsr_sdp_opts: a zero field selects its default
+    rho::Float64; eps::Float64
+    max_iters::Int32; check_every::Int32; adapt_rho::Int32; sense::Int32; nonneg::Int32
+    reserved::NTuple{5,Int32}
+end
+struct SdpInfo  # sdpsr_sdp_info
+    objective::Float64; r_primal::Float64; r_dual::Float64; rho::Float64; eq_residual::Float64; min_x::Float64; lambda_min::Float64
+    iters::Int32; rho_changes::Int32
+end
+# max / min newC x  s.t.  newA x = newB (independent rows), x >= 0, Z_k(x) PSD.  Returns (x, info, converged); the iteration limit is
+# not an error: every output is written as it stands
+function solve(op::BlockOperator, newA::AbstractMatrix{<:Real}, newB::AbstractVector{<:Real}, newC::AbstractVector{<:Real};
+               sense::Symbol=:max, rho::Real=1.0, eps::Real=1e-9, max_iters::Integer=20000, check_every::Integer=50,
+               adapt_rho::Bool=false, nonneg::Bool=true)
+    cx = ctx(); A = Matrix{Float64}(newA); b = Vector{Float64}(newB); c = Vector{Float64}(vec(newC))
+    opts = Ref(SdpOpts(rho, eps, max_iters, check_every, adapt_rho ? 1 : 0, sense == :max ? 1 : -1, nonneg ? 1 : -1, (0, 0, 0, 0, 0)))
+    info = Ref(SdpInfo(0, 0, 0, 0, 0, 0, 0, 0, 0)); x = Vector{Float64}(undef, op.d)
+    st = ccall((:sdpsr_sdp_solve, libsdpsr), Cint,
+               (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{SdpOpts}, Ptr{Float64}, Ptr{Float64},
+                Ptr{Float64}, Ref{SdpInfo}, Cint),
+               cx.handle, op.handle, size(A, 1), A, b, c, opts, x, C_NULL, C_NULL, info, MEM_HOST)
+    st == 9 || check(cx, st)  # SDPSR_NOT_CONVERGED
+    return x, info[], st == 0
+end
+
 # ---- blockDiagonalize(ComplexF64, P) (compat.jl:26-32,54-57; n <= 3072 in this library version) ---
 function SR.blockDiagonalize(::Type{ComplexF64}, P::HIPPartition, verbose=true;
                              epsilon=Base.rtoldefault(Float64))
