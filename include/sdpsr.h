@@ -977,8 +977,19 @@ int sdpsr_blocks_syev(sdpsr_ctx* ctx, int32_t nblocks, const int32_t* blk_sizes,
    sdpsr_syev_f64 -- a block whose max |a| lies outside [2^-400, 2^400] is projected as an exact power-of-two multiple and
    multiplied back: the result scales exactly.  A NaN or Inf in a block's lower triangle: that block's outputs are NaN, the
    others are intact, SDPSR_SOLVER_ERROR.  The Jacobi sweep limit (40): SDPSR_NOT_CONVERGED, outputs written as they stand.
-   An order above 64: SDPSR_BAD_ARGUMENT with a message that says so (not supported by this version); also nblocks < 1, some
-   s_k < 1, sum s_k^2 >= 2^32, NULL Z or P.  One host wait.  Equal inputs give equal bytes, on any ctx.
+   An order above the ctx's psd_max_order (64 unless set, below): SDPSR_BAD_ARGUMENT with a message that names the cap; also
+   nblocks < 1, some s_k < 1, sum s_k^2 >= 2^32, NULL Z or P.  One host wait.  Equal inputs give equal bytes, on any ctx.
+
+   sdpsr_set_psd_max_order(ctx, 128) opts a ctx into blocks of order 65 .. 128, for sdpsr_psd_project and sdpsr_sdp_solve
+   alike (the solver's final lambda_min included).  Those blocks run in a SECOND launch behind the first, one workgroup of
+   1024 threads per block on the one-workgroup Jacobi sdpsr_syev_f64 uses at these orders: A in LDS, the eigenvectors behind it
+   up to order 97 and in a per-block slice of a ctx scratch (128 KB a block) beyond.  The contract above holds word for word
+   (lower triangle, scaling, +0.0, NaN, sweep limit, aliasing, bitwise symmetry, equal bytes); the blocks of order <= 64 of a
+   mixed call get the bytes a default ctx gives them.  A call without such blocks makes no second launch, a call with only such
+   blocks no first one; still one job table and one host wait.  A ctx that is never told runs exactly what it ran before. */
+int sdpsr_set_psd_max_order(sdpsr_ctx* ctx, int order); /* 64 (default) or 128; other values: SDPSR_BAD_ARGUMENT, setting unchanged */
+int sdpsr_psd_max_order(sdpsr_ctx* ctx);
+/*
 
    sdpsr_sdp_solve.  B: R^d -> (+)_k Sym(s'_k) is sdpsr_blockop_apply, B' sdpsr_blockop_adjoint (both on full entries, so
    <Bx, S> = x'B'S as stored).  A: r x d, column-major, with INDEPENDENT rows (the output of sdpsr_compress_constraints), b: r,
@@ -1008,7 +1019,7 @@ int sdpsr_blocks_syev(sdpsr_ctx* ctx, int32_t nblocks, const int32_t* blk_sizes,
    not on the iteration count -- 5 for host arrays with d <= 64 and r > 0 (tests/test_gpu_sdp_solve.py holds the count).
    Every sum has an order fixed by the inputs alone: equal inputs give equal bytes, on any ctx.
    SDPSR_BAD_ARGUMENT, nothing written: d < 1 or d > 4096 (Kt is 134 MB at the cap; checked before any allocation); a virtual
-   block order above 64; r outside [0, min(d, 1024)]; a non-finite value in A, b or c; bad options; G numerically singular
+   block order above the ctx's psd_max_order (64, or 128 after sdpsr_set_psd_max_order); r outside [0, min(d, 1024)]; a non-finite value in A, b or c; bad options; G numerically singular
    ("rows of A are dependent: compress_constraints first").  r = 0 is legal.  The iteration limit: SDPSR_NOT_CONVERGED with every
    output and the report written as they stand.  A non-finite value met on the way (a NaN in the operator): SDPSR_SOLVER_ERROR.
    The ctx and the handle stay usable after every refusal.  The complex route needs nothing of its own (real embedding). */

@@ -213,6 +213,8 @@ def load_library():
         "sdpsr_hint_symmetric_basis": (C.c_int, [vp, C.c_int]),
         "sdpsr_set_label_width": (C.c_int, [vp, C.c_int]),
         "sdpsr_label_width": (C.c_int, [vp]),
+        "sdpsr_set_psd_max_order": (C.c_int, [vp, C.c_int]),
+        "sdpsr_psd_max_order": (C.c_int, [vp]),
         "sdpsr_labels_convert": (C.c_int, [vp, i64, vp, C.c_int, vp, C.c_int, C.c_int]),
         "sdpsr_meet_keys": (C.c_int, [vp, i32, vp, vp, i64, i64, vp, C.c_int]),
         "sdpsr_agree_partitions": (C.c_int, [vp, vp, i32, vp, vp, i64, pi64, pi32, C.c_int]),

@@ -75,13 +75,15 @@ class Context:
 
     def __init__(self, device=0, seed=0, square_mode=L.SQUARE_AUTO, channels=0, max_iters=0,
                  confirm_rounds=0, eig_driver=0, flags=0, round_mode="nearest", basis_image_kernel="auto",
-                 refine_path="auto", label_bits=0, insert_wgs_per_cu=0, square_kernel=0, label_width=32):
+                 refine_path="auto", label_bits=0, insert_wgs_per_cu=0, square_kernel=0, label_width=32,
+                 psd_max_order=64):
         """``flags``: OR of ``_lib.FLAG_*``; ``round_mode``: "nearest" (default) or "trunc" (the
         reference's ``unsafe_round``, src/utils.jl:49-53); ``label_bits``: 0, or the width of the
         reference's label type ``T`` in ``Partition{T}`` to get ``LabelOverflow`` where it would throw
         inside the algorithms; ``label_width``: 32, 16 or 8 -- the element width of every label array this
         context passes to or receives from the library (``sdpsr_set_label_width``; ``Partition.matrix``
-        then comes back as ``label_dtype``)."""
+        then comes back as ``label_dtype``); ``psd_max_order``: 64 or 128 -- the largest block order ``psd_project``,
+        ``BlockOperator.solve`` and ``reduce_and_solve`` take through this context (``sdpsr_set_psd_max_order``)."""
         self._lib = L.load_library()
         o = L.Opts()
         o.struct_size = C.sizeof(L.Opts)
@@ -104,12 +106,28 @@ class Context:
         self._h = h
         self.device = device
         self._label_width = 32
-        if int(label_width) != 32:
-            try:
+        self._psd_max_order = 64
+        try:
+            if int(label_width) != 32:
                 self.label_width = label_width
-            except Exception:
-                self.close()
-                raise
+            if int(psd_max_order) != 64:
+                self.psd_max_order = psd_max_order
+        except Exception:
+            self.close()
+            raise
+
+    @property
+    def psd_max_order(self):
+        """The largest block order of the PSD projection and the SDP solver through this context: 64 (default) or 128
+        (``sdpsr_psd_max_order``)."""
+        return self._psd_max_order
+
+    @psd_max_order.setter
+    def psd_max_order(self, order):
+        if int(order) not in (64, 128):
+            raise ValueError(f"psd_max_order is 64 or 128, got {order}")
+        self.check(self._lib.sdpsr_set_psd_max_order(self._h, int(order)))
+        self._psd_max_order = int(self._lib.sdpsr_psd_max_order(self._h))
 
     @property
     def label_width(self):
@@ -1790,7 +1808,7 @@ class BlockOperator:
         ``newB``: r, ``newC``: d -- NumPy arrays or torch tensors (read on the host).  Returns a ``SolveResult``: ``x``,
         ``objective``, ``status`` (``"converged"`` or ``"iteration_limit"``), the fields of ``sdpsr_sdp_info``, and on
         request ``S`` (the PSD split variable, a list of blocks) and ``Y = rho * Lambda`` (its multiplier).  Dependent rows,
-        non-finite inputs, d > 4096 or a block of order > 64: ``ValueError``.  ``raise_on_limit``: ``NotConverged`` instead
+        non-finite inputs, d > 4096 or a block of an order above the context's ``psd_max_order``: ``ValueError``.  ``raise_on_limit``: ``NotConverged`` instead
         of the ``"iteration_limit"`` status.  This is ADMM, not an interior-point method: see the README for what accuracy
         to expect."""
         ctx = self.ctx if ctx is None else ctx
@@ -1843,8 +1861,8 @@ def psd_project(Z, sizes, return_lambda_min=False, ctx=None):
     """The projection of every block onto the PSD cone, ``P_k = V max(w, 0) V'`` (``sdpsr_psd_project``): ``Z`` as
     ``BlockOperator.apply`` returns it (a list of blocks or the flat array; NumPy, or torch on the device; only the lower
     triangles are read).  Returns the blocks in the form they came in (list or flat), exactly symmetric; with
-    ``return_lambda_min=True`` the pair ``(P, lambda_min)`` with the smallest eigenvalue of each block.  Orders above 64:
-    ``ValueError``."""
+    ``return_lambda_min=True`` the pair ``(P, lambda_min)`` with the smallest eigenvalue of each block.  Orders above the
+    context's ``psd_max_order``: ``ValueError``."""
     ctx = _ctx(ctx)
     sizes = [int(s) for s in sizes]
     if not sizes or any(s < 1 for s in sizes):
@@ -1882,7 +1900,8 @@ def reduce_and_solve(C_, A, b, sense="max", complex=False, limit_size=3000, ctx=
     ``basis_image_sparse`` -> ``BlockOperator`` -> ``solve``.  Returns the reference's named tuple -- ``jTime``,
     ``blkTime``, ``solveTime`` (seconds), ``optVal``, ``blkSize``, ``originalSize``, ``newSize`` -- plus ``solution``, the
     ``SolveResult``; above ``limit_size`` the zero-filled tuple the reference returns; ``None`` when ``blockDiagonalize``
-    fails (``retries`` fresh generic elements first).  ``solver``: keyword arguments of ``BlockOperator.solve``."""
+    fails (``retries`` fresh generic elements first).  ``solver``: keyword arguments of ``BlockOperator.solve``.  A block
+    of an order above the context's ``psd_max_order``: ``ValueError`` from the solver."""
     import time
     ctx = _ctx(ctx)
     t0 = time.perf_counter()

@@ -332,6 +332,15 @@ int sdpsr_hint_symmetric_basis(sdpsr_ctx* c, int yes) {
     return SDPSR_OK;
 }
 
+int sdpsr_set_psd_max_order(sdpsr_ctx* c, int order) {
+    if (!c) return SDPSR_BAD_ARGUMENT;
+    if (order != 64 && order != 128) return ctx_fail(c, SDPSR_BAD_ARGUMENT, "psd max order must be 64 or 128");
+    c->psd_max_order = order;
+    return SDPSR_OK;
+}
+
+int sdpsr_psd_max_order(sdpsr_ctx* c) { return c ? c->psd_max_order : SDPSR_BAD_ARGUMENT; }
+
 int sdpsr_transfer_bytes(sdpsr_ctx* c, uint64_t* h2d, uint64_t* d2h) {
     if (!c) return SDPSR_BAD_ARGUMENT;
     uint64_t a = c->h2d_bytes, b = c->d2h_bytes;

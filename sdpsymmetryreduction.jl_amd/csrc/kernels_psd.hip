@@ -17,8 +17,12 @@
 // the element's own thread reads it before it writes there, and the upper triangle is never read, so P may alias Z.
 // No positive eigenvalue: every sum is empty and P is exactly +0.0.  A NaN or Inf in the lower triangle: the block's outputs are
 // NaN and bit 2 of the flag is set; the sweep limit sets bit 1.
+//
+// Blocks of order 65 .. 128 (opt-in per ctx, sdpsr_set_psd_max_order) go through psd_project_mid_kernel, in a launch of its own
+// behind this one: the same contract on the one-workgroup Jacobi of jacobi128.h (what sdpsr_syev_f64 runs at these orders).
 #include "sdpsr_internal.h"
 #include "jacobi64.h"
+#include "jacobi128.h"
 
 namespace sdpsr {
 
@@ -193,6 +197,134 @@ psd_project_kernel(PsdArgs a) {
     if (tid == 0 && sweep >= 40) atomicOr(a.flag, 1);  // (an integer flag: order does not matter)
 }
 
+// The blocks of order 65 .. 128 (a ctx with sdpsr_set_psd_max_order(128)): one workgroup of 1024 threads per block on the
+// Jacobi core of jacobi128.h -- A in LDS (n x n, ld n | 1), V behind it while both fit (n <= 97), else in the block's slice
+// of a scratch in global memory: the jobs with V in global memory come FIRST, so slice = blockIdx.x.  The contract is that of
+// psd_project_kernel above, line by line: lower triangle (+ Lam), power-of-two scaling, the same stopping rule and sweep
+// limit, the positive columns or the complement with Z re-read by the element's own thread, (i, j) and (j, i) from one value,
+// flag bits 1 and 2, the block's residual terms summed lanes by shuffle and waves left to right.  The columns are selected by
+// two 64-lane ballots (waves 0 and 1), wave 1's columns behind wave 0's: k ascends.
+template <bool FUSED>
+__global__ void __launch_bounds__(JAC_MAXTHREADS)
+psd_project_mid_kernel(PsdArgs a, double* __restrict__ vglob) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];  // A, and V while n <= 97
+    __shared__ Jacobi128Shared s_jac;
+    __shared__ double s_red[2 * JAC_MAXTHREADS / 64];
+    __shared__ unsigned long long s_max[JAC_MAXTHREADS / 64];
+    __shared__ double s_w[JAC_MAXN];
+    __shared__ int s_sel[JAC_MAXN];
+    __shared__ unsigned long long s_bal[4];
+    const int tid = threadIdx.x, nthr = blockDim.x, nw = nthr >> 6;
+    const double qnan = __longlong_as_double(0x7FF8000000000000ll);
+    const PsdJob jb = a.jobs[blockIdx.x];
+    const int n = jb.n;
+    const int ldl = n | 1;
+    const bool v_in_lds = jacobi128_v_in_lds(n);
+    double* sA = smem;
+    double* V = v_in_lds ? sA + (size_t)ldl * n + 8 : vglob + (size_t)blockIdx.x * PSD_MID_VSLICE;
+    const int ldv = v_in_lds ? ldl : n;
+    unsigned long long amax = 0;
+    for (int e = tid; e < n * n; e += nthr) {
+        const int j = e / n, i = e - j * n;
+        const int ii = i > j ? i : j, jj = i > j ? j : i;
+        const double v = psd_input<FUSED>(a, jb.zoff + ii + (int64_t)jj * n);
+        const unsigned long long b = (unsigned long long)__double_as_longlong(v) & 0x7FFFFFFFFFFFFFFFull;
+        amax = b > amax ? b : amax;  // non-negative doubles order like their bit patterns (NaN above Inf)
+        sA[i + j * ldl] = v;
+        V[i + j * ldv] = (i == j) ? 1.0 : 0.0;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long x = __shfl_down(amax, o, 64);
+        amax = x > amax ? x : amax;
+    }
+    if ((tid & 63) == 0) s_max[tid >> 6] = amax;
+    __syncthreads();
+    amax = 0;
+    for (int k = 0; k < nw; ++k) amax = s_max[k] > amax ? s_max[k] : amax;
+    double rp = 0.0, rd = 0.0;
+    if (amax >= 0x7FF0000000000000ull) {  // uniform: an Inf or a NaN in the lower triangle
+        for (int e = tid; e < n * n; e += nthr) psd_store<FUSED>(a, jb.zoff + e, qnan, rp, rd);
+        if (tid == 0) {
+            if (a.lam_min) a.lam_min[jb.blk] = qnan;
+            if (FUSED) a.slots[2 * (int64_t)jb.blk] = a.slots[2 * (int64_t)jb.blk + 1] = qnan;
+            atomicOr(a.flag, 2);
+        }
+        return;
+    }
+    const int ex = syev_scale_exponent(amax);
+    const double fwd = __longlong_as_double((long long)(1023 - ex) << 52), back = __longlong_as_double((long long)(1023 + ex) << 52);
+    if (ex != 0) {  // uniform
+        for (int e = tid; e < n * n; e += nthr) {
+            const int j = e / n, i = e - j * n;
+            sA[i + j * ldl] *= fwd;
+        }
+        __syncthreads();
+    }
+    const int sweep = jacobi128_sweeps(n, ldl, sA, V, ldv, s_jac);
+    // the eigenvalues (scaled), how many are positive, and the columns the reconstruction sums over: one ballot per wave
+    if (tid < JAC_MAXN) {
+        const double w = tid < n ? sA[tid + tid * ldl] : 0.0;
+        s_w[tid] = w;
+        const unsigned long long pos = __ballot(tid < n && w > 0.0), neg = __ballot(tid < n && w < 0.0);
+        if ((tid & 63) == 0) {
+            s_bal[tid >> 6] = pos;
+            s_bal[2 + (tid >> 6)] = neg;
+        }
+    }
+    __syncthreads();
+    const bool use_pos = 2 * (__popcll(s_bal[0]) + __popcll(s_bal[1])) <= n;
+    const unsigned long long sel0 = use_pos ? s_bal[0] : s_bal[2], sel1 = use_pos ? s_bal[1] : s_bal[3];
+    const int nsel0 = __popcll(sel0), nsel = nsel0 + __popcll(sel1);
+    if (tid < JAC_MAXN) {
+        const int lane = tid & 63;
+        const unsigned long long mine = tid < 64 ? sel0 : sel1;
+        if ((mine >> lane) & 1ull) s_sel[(tid < 64 ? 0 : nsel0) + __popcll(mine & ((1ull << lane) - 1ull))] = tid;
+    }
+    if (a.lam_min && tid < 64) {
+        double mn = fmin(tid < n ? s_w[tid] : INFINITY, tid + 64 < n ? s_w[tid + 64] : INFINITY);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) mn = fmin(mn, __shfl_down(mn, o, 64));
+        if (tid == 0) a.lam_min[jb.blk] = mn * back;
+    }
+    __syncthreads();
+    for (int e = tid; e < n * n; e += nthr) {
+        const int j = e / n, i = e - j * n;
+        if (i < j) continue;
+        double acc = 0.0;
+        for (int q = 0; q < nsel; ++q) {
+            const int k = s_sel[q];
+            acc = fma(s_w[k] * V[i + k * ldv], V[j + k * ldv], acc);
+        }
+        if (!use_pos) acc = psd_input<FUSED>(a, jb.zoff + i + (int64_t)j * n) * fwd - acc;
+        const double v = acc * back;
+        psd_store<FUSED>(a, jb.zoff + i + (int64_t)j * n, v, rp, rd);
+        if (i != j) psd_store<FUSED>(a, jb.zoff + j + (int64_t)i * n, v, rp, rd);
+    }
+    if (FUSED) {  // the block's two residual terms: lanes by shuffle, waves left to right -- an order fixed by the block's order alone
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            rp += __shfl_down(rp, o, 64);
+            rd += __shfl_down(rd, o, 64);
+        }
+        if ((tid & 63) == 0) {
+            s_red[tid >> 6] = rp;
+            s_red[nw + (tid >> 6)] = rd;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            double tp = 0.0, td = 0.0;
+            for (int k = 0; k < nw; ++k) {
+                tp += s_red[k];
+                td += s_red[nw + k];
+            }
+            a.slots[2 * (int64_t)jb.blk] = tp;
+            a.slots[2 * (int64_t)jb.blk + 1] = td;
+        }
+    }
+    if (tid == 0 && sweep >= 40) atomicOr(a.flag, 1);  // (an integer flag: order does not matter)
+}
+
 }  // namespace
 
 bool psd_set_device_attributes() {
@@ -201,7 +333,26 @@ bool psd_set_device_attributes() {
                         hipFuncAttributeMaxDynamicSharedMemorySize, 136 * 1024);
     ok &= hipSuccess == hipFuncSetAttribute(reinterpret_cast<const void*>(&psd_project_kernel<true>),
                         hipFuncAttributeMaxDynamicSharedMemorySize, 136 * 1024);
+    ok &= hipSuccess == hipFuncSetAttribute(reinterpret_cast<const void*>(&psd_project_mid_kernel<false>),
+                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)JAC_MAX_LDS);
+    ok &= hipSuccess == hipFuncSetAttribute(reinterpret_cast<const void*>(&psd_project_mid_kernel<true>),
+                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)JAC_MAX_LDS);
     return ok;
+}
+
+bool psd_mid_v_in_global(int n) { return !jacobi128_v_in_lds(n); }
+
+size_t psd_mid_lds_bytes(int n) { return jacobi128_lds_bytes(n) * (jacobi128_v_in_lds(n) ? 2 : 1); }
+
+// The nmid blocks of order 65 .. 128 in a launch of their own (jobs: those with psd_mid_v_in_global first -- block b of the
+// grid owns slice b of vscratch, PSD_MID_VSLICE doubles each; lds: the largest psd_mid_lds_bytes of the jobs).  The other
+// arguments and the two forms are launch_psd_project's.
+void launch_psd_project_mid(hipStream_t s, const PsdJob* jobs, int nmid, size_t lds, const double* Z, double* P, double* lam_min,
+                            double* Lam, double* D, double* slots, double* vscratch, int* flag) {
+    if (nmid <= 0) return;
+    const PsdArgs a{jobs, nmid, 0, Z, P, lam_min, Lam, D, slots, flag};
+    if (Lam) psd_project_mid_kernel<true><<<nmid, JAC_MAXTHREADS, lds, s>>>(a, vscratch);
+    else psd_project_mid_kernel<false><<<nmid, JAC_MAXTHREADS, lds, s>>>(a, vscratch);
 }
 
 // max_n: the largest order among the njac Jacobi jobs (2 .. 64; ignored when njac == 0); flag: one int, zeroed by the caller.

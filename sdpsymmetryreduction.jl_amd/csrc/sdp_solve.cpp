@@ -14,15 +14,20 @@ using namespace sdpsr;
 namespace {
 
 constexpr int64_t SDP_MAX_D = 4096, SDP_MAX_R = 1024;
-constexpr int PSD_MAX_ORDER = 64;
+constexpr int PSD_SMALL_ORDER = 64;  // the reach of the ping-pong core (jacobi64.h); above it, up to the ctx's psd_max_order: the mid kernel
 
 struct PsdPlan {
-    std::vector<PsdJob> jobs;  // first the blocks of order >= 2, then those of order 1
+    // ONE table: the blocks of order 2 .. 64, those of order 1, then the mid blocks (65 .. 128) -- of those, first the nglob
+    // whose eigenvectors live in global memory (slice = position among the mid jobs), then the ones that keep them in LDS
+    std::vector<PsdJob> jobs;
     int njac = 0, n1 = 0, max_n = 0;
+    int nmid = 0, nglob = 0;
+    size_t mid_lds = 0;
     int64_t sum_sq = 0;
 };
 
 bool psd_plan(sdpsr_ctx* c, const char* who, int32_t nblocks, const int32_t* sizes, PsdPlan& p) {
+    const int cap = c->psd_max_order;
     if (nblocks < 1 || !sizes) {
         ctx_fail(c, SDPSR_BAD_ARGUMENT, std::string(who) + ": nblocks < 1 or blk_sizes is NULL");
         return false;
@@ -35,9 +40,9 @@ bool psd_plan(sdpsr_ctx* c, const char* who, int32_t nblocks, const int32_t* siz
             ctx_fail(c, SDPSR_BAD_ARGUMENT, std::string(who) + ": a block size is < 1");
             return false;
         }
-        if (s > PSD_MAX_ORDER) {
+        if (s > cap) {
             ctx_fail(c, SDPSR_BAD_ARGUMENT, std::string(who) + ": block " + std::to_string(k) + " has order " + std::to_string(s) +
-                                                ": orders above 64 are not supported by the PSD projection");
+                                                ": orders above " + std::to_string(cap) + " are not supported by the PSD projection");
             return false;
         }
         off[k] = sum;
@@ -49,7 +54,7 @@ bool psd_plan(sdpsr_ctx* c, const char* who, int32_t nblocks, const int32_t* siz
     }
     p.sum_sq = sum;
     for (int32_t k = 0; k < nblocks; ++k)
-        if (sizes[k] >= 2) {
+        if (sizes[k] >= 2 && sizes[k] <= PSD_SMALL_ORDER) {
             p.jobs.push_back({off[k], sizes[k], k});
             p.max_n = std::max(p.max_n, (int)sizes[k]);
             ++p.njac;
@@ -59,7 +64,30 @@ bool psd_plan(sdpsr_ctx* c, const char* who, int32_t nblocks, const int32_t* siz
             p.jobs.push_back({off[k], 1, k});
             ++p.n1;
         }
+    for (int pass = 0; pass < 2; ++pass)
+        for (int32_t k = 0; k < nblocks; ++k)
+            if (sizes[k] > PSD_SMALL_ORDER && psd_mid_v_in_global(sizes[k]) == (pass == 0)) {
+                p.jobs.push_back({off[k], sizes[k], k});
+                p.mid_lds = std::max(p.mid_lds, psd_mid_lds_bytes(sizes[k]));
+                ++p.nmid;
+                if (pass == 0) ++p.nglob;
+            }
     return true;
+}
+
+// the eigenvector slices of the mid blocks that do not fit the LDS (nullptr with *st untouched when there is none)
+double* psd_mid_scratch(sdpsr_ctx* c, const PsdPlan& p, const char* name, int* st) {
+    if (p.nglob == 0) return nullptr;
+    double* v = (double*)ctx_buf(c, name, (size_t)p.nglob * PSD_MID_VSLICE * sizeof(double));
+    if (!v && !*st) *st = SDPSR_OUT_OF_MEMORY;
+    return v;
+}
+
+// both launches of a projection over the uploaded table: the blocks of order <= 64, then the mid blocks; either is skipped when empty
+void psd_launch_plan(hipStream_t s, const PsdPlan& p, const PsdJob* djobs, const double* Z, double* P, double* lam_min, double* Lam,
+                     double* D, double* slots, double* vmid, int* flag) {
+    launch_psd_project(s, djobs, p.njac, p.n1, p.max_n, Z, P, lam_min, Lam, D, slots, flag);
+    launch_psd_project_mid(s, djobs + p.njac + p.n1, p.nmid, p.mid_lds, Z, P, lam_min, Lam, D, slots, vmid, flag);
 }
 
 // the job table on the device (stream-ordered) and the flag word, zeroed
@@ -206,6 +234,7 @@ int sdpsr_psd_project(sdpsr_ctx* c, int32_t nblocks, const int32_t* blk_sizes, c
     const double* dZ = in_dev(c, "psd_z", Z, (size_t)plan.sum_sq, mem, &st);
     double* dP = out_dev(c, "psd_p", P, (size_t)plan.sum_sq, mem, &st);
     double* dL = lambda_min ? out_dev(c, "psd_lmin", lambda_min, (size_t)nblocks, mem, &st) : nullptr;
+    double* vmid = psd_mid_scratch(c, plan, "psd_vmid", &st);
     PsdJob* djobs = nullptr;
     int* dflag = nullptr;
     if (!st) st = psd_upload_plan(c, plan, "psd_jobs", "psd_flag", &djobs, &dflag);
@@ -213,7 +242,7 @@ int sdpsr_psd_project(sdpsr_ctx* c, int32_t nblocks, const int32_t* blk_sizes, c
         (void)ctx_sync_stream(c, s);  // (pageable sources: nothing reads them after the return)
         return st;
     }
-    launch_psd_project(s, djobs, plan.njac, plan.n1, plan.max_n, dZ, dP, dL, nullptr, nullptr, nullptr, dflag);
+    psd_launch_plan(s, plan, djobs, dZ, dP, dL, nullptr, nullptr, nullptr, vmid, dflag);
     HIP_TRY(c, hipGetLastError());
     if (host) {
         HIP_TRY(c, hipMemcpyAsync(P, dP, (size_t)plan.sum_sq * 8, hipMemcpyDeviceToHost, s));
@@ -287,6 +316,8 @@ int sdpsr_sdp_solve(sdpsr_ctx* c, const sdpsr_blockop* op, int64_t r, const doub
     PsdJob* djobs = nullptr;
     int* dflag = nullptr;
     if (!vec || !blk || !carry) return SDPSR_OUT_OF_MEMORY;
+    double* vmid = psd_mid_scratch(c, plan, "sdp_vmid", &st);
+    if (st) return st;
     st = psd_upload_plan(c, plan, "sdp_jobs", "sdp_flag", &djobs, &dflag);
     if (st) return st;
     double *dx = vec, *du = vec + d, *dlam = vec + 2 * d, *dadj = vec + 3 * d, *dchat = vec + 4 * d, *dvs = vec + 5 * d;
@@ -308,7 +339,7 @@ int sdpsr_sdp_solve(sdpsr_ctx* c, const sdpsr_blockop* op, int64_t r, const doub
         launch_sdp_affine_step(s, d, nonneg ? 1 : 0, rho, su.Kt, su.x0, dadj, dchat, duml[iters & 1], dx, du, dlam, duml[(iters + 1) & 1], dvs);
         st = blockop_map_enqueue(c, op, false, dx, carry, dBx);  // Bx
         if (st) return st;
-        launch_psd_project(s, djobs, plan.njac, plan.n1, plan.max_n, dBx, dS, nullptr, dLam, dD, dbs, dflag);
+        psd_launch_plan(s, plan, djobs, dBx, dS, nullptr, dLam, dD, dbs, vmid, dflag);
         ++iters;
         if (iters % o.check_every != 0 && iters != o.max_iters) continue;
         launch_sdp_verdict(s, d, dvs, nb, dbs, (double*)verdict);
@@ -337,7 +368,7 @@ int sdpsr_sdp_solve(sdpsr_ctx* c, const sdpsr_blockop* op, int64_t r, const doub
     // ---- outputs and the report, from the returned x itself: lambda_min through the projection kernel on Bx = B x
     double* scratchP = (double*)ctx_buf(c, "sdp_proj", (size_t)n * 8);
     if (!scratchP) return SDPSR_OUT_OF_MEMORY;
-    launch_psd_project(s, djobs, plan.njac, plan.n1, plan.max_n, dBx, scratchP, dlmin, nullptr, nullptr, nullptr, dflag);
+    psd_launch_plan(s, plan, djobs, dBx, scratchP, dlmin, nullptr, nullptr, nullptr, vmid, dflag);
     HIP_TRY(c, hipGetLastError());
     std::vector<double> hx((size_t)d), hl((size_t)nb);
     int flag = 0;

@@ -156,6 +156,7 @@ struct sdpsr_ctx {
     uint64_t stream_counter = 0;  // fresh RNG stream per randomize call
     sdpsr_opts opts{};
     int label_width = 32;  // sdpsr_set_label_width: bits of every label array that crosses the interface (labels.cpp); inside, labels are uint32
+    int psd_max_order = 64;  // sdpsr_set_psd_max_order: the largest block order sdpsr_psd_project / sdpsr_sdp_solve take, 64 or 128 (sdp_solve.cpp)
     hipStream_t stream = nullptr;
     hipStream_t side_stream = nullptr;  // lazily created: work that overlaps a one-workgroup kernel
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_wait = nullptr;
@@ -744,6 +745,14 @@ void launch_blocks_syev64(hipStream_t s, const BlocksSyevJob* jobs, int njac, in
 // out), Lam <- (Bx + Lam) - S+, D = S+ - Lam+, slots[2 blk], [2 blk + 1] = the block's |Bx - S+|^2, |S+ - S|^2.
 void launch_psd_project(hipStream_t s, const PsdJob* jobs, int njac, int n1, int max_n, const double* Z, double* P, double* lam_min,
                         double* Lam, double* D, double* slots, int* flag);
+// The blocks of order 65 .. 128 (a ctx with psd_max_order = 128), one workgroup each, in a launch of their own.  jobs: the nmid
+// mid jobs, those with psd_mid_v_in_global(n) FIRST: block b of the grid keeps its eigenvectors in slice b (PSD_MID_VSLICE
+// doubles) of vscratch, which may be nullptr when no job needs one.  lds: the largest psd_mid_lds_bytes(n) of the jobs.
+constexpr size_t PSD_MID_VSLICE = 128 * 128;
+bool psd_mid_v_in_global(int n);
+size_t psd_mid_lds_bytes(int n);
+void launch_psd_project_mid(hipStream_t s, const PsdJob* jobs, int nmid, size_t lds, const double* Z, double* P, double* lam_min,
+                            double* Lam, double* D, double* slots, double* vscratch, int* flag);
 // kernels_sdp.hip: the setup and the affine step of sdpsr_sdp_solve (sdp_solve.cpp); stream-ordered, no host wait
 void launch_sdp_record_class(hipStream_t s, int64_t n, const void* rec, uint32_t* cls);
 void launch_sdp_gram(hipStream_t s, int64_t d, int64_t n, const void* rec_by_class_pos, int64_t* cptr, double* M);  // cptr: d + 1

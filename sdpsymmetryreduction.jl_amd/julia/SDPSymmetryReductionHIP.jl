@@ -510,7 +510,14 @@ end
 
 # ---- solving the reduced SDP (sdpsr_psd_project, sdpsr_sdp_solve): the model of docs/src/examples/ReduceAndSolveJuMP.jl:40-84 by the
 # library's first-order (ADMM) solver in CSDP's place -- not an interior-point replacement, see the README ----
-# P_k = V max(w, 0) V' of every block (orders <= 64) and the blocks' smallest eigenvalues
+# the largest block order psd_project and sdp_solve take through the ctx: 64 (default) or 128 (sdpsr_set_psd_max_order)
+function psd_max_order!(order::Integer)
+    cx = ctx()
+    check(cx, ccall((:sdpsr_set_psd_max_order, libsdpsr), Cint, (Ptr{Cvoid}, Cint), cx.handle, order))
+    return psd_max_order()
+end
+psd_max_order() = Int(ccall((:sdpsr_psd_max_order, libsdpsr), Cint, (Ptr{Cvoid},), ctx().handle))
+# P_k = V max(w, 0) V' of every block (orders up to psd_max_order()) and the blocks' smallest eigenvalues
 function psd_project(Z::AbstractVector{<:AbstractMatrix{<:Real}})
     cx = ctx(); sizes = Int32[size(b, 1) for b in Z]; flat = Float64[]
     for b in Z
