@@ -1,12 +1,14 @@
 // Workgroup-level parallel cyclic Jacobi for symmetric matrices of order 65 <= n <= 128 (any n <= 128 works): A resident in
 // LDS, the eigenvector accumulator next to it while both fit the 150 KB opt-in, else in global memory.  Device code only;
-// included by kernels_sytrd.hip (one problem per launch, sdpsr_syev_f64's small path) and kernels_psd.hip (one problem per
-// workgroup: the PSD projection of the blocks of order 65 .. 128).
+// included through jacobi_frame.h, whose one-workgroup policy wraps it, by kernels_sytrd.hip (one problem per launch,
+// sdpsr_syev_f64's small path) and kernels_psd.hip (one problem per workgroup: the PSD projection of the blocks of order
+// 65 .. 128); kernels_batched.hip gets it the same way and does not use it.
 //
 // Round-robin ordering: n/2 disjoint rotations per step, n-1 steps per sweep; every step is
 // (angles) -> barrier -> (two-sided 2 x 2 block updates of A, column rotations of V) -> barrier.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "jacobi64.h"  // jacobi_angle_newton
 
 namespace sdpsr {
 
@@ -90,36 +92,7 @@ __device__ __forceinline__ int jacobi128_sweeps(int n, int ldl, double* __restri
                 double c = 1.0, s = 0.0;
                 if (q < n) {
                     const double apq = sA[p + q * ldl];
-                    if (apq != 0.0) {
-                        // t = tan of the rotation angle (smaller root), c = 1/sqrt(1+t^2), s = t c.
-                        // Hardware reciprocal / reciprocal-square-root seeds plus Newton steps in
-                        // FMAs instead of the IEEE division and sqrt sequences (which dominated the
-                        // step): only c needs full precision (c^2 + s^2 = 1 keeps V orthogonal), an
-                        // error in t merely leaves a residual a_pq for the next sweep.
-                        const double dd = sA[q + q * ldl] - sA[p + p * ldl], bb = 2.0 * apq;
-                        const double h2 = fma(dd, dd, bb * bb);
-                        if (!(h2 > 1e-280 && h2 < 1e280)) {  // out of the seeds' range: IEEE sequences
-                            const double theta = dd / bb;
-                            const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                            c = 1.0 / sqrt(t * t + 1.0);
-                            s = t * c;
-                        } else {
-                        double y = __builtin_amdgcn_rsq(h2);
-                        y = y * fma(-0.5 * h2 * y, y, 1.5);
-                        const double r = h2 * y;  // hypot(dd, bb)
-                        const double den = fabs(dd) + r;
-                        double ri = __builtin_amdgcn_rcp(den);
-                        ri = ri * fma(-den, ri, 2.0);
-                        ri = ri * fma(-den, ri, 2.0);
-                        const double t = (dd >= 0 ? bb : -bb) * ri;
-                        const double u = fma(t, t, 1.0);
-                        double z = __builtin_amdgcn_rsq(u);
-                        z = z * fma(-0.5 * u * z, z, 1.5);
-                        z = z * fma(-0.5 * u * z, z, 1.5);
-                        c = z;
-                        s = t * c;
-                        }
-                    }
+                    if (apq != 0.0) jacobi_angle_newton(sA[p + p * ldl], sA[q + q * ldl], apq, c, s);
                 }
                 sh.c[tid] = c;
                 sh.s[tid] = s;

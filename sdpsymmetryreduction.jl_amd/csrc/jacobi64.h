@@ -1,7 +1,10 @@
 // Workgroup-level parallel cyclic Jacobi for symmetric matrices of order n <= 64 resident in LDS
 // (eigen(A) of src/eigen_decomposition.jl:246 for the small algebras and for the compressed
-// problems of the module-compression driver).  Device code only; included by kernels_sytrd.hip
-// (one problem per launch) and kernels_batched.hip (one problem per workgroup, all CUs).
+// problems of the module-compression driver).  Device code only: the sweeps (two-barrier and ping-pong), the two angle
+// functions and the solvers' scale exponent.  Included by jacobi128.h (the angle), through jacobi_frame.h by
+// kernels_sytrd.hip, kernels_batched.hip and kernels_psd.hip (the ping-pong core behind the shared block frame), and
+// directly by kernels_complex.hip and kernels_stedc.hip; eigdec_batched64_kernel of kernels_batched.hip runs the two-barrier
+// sweeps.
 //
 // One thread per 2 x 2 block (row pair k1, column pair k2) of a tournament step.  Every thread
 // derives the two rotation angles it needs from the diagonal blocks itself (redundantly, in
@@ -47,6 +50,36 @@ __device__ __forceinline__ void jacobi_angle(double app, double aqq, double apq,
     } else {
         c = 1.0;
         s = 0.0;
+    }
+}
+
+// The angle of the one-workgroup core (jacobi128_sweeps), for a_pq != 0.  It differs from jacobi_angle in the Newton steps on
+// the seeds of t: one on the rsq of h2 and two on the rcp of den, where jacobi_angle takes both raw.  (That core derives a
+// step's n/2 angles once, in one wave, and shares them; jacobi64's threads derive two each, on the step's critical path.)
+// Two functions, not one: either arithmetic in the other's place changes the rotations' bits.
+__device__ __forceinline__ void jacobi_angle_newton(double app, double aqq, double apq, double& c, double& s) {
+    const double dd = aqq - app, bb = 2.0 * apq;
+    const double h2 = fma(dd, dd, bb * bb);
+    if (!(h2 > 1e-280 && h2 < 1e280)) {  // out of the seeds' range: IEEE sequences
+        const double theta = dd / bb;
+        const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+        c = 1.0 / sqrt(t * t + 1.0);
+        s = t * c;
+    } else {
+        double y = __builtin_amdgcn_rsq(h2);
+        y = y * fma(-0.5 * h2 * y, y, 1.5);
+        const double r = h2 * y;  // hypot(dd, bb)
+        const double den = fabs(dd) + r;
+        double ri = __builtin_amdgcn_rcp(den);
+        ri = ri * fma(-den, ri, 2.0);
+        ri = ri * fma(-den, ri, 2.0);
+        const double t = (dd >= 0 ? bb : -bb) * ri;
+        const double u = fma(t, t, 1.0);
+        double z = __builtin_amdgcn_rsq(u);
+        z = z * fma(-0.5 * u * z, z, 1.5);
+        z = z * fma(-0.5 * u * z, z, 1.5);
+        c = z;
+        s = t * c;
     }
 }
 

@@ -13,7 +13,7 @@
 // Outputs per run: status (OK / NUMERICAL_INCONSISTENCY / NOT_CONVERGED), number of
 // eigenspaces, number of isomorphism classes.
 #include "sdpsr_internal.h"
-#include "jacobi64.h"
+#include "jacobi_frame.h"
 
 namespace sdpsr {
 
@@ -283,7 +283,6 @@ blocks_syev64_kernel(const BlocksSyevJob* __restrict__ jobs, int njac, int n1, c
     extern __shared__ __attribute__((aligned(16))) double smem[];  // A, V and their ping-pong twins (m x m, ld ldl)
     __shared__ double s_red[2 * BE_THREADS / 64];
     __shared__ unsigned long long s_max[BE_THREADS / 64];
-    __shared__ int s_rank[64];
     const int tid = threadIdx.x, nthr = blockDim.x;
     if ((int)blockIdx.x >= njac) {
         const int64_t t = (int64_t)(blockIdx.x - njac) * nthr + tid;
@@ -297,58 +296,11 @@ blocks_syev64_kernel(const BlocksSyevJob* __restrict__ jobs, int njac, int n1, c
     const BlocksSyevJob jb = jobs[blockIdx.x];
     const int n = jb.n;
     const double* __restrict__ Ag = Z + jb.zoff;
-    const int m = (n + 1) & ~1;
-    const int ldl = m | 1;
-    double* sA = smem;
-    double* sV = sA + (size_t)ldl * m;
-    unsigned long long amax = 0;
-    for (int e = tid; e < m * m; e += nthr) {
-        const int j = e / m, i = e - j * m;
-        const int ii = i > j ? i : j, jj = i > j ? j : i;
-        const double a = (ii < n) ? Ag[ii + (int64_t)jj * n] : 0.0;
-        const unsigned long long b = (unsigned long long)__double_as_longlong(a) & 0x7FFFFFFFFFFFFFFFull;
-        amax = b > amax ? b : amax;  // non-negative doubles order like their bit patterns (NaN above Inf)
-        sA[i + j * ldl] = a;
-        sV[i + j * ldl] = (i == j) ? 1.0 : 0.0;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long x = __shfl_down(amax, o, 64);
-        amax = x > amax ? x : amax;
-    }
-    if ((tid & 63) == 0) s_max[tid >> 6] = amax;
-    __syncthreads();
-    amax = 0;
-    for (int k = 0; k < (nthr >> 6); ++k) amax = s_max[k] > amax ? s_max[k] : amax;
-    const int ex = syev_scale_exponent(amax);
-    if (ex != 0) {  // uniform
-        const double f = __longlong_as_double((long long)(1023 - ex) << 52);
-        for (int e = tid; e < m * m; e += nthr) {
-            const int j = e / m, i = e - j * m;
-            sA[i + j * ldl] *= f;
-        }
-        __syncthreads();
-    }
-    const int sweep = jacobi64_sweeps_pp(n, m, ldl, sA, sV, sV + (size_t)ldl * m, sV + 2 * (size_t)ldl * m, s_red);
-    const double back = __longlong_as_double((long long)(1023 + ex) << 52);
-    for (int i = tid; i < n; i += nthr) {
-        const double li = sA[i + i * ldl];
-        int rk = 0;
-        for (int j = 0; j < n; ++j) {
-            const double lj = sA[j + j * ldl];
-            rk += (lj < li) || (lj == li && j < i);
-        }
-        s_rank[i] = rk;
-        wout[jb.woff + rk] = li * back;
-    }
-    __syncthreads();
-    if (V) {
-        double* __restrict__ Vg = V + jb.zoff;
-        for (int e = tid; e < n * n; e += nthr) {
-            const int j = e / n, i = e - j * n;
-            Vg[i + (int64_t)s_rank[j] * n] = sV[i + j * ldl];
-        }
-    }
+    const JacobiPP core(n, smem, s_red);
+    const int ex = syev_scale_exponent(jacobi_frame_load<true>(core, [&](int i, int j) { return Ag[i + (int64_t)j * n]; }, s_max));
+    if (ex != 0) jacobi_frame_scale(core, __longlong_as_double((long long)(1023 - ex) << 52));  // uniform
+    const int sweep = core.sweeps();
+    jacobi_frame_store_sorted(core, __longlong_as_double((long long)(1023 + ex) << 52), wout + jb.woff, V ? V + jb.zoff : nullptr, n);
     if (tid == 0 && sweep >= 40) atomicOr(flag, 1);  // (an integer flag: order does not matter)
 }
 
@@ -357,7 +309,7 @@ bool batched_set_device_attributes() {
     ok &= hipSuccess == hipFuncSetAttribute(reinterpret_cast<const void*>(&eigdec_batched64_kernel),
                         hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
     ok &= hipSuccess == hipFuncSetAttribute(reinterpret_cast<const void*>(&blocks_syev64_kernel),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, 136 * 1024);
+                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)JAC64_MAX_LDS);
     return ok;
 }
 
@@ -368,9 +320,8 @@ void launch_blocks_syev64(hipStream_t s, const BlocksSyevJob* jobs, int njac, in
     int threads = 64;
     size_t lds = 0;
     if (njac > 0) {
-        const int half = (max_n + 1) / 2, mm = 2 * half;
-        threads = (half * half + 63) / 64 * 64;
-        lds = 4 * (size_t)(mm | 1) * mm * sizeof(double) + 64;
+        threads = jacobi64_pp_threads(max_n);
+        lds = jacobi64_pp_lds_bytes(max_n);
     } else if (n1 > 64) {
         threads = 256;
     }

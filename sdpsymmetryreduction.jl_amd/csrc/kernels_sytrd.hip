@@ -34,8 +34,7 @@
 #include <cstdlib>
 
 #include "sdpsr_internal.h"
-#include "jacobi64.h"
-#include "jacobi128.h"
+#include "jacobi_frame.h"
 
 namespace sdpsr {
 
@@ -1350,104 +1349,40 @@ void launch_sytrd(sdpsr_ctx* c, int64_t n64, double* A, int64_t ld, double* d, d
 // matrix resident in LDS.  The compressed problems of the module-compression driver (w x w,
 // w < 2 dim P) and the reference's small test algebras are this size; the blocked
 // tridiagonalisation path costs ~5 launches per column there, i.e. pure launch latency.
-// The sweeps are jacobi128_sweeps of jacobi128.h (round-robin ordering: n/2 disjoint rotations per
-// step, n-1 steps per sweep), shared with the batched PSD projection of kernels_psd.hip.
+// Both kernels are the block frame of jacobi_frame.h -- load, sweeps, ranked store -- around one of its two cores, shared with
+// the batched block spectra of kernels_batched.hip and the PSD projection of kernels_psd.hip.
 // ---------------------------------------------------------------------------
 namespace sdpsr {
 
 __global__ void __launch_bounds__(JAC_MAXTHREADS)
 small_syev_jacobi_kernel(int n, double* __restrict__ Ag, int64_t lda, double* __restrict__ wout,
-                         double* __restrict__ Vglob, int* __restrict__ info, int v_in_lds) {
-    extern __shared__ __attribute__((aligned(16))) double sA[];  // n x n, leading dimension ldl
+                         double* __restrict__ Vglob, int* __restrict__ info) {
+    extern __shared__ __attribute__((aligned(16))) double jac_smem[];  // A (n x n, odd leading dimension), V behind it while both fit
     __shared__ Jacobi128Shared s_jac;
-    __shared__ int s_rank[JAC_MAXN];
-    const int tid = threadIdx.x;
-    const int JAC_THREADS = blockDim.x;
-    const int ldl = n | 1;  // odd leading dimension: column walks hit distinct banks
-    // the eigenvector accumulator lives in LDS next to A when both fit (n <= 96), else in global
-    double* __restrict__ Vtmp = v_in_lds ? (sA + (size_t)ldl * n + 8) : Vglob;
-    const int ldv = v_in_lds ? ldl : n;
-    // load A (symmetric part from the lower triangle, like LAPACK with uplo = 'L') and V = I
-    for (int e = tid; e < n * n; e += JAC_THREADS) {
-        const int j = e / n, i = e - j * n;
-        const int ii = i > j ? i : j, jj = i > j ? j : i;
-        sA[i + j * ldl] = Ag[ii + (int64_t)jj * lda];
-        Vtmp[i + j * ldv] = (i == j) ? 1.0 : 0.0;
-    }
-    __syncthreads();
-    const int sweep = jacobi128_sweeps(n, ldl, sA, Vtmp, ldv, s_jac);  // (jacobi128.h, shared with the PSD projection)
-    // ascending order: rank of every diagonal entry (ties broken by index)
-    for (int i = tid; i < n; i += JAC_THREADS) {
-        const double li = sA[i + i * ldl];
-        int rk = 0;
-        for (int j = 0; j < n; ++j) {
-            const double lj = sA[j + j * ldl];
-            rk += (lj < li) || (lj == li && j < i);
-        }
-        s_rank[i] = rk;
-        wout[rk] = li;
-    }
-    __syncthreads();
-    for (int e = tid; e < n * n; e += JAC_THREADS) {
-        const int j = e / n, i = e - j * n;
-        Ag[i + (int64_t)s_rank[j] * lda] = Vtmp[i + j * ldv];
-    }
-    if (tid == 0) {
+    const JacobiWG core(n, jac_smem, Vglob, 0, s_jac);
+    // A is the symmetric matrix of the lower triangle, like LAPACK with uplo = 'L'
+    jacobi_frame_load<false>(core, [&](int i, int j) { return Ag[i + (int64_t)j * lda]; }, nullptr);
+    const int sweep = core.sweeps();
+    jacobi_frame_store_sorted(core, 1.0, wout, Ag, lda);
+    if (threadIdx.x == 0) {
         info[0] = (sweep >= 40) ? 1 : 0;
         info[1] = sweep;
     }
 }
 
-// The matrix is padded to an even order m with a zero row/column (the dummy player of the
-// tournament: a_pq = 0 gives the identity rotation), so the step has no validity branches; the
-// pairs of a round come from register arithmetic and the step ping-pongs between two LDS copies.
-//
-// jacobi64_fill_pairs / jacobi64_sweeps are the workgroup-level core, shared by the single-problem
-// kernel below and by the batched eigen_decomposition kernel (kernels_batched.hip includes this
-// file's declarations through jacobi64.h).
-template <bool PP>
+// Orders up to 64 on the ping-pong core: the matrix is padded to an even order m with a zero row/column (the dummy player of
+// the tournament: a_pq = 0 gives the identity rotation), so the step has no validity branches; the pairs of a round come from
+// register arithmetic and the step ping-pongs between two LDS copies.
 __global__ void __launch_bounds__(JAC_MAXTHREADS)
 small_syev_jacobi64_kernel(int n, double* __restrict__ Ag, int64_t lda, double* __restrict__ wout,
                            int* __restrict__ info) {
-    extern __shared__ __attribute__((aligned(16))) double sA[];  // A, V and their ping-pong twins (m x m, ld ldl)
+    extern __shared__ __attribute__((aligned(16))) double jac_smem[];  // A, V and their ping-pong twins (m x m, ld ldl)
     __shared__ double s_red[2 * JAC_MAXTHREADS / 64];
-    __shared__ int s_rank[64];
-    const int tid = threadIdx.x, nthr = blockDim.x;
-    const int m = (n + 1) & ~1;
-    const int ldl = m | 1;
-    double* sV = sA + (size_t)ldl * m;
-    for (int e = tid; e < m * m; e += nthr) {
-        const int j = e / m, i = e - j * m;
-        const int ii = i > j ? i : j, jj = i > j ? j : i;
-        sA[i + j * ldl] = (ii < n) ? Ag[ii + (int64_t)jj * lda] : 0.0;
-        sV[i + j * ldl] = (i == j) ? 1.0 : 0.0;
-    }
-    int sweep;
-    if (PP) {
-        __syncthreads();
-        sweep = jacobi64_sweeps_pp(n, m, ldl, sA, sV, sV + (size_t)ldl * m, sV + 2 * (size_t)ldl * m, s_red);
-    } else {
-        int* s_pq = reinterpret_cast<int*>(sV + (size_t)ldl * m);
-        jacobi64_fill_pairs(m, s_pq);
-        __syncthreads();
-        sweep = jacobi64_sweeps(n, m, ldl, sA, sV, s_pq, s_red);
-    }
-    for (int i = tid; i < n; i += nthr) {
-        const double li = sA[i + i * ldl];
-        int rk = 0;
-        for (int j = 0; j < n; ++j) {
-            const double lj = sA[j + j * ldl];
-            rk += (lj < li) || (lj == li && j < i);
-        }
-        s_rank[i] = rk;
-        wout[rk] = li;
-    }
-    __syncthreads();
-    for (int e = tid; e < n * n; e += nthr) {
-        const int j = e / n, i = e - j * n;
-        Ag[i + (int64_t)s_rank[j] * lda] = sV[i + j * ldl];
-    }
-    if (tid == 0) {
+    const JacobiPP core(n, jac_smem, s_red);
+    jacobi_frame_load<false>(core, [&](int i, int j) { return Ag[i + (int64_t)j * lda]; }, nullptr);
+    const int sweep = core.sweeps();
+    jacobi_frame_store_sorted(core, 1.0, wout, Ag, lda);
+    if (threadIdx.x == 0) {
         info[0] = (sweep >= 40) ? 1 : 0;
         info[1] = sweep;
     }
@@ -1455,33 +1390,20 @@ small_syev_jacobi64_kernel(int n, double* __restrict__ Ag, int64_t lda, double* 
 
 bool small_syev_set_device_attributes() {
     bool ok = true;
-    ok &= hipSuccess == hipFuncSetAttribute(reinterpret_cast<const void*>(&small_syev_jacobi64_kernel<true>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, 136 * 1024);
-    ok &= hipSuccess == hipFuncSetAttribute(reinterpret_cast<const void*>(&small_syev_jacobi64_kernel<false>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, 136 * 1024);
+    ok &= hipSuccess == hipFuncSetAttribute(reinterpret_cast<const void*>(&small_syev_jacobi64_kernel),
+                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)JAC64_MAX_LDS);
     ok &= hipSuccess == hipFuncSetAttribute(reinterpret_cast<const void*>(&small_syev_jacobi_kernel),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)JAC_MAX_LDS);
     return ok;
 }
 
+// Vtmp: n * n doubles, the eigenvector accumulator of the orders whose V does not fit the LDS next to A (n >= 98)
 bool launch_small_syev(hipStream_t s, int64_t n, double* A, int64_t lda, double* w, double* Vtmp, int* info) {
     if (n < 1 || n > JAC_MAXN) return false;
-    size_t lds = (size_t)((n | 1) * n + 8) * sizeof(double);
-    if (n <= 64) {
-        const int half = (int)((n + 1) / 2), mm = 2 * half;
-        int threads = (half * half + 63) / 64 * 64;
-        if (threads < 64) threads = 64;
-        const size_t lds64 = 4 * (size_t)(mm | 1) * mm * sizeof(double) + 64;
-        small_syev_jacobi64_kernel<true><<<1, threads, lds64, s>>>((int)n, A, lda, w, info);
-        return true;
-    }
-    const int v_in_lds = (2 * lds <= 150 * 1024) ? 1 : 0;
-    if (v_in_lds) lds *= 2;
-    // one thread per element of the n/2 rotated column pairs, whole waves, at most 1024
-    int threads = (int)(((n + 1) / 2) * n + 63) / 64 * 64;
-    if (threads > JAC_MAXTHREADS) threads = JAC_MAXTHREADS;
-    if (threads < 64) threads = 64;
-    small_syev_jacobi_kernel<<<1, threads, lds, s>>>((int)n, A, lda, w, Vtmp, info, v_in_lds);
+    if (n <= JAC64_MAXN)
+        small_syev_jacobi64_kernel<<<1, jacobi64_pp_threads((int)n), jacobi64_pp_lds_bytes((int)n), s>>>((int)n, A, lda, w, info);
+    else
+        small_syev_jacobi_kernel<<<1, jacobi128_threads((int)n), jacobi128_frame_lds_bytes((int)n), s>>>((int)n, A, lda, w, Vtmp, info);
     return true;
 }
 

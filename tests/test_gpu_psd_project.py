@@ -127,6 +127,33 @@ def test_special_inputs(gpu_ctx, s):
     assert np.abs(Pk[4]).max() <= 4e-12 * s * np.abs(rank_one).max()
 
 
+@pytest.fixture(scope="module")
+def own_ctx(pkg):
+    """A context of this module's own: tests/test_gpu_sdp_solve.py counts the host waits of the shared one, and those follow
+    the number of uploads the context has made before (its pinned upload ring wraps every 32)."""
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    with pkg.Context(device=0, seed=4321) as ctx:
+        yield ctx
+
+
+@pytest.mark.parametrize("s", [2, 3, 16, 17, 63, 64])
+def test_half_and_half_plus_one_positive(own_ctx, s):
+    """Exactly s // 2 positive eigenvalues sums the positive columns, one more takes the complement (which re-reads Z, so
+    it is run with P aliasing Z too), at even and odd orders on both sides of one wave per block."""
+    rng = np.random.default_rng(300 + s)
+    w = rng.uniform(0.5, 2.0, s)
+    counts = [s // 2, s // 2 + 1]
+    blocks = [_spectrum(rng, s, np.where(np.arange(s) < npos, w, -w)) for npos in counts]
+    for B, npos in zip(blocks, counts):
+        assert np.count_nonzero(np.linalg.eigvalsh(B) > 0) == npos
+    P, lm, _ = _check(own_ctx, [s, s], blocks)
+    for mem in (HOST, DEVICE):
+        st, P2, l2 = _project(own_ctx, [s, s], flatten_blocks(blocks), mem, alias=True)
+        assert st == OK and np.array_equal(_bits(P), _bits(P2)) and np.array_equal(_bits(lm), _bits(l2)), mem
+
+
 def test_triple_eigenvalue_that_includes_zero(gpu_ctx):
     rng = np.random.default_rng(31)
     blocks = [_spectrum(rng, 6, [0.0, 0.0, 0.0, -1.0, 0.5, 3.0]), _spectrum(rng, 7, [2.0, 2.0, 2.0, 0.0, -1.0, -1.0, -1.0]),

@@ -47,7 +47,7 @@ def run_cases(lib, ctx, route, cases, reference=fam.reference):
 
 
 def test_syev_families_ping_pong_jacobi(pkg, gpu_ctx):
-    """n <= 64, small_syev_jacobi64_kernel<true>: a random matrix at every order, every family (the extreme scales take the
+    """n <= 64, small_syev_jacobi64_kernel: a random matrix at every order, every family (the extreme scales take the
     IEEE branch of jacobi_angle) at orders around the even padding and the wave boundaries of the (n/2)^2 threads."""
     lib = pkg.load_library()
     cases = [("random symmetric", n) for n in range(1, 65)]
